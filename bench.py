@@ -2,11 +2,14 @@
 """Benchmark of the hot path: projected ranges / second on BASELINE.json's
 headline workload (1M-record synthetic PAF, 100k-range BED, `-x -m 3`).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path (lookup + CIGAR projection + transitive
 frontier updates) over the whole query batch, index and query ranges already
-resident in HBM.  Prints ONE JSON line (rank 0).  See DESIGN.md section 7.
+resident in HBM.  Prints ONE JSON line (rank 0).  See DESIGN.md section 8.
+A plain run sets up, warms up, times the K steps and prints; --full adds the
+other tiers, checks, legs and the CPU baseline; --dump-outputs writes what the
+last timed step computed (dump_outputs).
 """
 import argparse
 import json
@@ -30,6 +33,13 @@ HEADLINE_PROJECTED = 2_125_313_869
 # row's query id, query interval, target id and target interval, added up mod 2^64).  Pinned by the same test, which ties the
 # per-range checksums to the oracle on a sample; the self check recomputes it FROM THE ROWS the timed form leaves in HBM.
 HEADLINE_CHECKSUM = 16_006_759_611_715_120_108  # (tests/test_gpu_fullsize.py::test_headline_timed_form asserts it)
+# --dump-outputs: at most this many bytes in all; the rows of this many ranges of the batch, drawn with this seed, at most
+# DUMP_ROWS_MAX of them (the headline's 32 ranges hold ~7 x 10^5 rows, 19 MB as float32)
+DUMP_BYTES_MAX = 64 << 20
+DUMP_SAMPLE_RANGES = 32
+DUMP_SAMPLE_SEED = 20261016
+DUMP_ROWS_MAX = 1 << 20
+DUMP_ROW_COLUMNS = ("range", "query_id", "q_first", "q_last", "target_id", "t_first", "t_last")
 
 
 T_START = time.time()
@@ -91,8 +101,20 @@ def main():
                     help="one device, constant work: the batch through a multi handle of 1 / 2 / 4 / 8 ranks that all share device 0 "
                          "(threads of this process, LocalComm) -- what the sharded path's fixed costs do as the world grows, "
                          "measurable without a second GPU; every world is checked against the plain index first")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: the checksum of the rows left in HBM and the other tiers' timings, "
+                         "the full-results, row-stream and DFS legs, the CPU baseline, on a sharded index the parity check against "
+                         "one GPU, strong scaling and the multi handle (--no-tiers / --no-extras / --cpu-sample trim it).  Without "
+                         "it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, at most "
+                         "64 MB in all): see dump_outputs()")
     args = ap.parse_args()
     args.engine_option_changes_results = False  # (no engine option changes a result row: they are layout / schedule knobs)
+    if not args.full:  # a plain run: nothing but what the headline figure needs
+        args.cpu_sample, args.no_extras, args.no_tiers = 0, True, True
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs needs at least one timed step")
 
     # `--gpus N` without a launcher: bring the N ranks up ourselves (one process per GPU) and pass the
     # one JSON line through.  Under torch.distributed.run the world must agree with --gpus.
@@ -119,6 +141,8 @@ def main():
         args.ranges = 200_000 if wl == "config5" else 2_000 if wl == "skewed" else 100_000
     if args.max_depth is None:
         args.max_depth = 5 if wl == "config5" else 3
+    if args.dump_outputs and 24 * args.ranges > DUMP_BYTES_MAX // 2:
+        sys.exit("bench.py: --dump-outputs: the per-range arrays of %d ranges would not fit in %d bytes" % (args.ranges, DUMP_BYTES_MAX))
     sharded_run = args.gpus > 1 or args.force_sharded
     if args.chunk_ranges is None:
         # one GPU: the whole batch in one chunk (2.1e9 slots a level; every level's fixed costs paid once: 61.7 -> 59.5 ms per
@@ -210,24 +234,33 @@ def main():
         ranges["start"], ranges["end"] = bed["start"], bed["end"]
     d_ranges = torch.from_numpy(ranges.view(np.uint8)).to(dev)  # resident in HBM before the timed region
 
-    def step_count():  # (a collective call when the index is sharded: every rank brings its own ranges)
+    # keep=True (the last timed step of a --dump-outputs run): the step's rows stay in HBM, as last["rows"], for dump_outputs
+    last = {}
+
+    def step_count(keep=False):  # (a collective call when the index is sharded: every rank brings its own ranges)
         st, _, _ = index.query_batch_stats(None, params, counts=False, checksums=False,
                                            device_ptr=d_ranges.data_ptr(), n=args.ranges)
         return st
 
-    def step_rows():  # every row left in HBM, attributable; the handle's HBM goes back to the engine's pool for the next step
+    def step_rows(keep=False):  # every row left in HBM, attributable; the handle's HBM goes back to the engine's pool for the next step
         dr = index.query_batch_device(None, params, device_ptr=d_ranges.data_ptr(), n=args.ranges)
         st = dr.stats
-        dr.free()
+        if keep:
+            last["rows"] = dr
+        else:
+            dr.free()
         return st
 
     # (rows left on the device belong to one GPU's index; config 5's 10^12 rows do not fit any HBM: a caller would take them chunk by chunk)
     form = "count" if (dist is not None or wl in ("config5", "skewed")) else args.form
-    def step_ordered():  # the rows grouped by range in the reference's emission order, in HBM (a profiling form: the tier's own step)
+    def step_ordered(keep=False):  # the rows grouped by range in the reference's emission order, in HBM (a profiling form: the tier's own step)
         import impg_amd._lib as _l
         dr = index.query_batch_device(None, params, device_ptr=d_ranges.data_ptr(), n=args.ranges, layout=_l.ROWS_ORDERED_SLOTS)
         st = dr.stats
-        dr.free()
+        if keep:
+            last["rows"] = dr
+        else:
+            dr.free()
         return st
 
     step = step_rows if form == "rows" else step_ordered if form == "ordered" else step_count
@@ -239,7 +272,7 @@ def main():
 
     log("index ready (%.1f s, %.2f GB in HBM); warmup" % (t_build, index.device_bytes() / 1e9))
     parity = None
-    if dist is not None and paf:
+    if dist is not None and paf and args.full:
         # Before anything is timed: the N-rank answer against the one-GPU answer.  Rank 0 submits its first 4096 ranges
         # (the other ranks none: the call is collective) with per-range counts and checksums, builds the PLAIN index of
         # the same PAF next to its shard, asks it the same, and the run goes on only if every count and checksum agrees.
@@ -287,13 +320,14 @@ def main():
     sync()
     t0 = time.perf_counter()
     stats, step_ms = [], []
-    for _ in range(args.steps):  # (a step returns when its results are complete: the per-step clock adds no synchronisation)
+    for k in range(args.steps):  # (a step returns when its results are complete: the per-step clock adds no synchronisation)
         ts = time.perf_counter()
-        stats.append(step())
+        stats.append(step(keep=bool(args.dump_outputs) and k == args.steps - 1))
         step_ms.append((time.perf_counter() - ts) * 1e3)
     sync()
     dt = time.perf_counter() - t0
     log("timed region: %.3f s for %d steps (%s ms)" % (dt, args.steps, " ".join("%.1f" % x for x in step_ms)))
+    dumped = dump_outputs(args.dump_outputs, form, last, stats, ranges, dev, dist, world, rank) if args.dump_outputs else None
     hops = sharded_diagnostics(index, stats, args, dist, dev, world) if dist is not None else None
     strong = strong_scaling_leg(index, args, params, dist, dev, rank, world, local_rank, n_seq, seq_len, bool(paf), sync) \
         if (dist is not None and wl == "headline" and not args.no_extras) else None
@@ -322,7 +356,9 @@ def main():
 
     proj_per_step = sum(s.projected for s in stats) / max(1, args.steps)
     self_check = self_check_timed(stats, args, wl, world, dist is not None)
-    if wl != "headline" and dist is None and self_check["status"] == "ok":
+    if dumped is not None:
+        self_check_dumped(dumped, self_check)
+    if args.full and wl != "headline" and dist is None and self_check["status"] == "ok":
         # no pinned constant for these workloads: the timed form (no per-range output, fused final level) and the counting
         # form (per-range counts and checksums, the form the suite compares with the oracle) on the same sample of the
         # batch must project the same ranges, and the counts must add up to it
@@ -407,6 +443,8 @@ def main():
     }
     if tiers:
         out.update(tiers)
+    if dumped is not None:
+        out["dump_outputs"] = {k: v for k, v in dumped.items() if not k.startswith("_")}
     if dist is not None:
         out["comm"] = comm_report
         out["parity"] = parity
@@ -460,6 +498,167 @@ def self_check_timed(stats, args, wl, world, sharded):
         if per[0] != HEADLINE_PROJECTED:
             chk["status"] = "FAILED: %d projections per step, the headline batch has %d" % (per[0], HEADLINE_PROJECTED)
     return chk
+
+
+def self_check_dumped(dumped, chk):
+    """What dump_outputs read back from the last step's rows, against the projections it counted and, at the headline, the
+    pinned checksum (no extra work: the dump computed every range's count and checksum anyway)."""
+    rows = dumped.get("_rows_check")
+    if rows is None:
+        return
+    chk["dumped_rows"] = rows
+    if chk["status"] != "ok":
+        return
+    if rows.get("stray_slots"):
+        chk["status"] = "FAILED: %d live slots of the last step name no frontier record of their part" % rows["stray_slots"]
+    elif "sum_of_per_range_counts" in rows and rows["sum_of_per_range_counts"] != rows["projected"]:
+        chk["status"] = "FAILED: the last step's rows (%d) are not the projections counted (%d)" % (rows["sum_of_per_range_counts"], rows["projected"])
+    elif not rows.get("sample_rows_match_counts", True):
+        chk["status"] = "FAILED: the sampled ranges' rows differ in number from their per-range counts"
+    elif chk.get("expected") is not None and "sum_of_per_range_checksums" in rows and rows["sum_of_per_range_checksums"] != HEADLINE_CHECKSUM:
+        chk["status"] = "FAILED: checksum of the last step's rows %d, the headline batch's is %d" % (rows["sum_of_per_range_checksums"], HEADLINE_CHECKSUM)
+    elif rows.get("bad_offsets"):
+        chk["status"] = "FAILED: %d sampled ranges' offsets lie outside the last step's rows" % rows["bad_offsets"]
+
+
+def dump_outputs(out_dir, form, last, stats, ranges, dev, dist, world, rank):
+    """--dump-outputs DIR: what the last timed step computed -- the arrays a caller of the timed path receives, or a fixed,
+    seeded sample of them -- as DIR/<name>.npy, integers held exactly in float32 / float64, at most DUMP_BYTES_MAX in all.
+    The inputs are seeded too, so two builds run with the same arguments can be compared file by file.
+      projected        [ranks]  the step's projections (every form; a sharded index: rank r's batch at [r])
+    rows form (impg_gpu_query_batch_device, IMPG_ROWS_ATTRIBUTED: its slot order is free, so every file is per range and
+    independent of that order):
+      range_counts     [n]      the rows of every range of the batch, recomputed from the rows in HBM (impg_gpu_device_rows_check)
+      range_checksums  [n, 2]   their order-independent 64-bit checksums, high and low 32 bits
+      sample_ranges    [<= 32]  the ranges drawn (DUMP_SAMPLE_SEED), ascending
+      sample_rows      [k, 7]   every row of those ranges (DUMP_ROW_COLUMNS; holes left out), sorted column by column
+    ordered form (IMPG_ROWS_ORDERED_SLOTS): range_slots [n] (the offsets' differences, hole rows included), sample_ranges,
+    and sample_rows: the drawn ranges' rows without the holes, in the layout's own (the reference's emission) order."""
+    import numpy as np
+    import torch
+    arrays = {"projected": np.array([float(stats[-1].projected)], dtype=np.float64)}
+    if dist is not None:  # (a collective: every rank brings its count)
+        mine = torch.tensor(arrays["projected"], device=dev)
+        every = [torch.zeros_like(mine) for _ in range(world)]
+        dist.all_gather(every, mine)
+        arrays["projected"] = torch.cat(every).cpu().numpy()
+    info = {"dir": out_dir, "form": form}
+    dr = last.pop("rows", None)
+    if dr is not None:
+        n = len(ranges)
+        sample = np.sort(np.random.RandomState(DUMP_SAMPLE_SEED).permutation(n)[:DUMP_SAMPLE_RANGES])
+        try:
+            rows, info["_rows_check"] = (_dump_attributed if form == "rows" else _dump_ordered)(dr, n, sample, dev, arrays)
+        finally:
+            dr.free()
+        arrays["sample_ranges"] = sample.astype(np.float64)
+        rows = _exact_float(rows)
+        cap = min(DUMP_ROWS_MAX, (DUMP_BYTES_MAX - sum(a.nbytes for a in arrays.values()) - 65536) // (rows.itemsize * rows.shape[1]))
+        info["sample_rows"] = int(len(rows))
+        if len(rows) > cap:  # (a fixed prefix of a fixed order: still the same rows from run to run)
+            rows = rows[:cap]
+            info["sample_rows_kept"] = int(cap)
+        arrays["sample_rows"] = rows
+    info["bytes"] = int(sum(a.nbytes for a in arrays.values()))
+    assert info["bytes"] <= DUMP_BYTES_MAX, info["bytes"]
+    if rank == 0:
+        os.makedirs(out_dir, exist_ok=True)
+        for name, a in arrays.items():
+            np.save(os.path.join(out_dir, name + ".npy"), a)
+        log("outputs of the last step: %s in %s (%.1f MB)" % (", ".join(sorted(arrays)), out_dir, info["bytes"] / 1e6))
+    info["files"] = sorted(name + ".npy" for name in arrays)
+    return info
+
+
+def _exact_float(a):
+    """Integers as floats without rounding: float32 where every value fits its 24-bit significand, float64 otherwise."""
+    import numpy as np
+    a = np.asarray(a, dtype=np.int64)
+    big = int(np.abs(a).max()) if a.size else 0
+    assert big < (1 << 53), big
+    return a.astype(np.float32 if big < (1 << 24) else np.float64)
+
+
+class _DeviceWords:
+    """An int32 device array of the library as torch sees it, without a copy (valid while the handle that owns it lives)."""
+
+    def __init__(self, ptr, shape):
+        self.__cuda_array_interface__ = {"shape": tuple(int(x) for x in shape), "typestr": "<i4", "data": (int(ptr), False),
+                                         "strides": None, "version": 2}
+
+
+def _device_words(ptr, shape, dev):
+    import torch
+    return torch.as_tensor(_DeviceWords(ptr, shape), device=dev)
+
+
+def _dump_attributed(dr, n, sample, dev, arrays):
+    """The rows form: every range's count and checksum, and the rows of the sampled ranges gathered on the device (each slot
+    attributed through source[] -> frontier[]; a slot whose source lies outside its part's frontier is counted, never read)."""
+    import numpy as np
+    import torch
+    cnt, ck = dr.check()
+    arrays["range_counts"] = cnt.astype(np.float64)
+    arrays["range_checksums"] = np.stack([ck >> np.uint64(32), ck & np.uint64(0xFFFFFFFF)], axis=1).astype(np.float64)
+    pick = torch.zeros(n, dtype=torch.bool, device=dev)
+    pick[torch.from_numpy(sample).to(dev)] = True
+    got, stray, chunk = [], 0, 1 << 26
+    for d in dr.parts():
+        ns, nf, stride = int(d.n_slots), int(d.n_frontier), int(d.slot_stride)
+        if ns == 0:
+            continue
+        span = (ns - 1) * stride + 1  # words from the first slot's query_id (source) to the last one's
+        qid = _device_words(d.query_id, (span,), dev)[::stride]
+        if nf == 0:
+            stray += int((qid != -1).sum())
+            continue
+        src = _device_words(d.source, (span,), dev)[::stride]
+        co = _device_words(d.coords, (ns, 4), dev)
+        fr = _device_words(d.frontier, (nf, 4), dev).long()  # {target_id, start, end, range_idx}
+        fr_range = fr[:, 3] + int(d.first_range)
+        fr_ok = (fr_range >= 0) & (fr_range < n)
+        fr_pick = torch.zeros(nf, dtype=torch.bool, device=dev)
+        fr_pick[fr_ok] = pick[fr_range[fr_ok]]
+        for a in range(0, ns, chunk):
+            q, s = qid[a:a + chunk], src[a:a + chunk].long()
+            live, inside = q != -1, (s >= 0) & (s < nf)
+            stray += int((live & ~inside).sum())
+            s = torch.where(inside, s, torch.zeros_like(s))
+            idx = torch.nonzero(live & inside & fr_pick[s]).squeeze(1)
+            if idx.numel():
+                f, c = s[idx], co[a:a + chunk][idx].long()
+                got.append(torch.stack([fr_range[f], q[idx].long(), c[:, 0], c[:, 1], fr[f, 0], c[:, 2], c[:, 3]], dim=1).cpu())
+    rows = torch.cat(got).numpy() if got else np.zeros((0, len(DUMP_ROW_COLUMNS)), dtype=np.int64)
+    rows = rows[np.lexsort(rows.T[::-1])]  # by range, then column by column: the layout's slot order is free
+    per = np.bincount(rows[:, 0], minlength=n)[sample]
+    with np.errstate(over="ignore"):
+        ck_sum = int(ck.sum(dtype=np.uint64))
+    return rows, {"projected": int(dr.projected), "sum_of_per_range_counts": int(cnt.sum()), "sum_of_per_range_checksums": ck_sum,
+                  "stray_slots": stray, "sample_rows_match_counts": bool((per == cnt[sample]).all())}
+
+
+def _dump_ordered(dr, n, sample, dev, arrays):
+    """The ordered form: every range's slot count, and the sampled ranges' rows copied back from their places."""
+    import numpy as np
+    slots, got, bad = np.zeros(n, dtype=np.float64), [], 0
+    for d in dr.parts():
+        nr, first, ns = int(d.n_ranges), int(d.first_range), int(d.n_slots)
+        if nr == 0:
+            continue
+        off = _device_words(d.offsets, (nr + 1,), dev).cpu().numpy().view(np.uint32).astype(np.int64)
+        slots[first:first + nr] = np.diff(off)
+        for r in sample[(sample >= first) & (sample < first + nr)]:
+            a, b = int(off[r - first]), int(off[r - first + 1])
+            if not 0 <= a <= b <= ns:
+                bad += 1
+                continue
+            if b > a:  # impg_gpu_interval_t: query_id, q_first, q_last, target_id, t_first, t_last
+                iv = _device_words(int(d.rows) + 24 * a, (b - a, 6), dev).cpu().numpy().astype(np.int64)
+                iv = iv[iv[:, 0] != -1]
+                got.append(np.column_stack([np.full(len(iv), r, dtype=np.int64), iv]))
+    arrays["range_slots"] = slots
+    rows = np.concatenate(got) if got else np.zeros((0, len(DUMP_ROW_COLUMNS)), dtype=np.int64)
+    return rows, {"projected": int(dr.projected), "bad_offsets": bad}
 
 
 def rows_form_legs(index, ranges, params, args, d_ranges, step_count, sync, self_check, wl, dt_rows):

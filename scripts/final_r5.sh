@@ -24,17 +24,17 @@ python3 scripts/make_sq_json.py $OUT $OUT/sq.json $OUT/valu_mix_entries.json > /
 python3 scripts/make_per_kernel_json.py $OUT $OUT/per_kernel.json --asm /tmp/kernels.s > $F/per_kernel.txt
 for f in traffic sq per_kernel; do cp $OUT/$f.json $REPO/profiles/r5_final_$f.json 2>/dev/null; done  # (so that the bench lines below price against this build's counters)
 fi
-timeout 500 python bench.py > $F/bench_full.json 2> $F/bench_full.err
-timeout 300 python bench.py --force-sharded --steps 5 --warmup 2 --cpu-sample 0 --no-extras > $F/bench_sharded_1rank.json 2> $F/bench_sharded_1rank.err
-timeout 400 python bench.py --world-sweep --no-extras --cpu-sample 0 --steps 3 > $F/bench_world_sweep.json 2> $F/bench_world_sweep.err
-timeout 400 python bench.py --workload config4 --cpu-sample 0 --no-extras > $F/bench_config4.json 2> $F/bench_config4.err
-timeout 300 python bench.py --workload config5 --ranges 20000 --steps 2 --warmup 1 --cpu-sample 0 --no-extras > $F/bench_config5_20000.json 2> $F/bench_config5_20000.err
-timeout 300 python bench.py --min-identity 0.9 --steps 3 --cpu-sample 0 --no-extras > $F/bench_min_identity.json 2> $F/bench_min_identity.err
+timeout 500 python bench.py --full > $F/bench_full.json 2> $F/bench_full.err
+timeout 300 python bench.py --full --force-sharded --steps 5 --warmup 2 --cpu-sample 0 --no-extras > $F/bench_sharded_1rank.json 2> $F/bench_sharded_1rank.err
+timeout 400 python bench.py --full --world-sweep --no-extras --cpu-sample 0 --steps 3 > $F/bench_world_sweep.json 2> $F/bench_world_sweep.err
+timeout 400 python bench.py --full --workload config4 --cpu-sample 0 --no-extras > $F/bench_config4.json 2> $F/bench_config4.err
+timeout 300 python bench.py --full --workload config5 --ranges 20000 --steps 2 --warmup 1 --cpu-sample 0 --no-extras > $F/bench_config5_20000.json 2> $F/bench_config5_20000.err
+timeout 300 python bench.py --full --min-identity 0.9 --steps 3 --cpu-sample 0 --no-extras > $F/bench_min_identity.json 2> $F/bench_min_identity.err
 if [ -n "${CONFIG5_FULL:-}" ]; then  # BASELINE config 5 at its size: 10^6 windows, ~5 min
-  timeout 900 python bench.py --workload config5 --ranges 1000000 --steps 1 --warmup 0 --cpu-sample 0 --no-extras > $F/bench_config5_1e6.json 2> $F/bench_config5_1e6.err
+  timeout 900 python bench.py --full --workload config5 --ranges 1000000 --steps 1 --warmup 0 --cpu-sample 0 --no-extras > $F/bench_config5_1e6.json 2> $F/bench_config5_1e6.err
 fi
 if [ -n "${CONFIG4_FULL:-}" ]; then  # BASELINE config 4 at its size on ONE device: 10^8 records with prefix lines (222 GB)
-  timeout 900 python bench.py --workload config4 --records 100000000 --steps 3 --warmup 1 > $F/bench_config4_1e8.json 2> $F/bench_config4_1e8.err
+  timeout 900 python bench.py --full --workload config4 --records 100000000 --steps 3 --warmup 1 > $F/bench_config4_1e8.json 2> $F/bench_config4_1e8.err
 fi
 (timeout 1200 python -m pytest tests -m gpu -x -q --durations=20 2>&1 | tail -34) > $F/gputest.log
 tail -3 $F/gputest.log

@@ -44,20 +44,20 @@ if has config4prof; then  # config 4's counters on THIS round's index (the traff
   for f in trace_kernel_stats fetch_pmc write_pmc ea_pmc sq_pmc; do cp $OUT/$f.csv $F/r6_config4_$f.csv 2>/dev/null; done
 fi
 if has bench; then
-  timeout 600 python bench.py > $F/bench_full.json 2> $F/bench_full.err
-  timeout 300 python bench.py --form count --no-extras --cpu-sample 0 --steps 5 > $F/bench_count_form.json 2> $F/bench_count_form.err
-  timeout 300 python bench.py --force-sharded --steps 5 --warmup 2 --cpu-sample 0 --no-extras > $F/bench_sharded_1rank.json 2> $F/bench_sharded_1rank.err
-  timeout 400 python bench.py --workload config4 --cpu-sample 0 --no-extras > $F/bench_config4.json 2> $F/bench_config4.err
-  timeout 300 python bench.py --workload config5 --ranges 20000 --steps 2 --warmup 1 --cpu-sample 0 --no-extras > $F/bench_config5_20000.json 2> $F/bench_config5_20000.err
-  timeout 300 python bench.py --workload skewed --steps 3 --warmup 1 --cpu-sample 0 --no-extras > $F/bench_skewed.json 2> $F/bench_skewed.err
-  timeout 300 python bench.py --workload skewed --records 1000000 --steps 2 --warmup 1 --cpu-sample 0 --no-extras > $F/bench_skewed_1e6.json 2> $F/bench_skewed_1e6.err
+  timeout 600 python bench.py --full > $F/bench_full.json 2> $F/bench_full.err
+  timeout 300 python bench.py --full --form count --no-extras --cpu-sample 0 --steps 5 > $F/bench_count_form.json 2> $F/bench_count_form.err
+  timeout 300 python bench.py --full --force-sharded --steps 5 --warmup 2 --cpu-sample 0 --no-extras > $F/bench_sharded_1rank.json 2> $F/bench_sharded_1rank.err
+  timeout 400 python bench.py --full --workload config4 --cpu-sample 0 --no-extras > $F/bench_config4.json 2> $F/bench_config4.err
+  timeout 300 python bench.py --full --workload config5 --ranges 20000 --steps 2 --warmup 1 --cpu-sample 0 --no-extras > $F/bench_config5_20000.json 2> $F/bench_config5_20000.err
+  timeout 300 python bench.py --full --workload skewed --steps 3 --warmup 1 --cpu-sample 0 --no-extras > $F/bench_skewed.json 2> $F/bench_skewed.err
+  timeout 300 python bench.py --full --workload skewed --records 1000000 --steps 2 --warmup 1 --cpu-sample 0 --no-extras > $F/bench_skewed_1e6.json 2> $F/bench_skewed_1e6.err
   STEPS=2 TOP=14 BENCH_ARGS="--workload skewed" bash scripts/trace_r5.sh final_r6/skewed_trace > $F/skewed_trace.txt 2>&1
-  timeout 300 python bench.py --min-identity 0.9 --steps 3 --cpu-sample 0 --no-extras --no-tiers > $F/bench_min_identity.json 2> $F/bench_min_identity.err
+  timeout 300 python bench.py --full --min-identity 0.9 --steps 3 --cpu-sample 0 --no-extras --no-tiers > $F/bench_min_identity.json 2> $F/bench_min_identity.err
   if [ -n "${CONFIG5_FULL:-}" ]; then
-    timeout 900 python bench.py --workload config5 --ranges 1000000 --steps 1 --warmup 0 --cpu-sample 0 --no-extras > $F/bench_config5_1e6.json 2> $F/bench_config5_1e6.err
+    timeout 900 python bench.py --full --workload config5 --ranges 1000000 --steps 1 --warmup 0 --cpu-sample 0 --no-extras > $F/bench_config5_1e6.json 2> $F/bench_config5_1e6.err
   fi
   if [ -n "${CONFIG4_FULL:-}" ]; then
-    timeout 900 python bench.py --workload config4 --records 100000000 --form count --steps 3 --warmup 1 --no-extras --cpu-sample 0 > $F/bench_config4_1e8.json 2> $F/bench_config4_1e8.err
+    timeout 900 python bench.py --full --workload config4 --records 100000000 --form count --steps 3 --warmup 1 --no-extras --cpu-sample 0 > $F/bench_config4_1e8.json 2> $F/bench_config4_1e8.err
   fi
   for f in bench_full bench_count_form bench_sharded_1rank bench_config4 bench_config5_20000 bench_skewed bench_skewed_1e6 bench_min_identity bench_config5_1e6 bench_config4_1e8; do python3 -c "
 import json,sys
