@@ -56,6 +56,7 @@ EngineLease::EngineLease(impg_gpu_index &ix_) : ix(ix_) {
   e->seg_group = ix.opt_seg_group;
   e->seg_parts_force = ix.opt_seg_parts;
   e->seg_stats = ix.seg_stats;
+  e->proj_stats = ix.proj_stats;
 }
 EngineLease::~EngineLease() {
   e->remote = nullptr;
@@ -579,6 +580,14 @@ int impg_gpu_get_counter(const impg_gpu_index_t *ix, const char *key, int64_t *v
   else if (k == "segment_sliced_levels") *value_out = (int64_t)ix->seg_stats[0].load();
   else if (k == "segment_retries") *value_out = (int64_t)ix->seg_stats[1].load();
   else if (k == "segment_library_levels") *value_out = (int64_t)ix->seg_stats[2].load();
+  else if (k == "project_lane_levels") *value_out = (int64_t)ix->proj_stats[PROJ_ARM_LANE].load();
+  else if (k == "project_staged_levels") *value_out = (int64_t)ix->proj_stats[PROJ_ARM_STAGED].load();
+  else if (k == "project_staged_rows_levels") *value_out = (int64_t)ix->proj_stats[PROJ_ARM_STAGED_ROWS].load();
+  else if (k == "project_entries_slots_levels") *value_out = (int64_t)ix->proj_stats[PROJ_ARM_ENTRIES_SLOTS].load();
+  else if (k == "project_entries_qs_levels") *value_out = (int64_t)ix->proj_stats[PROJ_ARM_ENTRIES_QS].load();
+  else if (k == "project_entries_rows_levels") *value_out = (int64_t)ix->proj_stats[PROJ_ARM_ENTRIES_ROWS].load();
+  else if (k == "project_entries_ident_levels") *value_out = (int64_t)ix->proj_stats[PROJ_ARM_ENTRIES_IDENT].load();
+  else if (k == "project_tp_levels") *value_out = (int64_t)ix->proj_stats[PROJ_ARM_TP].load();
   else throw Error{IMPG_E_INVALID, "unknown counter " + k};
   return IMPG_OK;
   IMPG_CATCH

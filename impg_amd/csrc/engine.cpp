@@ -73,15 +73,15 @@ bool Engine::run_small(const impg_gpu_index &ix, const impg_gpu_range_t *h_range
   IMPG_HIP(hipMemsetAsync(counters.p, 0, 64, stream));
   IMPG_HIP(hipMemsetAsync(acc_slots.p, 0, COUNT_BYTES, stream));
   const FrontierRec *fr = frontier_a.as<FrontierRec>();
-  launch_ranges_to_frontier(ranges_dev.as<impg_gpu_range_t>(), n, frontier_a.as<FrontierRec>(), stream);
+  launch_ranges_to_frontier(ranges_dev.as<impg_gpu_range_t>(), n, frontier_a.as<FrontierRec>(), (uint32_t *)(counters.as<uint64_t>() + 5), stream);
   launch_lookup_count(v, fr, n, false, nullptr, cnt.as<uint32_t>(), win.as<uint4>(), wide_n.as<uint32_t>(), wide_list.as<uint32_t>(), stream);
   uint32_t *d_total = reinterpret_cast<uint32_t *>(counters.as<uint64_t>() + 3);
   launch_small_scan(cnt.as<uint32_t>(), n, pair_off.as<uint32_t>(), d_total, stream);
   launch_lookup_emit(v, fr, n, false, pair_off.as<uint32_t>(), win.as<uint4>(), L.pair_range.as<uint32_t>(), pair_entry.as<uint32_t>(),
                      nullptr, nullptr, ProjList{nullptr, nullptr, nullptr}, wide_n.as<uint32_t>(), wide_list.as<uint32_t>(), stream);
   HitArrays h{L.qid.as<uint32_t>(), L.coords.as<int4>()};
-  launch_project(v, fr, L.pair_range.as<uint32_t>(), pair_entry.as<uint32_t>(), B, false, h, acc_slots.as<unsigned long long>(),
-                 (uint32_t *)(counters.as<uint64_t>() + 2), min_identity, nullptr, ProjList{nullptr, nullptr, nullptr}, stream, d_total);
+  count_arm(launch_project(v, fr, L.pair_range.as<uint32_t>(), pair_entry.as<uint32_t>(), B, false, h, acc_slots.as<unsigned long long>(),
+                           (uint32_t *)(counters.as<uint64_t>() + 2), min_identity, nullptr, ProjList{nullptr, nullptr, nullptr}, stream, d_total));
   char *od = static_cast<char *>(small_out_dev);
   impg_gpu_interval_t *d_rows = reinterpret_cast<impg_gpu_interval_t *>(od + SMALL_HEADER_BYTES);
   uint32_t *d_rr = reinterpret_cast<uint32_t *>(od + SMALL_HEADER_BYTES + (size_t)SMALL_PAIRS * sizeof(impg_gpu_interval_t));
@@ -296,7 +296,7 @@ hipEvent_t Engine::event() {
 }
 
 // counters layout (device, 8 x u64): 0 total pairs, 1 accepted, 2 err flag,
-// 3 scan total (groups / caps / pieces), 4 active keys
+// 3 scan total (groups / caps / pieces), 4 active keys, 5 a range with start >= end (ranges_to_frontier_kernel)
 uint64_t Engine::read_counter(int k) {
   IMPG_HIP(hipMemcpyAsync(h_counters, counters.as<uint64_t>() + k, 8, hipMemcpyDeviceToHost, stream));
   IMPG_HIP(hipStreamSynchronize(stream));
@@ -315,7 +315,12 @@ uint64_t Engine::scan(const uint32_t *in, uint32_t *out, uint32_t n) {
   if (n == 0) return 0;
   scan_tmp.reserve(scan_scratch_bytes(n));
   launch_exclusive_scan(in, out, n, scan_tmp.as<unsigned long long>(), counters.as<unsigned long long>() + 3, stream);
-  return read_counter(3);
+  // (the bad-range flag of device-resident ranges comes back with the total: the first level's scan raises it before any
+  // pair is projected)
+  IMPG_HIP(hipMemcpyAsync(h_counters, counters.as<uint64_t>() + 3, 24, hipMemcpyDeviceToHost, stream));
+  IMPG_HIP(hipStreamSynchronize(stream));
+  if (h_counters[2]) throw Error{IMPG_E_INVALID, "query range must satisfy start < end"};
+  return h_counters[0];
 }
 
 void Engine::scan2(const uint32_t *in_a, uint32_t *out_a, const uint32_t *in_b, uint32_t *out_b, uint32_t n, uint64_t &total_a, uint64_t &total_b,
@@ -501,9 +506,9 @@ uint64_t Engine::expand(const DeviceIndexView &v, const FrontierRec *fr, uint32_
     L.sl_a.reserve(b); L.sl_n.reserve(b); L.sl_off.reserve(b); L.sl_rem.reserve(b);
     sl = SliceArrays{L.sl_a.as<uint32_t>(), L.sl_n.as<uint32_t>(), L.sl_off.as<int32_t>(), L.sl_rem.as<int32_t>()};
   }
-  launch_project(v, fr, L.pair_range.as<uint32_t>(), pair_entry.as<uint32_t>(), L.n_pairs, transitive, h,
-                 acc_slots.as<unsigned long long>(), (uint32_t *)(counters.as<uint64_t>() + 2), min_identity,
-                 store_cigar ? &sl : nullptr, pl, stream, nullptr, regroup_pairs, by_place ? &wlists : nullptr);
+  count_arm(launch_project(v, fr, L.pair_range.as<uint32_t>(), pair_entry.as<uint32_t>(), L.n_pairs, transitive, h,
+                           acc_slots.as<unsigned long long>(), (uint32_t *)(counters.as<uint64_t>() + 2), min_identity,
+                           store_cigar ? &sl : nullptr, pl, stream, nullptr, regroup_pairs, by_place ? &wlists : nullptr));
   if (!raw && !direct) {
     post_expand(fr, n_fr, L, pair_off.as<uint32_t>(), pair_entry.as<uint32_t>(), v.mrank, sl);
     h = HitArrays{L.qid.as<uint32_t>(), L.coords.as<int4>()};
@@ -949,7 +954,7 @@ void Engine::run(const impg_gpu_index &ix, const impg_gpu_range_t *d_ranges, uin
   cur->reserve(std::max<size_t>((size_t)n * sizeof(FrontierRec), 256));
   if (!n) {  // (a rank of a sharded batch that has no ranges of its own still takes part in every hop)
   } else if (!transitive) {
-    launch_ranges_to_frontier(d_ranges, n, cur->as<FrontierRec>(), stream);
+    launch_ranges_to_frontier(d_ranges, n, cur->as<FrontierRec>(), (uint32_t *)(counters.as<uint64_t>() + 5), stream);
     n_fr = n;
   } else {
     DevBuf &self = self_out ? *self_out : self_scratch;
@@ -1036,8 +1041,9 @@ void Engine::run(const impg_gpu_index &ix, const impg_gpu_range_t *d_ranges, uin
 void Engine::finish_run(impg_gpu_stats_t *st, hipEvent_t t0, hipEvent_t t1) {
   IMPG_HIP(hipEventRecord(t1, stream));
   IMPG_HIP(hipStreamSynchronize(stream));
-  uint64_t hc[3];
-  IMPG_HIP(hipMemcpy(hc, counters.p, 24, hipMemcpyDeviceToHost));
+  uint64_t hc[6];
+  IMPG_HIP(hipMemcpy(hc, counters.p, 48, hipMemcpyDeviceToHost));
+  if (hc[5]) throw Error{IMPG_E_INVALID, "query range must satisfy start < end"};  // (a run that scanned nothing)
   if (hc[2] & 2) throw Error{IMPG_E_INVALID, "Projection resulted in negative query coordinates"};  // the reference panics (impg.rs:1509-1514)
   if (hc[2]) throw Error{IMPG_E_INVALID, "an alignment hit by the query has no CIGAR (missing cg:Z tag)"};
   hc[1] = read_slots(acc_slots);

@@ -437,6 +437,8 @@ struct impg_gpu_index {
   // ... and how the visited updates of its batches grouped their hits: levels cut into slices, levels counted a second time
   // for one huge query, levels that went to the library sort ([0], [1], [2]; Engine::update)
   mutable std::atomic<uint64_t> seg_stats[3] = {};
+  // ... and which kernel projected each level (by impg::ProjArm: launch_project's return value, counted by the engine)
+  mutable std::atomic<uint64_t> proj_stats[8] = {};
   impg::ShardCtx *shard = nullptr;    // set: this index is one rank's shard; queries are collective calls
   impg::Cluster *cluster = nullptr;   // set: this handle fronts n_dev shards in this process (no arrays of its own)
   impg_gpu_index();

@@ -4799,7 +4799,7 @@ __global__ __launch_bounds__(256) void compact_frontier_kernel(const FrontierRec
   if (flag[i]) out[pos[i]] = in[i];
 }
 __global__ __launch_bounds__(256) void ranges_to_frontier_kernel(const impg_gpu_range_t *__restrict__ ranges, uint32_t n,
-                                                                 FrontierRec *__restrict__ out) {
+                                                                 FrontierRec *__restrict__ out, uint32_t *__restrict__ bad) {
   const uint32_t q = blockIdx.x * 256u + threadIdx.x;
   if (q >= n) return;
   FrontierRec f;
@@ -4808,6 +4808,7 @@ __global__ __launch_bounds__(256) void ranges_to_frontier_kernel(const impg_gpu_
   f.end = ranges[q].end;
   f.qidx = q;
   out[q] = f;
+  if (f.start >= f.end) *bad = 1u;  // (check_ranges for device-resident ranges: the engine reads it with the first scan total)
 }
 
 // ---------------------------------------------------------------------------
@@ -5437,11 +5438,11 @@ bool project_entry_major(const DeviceIndexView &v, uint64_t n_pairs, double min_
 }
 uint32_t project_entry_blocks(uint32_t n_fr) { return (cdiv(n_fr, ENT_RANGES) + 7u) & ~7u; }
 uint32_t project_entry_slice_cap(uint64_t n_pairs) { return (uint32_t)(n_pairs / ENT_SLICE_PAIRS) + 16u; }
-void launch_project(const DeviceIndexView &v, const FrontierRec *fr, const uint32_t *pair_range,
-                    const uint32_t *pair_entry, uint32_t n_pairs, bool transitive, HitArrays h,
-                    unsigned long long *accepted, uint32_t *err_flag, double min_identity, const SliceArrays *slices,
-                    ProjList pl, hipStream_t s, const uint32_t *n_pairs_dev, bool regroup, const WindowLists *wlp) {
-  if (!n_pairs) return;
+int launch_project(const DeviceIndexView &v, const FrontierRec *fr, const uint32_t *pair_range,
+                   const uint32_t *pair_entry, uint32_t n_pairs, bool transitive, HitArrays h,
+                   unsigned long long *accepted, uint32_t *err_flag, double min_identity, const SliceArrays *slices,
+                   ProjList pl, hipStream_t s, const uint32_t *n_pairs_dev, bool regroup, const WindowLists *wlp) {
+  if (!n_pairs) return PROJ_ARM_NONE;
   const WindowLists wl = wlp ? *wlp : WindowLists{nullptr, nullptr, nullptr, nullptr, nullptr, 0u, nullptr, 0u, 0u};
   const int rg = regroup ? 1 : 0;
   bool ident = min_identity == min_identity;  // NaN = no filter
@@ -5456,7 +5457,7 @@ void launch_project(const DeviceIndexView &v, const FrontierRec *fr, const uint3
                                                                ident ? min_identity : 0.0, ident ? 1 : 0, pl, n_pairs_dev);
     else project_tp_kernel<false><<<gt, 256, 0, s>>>(v, fr, pair_range, pair_entry, n_pairs, h, accepted, err_flag,
                                                      ident ? min_identity : 0.0, ident ? 1 : 0, pl, n_pairs_dev);
-    return;
+    return PROJ_ARM_TP;
   }
   const uint32_t g = (cdiv(n_pairs, PROJ_BLOCK) + 7u) & ~7u;  // a multiple of the 8 XCDs (see the block mapping in the kernel)
   const int xcd_map = 1;
@@ -5474,7 +5475,7 @@ void launch_project(const DeviceIndexView &v, const FrontierRec *fr, const uint3
     const uint32_t gs = (cdiv(wl.n_fr, STG_RANGES) + 7u) & ~7u;
     if (transitive) project_staged_kernel<true, true, OUT_ROWS><<<gs, STG_THREADS, 0, s>>>(v, pair_entry, n_pairs, h, accepted, err_flag, rg, wl);
     else project_staged_kernel<false, true, OUT_ROWS><<<gs, STG_THREADS, 0, s>>>(v, pair_entry, n_pairs, h, accepted, err_flag, rg, wl);
-    return;
+    return PROJ_ARM_STAGED_ROWS;
   }
   if (dense && wl.masks != 0 && entry_major() && (mode == 0 || (mode == MODE_IDENT && v.idp))) {
     // the final level of a counting run, entry by entry; also under the identity filter
@@ -5498,7 +5499,8 @@ void launch_project(const DeviceIndexView &v, const FrontierRec *fr, const uint3
       if (transitive) IMPG_LAUNCH_ENT(true, MODE_IDENT, OUT_SLOTS); else IMPG_LAUNCH_ENT(false, MODE_IDENT, OUT_SLOTS);
     }
 #undef IMPG_LAUNCH_ENT
-    return;
+    if (mode != 0) return PROJ_ARM_ENTRIES_IDENT;
+    return out == OUT_ROWS ? PROJ_ARM_ENTRIES_ROWS : out == OUT_QS ? PROJ_ARM_ENTRIES_QS : PROJ_ARM_ENTRIES_SLOTS;
   }
   // (a level named by masks has no tile_first[] once the engine has seen it dense: it stays on the staged kernels)
   if (mode == 0 && dense && (wl.masks != 0 || (double)n_pairs >= stage_density_listed() * (double)v.n_entries)) {
@@ -5508,7 +5510,7 @@ void launch_project(const DeviceIndexView &v, const FrontierRec *fr, const uint3
     if (transitive) { if (masks) IMPG_LAUNCH_STG(true, true); else IMPG_LAUNCH_STG(true, false); }
     else { if (masks) IMPG_LAUNCH_STG(false, true); else IMPG_LAUNCH_STG(false, false); }
 #undef IMPG_LAUNCH_STG
-    return;
+    return PROJ_ARM_STAGED;
   }
 #define IMPG_LAUNCH(T, M) project_kernel<T, M><<<g, PROJ_BLOCK, 0, s>>>(v, fr, pair_range, pair_entry, n_pairs, h, accepted, err_flag, ident ? min_identity : 0.0, sl, pl, xcd_map, n_pairs_dev, rg, wl)
   if (transitive) {
@@ -5519,6 +5521,7 @@ void launch_project(const DeviceIndexView &v, const FrontierRec *fr, const uint3
                     case 2: IMPG_LAUNCH(false, 2); break; case 3: IMPG_LAUNCH(false, 3); break; default: IMPG_LAUNCH(false, 5); }
   }
 #undef IMPG_LAUNCH
+  return PROJ_ARM_LANE;
 }
 void launch_slice_counts(HitArrays h, SliceArrays sl, uint32_t n_pairs, uint32_t *cnt, hipStream_t s) {
   if (n_pairs) slice_counts_kernel<<<cdiv(n_pairs, 256), 256, 0, s>>>(h, sl, n_pairs, cnt);
@@ -5710,9 +5713,9 @@ void launch_compact_frontier(const FrontierRec *in, const uint32_t *flag, const 
   if (!n) return;
   compact_frontier_kernel<<<cdiv(n, 256), 256, 0, s>>>(in, flag, pos, n, out);
 }
-void launch_ranges_to_frontier(const impg_gpu_range_t *ranges, uint32_t n, FrontierRec *out, hipStream_t s) {
+void launch_ranges_to_frontier(const impg_gpu_range_t *ranges, uint32_t n, FrontierRec *out, uint32_t *bad, hipStream_t s) {
   if (!n) return;
-  ranges_to_frontier_kernel<<<cdiv(n, 256), 256, 0, s>>>(ranges, n, out);
+  ranges_to_frontier_kernel<<<cdiv(n, 256), 256, 0, s>>>(ranges, n, out, bad);
 }
 void launch_frontier_to_stack(const FrontierRec *fr, uint32_t n, const uint32_t *pop_depth, bool use_depth,
                               unsigned long long *key, int32_t *st, int32_t *en, uint32_t *depth, hipStream_t s) {

@@ -142,11 +142,26 @@ void launch_scatter_u32(const uint32_t *in, const uint32_t *perm, uint32_t n, ui
 void launch_exclusive_scan(const uint32_t *d_in, uint32_t *d_out, uint32_t n, unsigned long long *d_bsum,
                            unsigned long long *d_total, hipStream_t s);
 size_t scan_scratch_bytes(uint32_t n);
-void launch_project(const DeviceIndexView &v, const FrontierRec *fr, const uint32_t *pair_range,
-                    const uint32_t *pair_entry, uint32_t n_pairs, bool transitive, HitArrays h,
-                    unsigned long long *accepted, uint32_t *err_flag, double min_identity, const SliceArrays *slices,
-                    ProjList pl, hipStream_t s, const uint32_t *n_pairs_dev = nullptr, bool regroup = false,
-                    const WindowLists *wl = nullptr);
+// Which kernel launch_project ran a level on (its return value; PROJ_ARM_NONE: no pairs, nothing launched).  The handle counts
+// them per arm (impg_gpu_get_counter "project_*_levels"), on the host.
+enum ProjArm : int {
+  PROJ_ARM_NONE = -1,
+  PROJ_ARM_LANE = 0,          // project_kernel: a lane per pair
+  PROJ_ARM_STAGED,            // project_staged_kernel
+  PROJ_ARM_STAGED_ROWS,       // project_staged_kernel<.., OUT_ROWS>: the ordered rows of a dense fused level
+  PROJ_ARM_ENTRIES_SLOTS,     // project_entries_kernel<.., 0, OUT_SLOTS>
+  PROJ_ARM_ENTRIES_QS,        // project_entries_kernel<.., 0, OUT_QS>
+  PROJ_ARM_ENTRIES_ROWS,      // project_entries_kernel<.., 0, OUT_ROWS>
+  PROJ_ARM_ENTRIES_IDENT,     // project_entries_kernel<.., MODE_IDENT, OUT_SLOTS>
+  PROJ_ARM_TP,                // project_tp_kernel (tracepoint index)
+  PROJ_ARMS
+};
+static_assert(PROJ_ARMS == sizeof(impg_gpu_index::proj_stats) / sizeof(impg_gpu_index::proj_stats[0]), "one counter per arm");
+int launch_project(const DeviceIndexView &v, const FrontierRec *fr, const uint32_t *pair_range,
+                   const uint32_t *pair_entry, uint32_t n_pairs, bool transitive, HitArrays h,
+                   unsigned long long *accepted, uint32_t *err_flag, double min_identity, const SliceArrays *slices,
+                   ProjList pl, hipStream_t s, const uint32_t *n_pairs_dev = nullptr, bool regroup = false,
+                   const WindowLists *wl = nullptr);
 // small batches (engine.cpp: run_small): n <= 1024 counts scanned by one block, total left on the device; results
 // packed behind a 64-byte header {n_pairs, err, -, -, accepted} into (host-mapped) memory
 constexpr uint32_t SMALL_HEADER_BYTES = 64;
@@ -217,7 +232,8 @@ void launch_visited_init(const impg_gpu_range_t *ranges, uint32_t n, const int32
                          FrontierRec *self_iv, uint32_t *in_frontier, hipStream_t s);
 void launch_compact_frontier(const FrontierRec *in, const uint32_t *flag, const uint32_t *pos, uint32_t n,
                              FrontierRec *out, hipStream_t s);
-void launch_ranges_to_frontier(const impg_gpu_range_t *ranges, uint32_t n, FrontierRec *out, hipStream_t s);
+// bad: a word set to 1 when a range has start >= end (device-resident ranges are not checked on the host)
+void launch_ranges_to_frontier(const impg_gpu_range_t *ranges, uint32_t n, FrontierRec *out, uint32_t *bad, hipStream_t s);
 
 void launch_frontier_to_stack(const FrontierRec *fr, uint32_t n, const uint32_t *pop_depth, bool use_depth,
                               unsigned long long *key, int32_t *st, int32_t *en, uint32_t *depth, hipStream_t s);

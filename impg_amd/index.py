@@ -364,7 +364,12 @@ class GpuImpg:
         check(lib().impg_gpu_set_option(self._h, key.encode(), int(value)))
 
     def counter(self, key):
-        """impg_gpu_get_counter: "walk_launches", "walk_fallbacks", "walk_members"."""
+        """impg_gpu_get_counter: "walk_launches", "walk_fallbacks", "walk_members"; "segment_sliced_levels",
+        "segment_retries", "segment_library_levels"; and the levels projected per kernel (counted on the host, per
+        launch): "project_lane_levels" (project_kernel), "project_staged_levels", "project_staged_rows_levels"
+        (project_staged_kernel, listed pairs / ordered rows), "project_entries_slots_levels",
+        "project_entries_qs_levels", "project_entries_rows_levels", "project_entries_ident_levels"
+        (project_entries_kernel by output / the identity filter), "project_tp_levels" (tracepoint index)."""
         v = C.c_int64(0)
         check(lib().impg_gpu_get_counter(self._h, key.encode(), C.byref(v)))
         return v.value

@@ -1378,13 +1378,9 @@ def _cigar_spans(cg):
     return t, q, bounds
 
 
-def test_prefix_line_edges(tmp_path):
-    """The plain projection never replays ops: it locates the first / last overlapping op on the tiles' 16-bit
-    prefix lines and verifies the candidates (DESIGN 5.2 item 13).  Ranges that start and end on, one before and
-    one after EVERY op boundary of multi-tile records -- insertions and deletions sitting exactly on the range ends,
-    candidates across tile borders (26 ops per tile) and across the thirds of a tile, both strands, both entry
-    directions -- must project exactly as the oracle's op-by-op walk does; so must a record whose tiles overflow
-    16 bits (literal walk) and one whose CIGAR disagrees with its PAF coordinates."""
+def prefix_line_edges_fixture():
+    """(PAF text, ranges(g)) of test_prefix_line_edges: multi-tile records, ranges on and around every op boundary
+    (also run through every projection kernel by tests/test_gpu_projection_paths.py)."""
     unit = "7=2I5=3D1X4=1I6=2D"                      # 9 ops; insertions and deletions between matches
     cg_a = unit * 9                                   # 81 ops: 4 tiles, borders inside the unit
     cg_b = ("11=1X" * 13 + "5I" + "9=4D" * 14)        # 55 ops: a tile border between two matches, an insertion at op 26
@@ -1403,33 +1399,46 @@ def test_prefix_line_edges(tmp_path):
     rec("Q5", 2000, qw, "+", "T", 3000, tw, cg_w)
     rec("Q6", 2000, qw, "-", "T", 3500, tw, cg_w)
     rec("Q7", 50, qa, "+", "T", 900, ta + 40, cg_a)  # CIGAR shorter than the PAF target span: no end shortcut, odd tails
-    g, c = both(tmp_path, "\n".join(lines) + "\n")
-    T = g.seq_id("T")
-    pts = sorted({1000 + b + d for b in ba for d in (-1, 0, 1)} | {1200 + b + d for b in bb for d in (-1, 0, 1)} |
-                 {1003 + b for b in ba} | {1100 + b for b in bb})
-    pts = [p for p in pts if p > 0]
-    ranges = []
-    for i, p in enumerate(pts):
-        ranges.append((T, p, p + 1 + (i * 7) % 23))           # starts on / around a boundary
-        ranges.append((T, max(0, p - 1 - (i * 5) % 31), p))   # ends on / around a boundary
-    ranges += [(T, pts[i], pts[j]) for i in range(0, len(pts) - 40, 17) for j in (i + 9, i + 40)]
-    ranges += [(T, 2990, 3010), (T, 32990, 33020), (T, 3000 + 30000, 3000 + 30001), (T, 52000, 54000), (T, 3000, 3000 + tw), (T, 78000, 78100)]
-    # from the query side the reversed entries walk the same records (the reverse-strand ones back to front)
-    for q, qs, qspan in [("Q1", 500, qa), ("Q2", 700, qa), ("Q3", 100, qb), ("Q4", 900, qb)]:
-        qid = g.seq_id(q)
-        for k in range(0, qspan, 3):
-            ranges.append((qid, qs + k, qs + k + 1 + k % 19))
+
+    def make_ranges(g):
+        T = g.seq_id("T")
+        pts = sorted({1000 + b + d for b in ba for d in (-1, 0, 1)} | {1200 + b + d for b in bb for d in (-1, 0, 1)} |
+                     {1003 + b for b in ba} | {1100 + b for b in bb})
+        pts = [p for p in pts if p > 0]
+        ranges = []
+        for i, p in enumerate(pts):
+            ranges.append((T, p, p + 1 + (i * 7) % 23))           # starts on / around a boundary
+            ranges.append((T, max(0, p - 1 - (i * 5) % 31), p))   # ends on / around a boundary
+        ranges += [(T, pts[i], pts[j]) for i in range(0, len(pts) - 40, 17) for j in (i + 9, i + 40)]
+        ranges += [(T, 2990, 3010), (T, 32990, 33020), (T, 3000 + 30000, 3000 + 30001), (T, 52000, 54000), (T, 3000, 3000 + tw), (T, 78000, 78100)]
+        # from the query side the reversed entries walk the same records (the reverse-strand ones back to front)
+        for q, qs, qspan in [("Q1", 500, qa), ("Q2", 700, qa), ("Q3", 100, qb), ("Q4", 900, qb)]:
+            qid = g.seq_id(q)
+            for k in range(0, qspan, 3):
+                ranges.append((qid, qs + k, qs + k + 1 + k % 19))
+        return ranges
+    return "\n".join(lines) + "\n", make_ranges
+
+
+def test_prefix_line_edges(tmp_path):
+    """The plain projection never replays ops: it locates the first / last overlapping op on the tiles' 16-bit
+    prefix lines and verifies the candidates (DESIGN 5.2 item 13).  Ranges that start and end on, one before and
+    one after EVERY op boundary of multi-tile records -- insertions and deletions sitting exactly on the range ends,
+    candidates across tile borders (26 ops per tile) and across the thirds of a tile, both strands, both entry
+    directions -- must project exactly as the oracle's op-by-op walk does; so must a record whose tiles overflow
+    16 bits (literal walk) and one whose CIGAR disagrees with its PAF coordinates."""
+    text, make_ranges = prefix_line_edges_fixture()
+    g, c = both(tmp_path, text)
+    ranges = make_ranges(g)
     for kw in [dict(), dict(transitive=True, max_depth=2, min_transitive_len=1, min_distance_between_ranges=0)]:
         for lo in range(0, len(ranges), 400):
             assert_same(g, c, ranges[lo:lo + 400], **kw)
 
 
-def test_identity_filter_wide_last_tile(tmp_path):
-    """min_gap_compressed_identity when an end of the slice is answered by the no-read shortcut (the range covers the
-    alignment's start / end) and the record's LAST storage tile is `wide` (its sums pass 2^16, e.g. a 70000= op): the
-    identity line's 16-bit fields do not hold that tile's sums, so the pair must take the literal walk (round-3 advisory:
-    the flag was only tested inside the search, which a shortcut end skips).  Both strands, both entry directions,
-    ranges covering the end, the start, the whole alignment and neither."""
+def identity_wide_fixture():
+    """(PAF text, ranges(g)) of test_identity_filter_wide_last_tile: records whose last storage tile is wide, ranges
+    whose slice ends take the no-read shortcut (also run through every projection kernel by
+    tests/test_gpu_projection_paths.py)."""
     cgs = ["70000=10I70000=", "65536=5X", "3=1X" * 30 + "70000=10I70000=", "70000=10I70000=" + "3=1X" * 30, "40000=30000X5D"]
     L = 400000
     lines = []
@@ -1441,18 +1450,34 @@ def test_identity_filter_wide_last_tile(tmp_path):
             qs = 2000 + 11 * i
             lines.append("Q%d%s\t%d\t%d\t%d\t%s\tT\t%d\t%d\t%d\t1\t1\t60\tcg:Z:%s" % (i, "f" if strand == "+" else "r", L, qs, qs + q, strand, L, ts, ts + t, cg))
             spans.append(("Q%d%s" % (i, "f" if strand == "+" else "r"), qs, q, ts, t))
-    g, c = both(tmp_path, "\n".join(lines) + "\n")
-    T = g.seq_id("T")
-    ranges = []
-    for name, qs, q, ts, t in spans:
-        qid = g.seq_id(name)
-        for (a, b) in [(0, t + 5000), (ts, ts + t), (ts + t - 100, ts + t + 50), (ts + t - 70001, ts + t), (ts - 10, ts + 50), (ts + 10, ts + t - 10),
-                       (ts + 69990, ts + 70020), (ts + 100, ts + t)]:
-            ranges.append((T, max(0, a), min(L, b)))
-        for (a, b) in [(0, qs + q + 100), (qs, qs + q), (qs + q - 100, qs + q + 10), (qs - 5, qs + 70005), (qs + 50, qs + q - 50), (qs + 69995, qs + q)]:
-            ranges.append((qid, max(0, a), min(L, b)))
-    ranges = [r for r in ranges if r[1] < r[2]]
-    for thr in (0.5, 0.9999, 0.99995, 0.999929, 0.57, 1.0):
+
+    def make_ranges(g):
+        T = g.seq_id("T")
+        ranges = []
+        for name, qs, q, ts, t in spans:
+            qid = g.seq_id(name)
+            for (a, b) in [(0, t + 5000), (ts, ts + t), (ts + t - 100, ts + t + 50), (ts + t - 70001, ts + t), (ts - 10, ts + 50), (ts + 10, ts + t - 10),
+                           (ts + 69990, ts + 70020), (ts + 100, ts + t)]:
+                ranges.append((T, max(0, a), min(L, b)))
+            for (a, b) in [(0, qs + q + 100), (qs, qs + q), (qs + q - 100, qs + q + 10), (qs - 5, qs + 70005), (qs + 50, qs + q - 50), (qs + 69995, qs + q)]:
+                ranges.append((qid, max(0, a), min(L, b)))
+        return [r for r in ranges if r[1] < r[2]]
+    return "\n".join(lines) + "\n", make_ranges
+
+
+IDENTITY_WIDE_THRESHOLDS = (0.5, 0.9999, 0.99995, 0.999929, 0.57, 1.0)
+
+
+def test_identity_filter_wide_last_tile(tmp_path):
+    """min_gap_compressed_identity when an end of the slice is answered by the no-read shortcut (the range covers the
+    alignment's start / end) and the record's LAST storage tile is `wide` (its sums pass 2^16, e.g. a 70000= op): the
+    identity line's 16-bit fields do not hold that tile's sums, so the pair must take the literal walk (round-3 advisory:
+    the flag was only tested inside the search, which a shortcut end skips).  Both strands, both entry directions,
+    ranges covering the end, the start, the whole alignment and neither."""
+    text, make_ranges = identity_wide_fixture()
+    g, c = both(tmp_path, text)
+    ranges = make_ranges(g)
+    for thr in IDENTITY_WIDE_THRESHOLDS:
         assert_same(g, c, ranges, min_identity=thr)
     assert_same(g, c, ranges[:40], transitive=True, max_depth=2, min_transitive_len=1, min_identity=0.9999)
 
