@@ -147,6 +147,8 @@ SYMBOLS = [
     ("impg_gpu_device_rows_part", C.c_int, [_P, C.c_size_t, C.POINTER(DevicePart)]),
     ("impg_gpu_device_rows_stats", None, [_P, C.POINTER(Stats)]),
     ("impg_gpu_device_rows_place_ms", C.c_float, [_P]),
+    ("impg_gpu_device_rows_part_device", C.c_int, [_P, C.c_size_t, C.POINTER(C.c_int)]),
+    ("impg_gpu_device_rows_batch_offset", C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("impg_gpu_device_rows_check", C.c_int, [_P, _P, _P]),
     ("impg_gpu_device_rows_free", None, [_P]),
     ("impg_gpu_bed_merge", C.c_long, [_P, C.c_size_t, C.c_int32, C.c_int]),

@@ -981,6 +981,11 @@ struct impg_gpu_device_rows {
   std::vector<std::unique_ptr<Chunk>> chunks;  // (a chunk owns device buffers: not movable)
   struct Part { size_t chunk; size_t level; };
   std::vector<Part> parts;
+  // a sharded index: every rank's share (one in a rank process), parts numbered rank by rank; offset / total of the
+  // caller's ranges in the collective batch
+  std::vector<std::unique_ptr<impg::ShardRows>> shard_rows;
+  std::vector<std::pair<size_t, size_t>> shard_parts;  // (rank share, part)
+  uint64_t batch_offset = 0, batch_total = 0;
   impg_gpu_index *ix = nullptr;
   impg_gpu_params_t params{};
   size_t n = 0;
@@ -997,8 +1002,27 @@ int impg_gpu_query_batch_device(impg_gpu_index_t *ix, const impg_gpu_range_t *ra
   if (n >= (1ull << 31)) throw Error{IMPG_E_UNSUPPORTED, "more than 2^31 ranges in one batch"};
   if (!ranges_on_device) check_ranges(ranges, n);
   Engine::check_params(*params);
-  if (ix->shard || ix->cluster)
-    throw Error{IMPG_E_UNSUPPORTED, "rows left on the device belong to one GPU: a sharded index returns rows through impg_gpu_query_batch"};
+  if (ix->shard || ix->cluster) {
+    // The final level stays with the ranks that project it (sharded.cpp rank_rows); the ranges are numbered in the collective
+    // batch.  Ordered layouts need that level at home in emission order: not offered here.
+    if (layout != IMPG_ROWS_ATTRIBUTED)
+      throw Error{IMPG_E_UNSUPPORTED, "a sharded index leaves its rows on the device in the attributed layout only (IMPG_ROWS_ATTRIBUTED)"};
+    if (params->store_cigar || params->multi_impg || (params->transitive && params->dfs))
+      throw Error{IMPG_E_UNSUPPORTED, "impg_gpu_query_batch_device on a sharded index takes Impg::query and query_transitive_bfs without store_cigar"};
+    if (ix->cluster && ranges_on_device) throw Error{IMPG_E_INVALID, "device-resident ranges belong to one GPU: a multi-GPU handle takes host ranges"};
+    auto h = std::make_unique<impg_gpu_device_rows>();
+    h->ix = ix;
+    h->params = *params;
+    h->n = n;
+    h->layout = layout;
+    sharded_query_device(*ix, ranges, ranges_on_device != 0, n, *params, h->shard_rows, &h->stats);
+    for (size_t r = 0; r < h->shard_rows.size(); r++)
+      for (size_t k = 0; k < h->shard_rows[r]->parts.size(); k++) h->shard_parts.push_back({r, k});
+    h->batch_offset = ix->cluster ? 0 : h->shard_rows[0]->offset;
+    h->batch_total = h->shard_rows[0]->total;
+    *out = h.release();
+    return IMPG_OK;
+  }
   if (params->store_cigar || params->multi_impg || (params->transitive && params->dfs))
     throw Error{IMPG_E_UNSUPPORTED, "impg_gpu_query_batch_device takes Impg::query and query_transitive_bfs without store_cigar"};
   IMPG_HIP(hipSetDevice(ix->device));
@@ -1070,27 +1094,39 @@ int impg_gpu_query_batch_device(impg_gpu_index_t *ix, const impg_gpu_range_t *ra
     else for (size_t l = 0; l < h->chunks[c]->levels.size(); l++) h->parts.push_back({c, l});
   }
   h->stats = tot;
+  h->batch_total = n;
   *out = h.release();
   return IMPG_OK;
   IMPG_CATCH
 }
 
-size_t impg_gpu_device_rows_num_parts(const impg_gpu_device_rows_t *h) { return h ? h->parts.size() : 0; }
+static size_t num_parts(const impg_gpu_device_rows_t *h) { return h->shard_rows.empty() ? h->parts.size() : h->shard_parts.size(); }
+size_t impg_gpu_device_rows_num_parts(const impg_gpu_device_rows_t *h) { return h ? num_parts(h) : 0; }
 int impg_gpu_device_rows_part(const impg_gpu_device_rows_t *h, size_t k, impg_gpu_device_part_t *out) {
   IMPG_TRY
-  if (!h || !out || k >= h->parts.size()) throw Error{IMPG_E_INVALID, "no such part"};
-  const auto &c = *h->chunks[h->parts[k].chunk];
+  if (!h || !out || k >= num_parts(h)) throw Error{IMPG_E_INVALID, "no such part"};
   memset(out, 0, sizeof *out);
-  out->first_range = c.first;
-  out->n_ranges = c.n;
-  if (h->layout != IMPG_ROWS_ATTRIBUTED) {
-    out->n_slots = c.n_rows;
-    out->rows = c.rows.as<impg_gpu_interval_t>();
-    out->offsets = c.offsets.as<uint32_t>();
-    return IMPG_OK;
+  const LevelBufs *Lp = nullptr;
+  if (!h->shard_rows.empty()) {
+    const ShardRowsPart &pt = h->shard_rows[h->shard_parts[k].first]->parts[h->shard_parts[k].second];
+    out->first_range = pt.first_range;
+    out->n_ranges = pt.n_ranges;
+    out->level = pt.level;
+    Lp = pt.L.get();
+  } else {
+    const auto &c = *h->chunks[h->parts[k].chunk];
+    out->first_range = c.first;
+    out->n_ranges = c.n;
+    if (h->layout != IMPG_ROWS_ATTRIBUTED) {
+      out->n_slots = c.n_rows;
+      out->rows = c.rows.as<impg_gpu_interval_t>();
+      out->offsets = c.offsets.as<uint32_t>();
+      return IMPG_OK;
+    }
+    Lp = c.levels[h->parts[k].level].get();
+    out->level = (uint32_t)h->parts[k].level;
   }
-  const LevelBufs &L = *c.levels[h->parts[k].level];
-  out->level = (uint32_t)h->parts[k].level;
+  const LevelBufs &L = *Lp;
   out->n_slots = L.n_pairs;
   out->n_frontier = L.n_frontier;
   out->query_id = L.qid.as<uint32_t>();
@@ -1099,6 +1135,21 @@ int impg_gpu_device_rows_part(const impg_gpu_device_rows_t *h, size_t k, impg_gp
   out->source = L.qs_interleaved ? L.qid.as<uint32_t>() + 1 : L.pair_range.as<uint32_t>();
   out->slot_stride = L.qs_interleaved ? 2u : 1u;
   out->frontier = L.frontier.as<impg_gpu_frontier_t>();
+  return IMPG_OK;
+  IMPG_CATCH
+}
+int impg_gpu_device_rows_part_device(const impg_gpu_device_rows_t *h, size_t k, int *device_out) {
+  IMPG_TRY
+  if (!h || !device_out || k >= num_parts(h)) throw Error{IMPG_E_INVALID, "no such part"};
+  *device_out = h->shard_rows.empty() ? h->ix->device : h->shard_rows[h->shard_parts[k].first]->device;
+  return IMPG_OK;
+  IMPG_CATCH
+}
+int impg_gpu_device_rows_batch_offset(const impg_gpu_device_rows_t *h, uint64_t *offset_out, uint64_t *total_out) {
+  IMPG_TRY
+  if (!h) throw Error{IMPG_E_INVALID, "null argument"};
+  if (offset_out) *offset_out = h->batch_offset;
+  if (total_out) *total_out = h->batch_total;
   return IMPG_OK;
   IMPG_CATCH
 }
@@ -1111,6 +1162,10 @@ int impg_gpu_device_rows_check(impg_gpu_device_rows_t *h, uint64_t *per_range_co
   IMPG_TRY
   if (!h) throw Error{IMPG_E_INVALID, "null argument"};
   if (h->layout != IMPG_ROWS_ATTRIBUTED) throw Error{IMPG_E_UNSUPPORTED, "impg_gpu_device_rows_check reads the attributed layout (ordered rows: compare them with impg_gpu_query_batch's)"};
+  if (!h->shard_rows.empty()) {  // (collective in rank processes: partial sums go to their homes)
+    sharded_rows_check(*h->ix, h->shard_rows, h->params, per_range_count, per_range_checksum);
+    return IMPG_OK;
+  }
   Engine &E = **h->lease;
   IMPG_HIP(hipSetDevice(h->ix->device));
   const size_t n = h->n;

@@ -984,10 +984,13 @@ void Engine::run(const impg_gpu_index &ix, const impg_gpu_range_t *d_ranges, uin
     std::unique_ptr<LevelBufs> own;
     LevelBufs *L = &level_scratch;
     if (keep) {
-      own = std::make_unique<LevelBufs>(&level_pool);
+      own = std::make_unique<LevelBufs>(remote_rows ? remote_rows->pool : &level_pool);
       L = own.get();
     }
     const bool want_stats = d_count || d_cksum;
+    // (a sharded rows batch: the final level stays with the owners -- no hits come home from its hop, as in a counting run)
+    const bool owners_keep = keep && remote && remote_rows && last;
+    if (owners_keep) remote_rows->level = depth;
     // (kept levels too when their reader takes the slots in any order and finds a slot's frontier record through
     // pair_range -- the rows left in HBM, impg_gpu_query_batch_device's attributed layout: keep_any_order)
     fuse_final = fuse_allowed && last && (!keep || keep_any_order || ordered_rows) && !remote;
@@ -1000,8 +1003,8 @@ void Engine::run(const impg_gpu_index &ix, const impg_gpu_range_t *d_ranges, uin
     // copy of the frontier in that order; the per-range statistics and the subset filter index the frontier itself)
     fuse_range_places = keep != nullptr && !want_stats && !subset_on;
     if (ordered_rows) fuse_need_ranges = fuse_range_places = false;  // (a fused level of ordered rows writes rows, nothing else)
-    const HopResult hr = hop(v, cur->as<FrontierRec>(), alive ? n_fr : 0, transitive, *L, st, keep || want_stats || !last,
-                             keep || d_cksum, alive);
+    const HopResult hr = hop(v, cur->as<FrontierRec>(), alive ? n_fr : 0, transitive, *L, st,
+                             !owners_keep && (keep || want_stats || !last), !owners_keep && (keep || d_cksum), alive);
     fuse_final = false;
     if (hr.all_dead) break;
     uint32_t n_next = 0;
@@ -1015,7 +1018,7 @@ void Engine::run(const impg_gpu_index &ix, const impg_gpu_range_t *d_ranges, uin
       }
       if (st) st->levels += 1;
       if (!last) n_next = update(v, cur->as<FrontierRec>(), *L, n, p, *nxt);
-      if (keep) {
+      if (keep && !owners_keep) {
         // the level keeps its own copy of the frontier (qidx / target per pair)
         if (L->placed) {  // (its rows are written: nobody reads its slots)
         } else if (last_range_places && !remote) {

@@ -164,6 +164,18 @@ struct Engine {
   void post_expand(const FrontierRec *fr, uint32_t n_fr, LevelBufs &L, const uint32_t *d_pair_off, uint32_t *tie_idx,
                    const uint32_t *tie_rank, SliceArrays sl);
   Expander *remote = nullptr;  // set: frontiers are expanded on the owning shards
+  // The rows form of a sharded index (sharded.cpp rank_rows): the final level of the walk stays with the ranks that
+  // project it.  Set by the caller around run(), with `keep`: the kept levels then take their blocks from `pool` (they
+  // belong to the caller's handle, not to this engine), the last hop routes its records tagged range_base + their range
+  // index -- their range in the collective batch -- and nothing comes home from it; what this rank projects in that hop,
+  // as an owner, for whichever home, lands in `parts` (one level per slice, frontier[].qidx = the collective range).
+  struct RemoteRows {
+    std::vector<std::unique_ptr<LevelBufs>> *parts;
+    BufPool *pool;  // where every kept level's blocks come from (the rank index's rows_pool)
+    uint64_t range_base;
+    uint32_t level;  // depth of the final level (set by run())
+  };
+  RemoteRows *remote_rows = nullptr;
   HopResult hop(const DeviceIndexView &v, const FrontierRec *fr, uint32_t n_fr, bool transitive, LevelBufs &L,
                 impg_gpu_stats_t *st, bool need_hits, bool need_rows, bool alive);
   uint32_t update(const DeviceIndexView &v, const FrontierRec *fr, LevelBufs &L, uint32_t n_queries,
@@ -313,6 +325,31 @@ int sharded_query_batch(impg_gpu_index &ix, const impg_gpu_range_t *ranges, size
 int sharded_query_stats(impg_gpu_index &ix, const impg_gpu_range_t *ranges, bool on_device, size_t n,
                         const impg_gpu_params_t &p, uint64_t *per_range_count, uint64_t *per_range_checksum,
                         impg_gpu_stats_t *stats);
+// impg_gpu_query_batch_device on a sharded index (IMPG_ROWS_ATTRIBUTED).  Ranges are numbered in the COLLECTIVE batch:
+// the multi handle's batch, or the ranks' batches concatenated in rank order.  A level whose hits came home stays with
+// the home as parts of the single-GPU form (first_range = the home's offset + the chunk's first range); the final level
+// stays with the rank that projected it, one part per owner slice, its frontier[].qidx the collective range
+// (first_range 0, n_ranges = the collective batch).  Every array belongs to the handle: no engine, pool or lane buffer.
+struct ShardRowsPart {
+  uint64_t first_range, n_ranges;
+  uint32_t level;
+  std::unique_ptr<LevelBufs> L;
+};
+struct ShardRows {  // one rank's share of the handle
+  impg_gpu_index *ix = nullptr;  // the rank's index
+  int device = 0;
+  uint64_t offset = 0, n = 0, total = 0;  // its own ranges: [offset, offset + n) of the collective batch of `total`
+  std::vector<ShardRowsPart> parts;
+  ~ShardRows() {
+    if (!parts.empty()) (void)hipSetDevice(device);  // (the arrays are freed on the device that holds them)
+    parts.clear();
+  }
+};
+void sharded_query_device(impg_gpu_index &ix, const impg_gpu_range_t *ranges, bool on_device, size_t n, const impg_gpu_params_t &p,
+                          std::vector<std::unique_ptr<ShardRows>> &out, impg_gpu_stats_t *stats);
+// per-range counts / checksums of the caller's own ranges, recomputed from the rows (collective in rank processes)
+void sharded_rows_check(impg_gpu_index &ix, std::vector<std::unique_ptr<ShardRows>> &rows, const impg_gpu_params_t &p, uint64_t *count,
+                        uint64_t *cksum);
 // targets bin-packed onto shards by entry count: heaviest first onto the least loaded shard
 void shard_assign(const uint64_t *entries_per_target, uint32_t n_seq, uint32_t n_shards, uint32_t *owner);
 void count_entries_per_target(const impg_gpu_record_t *records, size_t n_records, uint32_t n_seq, bool bidirectional,

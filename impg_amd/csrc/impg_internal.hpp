@@ -184,8 +184,13 @@ struct BufPool {
   size_t held = 0;                                  // bytes on the free list
   static constexpr size_t MAX_HELD = 16ull << 30;   // beyond this the largest blocks are really freed
   size_t max_held = MAX_HELD;                       // (raised by callers whose blocks are larger: the rows a batch leaves in HBM)
+  // shared: blocks are taken and given back from several threads (impg_gpu_index::rows_pool); an engine's pools are used by
+  // the one thread that holds the engine and take no lock
+  bool shared = false;
+  std::mutex m;
   void *take(size_t bytes, size_t &cap_out);
   void give(void *p, size_t cap);
+  void raise_max_held(size_t bytes);
   ~BufPool();
 };
 
@@ -425,6 +430,9 @@ struct impg_gpu_index {
   uint32_t opt_debug_fail_owner = 0, opt_debug_fail_home = 0;
   uint64_t opt_lane_schedule = 0;  // IMPG_LANE_SCHEDULE / option "lane_schedule": see run_lanes (sharded.cpp); 0 = off
   uint64_t opt_device_rows_pool = 160ull << 30;  // option "device_rows_pool_bytes"
+  // a rank of a sharded index: the blocks of the rows impg_gpu_query_batch_device leaves in HBM (sharded.cpp rank_rows).  Not an
+  // engine's: a handle gives its blocks back from whichever thread frees it, while the engines serve other calls.
+  struct RowsPool : impg::BufPool { RowsPool() { shared = true; } } rows_pool;
   bool opt_free_slots = true;
   bool opt_regroup = true;
   bool opt_fuse_final = true;

@@ -55,6 +55,8 @@ void DevBuf::release() {
 }
 
 void *BufPool::take(size_t bytes, size_t &cap_out) {
+  std::unique_lock<std::mutex> lk(m, std::defer_lock);
+  if (shared) lk.lock();
   // best fit among the blocks that are not wastefully large for the request
   const size_t limit = std::max<size_t>(4 * bytes, 1u << 20);
   size_t best = free_.size();
@@ -83,6 +85,8 @@ void *BufPool::take(size_t bytes, size_t &cap_out) {
   return p;
 }
 void BufPool::give(void *p, size_t cap) {
+  std::unique_lock<std::mutex> lk(m, std::defer_lock);
+  if (shared) lk.lock();
   free_.push_back({p, cap});
   held += cap;
   while (held > max_held && !free_.empty()) {
@@ -93,6 +97,11 @@ void BufPool::give(void *p, size_t cap) {
     free_[big] = free_.back();
     free_.pop_back();
   }
+}
+void BufPool::raise_max_held(size_t bytes) {
+  std::unique_lock<std::mutex> lk(m, std::defer_lock);
+  if (shared) lk.lock();
+  max_held = std::max(max_held, bytes);
 }
 BufPool::~BufPool() {
   for (Blk &b : free_) (void)hipFree(b.p);

@@ -511,6 +511,28 @@ __global__ __launch_bounds__(256) void route_gather_kernel(const FrontierRec *__
   out[i] = f;
 }
 
+// The final hop of a sharded rows batch (sharded.cpp rank_rows): nothing comes home, so the record carries the range it
+// belongs to in the collective batch instead of its home index -- the owner keeps its hits tagged with it.
+__global__ __launch_bounds__(256) void route_gather_ranges_kernel(const FrontierRec *__restrict__ fr, const uint32_t *__restrict__ perm,
+                                                                  uint32_t n, uint32_t range_base, FrontierRec *__restrict__ out) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  FrontierRec f = fr[perm[i]];
+  f.qidx += range_base;
+  out[i] = f;
+}
+
+// impg_gpu_device_rows_check on a sharded handle: a home's per-range sums from the `blocks` partial arrays its peers sent
+// (block k = [k * n, (k + 1) * n)); wrapping adds, as the checksums themselves are
+__global__ __launch_bounds__(256) void partial_stats_add_kernel(const unsigned long long *__restrict__ in, uint32_t blocks, uint32_t n,
+                                                                unsigned long long *__restrict__ out) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  unsigned long long a = 0;
+  for (uint32_t k = 0; k < blocks; k++) a += in[(size_t)k * n + i];
+  out[i] = a;
+}
+
 // a level's frontier in its lookup order: what a kept fused level's pair_range indexes (Engine::run, fuse_range_places)
 __global__ __launch_bounds__(256) void frontier_gather_kernel(const FrontierRec *__restrict__ fr, const uint32_t *__restrict__ perm,
                                                               uint32_t n, FrontierRec *__restrict__ out) {
@@ -5387,6 +5409,12 @@ void launch_route_keys(const FrontierRec *fr, uint32_t n, uint32_t world, const 
 }
 void launch_route_gather(const FrontierRec *fr, const uint32_t *perm, uint32_t n, FrontierRec *out, hipStream_t s) {
   if (n) route_gather_kernel<<<cdiv(n, 256), 256, 0, s>>>(fr, perm, n, out);
+}
+void launch_route_gather_ranges(const FrontierRec *fr, const uint32_t *perm, uint32_t n, uint32_t range_base, FrontierRec *out, hipStream_t s) {
+  if (n) route_gather_ranges_kernel<<<cdiv(n, 256), 256, 0, s>>>(fr, perm, n, range_base, out);
+}
+void launch_partial_stats_add(const unsigned long long *in, uint32_t blocks, uint32_t n, unsigned long long *out, hipStream_t s) {
+  if (n) partial_stats_add_kernel<<<cdiv(n, 256), 256, 0, s>>>(in, blocks, n, out);
 }
 void launch_frontier_gather(const FrontierRec *fr, const uint32_t *perm, uint32_t n, FrontierRec *out, hipStream_t s) {
   if (n) frontier_gather_kernel<<<cdiv(n, 256), 256, 0, s>>>(fr, perm, n, out);

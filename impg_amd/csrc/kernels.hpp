@@ -132,6 +132,10 @@ void launch_hits_unpack(const void *in, uint32_t n, uint32_t words, uint32_t n_f
                         uint32_t *pair_range, HitArrays h, uint32_t *mslot, hipStream_t s, const uint32_t *slice_at = nullptr,
                         uint32_t *slice_pos = nullptr, uint32_t *slice_n = nullptr);
 void launch_route_gather(const FrontierRec *fr, const uint32_t *perm, uint32_t n, FrontierRec *out, hipStream_t s);
+// the final hop of a sharded rows batch: the record's qidx becomes range_base + qidx (its range in the collective batch)
+void launch_route_gather_ranges(const FrontierRec *fr, const uint32_t *perm, uint32_t n, uint32_t range_base, FrontierRec *out, hipStream_t s);
+// out[i] = sum of in[k * n + i] over k < blocks (wrapping)
+void launch_partial_stats_add(const unsigned long long *in, uint32_t blocks, uint32_t n, unsigned long long *out, hipStream_t s);
 void launch_frontier_gather(const FrontierRec *fr, const uint32_t *perm, uint32_t n, FrontierRec *out, hipStream_t s);  // out[i] = fr[perm[i]]
 // stable order of hit records (words u32 each, fidx first) by fidx when equal fidx are already contiguous
 void launch_reorder_runs(const uint32_t *hits, uint32_t n, uint32_t words, uint32_t n_front, uint32_t *run_start,

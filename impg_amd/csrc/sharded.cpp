@@ -130,7 +130,8 @@ struct ShardedExpander : Expander {
       if (mat[(size_t)r * K + comm->world] & ST_FAILED) { agreed = true; throw Error{IMPG_E_HIP, "a peer rank failed"}; }
   }
 
-  void route(Engine &E, const FrontierRec *fr, uint32_t n, uint64_t *counts) {
+  // range_base: the final hop of a rows batch (Engine::RemoteRows) -- records carry range_base + their range, not their home index
+  void route(Engine &E, const FrontierRec *fr, uint32_t n, uint64_t *counts, const uint64_t *range_base = nullptr) {
     const uint32_t W = (uint32_t)comm->world;
     hipStream_t s = E.stream;
     const size_t nb = std::max<size_t>((size_t)n * 4, 256);
@@ -145,10 +146,10 @@ struct ShardedExpander : Expander {
       E.sort_tmp.reserve(order_sort_scratch_bytes(n));
       launch_order_sort(E.lo_key.as<uint32_t>(), E.lo_key2.as<uint32_t>(), E.lo_perm.as<uint32_t>(), E.lo_idx.as<uint32_t>(), n, bits,
                         E.sort_tmp.p, s);  // stable: frontier order within an owner
-      launch_route_gather(fr, E.lo_perm.as<uint32_t>(), n, send_fr.as<FrontierRec>(), s);
-    } else {
-      launch_route_gather(fr, E.lo_idx.as<uint32_t>(), n, send_fr.as<FrontierRec>(), s);
     }
+    const uint32_t *perm = W > 1 ? E.lo_perm.as<uint32_t>() : E.lo_idx.as<uint32_t>();
+    if (range_base) launch_route_gather_ranges(fr, perm, n, (uint32_t)*range_base, send_fr.as<FrontierRec>(), s);
+    else launch_route_gather(fr, perm, n, send_fr.as<FrontierRec>(), s);
     pinned_words(W);
     unsigned long long *h = h_hist(W);
     IMPG_HIP(hipMemcpyAsync(h, route_hist.p, (size_t)W * 8, hipMemcpyDeviceToHost, s));
@@ -182,9 +183,21 @@ struct ShardedExpander : Expander {
     if (gpu_turn) gpu_turn->lock();
   }
 
+  // (the final level of a rows batch: a slice is expanded into a level of its own, blocks of the rank's rows pool, and kept
+  // with a copy of the records its source[] indexes -- places of the lookup order where the fused level wrote them: the
+  // records in that order, win_se)
+  void keep_slice(Engine &E, const FrontierRec *sub, std::unique_ptr<LevelBufs> K, Engine::RemoteRows &rr) {
+    const size_t bytes = (size_t)K->n_frontier * sizeof(FrontierRec);
+    K->frontier.reserve(std::max<size_t>(bytes, 256));
+    IMPG_HIP(hipMemcpyAsync(K->frontier.p, E.last_range_places ? E.win_se.p : (const void *)sub, bytes, hipMemcpyDeviceToDevice, E.stream));
+    rr.parts->push_back(std::move(K));
+  }
+
   HopResult hop(Engine &E, const DeviceIndexView &v, const FrontierRec *fr, uint32_t n_fr, bool transitive, LevelBufs &L,
                 impg_gpu_stats_t *st, bool need_hits, bool need_rows, bool alive) override {
     const int W = comm->world, me = comm->rank;
+    // the final hop of a rows batch (every rank is in it at the same point): owners keep what they project
+    Engine::RemoteRows *rr = need_hits ? nullptr : E.remote_rows;
     hipStream_t s = E.stream;
     const size_t K = (size_t)W + 1;
     std::vector<uint64_t> mine(K, 0), mat(K * W);
@@ -200,7 +213,7 @@ struct ShardedExpander : Expander {
     pf[PF_HOPS] += 1;
     // ---- home: the frontier bucketed by owner; sizes and liveness to everybody
     send_fr.reserve(std::max<size_t>((size_t)n_fr * sizeof(FrontierRec), 256));
-    if (n_fr) route(E, fr, n_fr, mine.data());
+    if (n_fr) route(E, fr, n_fr, mine.data(), rr ? &rr->range_base : nullptr);
     mine[W] = alive ? ST_ALIVE : 0;
     lap(PF_ROUTE);
     timed_comm([&] { comm->allgather_u64(mine.data(), K, mat.data()); });
@@ -274,9 +287,12 @@ struct ShardedExpander : Expander {
         // (a hop nobody at home reads hits of -- the final level of a counting run -- takes its pairs from the count
         // pass's windows: no emit pass, Engine::fuse_final)
         E.fuse_final = E.fuse_allowed && !need_hits;
-        E.fuse_need_ranges = false;
-        P = E.expand(v, sub, (uint32_t)m, transitive, owner_L, st, /*raw=*/true, owner_order ? &blocks : nullptr);
+        E.fuse_need_ranges = rr != nullptr;
+        if (rr) E.fuse_range_places = true;  // (a kept level names every slot's record by its place, as on one GPU)
+        std::unique_ptr<LevelBufs> kept = rr ? std::make_unique<LevelBufs>(rr->pool) : nullptr;
+        P = E.expand(v, sub, (uint32_t)m, transitive, kept ? *kept : owner_L, st, /*raw=*/true, owner_order ? &blocks : nullptr);
         E.fuse_final = false;
+        if (kept && P) keep_slice(E, sub, std::move(kept), *rr);
         any_by_place = any_by_place || E.last_by_place;
       } catch (const SplitBatch &) {
         E.fuse_final = false;
@@ -770,6 +786,145 @@ template <class F> void on_every_rank(Cluster &C, F f) {
   if (auto first = first_cause(errs)) std::rethrow_exception(first);
 }
 
+// the options of a multi handle its ranks run a rows batch with
+void forward_options(impg_gpu_index &ix, Cluster &C) {
+  for (auto &r : C.ranks) { r->opt_chunk_ranges = ix.opt_chunk_ranges; r->opt_pair_budget = ix.opt_pair_budget; r->opt_locality_min = ix.opt_locality_min;
+                            r->opt_debug_fail_owner = ix.opt_debug_fail_owner; r->opt_debug_fail_home = ix.opt_debug_fail_home; r->opt_lane_schedule = ix.opt_lane_schedule;
+                            r->opt_fuse_final = ix.opt_fuse_final; r->opt_device_rows_pool = ix.opt_device_rows_pool; }
+}
+// work adds up; the ranks ran side by side, so time is the slowest rank's
+void merge_rank_stats(const std::vector<impg_gpu_stats_t> &sts, impg_gpu_stats_t *stats) {
+  if (!stats) return;
+  memset(stats, 0, sizeof *stats);
+  for (auto &s : sts) {
+    stats->projected += s.projected; stats->pairs += s.pairs; stats->frontier_ranges += s.frontier_ranges;
+    stats->project_launches += s.project_launches;
+    stats->levels = std::max(stats->levels, s.levels);
+    stats->ms_total = std::max(stats->ms_total, s.ms_total); stats->ms_lookup = std::max(stats->ms_lookup, s.ms_lookup);
+    stats->ms_project = std::max(stats->ms_project, s.ms_project); stats->ms_update = std::max(stats->ms_update, s.ms_update);
+    stats->ms_exchange = std::max(stats->ms_exchange, s.ms_exchange);
+  }
+}
+
+// one rank's part of a collective rows batch (impg_gpu_query_batch_device): its ranges are [offset, offset + n) of the
+// collective batch of `total`.  Home levels and the final levels this rank projected as an owner, lane by lane.
+void rank_rows(impg_gpu_index &ix, const impg_gpu_range_t *ranges, bool on_device, size_t n, uint64_t offset, uint64_t total,
+               const impg_gpu_params_t &p, ShardRows &R, impg_gpu_stats_t *stats) {
+  IMPG_HIP(hipSetDevice(ix.device));
+  R.ix = &ix; R.device = ix.device; R.offset = offset; R.n = n; R.total = total;
+  DevBuf d_ranges;
+  const impg_gpu_range_t *dr = ranges;
+  if (!on_device) {
+    check_ranges(ranges, n);
+    d_ranges.reserve(std::max<size_t>(n * sizeof(impg_gpu_range_t), 256));
+    if (n) IMPG_HIP(hipMemcpy(d_ranges.p, ranges, n * sizeof(impg_gpu_range_t), hipMemcpyHostToDevice));
+    dr = d_ranges.as<impg_gpu_range_t>();
+  }
+  ShardCtx &S = *ix.shard;
+  // (the rows of a big batch are tens of GB: their blocks go back to the pool when the handle is freed and are the next
+  // call's -- a fresh hipMalloc of them costs more than the batch)
+  ix.rows_pool.raise_max_held((size_t)ix.opt_device_rows_pool);
+  const size_t n_lanes = S.comm->lanes.size();
+  std::vector<impg_gpu_stats_t> per_lane(n_lanes);
+  for (auto &x : per_lane) memset(&x, 0, sizeof x);
+  std::vector<std::vector<ShardRowsPart>> lane_parts(n_lanes);
+  for (auto &x : S.lanes) x->exchange_s = 0;
+  run_lanes(ix, n, [](Engine &) {}, [&](size_t l, Engine &E, size_t b, size_t e) {
+    std::vector<std::unique_ptr<LevelBufs>> levels, owned;
+    Engine::RemoteRows rr{&owned, &ix.rows_pool, offset + b, 0};
+    impg_gpu_stats_t st;
+    {
+      std::unique_lock<std::mutex> turn(S.gpu_turn, std::defer_lock);
+      if (n_lanes > 1) turn.lock();
+      E.keep_any_order = true;
+      E.remote_rows = &rr;
+      try {
+        E.run(ix, dr + b, (uint32_t)(e - b), p, &levels, nullptr, nullptr, &st, nullptr);
+      } catch (...) {
+        E.keep_any_order = false;
+        E.remote_rows = nullptr;
+        throw;
+      }
+      E.keep_any_order = false;
+      E.remote_rows = nullptr;
+    }
+    add_stats(per_lane[l], st);
+    for (size_t k = 0; k < levels.size(); k++)
+      if (levels[k]->n_pairs) lane_parts[l].push_back(ShardRowsPart{offset + b, e - b, (uint32_t)k, std::move(levels[k])});
+    for (auto &o : owned) lane_parts[l].push_back(ShardRowsPart{0, total, rr.level, std::move(o)});
+  });
+  impg_gpu_stats_t tot;
+  memset(&tot, 0, sizeof tot);
+  for (size_t l = 0; l < n_lanes; l++) {
+    per_lane[l].ms_exchange = (float)(S.lanes[l]->exchange_s * 1e3);
+    add_stats(tot, per_lane[l]);
+  }
+  if (stats) *stats = tot;
+  for (auto &lp : lane_parts)
+    for (auto &pt : lp) R.parts.push_back(std::move(pt));
+}
+
+// one rank's part of a collective check: per-range sums of every part this rank holds, over the collective batch; each
+// rank's stretch goes to that rank (lane 0's all-to-all-v), which adds what its peers sent
+void rank_rows_check(ShardRows &R, const impg_gpu_params_t &p, uint64_t *count, uint64_t *cksum) {
+  impg_gpu_index &ix = *R.ix;
+  Comm &cm = *ix.shard->comm->lanes[0];
+  const int W = cm.world;
+  const uint64_t N = R.total, n = R.n;
+  if (!N) return;  // (the same on every rank)
+  IMPG_HIP(hipSetDevice(ix.device));
+  EngineLease lease(ix);
+  Engine &E = *lease;
+  hipStream_t s = E.stream;
+  DevBuf part, recv, sum;  // part: [counts N | checksums N]; recv: W blocks of n per array; sum: [counts n | checksums n]
+  const size_t K = 3;
+  std::vector<uint64_t> mine(K, 0), all(K * W);
+  std::exception_ptr failed;
+  try {
+    part.reserve(std::max<size_t>(N * 16, 256));
+    recv.reserve(std::max<size_t>((size_t)W * n * 16, 256));
+    sum.reserve(std::max<size_t>(n * 16, 256));
+    IMPG_HIP(hipMemsetAsync(part.p, 0, N * 16, s));
+    unsigned long long *pc = part.as<unsigned long long>(), *pk = pc + N;
+    for (auto &pt : R.parts) {
+      LevelBufs &L = *pt.L;
+      if (!L.n_pairs) continue;
+      HitArrays ha{L.qid.as<uint32_t>(), L.coords.as<int4>()};
+      E.rstat.reserve(std::max<size_t>((size_t)L.n_frontier * 16, 256));
+      launch_hit_stats(L.frontier.as<FrontierRec>(), L.n_frontier, L.qs_interleaved ? L.qid.as<uint32_t>() + 1 : L.pair_range.as<uint32_t>(), L.n_pairs,
+                       ha, p.transitive ? p.min_output_length : -1, false, E.rstat.as<unsigned long long>(), pc + pt.first_range,
+                       pk + pt.first_range, s, L.qs_interleaved ? 2u : 1u);
+    }
+    IMPG_HIP(hipStreamSynchronize(s));
+  } catch (...) {
+    failed = std::current_exception();
+    mine[2] = ShardedExpander::ST_FAILED;
+  }
+  mine[0] = R.offset; mine[1] = n;
+  cm.allgather_u64(mine.data(), K, all.data());  // (a failure above is announced here: nobody waits in the exchange below)
+  if (failed) std::rethrow_exception(failed);
+  for (int r = 0; r < W; r++)
+    if (all[(size_t)r * K + 2] & ShardedExpander::ST_FAILED) throw Error{IMPG_E_HIP, "a peer rank failed"};
+  std::vector<uint64_t> so(W), sb(W), ro(W), rb(W);
+  for (int r = 0; r < W; r++) {
+    so[r] = all[(size_t)r * K] * 8; sb[r] = all[(size_t)r * K + 1] * 8;
+    ro[r] = (uint64_t)r * n * 8; rb[r] = n * 8;
+  }
+  unsigned long long *rv = recv.as<unsigned long long>(), *sm = sum.as<unsigned long long>();
+  try {
+    for (int a = 0; a < 2; a++) {  // counts, then checksums
+      cm.alltoallv(part.as<unsigned long long>() + (size_t)a * N, so.data(), sb.data(), rv, ro.data(), rb.data(), s);
+      launch_partial_stats_add(rv, (uint32_t)W, (uint32_t)n, sm + (size_t)a * n, s);
+      IMPG_HIP(hipStreamSynchronize(s));  // (recv is the next array's)
+    }
+  } catch (...) {
+    cm.abort();  // a failure inside the transport: release whoever waits for this rank
+    throw;
+  }
+  if (count && n) IMPG_HIP(hipMemcpy(count, sm, n * 8, hipMemcpyDeviceToHost));
+  if (cksum && n) IMPG_HIP(hipMemcpy(cksum, sm + n, n * 8, hipMemcpyDeviceToHost));
+}
+
 }  // namespace
 
 int sharded_query_stats(impg_gpu_index &ix, const impg_gpu_range_t *ranges, bool on_device, size_t n,
@@ -791,17 +946,7 @@ int sharded_query_stats(impg_gpu_index &ix, const impg_gpu_range_t *ranges, bool
     rank_stats(*C.ranks[r], ranges + cut[r], false, cut[r + 1] - cut[r], p, per_range_count ? per_range_count + cut[r] : nullptr,
                per_range_checksum ? per_range_checksum + cut[r] : nullptr, &sts[r]);
   });
-  if (stats) {
-    memset(stats, 0, sizeof *stats);
-    for (auto &s : sts) {  // work adds up; the ranks ran side by side, so time is the slowest rank's
-      stats->projected += s.projected; stats->pairs += s.pairs; stats->frontier_ranges += s.frontier_ranges;
-      stats->project_launches += s.project_launches;
-      stats->levels = std::max(stats->levels, s.levels);
-      stats->ms_total = std::max(stats->ms_total, s.ms_total); stats->ms_lookup = std::max(stats->ms_lookup, s.ms_lookup);
-      stats->ms_project = std::max(stats->ms_project, s.ms_project); stats->ms_update = std::max(stats->ms_update, s.ms_update);
-      stats->ms_exchange = std::max(stats->ms_exchange, s.ms_exchange);
-    }
-  }
+  merge_rank_stats(sts, stats);
   return IMPG_OK;
 }
 
@@ -829,6 +974,48 @@ void sharded_bed_batch(impg_gpu_index &ix, const impg_gpu_range_t *ranges, size_
   for (auto &pr : parts)
     for (auto &c : pr) if (!c.empty()) sink(c.data(), c.size());
   if (seconds3) for (int k = 0; k < 3; k++) { seconds3[k] = 0; for (auto &x : secs) seconds3[k] = std::max(seconds3[k], x[k]); }
+}
+
+void sharded_query_device(impg_gpu_index &ix, const impg_gpu_range_t *ranges, bool on_device, size_t n, const impg_gpu_params_t &p,
+                          std::vector<std::unique_ptr<ShardRows>> &out, impg_gpu_stats_t *stats) {
+  out.clear();
+  if (!ix.cluster) {  // a rank process: where its ranges start in the collective batch
+    ShardCtx &S = *ix.shard;
+    std::vector<uint64_t> all((size_t)S.comm->world);
+    const uint64_t mine = n;
+    S.comm->lanes[0]->allgather_u64(&mine, 1, all.data());
+    uint64_t offset = 0, total = 0;
+    for (int r = 0; r < S.comm->world; r++) {
+      if (r < S.comm->rank) offset += all[(size_t)r];
+      total += all[(size_t)r];
+    }
+    if (total >= 0xFFFFFFF0ull) throw Error{IMPG_E_UNSUPPORTED, "more than 2^32 ranges in one collective batch"};  // (every rank: same total)
+    out.push_back(std::make_unique<ShardRows>());
+    rank_rows(ix, ranges, on_device, n, offset, total, p, *out[0], stats);
+    return;
+  }
+  Cluster &C = *ix.cluster;
+  check_ranges(ranges, n);
+  const size_t W = C.ranks.size();
+  std::vector<size_t> cut;
+  split_blocks(n, W, cut);
+  std::vector<impg_gpu_stats_t> sts(W);
+  forward_options(ix, C);
+  for (size_t r = 0; r < W; r++) out.push_back(std::make_unique<ShardRows>());
+  on_every_rank(C, [&](size_t r) { rank_rows(*C.ranks[r], ranges + cut[r], false, cut[r + 1] - cut[r], cut[r], n, p, *out[r], &sts[r]); });
+  merge_rank_stats(sts, stats);
+}
+
+void sharded_rows_check(impg_gpu_index &ix, std::vector<std::unique_ptr<ShardRows>> &rows, const impg_gpu_params_t &p, uint64_t *count,
+                        uint64_t *cksum) {
+  if (!ix.cluster) {
+    rank_rows_check(*rows.at(0), p, count, cksum);
+    return;
+  }
+  on_every_rank(*ix.cluster, [&](size_t r) {
+    ShardRows &R = *rows.at(r);
+    rank_rows_check(R, p, count ? count + R.offset : nullptr, cksum ? cksum + R.offset : nullptr);
+  });
 }
 
 uint64_t shard_agree_max(impg_gpu_index &ix, uint64_t mine) {

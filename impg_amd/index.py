@@ -112,22 +112,36 @@ class QueryResults:
 _HIP = None
 
 
-def _hip_memcpy_d2h(dst, src, nbytes):
-    """hipMemcpy device -> host through the HIP runtime the library itself links (tests and probes read device rows back)."""
+def _hip_memcpy_d2h(dst, src, nbytes, device=None):
+    """hipMemcpy device -> host through the HIP runtime the library itself links (tests and probes read device rows back);
+    device: the HIP device that holds `src` (made current for the copy)."""
     global _HIP
     if _HIP is None:
         _HIP = C.CDLL("libamdhip64.so")
         _HIP.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
         _HIP.hipMemcpy.restype = C.c_int
+        _HIP.hipGetDevice.argtypes = [C.POINTER(C.c_int)]
+        _HIP.hipGetDevice.restype = C.c_int
+        _HIP.hipSetDevice.argtypes = [C.c_int]
+        _HIP.hipSetDevice.restype = C.c_int
     if nbytes:
-        rc = _HIP.hipMemcpy(dst, src, nbytes, 2)
+        prev = C.c_int(-1)
+        if device is not None and _HIP.hipGetDevice(C.byref(prev)) == 0 and prev.value != device:
+            _HIP.hipSetDevice(device)
+        try:
+            rc = _HIP.hipMemcpy(dst, src, nbytes, 2)
+        finally:
+            if device is not None and prev.value >= 0 and prev.value != device:
+                _HIP.hipSetDevice(prev.value)
         if rc != 0:
             raise ImpgGpuError(_lib.IMPG_E_HIP, "hipMemcpy (device to host) failed: %d" % rc)
 
 
 class DeviceRows:
-    """impg_gpu_device_rows_t: the rows of a batch left in HBM (impg_gpu_query_batch_device).  Holds one of the index's
-    engines until freed (free() or garbage collection)."""
+    """impg_gpu_device_rows_t: the rows of a batch left in HBM (impg_gpu_query_batch_device).  On one GPU it holds one of
+    the index's engines until freed (free() or garbage collection).  On a sharded index the parts lie on the ranks that
+    hold them (part_device) and range indices are those of the collective batch (batch_offset); in rank processes check()
+    is collective: every rank calls it."""
 
     def __init__(self, handle, owner, n):
         self._h = handle
@@ -147,24 +161,39 @@ class DeviceRows:
             out.append(d)
         return out
 
+    def part_device(self, k):
+        """The HIP device that holds part k's arrays."""
+        dev = C.c_int(-1)
+        check(lib().impg_gpu_device_rows_part_device(self._h, k, C.byref(dev)))
+        return dev.value
+
+    def batch_offset(self):
+        """(first range of this caller's ranges in the collective batch, size of that batch); (0, n) on one GPU and on a
+        multi-GPU handle."""
+        off, tot = C.c_uint64(0), C.c_uint64(0)
+        check(lib().impg_gpu_device_rows_batch_offset(self._h, C.byref(off), C.byref(tot)))
+        return int(off.value), int(tot.value)
+
     def part_to_host(self, k):
-        """One part copied back: (first_range, level, query_id[n], coords[n, 4], source[n], frontier[n_frontier])."""
+        """One part copied back from the device that holds it: (first_range, level, query_id[n], coords[n, 4], source[n],
+        frontier[n_frontier])."""
         d = self.parts()[k]
+        dev = self.part_device(k)
         n, nf, st = int(d.n_slots), int(d.n_frontier), int(d.slot_stride)
         co = np.empty((n, 4), dtype=np.int32)
         fr = np.empty(nf, dtype=_lib.FRONTIER_DTYPE)
         if st == 1:
             qid = np.empty(n, dtype=np.uint32)
             src = np.empty(n, dtype=np.uint32)
-            _hip_memcpy_d2h(qid.ctypes.data, d.query_id, n * 4)
-            _hip_memcpy_d2h(src.ctypes.data, d.source, n * 4)
+            _hip_memcpy_d2h(qid.ctypes.data, d.query_id, n * 4, dev)
+            _hip_memcpy_d2h(src.ctypes.data, d.source, n * 4, dev)
         else:  # query_id and source side by side (source = query_id + 1 word)
             assert d.source == d.query_id + 4 and st == 2
             both = np.empty((n, 2), dtype=np.uint32)
-            _hip_memcpy_d2h(both.ctypes.data, d.query_id, n * 8)
+            _hip_memcpy_d2h(both.ctypes.data, d.query_id, n * 8, dev)
             qid, src = np.ascontiguousarray(both[:, 0]), np.ascontiguousarray(both[:, 1])
-        _hip_memcpy_d2h(co.ctypes.data, d.coords, n * 16)
-        _hip_memcpy_d2h(fr.ctypes.data, d.frontier, nf * 16)
+        _hip_memcpy_d2h(co.ctypes.data, d.coords, n * 16, dev)
+        _hip_memcpy_d2h(fr.ctypes.data, d.frontier, nf * 16, dev)
         return int(d.first_range), int(d.level), qid, co, src, fr
 
     def ordered_to_host(self, k=0):
@@ -177,7 +206,8 @@ class DeviceRows:
         return int(d.first_range), rows, off
 
     def check(self, counts=True, checksums=True):
-        """impg_gpu_device_rows_check: per-range counts / checksums recomputed from the rows in HBM."""
+        """impg_gpu_device_rows_check: per-range counts / checksums recomputed from the rows in HBM, for this caller's
+        ranges (collective in rank processes)."""
         n = self._n
         cnt = np.zeros(n, dtype=np.uint64) if counts else None
         ck = np.zeros(n, dtype=np.uint64) if checksums else None

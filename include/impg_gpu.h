@@ -366,16 +366,28 @@ int impg_gpu_query_batch_stats_dev(impg_gpu_index_t *, const impg_gpu_range_t *d
  *                   (s = slot_stride: 1, or 2 where the part keeps a slot's query_id and source side by side as one
  *                   8-byte pair -- the fused final level, which writes them with one store)
  *     frontier[j]   {target_id, start, end, range_idx}: the row's target sequence (the target interval's metadata) and
- *                   the range of the batch it belongs to, as ranges[first_range + range_idx]
+ *                   the range of the batch it belongs to, as ranges[first_range + range_idx] (a sharded index: the
+ *                   collective batch, below)
  * i.e. SURVEY-style 24 bytes per slot (query_id, four coordinates, source) with range_idx and target_id one
  * look-up away.  Slot order within a part is unspecified (IMPG_ROWS_ATTRIBUTED): the final level is written entry by
  * entry, which is what makes it fast; a caller that needs the reference's emission order asks impg_gpu_query_batch /
  * _stream for it.  Transitive rows shorter than min_output_length (impg.rs:2482-2504) are NOT removed from the
  * slots: compare |q_last - q_first| as the reference does.  The self interval of a range is the range itself
  * (impg.rs:1864-1880, :2345-2363) and is not stored.
- * Takes Impg::query and query_transitive_bfs on a single-GPU CIGAR or tracepoint index (IMPG_E_UNSUPPORTED: DFS,
- * MultiImpg worklists, store_cigar, sharded handles).  ranges_on_device != 0: `ranges` is a device pointer.
- * The handle holds one of the index's engines (max 4) and its HBM until impg_gpu_device_rows_free. */
+ * Takes Impg::query and query_transitive_bfs on a CIGAR or tracepoint index (IMPG_E_UNSUPPORTED: DFS, MultiImpg
+ * worklists, store_cigar).  ranges_on_device != 0: `ranges` is a device pointer.
+ * One GPU: the handle holds one of the index's engines (max 4) and its HBM until impg_gpu_device_rows_free.
+ * A sharded index (IMPG_ROWS_ATTRIBUTED only; the ordered layouts are IMPG_E_UNSUPPORTED there): a multi-GPU handle takes
+ * host ranges (ranges_on_device: IMPG_E_INVALID); in rank processes the call is COLLECTIVE -- every rank passes its own
+ * ranges, host or device, as with impg_gpu_query_batch_stats.  Ranges are numbered in the COLLECTIVE BATCH: the multi
+ * handle's batch, or the ranks' batches concatenated in rank order (impg_gpu_device_rows_batch_offset).  Levels whose hits
+ * came home for the visited-set update stay with the home rank, first_range = the home's offset in the collective batch
+ * + the chunk's first range.  The final level is never shipped home: it stays in the HBM of the rank that projected
+ * it, as OWNER PARTS -- one per slice that owner expanded, first_range = 0, n_ranges = the collective batch size,
+ * frontier[].range_idx = the collective range, each with its own copy of the records its source[] indexes.  So
+ * first_range + frontier[source[s]].range_idx names a slot's range in every part.  A part's arrays are on the device
+ * impg_gpu_device_rows_part_device names.  A sharded handle holds no engine: every array belongs to the handle, freed
+ * by impg_gpu_device_rows_free. */
 typedef struct impg_gpu_device_rows impg_gpu_device_rows_t;
 #define IMPG_ROWS_ATTRIBUTED 0
 /* IMPG_ROWS_ORDERED: the trait's own rows instead -- one part per chunk: rows[n_slots] (impg_gpu_interval_t, no holes)
@@ -412,12 +424,19 @@ int impg_gpu_query_batch_device(impg_gpu_index_t *, const impg_gpu_range_t *rang
                                 const impg_gpu_params_t *params, int layout, impg_gpu_device_rows_t **out);
 size_t impg_gpu_device_rows_num_parts(const impg_gpu_device_rows_t *);
 int impg_gpu_device_rows_part(const impg_gpu_device_rows_t *, size_t k, impg_gpu_device_part_t *out);
+/* the HIP device that holds part k's arrays (a multi-GPU handle: the device of the rank that holds the part) */
+int impg_gpu_device_rows_part_device(const impg_gpu_device_rows_t *, size_t k, int *device_out);
+/* where the caller's ranges start in the collective batch, and its size: a rank process's offset = the sizes of the
+ * lower ranks' batches; one GPU and a multi-GPU handle: 0 and n */
+int impg_gpu_device_rows_batch_offset(const impg_gpu_device_rows_t *, uint64_t *offset_out, uint64_t *total_out);
 /* projections, candidate pairs and per-stage times of the call (impg_gpu_stats_t as above) */
 void impg_gpu_device_rows_stats(const impg_gpu_device_rows_t *, impg_gpu_stats_t *stats);
 /* ordered layout: HIP-event milliseconds the row placement took on top of stats->ms_total */
 float impg_gpu_device_rows_place_ms(const impg_gpu_device_rows_t *);
 /* Verification: the per-range counts and order-independent checksums of impg_gpu_query_batch_stats, recomputed FROM
- * THE ROWS the call left in HBM (every slot attributed through source[] / frontier[]); either may be NULL. */
+ * THE ROWS the call left in HBM (every slot attributed through source[] / frontier[]); either may be NULL.  Arrays of
+ * the caller's own ranges.  A sharded index: every rank's partial sums are added (wrapping, as the checksums are); in
+ * rank processes the call is COLLECTIVE -- the partial arrays go to their home ranks through the index's communicator. */
 int impg_gpu_device_rows_check(impg_gpu_device_rows_t *, uint64_t *per_range_count, uint64_t *per_range_checksum);
 void impg_gpu_device_rows_free(impg_gpu_device_rows_t *);
 
