@@ -69,6 +69,15 @@ class DevicePart(C.Structure):  # impg_gpu_device_part_t
 
 
 ROWS_ATTRIBUTED, ROWS_ORDERED, ROWS_ORDERED_SLOTS = 0, 1, 2
+REGIONS_MASKED, REGIONS_MISSING = 0, 1
+SELECT_LONGEST, SELECT_TOTAL, SELECT_SAMPLE, SELECT_HAPLOTYPE = 0, 1, 2, 3
+PARTITION_ROW_DTYPE = np.dtype([("seq_id", "<u4"), ("start", "<i4"), ("end", "<i4")])  # impg_gpu_partition_row_t
+
+
+class PartitionOpts(C.Structure):  # impg_gpu_partition_opts_t
+    _fields_ = [("window_size", C.c_int64), ("merge_distance", C.c_int32), ("min_missing_size", C.c_int32),
+                ("min_boundary_distance", C.c_int32), ("selection", C.c_int32), ("separator", C.c_char_p),
+                ("rehome_singletons", C.c_int32), ("state_on_host", C.c_int32)]
 FRONTIER_DTYPE = np.dtype([("target_id", "<u4"), ("start", "<i4"), ("end", "<i4"), ("range_idx", "<u4")])
 
 
@@ -175,6 +184,22 @@ SYMBOLS = [
     ("impg_gpu_shard_assign", C.c_int, [_P, C.c_uint32, C.c_uint32, _P]),
     ("impg_gpu_index_shard_info", C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), _P, C.c_size_t]),
     ("impg_gpu_index_hop_profile", C.c_int, [_P, _P, C.c_size_t, C.c_int, C.POINTER(C.c_size_t)]),
+    ("impg_gpu_regions_create", C.c_int, [_P, C.c_uint32, C.c_int, C.c_int, C.POINTER(_P)]),
+    ("impg_gpu_regions_apply", C.c_int, [_P, _P, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("impg_gpu_regions_last_rows", C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("impg_gpu_regions_get", C.c_int, [_P, C.c_int, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("impg_gpu_regions_select", C.c_int, [_P, C.c_int, C.c_char_p, _P, C.c_int64, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("impg_gpu_regions_free", None, [_P]),
+    ("impg_gpu_partition_starting_windows", C.c_int, [_P, C.c_size_t, _P, C.c_uint32, C.c_int64, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("impg_gpu_partition_rehome", C.c_int, [_P, _P, C.c_size_t]),
+    ("impg_gpu_partition_bed_text", C.c_int, [_P, _P, C.c_size_t, _P, C.c_uint32, C.POINTER(_P), C.POINTER(C.c_size_t)]),
+    ("impg_gpu_partition_create", C.c_int, [_P, C.POINTER(Params), C.POINTER(PartitionOpts), _P, C.c_size_t, C.POINTER(_P)]),
+    ("impg_gpu_partition_next_windows", C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("impg_gpu_partition_window", C.c_int, [_P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("impg_gpu_partition_run", C.c_int, [_P, C.c_char_p, C.c_int, C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]),
+    ("impg_gpu_partition_regions", _P, [_P]),
+    ("impg_gpu_partition_counter", C.c_int, [_P, C.c_char_p, C.POINTER(C.c_int64)]),
+    ("impg_gpu_partition_destroy", None, [_P]),
     ("impg_synth_paf", C.c_int, [C.c_uint64, C.c_size_t, C.c_uint32, C.c_int32, C.c_int32, C.c_uint32, _P, _P, C.c_size_t,
                                  C.POINTER(C.c_size_t)]),
     ("impg_synth_paf_text", C.c_int, [C.c_uint64, C.c_size_t, C.c_uint32, C.c_int32, C.c_int32, C.c_uint32, C.c_char_p]),

@@ -14,6 +14,7 @@
 #include <new>
 
 #include "engine.hpp"
+#include "partition.hpp"
 
 namespace impg {
 thread_local std::string g_error;
@@ -32,17 +33,7 @@ namespace impg {
 // One engine = one stream + one set of scratch buffers + the visited sets of the batch in flight.  Calls on one
 // handle from several host threads (the trait is Send + Sync: rayon workers share the index) each take their
 // own engine: up to max_engines run side by side, further callers wait for one to come back.
-EngineLease::EngineLease(impg_gpu_index &ix_) : ix(ix_) {
-  std::unique_lock<std::mutex> lk(ix.eng_m);
-  for (;;) {
-    if (!ix.eng_free.empty()) { e = ix.eng_free.back(); ix.eng_free.pop_back(); break; }
-    if ((int)ix.engines.size() < ix.max_engines) {
-      ix.engines.emplace_back(new Engine(ix.device));
-      e = ix.engines.back().get();
-      break;
-    }
-    ix.eng_cv.wait(lk);
-  }
+static void engine_options(impg_gpu_index &ix, Engine *e) {
   e->pair_budget = ix.opt_pair_budget;
   e->chunk_ranges = ix.opt_chunk_ranges;
   e->locality_min = ix.opt_locality_min;
@@ -58,7 +49,32 @@ EngineLease::EngineLease(impg_gpu_index &ix_) : ix(ix_) {
   e->seg_stats = ix.seg_stats;
   e->proj_stats = ix.proj_stats;
 }
-EngineLease::~EngineLease() {
+EngineLease::EngineLease(impg_gpu_index &ix_) : ix(ix_) {
+  std::unique_lock<std::mutex> lk(ix.eng_m);
+  for (;;) {
+    if (!ix.eng_free.empty()) { e = ix.eng_free.back(); ix.eng_free.pop_back(); break; }
+    if ((int)ix.engines.size() < ix.max_engines) {
+      ix.engines.emplace_back(new Engine(ix.device));
+      e = ix.engines.back().get();
+      break;
+    }
+    ix.eng_cv.wait(lk);
+  }
+  engine_options(ix, e);
+}
+// An engine for a handle that keeps it (a partition session): never waits -- null when every engine is out.
+Engine *try_lease_engine(impg_gpu_index &ix) {
+  std::unique_lock<std::mutex> lk(ix.eng_m);
+  Engine *e = nullptr;
+  if (!ix.eng_free.empty()) { e = ix.eng_free.back(); ix.eng_free.pop_back(); }
+  else if ((int)ix.engines.size() < ix.max_engines) {
+    ix.engines.emplace_back(new Engine(ix.device));
+    e = ix.engines.back().get();
+  } else return nullptr;
+  engine_options(ix, e);
+  return e;
+}
+void return_engine(impg_gpu_index &ix, Engine *e) {
   e->remote = nullptr;
   e->masked = false;
   e->subset_on = false;
@@ -69,6 +85,8 @@ EngineLease::~EngineLease() {
   ix.eng_free.push_back(e);
   ix.eng_cv.notify_one();
 }
+void return_engine(impg_gpu_index &ix, Engine *e);
+EngineLease::~EngineLease() { return_engine(ix, e); }
 }  // namespace impg
 
 #define IMPG_TRY try {
@@ -241,12 +259,69 @@ bool walk_query(impg_gpu_index &ix, Engine &E, const impg_gpu_range_t *h_ranges,
                                 hipMemcpyDeviceToHost, s));
   }
   IMPG_HIP(hipStreamSynchronize(s));
+  ix.result_rows_to_host += total;
   res.has_cigar = false;
   res.projected = E.last_projected;
   (void)h_ranges;
   return true;
 }
 }  // namespace
+
+namespace impg {
+// One transitive query's rows left in HBM for the partition update (partition_device.hip): the per-query walk writes them
+// into a generous region first and is run again at the exact size if the query outgrew it; where the walk does not apply
+// the batch engine's kept levels are placed in emission order (rows_device.hip), as assemble_results does ahead of its copy.
+uint32_t query_rows_device(impg_gpu_index &ix, Engine &E, const impg_gpu_range_t &range, const impg_gpu_params_t &p, DevBuf &rows,
+                           const impg_gpu_interval_t *&d_rows, bool &walked) {
+  hipStream_t s = E.stream;
+  walked = false;
+  E.ranges_dev.reserve(256);
+  IMPG_HIP(hipMemcpyAsync(E.ranges_dev.p, &range, sizeof range, hipMemcpyHostToDevice, s));
+  if (E.walk_applicable(ix, 1, p)) {
+    Engine::WalkRows W;
+    for (DevBuf *b : {&W.rows, &W.base, &W.cap, &W.n_rows}) b->pool = &E.level_pool;
+    W.base.reserve(256); W.cap.reserve(256); W.n_rows.reserve(256);
+    unsigned long long base = 0;
+    uint32_t cap = 1u << 17, cnt = 0;
+    auto pass = [&]() {
+      W.rows.reserve(std::max<size_t>((size_t)cap * sizeof(impg_gpu_interval_t), 256));
+      IMPG_HIP(hipMemcpyAsync(W.base.p, &base, 8, hipMemcpyHostToDevice, s));
+      IMPG_HIP(hipMemcpyAsync(W.cap.p, &cap, 4, hipMemcpyHostToDevice, s));
+      return E.run_walk(ix, E.ranges_dev.as<impg_gpu_range_t>(), 1, p, nullptr, nullptr, nullptr, &W, &cnt);
+    };
+    bool ok = pass();
+    if (ok && cnt > cap) {
+      const uint32_t want = cnt;
+      cap = cnt;
+      ok = pass();
+      if (ok && cnt != want) throw Error{IMPG_E_INVALID, "internal: the walk's second pass disagrees with its first"};
+    }
+    if (ok) {
+      rows.adopt(W.rows);
+      d_rows = rows.as<impg_gpu_interval_t>();
+      walked = true;
+      return cnt;
+    }
+  }
+  std::vector<std::unique_ptr<LevelBufs>> levels;
+  DevBuf self_dev;
+  self_dev.pool = &E.level_pool;
+  try {
+    E.run(ix, E.ranges_dev.as<impg_gpu_range_t>(), 1, p, &levels, nullptr, nullptr, nullptr, &self_dev);
+  } catch (const SplitBatch &) {
+    throw Error{IMPG_E_UNSUPPORTED, "a single range exceeds the pair budget"};
+  }
+  RowPlan pl;
+  plan_rows(E, 1, p, levels, self_dev, false, pl);
+  if (!rows.pool) rows.pool = &E.level_pool;
+  rows.reserve(std::max<size_t>((size_t)pl.n_rows * sizeof(impg_gpu_interval_t), 256));
+  scatter_rows(E, levels, pl, RowSinks{rows.as<impg_gpu_interval_t>(), nullptr, nullptr, nullptr, nullptr, nullptr});
+  IMPG_HIP(hipStreamSynchronize(s));
+  levels.clear();
+  d_rows = rows.as<impg_gpu_interval_t>();
+  return pl.n_rows;
+}
+}  // namespace impg
 
 namespace impg {
 std::vector<std::string> bed_range_names(const impg_gpu_index &ix, const impg_gpu_range_t *ranges, const char *const *range_names,
@@ -642,10 +717,12 @@ void apply_mask(Engine &E, const impg_gpu_index &ix, const impg_gpu_mask_t *m, c
     E.mask_init_len.reserve(std::max<size_t>((size_t)n_seq * 4, 256));
     E.mask_touch_len.reserve(std::max<size_t>((size_t)n_seq * 4, 256));
     IMPG_HIP(hipMemcpy(E.mask_off.p, off.data(), (size_t)(n_seq + 1) * 4, hipMemcpyHostToDevice));
-    if (total) IMPG_HIP(hipMemcpy(E.mask_ranges.p, m->ranges, total * 8, hipMemcpyHostToDevice));
+    ix.mask_table_uploads++;
+    if (total) { IMPG_HIP(hipMemcpy(E.mask_ranges.p, m->ranges, total * 8, hipMemcpyHostToDevice)); ix.mask_table_uploads++; }
     if (n_seq) {
       IMPG_HIP(hipMemcpy(E.mask_init_len.p, init_len.data(), (size_t)n_seq * 4, hipMemcpyHostToDevice));
       IMPG_HIP(hipMemcpy(E.mask_touch_len.p, touch_len.data(), (size_t)n_seq * 4, hipMemcpyHostToDevice));
+      ix.mask_table_uploads += 2;
     }
     E.masked = true;
     E.mask_has_empty = has_empty;
@@ -717,6 +794,7 @@ int impg_gpu_query_batch_filtered(impg_gpu_index_t *ix, const impg_gpu_range_t *
     const auto c1 = std::chrono::steady_clock::now();
     impg_gpu_results part;
     assemble_results(E, ranges + b, (uint32_t)(e - b), *params, levels, self_dev, part);
+    ix->result_rows_to_host += part.intervals.size();
     part.run_s = std::chrono::duration<double>(c1 - c0).count();
     part.assemble_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - c1).count();
     append_results(*res, part);
@@ -841,6 +919,7 @@ int impg_gpu_query_batch_stream(impg_gpu_index_t *ix, const impg_gpu_range_t *ra
             const auto c1 = std::chrono::steady_clock::now();
             part.offsets.clear(); part.intervals.clear(); part.cigar_off.clear(); part.cigar_ops.clear();
             assemble_results(E, ranges + pb, (uint32_t)(pe - pb), *params, levels, self_dev, part, max_rows, done);
+            ix->result_rows_to_host += part.intervals.size();
             part.run_s = std::chrono::duration<double>(c1 - c0).count();
             part.assemble_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - c1).count();
           } catch (const SplitBatch &) {

@@ -97,12 +97,147 @@ void usage() {
           "               [--transitive-dfs] [--multi-impg] [--min-transitive-len N] [--min-distance-between-ranges N]\n"
           "               [-l N] [--min-result-identity F] [--subset-sequence-list FILE] [--original-sequence-coordinates]\n"
           "               [--consider-strandness] [-o auto|bed|bedpe|paf] [--unidirectional] [--order coitrees|sorted]\n"
-          "               [--device N]\n");
+          "               [--device N]\n"
+          "impg-gpu partition (-a <paf>... | -i <file>) -w <bp> -d <bp> [--min-missing-size N] [--min-boundary-distance N]\n"
+          "               [--selection-mode longest|total|sample[,sep]|haplotype[,sep]] [--starting-sequences-file FILE]\n"
+          "               [--separate-files] [--no-rehome-singletons] [--output-folder DIR] [-o bed] [--host-state] [-m N]\n"
+          "               [--transitive-dfs] [--min-transitive-len N] [--min-distance-between-ranges N] [--min-identity F]\n"
+          "               [--unidirectional] [--order coitrees|sorted] [--device N]\n");
+}
+
+// `impg partition` (reference src/main.rs partition arguments; src/commands/partition.rs:158-712) with BED output:
+// partitions.bed (or partition{N}.bed with --separate-files) in --output-folder, as the reference writes them.
+int partition_main(int argc, char **argv) {
+  std::vector<std::string> pafs;
+  std::string index_file, ofmt = "bed", mode = "longest", starting, folder;
+  long long window = -1, merge_d = 0, v = 0;
+  bool have_d = false, no_merge = false, dfs = false, unidirectional = false, separate = false, rehome = true, host_state = false;
+  long max_depth = 2, min_tl = -1, mdbr = 10, min_missing = 3000, min_boundary = 3000;
+  double min_ident = NAN;
+  int device = 0, order = IMPG_ORDER_COITREES;
+  auto num = [](const std::string &flag, const char *x, long lo, long hi) -> long {
+    char *end = nullptr;
+    errno = 0;
+    const long r = strtol(x, &end, 10);
+    if (errno || end == x || *end != '\0' || r < lo || r > hi) die("invalid value '" + std::string(x) + "' for '" + flag + "'", 2);
+    return r;
+  };
+  for (int i = 2; i < argc; i++) {
+    std::string a = argv[i];
+    auto need = [&](const char *f) -> const char * {
+      if (i + 1 >= argc) die(std::string("a value is required for '") + f + "'", 2);
+      return argv[++i];
+    };
+    if (a == "-a" || a == "--alignment-files") {
+      pafs.push_back(need("-a"));
+      while (i + 1 < argc && argv[i + 1][0] != '-') pafs.push_back(argv[++i]);
+    } else if (a == "-i" || a == "--index") index_file = need("-i");
+    else if (a == "-w" || a == "--window-size") {
+      if (!parse_metric(need("-w"), &window) || window < 0 || window > 2147483647ll) die("invalid value for '-w'", 2);
+    } else if (a == "-d" || a == "--merge-distance") {
+      if (!parse_metric(need("-d"), &merge_d) || merge_d < 0 || merge_d > 2147483647ll) die("invalid value for '-d'", 2);
+      have_d = true;
+    } else if (a == "--no-merge") no_merge = true;
+    else if (a == "--min-missing-size") { if (!parse_metric(need(a.c_str()), &v) || v < 0 || v > 2147483647ll) die("invalid value for '" + a + "'", 2); min_missing = (long)v; }
+    else if (a == "--min-boundary-distance") { if (!parse_metric(need(a.c_str()), &v) || v < 0 || v > 2147483647ll) die("invalid value for '" + a + "'", 2); min_boundary = (long)v; }
+    else if (a == "--selection-mode") mode = need(a.c_str());
+    else if (a == "--starting-sequences-file") starting = need(a.c_str());
+    else if (a == "--separate-files") separate = true;
+    else if (a == "--no-rehome-singletons") rehome = false;
+    else if (a == "--output-folder") folder = need(a.c_str());
+    else if (a == "-o" || a == "--output-format") ofmt = need("-o");
+    else if (a == "--host-state") host_state = true;
+    else if (a == "--transitive-dfs") dfs = true;
+    else if (a == "-m" || a == "--max-depth") max_depth = num(a, need("-m"), 0, 65535);
+    else if (a == "--min-transitive-len") min_tl = num(a, need(a.c_str()), 0, 2147483647);
+    else if (a == "--min-distance-between-ranges") mdbr = num(a, need(a.c_str()), 0, 2147483647);
+    else if (a == "--min-identity") {
+      char *end = nullptr;
+      const char *x = need(a.c_str());
+      min_ident = strtod(x, &end);
+      if (end == x || *end || !(min_ident == min_ident)) die("invalid value '" + std::string(x) + "' for '" + a + "'", 2);
+    } else if (a == "--unidirectional") unidirectional = true;
+    else if (a == "--device") device = (int)num(a, need(a.c_str()), 0, 1023);
+    else if (a == "--order") {
+      std::string o = need("--order");
+      if (o != "sorted" && o != "coitrees") die("invalid value '" + o + "' for '--order'", 2);
+      order = o == "sorted" ? IMPG_ORDER_SORTED : IMPG_ORDER_COITREES;
+    } else if (a == "-t" || a == "--threads" || a == "-v" || a == "--verbose") need(a.c_str());  // accepted, unused
+    else if (a == "-h" || a == "--help") { usage(); return 0; }
+    else die("unexpected argument '" + a + "'", 2);
+  }
+  if (pafs.empty() && index_file.empty()) die("the following required arguments were not provided: --alignment-files", 2);
+  if (window < 0) die("the following required arguments were not provided: --window-size", 2);
+  if (window == 0) die("--window-size must be greater than 0");
+  if (!have_d && !no_merge) die("-d/--merge-distance is required. For `impg partition`, pass `-d <bp>`.");
+  if (no_merge) die("--no-merge is not built in impg-gpu partition", 2);
+  if (ofmt != "bed") die("output format '" + ofmt + "' is not built in impg-gpu partition (bed): it needs sequence files", 2);
+  int selection = IMPG_SELECT_LONGEST;
+  std::string kind = mode.substr(0, mode.find(',')), sep = mode.find(',') == std::string::npos ? "#" : mode.substr(mode.find(',') + 1);
+  if (kind == "longest" && mode == kind) selection = IMPG_SELECT_LONGEST;
+  else if (kind == "total" && mode == kind) selection = IMPG_SELECT_TOTAL;
+  else if (kind == "sample") selection = IMPG_SELECT_SAMPLE;
+  else if (kind == "haplotype") selection = IMPG_SELECT_HAPLOTYPE;
+  else die("Invalid selection mode. Must be 'longest', 'total', 'sample[,sep]', or 'haplotype[,sep]'.");
+  std::vector<const char *> pp;
+  for (auto &p : pafs) pp.push_back(p.c_str());
+  impg_gpu_index_t *ix = nullptr;
+  FILE *probe = index_file.empty() ? nullptr : fopen(index_file.c_str(), "rb");
+  if (probe) {
+    fclose(probe);
+    if (impg_gpu_index_load(index_file.c_str(), device, &ix) != IMPG_OK) die(impg_gpu_last_error());
+  } else {
+    if (pafs.empty()) die("No such file or directory: " + index_file);
+    if (impg_gpu_index_create_from_paf(pp.data(), (int)pp.size(), unidirectional ? 0 : 1, order, device, &ix) != IMPG_OK) die(impg_gpu_last_error());
+    if (!index_file.empty() && impg_gpu_index_save(ix, index_file.c_str()) != IMPG_OK) die(impg_gpu_last_error());
+  }
+  std::vector<uint32_t> start_ids;
+  if (!starting.empty()) {  // partition.rs:186-212: first tab field, trimmed; empty lines, '#' comments and unknown names skipped
+    std::ifstream in(starting);
+    if (!in) die("Could not open starting sequences file " + starting);
+    std::string line;
+    while (std::getline(in, line)) {
+      std::string name = line.substr(0, line.find('\t'));
+      const size_t b = name.find_first_not_of(" \t\r\n\v\f"), e = name.find_last_not_of(" \t\r\n\v\f");
+      name = b == std::string::npos ? "" : name.substr(b, e - b + 1);
+      if (name.empty() || name[0] == '#') continue;
+      const long long id = impg_gpu_seq_id(ix, name.c_str());
+      if (id >= 0) start_ids.push_back((uint32_t)id);
+    }
+  }
+  impg_gpu_params_t p;
+  memset(&p, 0, sizeof p);
+  p.transitive = 1;
+  p.dfs = dfs;
+  p.max_depth = (uint32_t)max_depth;
+  p.min_transitive_len = min_tl < 0 ? 101 : (int32_t)min_tl;
+  p.min_distance_between_ranges = (int32_t)mdbr;
+  p.min_output_length = -1;
+  p.min_identity = min_ident;
+  impg_gpu_partition_opts_t o;
+  memset(&o, 0, sizeof o);
+  o.window_size = window;
+  o.merge_distance = (int32_t)merge_d;
+  o.min_missing_size = (int32_t)min_missing;
+  o.min_boundary_distance = (int32_t)min_boundary;
+  o.selection = selection;
+  o.separator = sep.c_str();
+  o.rehome_singletons = rehome;
+  o.state_on_host = host_state;
+  impg_gpu_partition_t *ps = nullptr;
+  if (impg_gpu_partition_create(ix, &p, &o, start_ids.data(), start_ids.size(), &ps) != IMPG_OK) die(impg_gpu_last_error());
+  uint64_t n_parts = 0;
+  if (impg_gpu_partition_run(ps, folder.empty() ? nullptr : folder.c_str(), separate, nullptr, nullptr, &n_parts) != IMPG_OK) die(impg_gpu_last_error());
+  fprintf(stderr, "[impg-gpu] partitioned into %llu regions\n", (unsigned long long)n_parts);
+  impg_gpu_partition_destroy(ps);
+  impg_gpu_index_destroy(ix);
+  return 0;
 }
 
 }  // namespace
 
 int main(int argc, char **argv) {
+  if (argc >= 2 && strcmp(argv[1], "partition") == 0) return partition_main(argc, argv);
   if (argc < 2 || (strcmp(argv[1], "query") != 0 && strcmp(argv[1], "index") != 0)) {
     usage();
     return 2;

@@ -444,6 +444,9 @@ struct impg_gpu_index {
   mutable std::atomic<uint64_t> walk_launches{0}, walk_fallbacks{0}, walk_last_members{1};  // impg_gpu_get_counter
   // ... and how the visited updates of its batches grouped their hits: levels cut into slices, levels counted a second time
   // for one huge query, levels that went to the library sort ([0], [1], [2]; Engine::update)
+  // host <-> device traffic of the masked queries, counted where the copies are issued: mask tables uploaded (apply_mask,
+  // one per hipMemcpy) and result rows copied back (assemble_results, walk_query); a partition session reads their deltas
+  mutable std::atomic<uint64_t> mask_table_uploads{0}, result_rows_to_host{0};
   mutable std::atomic<uint64_t> seg_stats[3] = {};
   // ... and which kernel projected each level (by impg::ProjArm: launch_project's return value, counted by the engine)
   mutable std::atomic<uint64_t> proj_stats[8] = {};

@@ -358,6 +358,35 @@ class GpuImpg:
             self._h = None
 
     # ---- seq_index() / target_ids() / num_targets() ---------------------------
+    def partition_session(self, window_size, merge_distance, params=None, **kw):
+        """A PartitionSession on this index; params default to the reference CLI's transitive BFS."""
+        return PartitionSession(self, params or make_params(transitive=True), window_size, merge_distance, **kw)
+
+    def partition(self, window_size, merge_distance, params=None, **kw):
+        """`impg partition` window by window: yields (partition_num, [(seq_id, start, end)]) before rehoming."""
+        s = self.partition_session(window_size, merge_distance, params, **kw)
+        try:
+            num = 0
+            while True:
+                ws = s.next_windows()
+                if not ws:
+                    return
+                for w in ws:
+                    rows = s.window(*w)
+                    if rows:
+                        yield num, rows
+                        num += 1
+        finally:
+            s.close()
+
+    def partitions_bed(self, window_size, merge_distance, params=None, **kw):
+        """The text of partitions.bed (write_single_partition_file, partition.rs:1682-1717)."""
+        s = self.partition_session(window_size, merge_distance, params, **kw)
+        try:
+            return s.run_text()[0]
+        finally:
+            s.close()
+
     def num_seqs(self):
         return lib().impg_gpu_num_seqs(self._h)
 
@@ -606,6 +635,206 @@ class GpuImpg:
 
 HOP_PROFILE_FIELDS = ["hops", "route_s", "gather_sizes_s", "records_out_s", "owner_expand_s", "gather_hits_s", "hits_home_s", "reorder_s",
                       "bytes_records_out", "bytes_hits_out", "records_in", "hits_home"]
+
+
+SELECTION_MODES = {"longest": _lib.SELECT_LONGEST, "total": _lib.SELECT_TOTAL, "sample": _lib.SELECT_SAMPLE,
+                   "haplotype": _lib.SELECT_HAPLOTYPE}
+
+
+def parse_selection_mode(mode):
+    """'longest' | 'total' | 'sample[,sep]' | 'haplotype[,sep]' -> (IMPG_SELECT_*, separator) (partition.rs:724-805)."""
+    kind, _, sep = mode.partition(",")
+    if kind not in SELECTION_MODES or (sep and kind in ("longest", "total")):
+        raise ValueError("Invalid selection mode. Must be 'longest', 'total', 'sample[,sep]', or 'haplotype[,sep]'.")
+    return SELECTION_MODES[kind], (sep or "#")
+
+
+def _names_array(names):
+    return (C.c_char_p * len(names))(*[n.encode() for n in names])
+
+
+class Regions:
+    """masked_regions / missing_regions of `impg partition` (impg_gpu_regions_t): in HBM, or on the host
+    (on_host=True: the host twin, no GPU needed)."""
+
+    def __init__(self, seq_len=None, on_host=False, device=0, _borrowed=None, _owner=None):
+        self._owner = _owner
+        self._own = _borrowed is None
+        if _borrowed is not None:
+            self._h = _borrowed
+            self.n_seq = _owner.index.num_seqs()
+            return
+        sl = np.ascontiguousarray(seq_len, dtype=np.int64)
+        self.n_seq = int(sl.size)
+        h = C.c_void_p()
+        _lib.check(_lib.lib().impg_gpu_regions_create(sl.ctypes.data, sl.size, int(on_host), device, C.byref(h)))
+        self._h = h
+
+    def apply(self, rows, merge_distance, min_missing_size=3000, min_boundary_distance=3000):
+        """One window's update on rows (INTERVAL_DTYPE); returns the window's [(seq_id, start, end)]."""
+        a = np.ascontiguousarray(rows, dtype=_lib.INTERVAL_DTYPE)
+        cap = max(16, 2 * a.size)
+        out = np.zeros(cap, dtype=_lib.PARTITION_ROW_DTYPE)
+        n = C.c_size_t(0)
+        _lib.check(_lib.lib().impg_gpu_regions_apply(self._h, a.ctypes.data, a.size, merge_distance, min_missing_size,
+                                                     min_boundary_distance, out.ctypes.data, cap, C.byref(n)))
+        return self._rows(out, n.value)
+
+    def _rows(self, out, n):
+        """The first n rows of `out`, or -- more than it holds -- the rows the object kept, fetched whole."""
+        if n > out.size:
+            out = np.zeros(n, dtype=_lib.PARTITION_ROW_DTYPE)
+            m = C.c_size_t(0)
+            _lib.check(_lib.lib().impg_gpu_regions_last_rows(self._h, out.ctypes.data, n, C.byref(m)))
+            n = m.value
+        return [(int(r["seq_id"]), int(r["start"]), int(r["end"])) for r in out[:n]]
+
+    def get(self, which):
+        """{seq id: [(start, end), ...]} of the masked ('masked') or missing ('missing') map; empty lists included."""
+        w = {"masked": _lib.REGIONS_MASKED, "missing": _lib.REGIONS_MISSING}[which]
+        off = np.zeros(self.n_seq + 1, dtype=np.uint64)
+        n = C.c_size_t(0)
+        _lib.check(_lib.lib().impg_gpu_regions_get(self._h, w, off.ctypes.data, None, 0, C.byref(n)))
+        rng = np.zeros((max(n.value, 1), 2), dtype=np.int32)
+        _lib.check(_lib.lib().impg_gpu_regions_get(self._h, w, off.ctypes.data, rng.ctypes.data, n.value, C.byref(n)))
+        return {s: [(int(a), int(b)) for a, b in rng[int(off[s]):int(off[s + 1])]] for s in range(self.n_seq)}
+
+    def select(self, mode, window_size, names=None):
+        sel, sep = parse_selection_mode(mode)
+        arr = _names_array(names) if names is not None else None
+        cap = 1 << 10
+        while True:
+            w = np.zeros(cap, dtype=_lib.RANGE_DTYPE)
+            n = C.c_size_t(0)
+            _lib.check(_lib.lib().impg_gpu_regions_select(self._h, sel, sep.encode(), arr, window_size, w.ctypes.data, cap, C.byref(n)))
+            if n.value <= cap:
+                return [(int(r["target_id"]), int(r["start"]), int(r["end"])) for r in w[:n.value]]
+            cap = n.value
+
+    def close(self):
+        if getattr(self, "_h", None) and self._own:
+            _lib.lib().impg_gpu_regions_free(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # interpreter shutdown
+            pass
+
+
+def starting_windows(seq_ids, seq_len, window_size):
+    ids = np.ascontiguousarray(seq_ids, dtype=np.uint32)
+    sl = np.ascontiguousarray(seq_len, dtype=np.int64)
+    cap = int(sum(int(sl[i]) // window_size + 1 for i in ids)) + 1
+    w = np.zeros(cap, dtype=_lib.RANGE_DTYPE)
+    n = C.c_size_t(0)
+    _lib.check(_lib.lib().impg_gpu_partition_starting_windows(ids.ctypes.data, ids.size, sl.ctypes.data, sl.size, window_size,
+                                                              w.ctypes.data, cap, C.byref(n)))
+    return [(int(r["target_id"]), int(r["start"]), int(r["end"])) for r in w[:n.value]]
+
+
+def _flatten_partitions(partitions):
+    rows = np.array([(s, a, b) for _, ivs in partitions for s, a, b in ivs], dtype=_lib.PARTITION_ROW_DTYPE)
+    num = np.array([p for p, ivs in partitions for _ in ivs], dtype=np.uint64)
+    return rows, num
+
+
+def rehome_singleton_slivers(partitions):
+    """[(partition_num, [(seq, start, end), ...])] -> the same after rehome_singleton_slivers (partition.rs:45-156)."""
+    rows, num = _flatten_partitions(partitions)
+    _lib.check(_lib.lib().impg_gpu_partition_rehome(rows.ctypes.data, num.ctypes.data, rows.size))
+    out = []
+    for r, p in zip(rows, num):
+        if not out or out[-1][0] != int(p):
+            out.append((int(p), []))
+        out[-1][1].append((int(r["seq_id"]), int(r["start"]), int(r["end"])))
+    return out
+
+
+def partitions_bed_text(partitions, names):
+    """write_single_partition_file's text (partition.rs:1682-1717)."""
+    rows, num = _flatten_partitions(partitions)
+    text = C.c_void_p()
+    ln = C.c_size_t(0)
+    _lib.check(_lib.lib().impg_gpu_partition_bed_text(rows.ctypes.data, num.ctypes.data, rows.size, _names_array(names), len(names),
+                                                      C.byref(text), C.byref(ln)))
+    try:
+        return C.string_at(text, ln.value).decode()
+    finally:
+        _lib.free(text)
+
+
+class PartitionSession:
+    """partition_alignments over an index (impg_gpu_partition_t); see GpuImpg.partition."""
+
+    def __init__(self, index, params, window_size, merge_distance, min_missing_size=3000, min_boundary_distance=3000,
+                 selection_mode="longest", starting_sequences=None, rehome_singletons=True, state_on_host=False):
+        sel, sep = parse_selection_mode(selection_mode)
+        self.index = index
+        self._sep = sep.encode()
+        o = _lib.PartitionOpts(window_size, merge_distance, min_missing_size, min_boundary_distance, sel, self._sep,
+                               int(rehome_singletons), int(state_on_host))
+        ids = None
+        if starting_sequences:
+            ids = np.array([s if isinstance(s, (int, np.integer)) else index.seq_id(s) for s in starting_sequences], dtype=np.uint32)
+        h = C.c_void_p()
+        _lib.check(_lib.lib().impg_gpu_partition_create(index._h, C.byref(params), C.byref(o), None if ids is None else ids.ctypes.data,
+                                                        0 if ids is None else ids.size, C.byref(h)))
+        self._h = h
+
+    def next_windows(self):
+        cap = 1 << 10
+        while True:
+            w = np.zeros(cap, dtype=_lib.RANGE_DTYPE)
+            n = C.c_size_t(0)
+            _lib.check(_lib.lib().impg_gpu_partition_next_windows(self._h, w.ctypes.data, cap, C.byref(n)))
+            if n.value <= cap:
+                return [(int(r["target_id"]), int(r["start"]), int(r["end"])) for r in w[:n.value]]
+            cap = n.value
+
+    def window(self, seq_id, start, end, cap=1 << 12):
+        w = np.array([(seq_id, start, end)], dtype=_lib.RANGE_DTYPE)
+        out = np.zeros(cap, dtype=_lib.PARTITION_ROW_DTYPE)
+        n = C.c_size_t(0)
+        _lib.check(_lib.lib().impg_gpu_partition_window(self._h, w.ctypes.data, out.ctypes.data, cap, C.byref(n)))
+        return self.regions()._rows(out, n.value)
+
+    def run_text(self, separate_files=False):
+        """The whole loop; returns (partitions.bed text, number of partitions)."""
+        text = C.c_void_p()
+        ln = C.c_size_t(0)
+        k = C.c_uint64(0)
+        _lib.check(_lib.lib().impg_gpu_partition_run(self._h, None, int(separate_files), C.byref(text), C.byref(ln), C.byref(k)))
+        try:
+            return C.string_at(text, ln.value).decode(), int(k.value)
+        finally:
+            _lib.free(text)
+
+    def run_files(self, folder, separate_files=False):
+        k = C.c_uint64(0)
+        _lib.check(_lib.lib().impg_gpu_partition_run(self._h, None if folder is None else folder.encode(), int(separate_files), None, None,
+                                                     C.byref(k)))
+        return int(k.value)
+
+    def regions(self):
+        return Regions(_borrowed=C.c_void_p(_lib.lib().impg_gpu_partition_regions(self._h)), _owner=self)
+
+    def counter(self, key):
+        v = C.c_int64(0)
+        _lib.check(_lib.lib().impg_gpu_partition_counter(self._h, key.encode(), C.byref(v)))
+        return int(v.value)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.lib().impg_gpu_partition_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # interpreter shutdown
+            pass
 
 
 def shard_assign(entries_per_target, n_shards):

@@ -575,6 +575,99 @@ int impg_gpu_index_shard_info(const impg_gpu_index_t *, int *rank, int *world, i
  * needed when out is NULL). */
 int impg_gpu_index_hop_profile(impg_gpu_index_t *, double *out, size_t cap, int reset, size_t *n_out);
 
+/* ---- partition: partition_alignments with BED output (src/commands/partition.rs:158-712) --------------------------
+ * The loop is sequential -- window k+1 is queried under the mask window k left -- so what lies between two queries is
+ * kept where the query's rows are: a REGIONS object holds masked_regions and missing_regions of every sequence as two
+ * CSR tables (u32 offsets over the sequence ids, (start, end) pairs), in HBM (on_host = 0) or on the host (on_host = 1:
+ * the host twin, the same algebra in plain C++, which needs no GPU).  One window's update is
+ *   merge_overlaps(merge_distance) (:939-976), extend_to_close_boundaries (:1369-1408, if min_boundary_distance > 0),
+ *   mask_and_update_regions (:978-1366), merge_overlaps(0)
+ * on the query-side interval (query_id, min, max) of every row; only those reach BED output, so the target side's
+ * proportional adjustments (:1120-1140, :1178-1188) are not built.  State at the start: masked = {}, missing =
+ * {(0, len)} for every sequence (a sequence of length 0 starts outside the missing map: it could never be windowed). */
+typedef struct impg_gpu_regions impg_gpu_regions_t;
+typedef struct impg_gpu_partition impg_gpu_partition_t;
+typedef struct {
+  uint32_t seq_id;
+  int32_t start, end;
+} impg_gpu_partition_row_t;
+#define IMPG_REGIONS_MASKED 0
+#define IMPG_REGIONS_MISSING 1
+#define IMPG_SELECT_LONGEST 0   /* the longest missing range; ties: higher sequence id, then the later range */
+#define IMPG_SELECT_TOTAL 1     /* the sequence with most missing bases; ties: higher sequence id */
+#define IMPG_SELECT_SAMPLE 2    /* "sample[,sep]": the name prefix (first field) with most missing bases, ties by prefix */
+#define IMPG_SELECT_HAPLOTYPE 3 /* "haplotype[,sep]": the first two fields */
+/* on_host = 0 needs `device`; on_host = 1 ignores it. */
+int impg_gpu_regions_create(const int64_t *seq_len, uint32_t n_seq, int on_host, int device, impg_gpu_regions_t **out);
+/* One window's update on caller-supplied rows in host memory (device state: the rows are uploaded and the kernels run).
+ * Writes at most cap rows -- sorted by (seq_id, start), disjoint -- and the count to *n_out.  The output of a window
+ * cannot be bounded ahead of the call and the state has moved on when it returns, so the object keeps the rows until its
+ * next apply / window: a count above cap is fetched whole with impg_gpu_regions_last_rows.  merge_distance < 0:
+ * IMPG_E_INVALID. */
+int impg_gpu_regions_apply(impg_gpu_regions_t *, const impg_gpu_interval_t *rows, size_t n_rows, int32_t merge_distance,
+                           int32_t min_missing_size, int32_t min_boundary_distance, impg_gpu_partition_row_t *out_rows, size_t cap,
+                           size_t *n_out);
+int impg_gpu_regions_last_rows(const impg_gpu_regions_t *, impg_gpu_partition_row_t *out_rows, size_t cap, size_t *n_out);
+/* which = IMPG_REGIONS_MASKED / _MISSING: off_out[n_seq + 1], and the first min(cap, total) ranges as (start, end)
+ * pairs; *n_ranges = total.  ranges_out may be NULL with cap 0 to size. */
+int impg_gpu_regions_get(impg_gpu_regions_t *, int which, uint64_t *off_out, int32_t *ranges_out, size_t cap, size_t *n_ranges);
+/* select_and_window_sequences (:715-937) on the current missing map.  names[n_seq] is needed by SAMPLE / HAPLOTYPE only
+ * (separator NULL = "#").  Inside the chosen group the reference orders the sequences by length with an unstable sort:
+ * ties go in ascending sequence id here.  *n = windows found (0: nothing is missing any more); at most cap are written. */
+int impg_gpu_regions_select(impg_gpu_regions_t *, int selection, const char *separator, const char *const *names,
+                            int64_t window_size, impg_gpu_range_t *windows_out, size_t cap, size_t *n);
+void impg_gpu_regions_free(impg_gpu_regions_t *);
+
+/* Host-only pieces of the command (no device needed): the windows of a starting-sequences list (:220-246: a short tail
+ * window is merged into the previous window OF THE SAME SEQUENCE), rehome_singleton_slivers (:45-156) over rows tagged
+ * with their partition's position in the list (partition_idx ascending; the rebuilt order comes back in place, *n_out
+ * rows), and write_single_partition_file's text (:1682-1717; *text is malloc'ed). */
+int impg_gpu_partition_starting_windows(const uint32_t *seq_ids, size_t n, const int64_t *seq_len, uint32_t n_seq,
+                                        int64_t window_size, impg_gpu_range_t *windows_out, size_t cap, size_t *n_out);
+int impg_gpu_partition_rehome(impg_gpu_partition_row_t *rows, uint64_t *partition_num, size_t n);
+int impg_gpu_partition_bed_text(const impg_gpu_partition_row_t *rows, const uint64_t *partition_num, size_t n,
+                                const char *const *names, uint32_t n_seq, char **text, size_t *len);
+
+/* The session: partition_alignments over an index.  state_on_host = 0: the regions live in HBM for the session's life, the
+ * query reads the mask table where the kernels maintain it (no host validation, no upload), the query's rows are
+ * consumed where the engine leaves them, and per window only the output rows and a few words cross PCIe; the session
+ * holds one engine of the index until it is destroyed (IMPG_E_UNSUPPORTED from create when every engine is out -- it
+ * never waits).  state_on_host = 1: the loop a host binding writes against the calls above -- mask rebuilt and uploaded
+ * every window, rows copied back, algebra on the CPU; holds no engine.  params: a transitive query (BFS or DFS) with
+ * store_cigar 0 and min_output_length < 0 (IMPG_E_INVALID otherwise); merge_distance < 0 (--no-merge): IMPG_E_INVALID;
+ * a sharded index: IMPG_E_UNSUPPORTED. */
+typedef struct {
+  int64_t window_size;
+  int32_t merge_distance;
+  int32_t min_missing_size;      /* reference default 3000 */
+  int32_t min_boundary_distance; /* reference default 3000 */
+  int32_t selection;             /* IMPG_SELECT_* */
+  const char *separator;         /* SAMPLE / HAPLOTYPE; NULL = "#" */
+  int32_t rehome_singletons;     /* reference default 1 */
+  int32_t state_on_host;
+} impg_gpu_partition_opts_t;
+int impg_gpu_partition_create(impg_gpu_index_t *, const impg_gpu_params_t *params, const impg_gpu_partition_opts_t *opts,
+                              const uint32_t *starting_seq_ids, size_t n_starting, impg_gpu_partition_t **out);
+/* The next set of windows (:183-247 first if starting sequences were given, else :715-937); *n = 0: done.  A set larger
+ * than cap is not handed out: *n says how many there are. */
+int impg_gpu_partition_next_windows(impg_gpu_partition_t *, impg_gpu_range_t *windows_out, size_t cap, size_t *n);
+/* Query + update for one window.  *n_out = 0: no partition.  At most cap rows are written; a larger result stays with the
+ * session until its next window: impg_gpu_regions_last_rows(impg_gpu_partition_regions(p), ...) fetches it whole. */
+int impg_gpu_partition_window(impg_gpu_partition_t *, const impg_gpu_range_t *window, impg_gpu_partition_row_t *rows_out, size_t cap,
+                              size_t *n_out);
+/* The whole loop, rehoming and text.  text != NULL: the partitions.bed text is returned (malloc'ed) instead of written;
+ * else folder/partitions.bed, or folder/partition{N}.bed with separate_files (:1509-1542; no rehoming then, as in the
+ * reference); folder NULL = the working directory. */
+int impg_gpu_partition_run(impg_gpu_partition_t *, const char *folder, int separate_files, char **text, size_t *len,
+                           uint64_t *n_partitions);
+impg_gpu_regions_t *impg_gpu_partition_regions(impg_gpu_partition_t *); /* borrowed */
+/* "windows", "partitions", "mask_uploads" (host-to-device copies of mask tables) and "rows_to_host" (query rows copied
+ * back): both read off the index's own counters, which are bumped where those copies are issued, as deltas around
+ * the session's windows (queries other threads run on the handle meanwhile are counted in), "walk_windows" (windows the per-query walk answered), "step_launches" (kernel launches + rocPRIM calls of the
+ * updates; a library sort or scan is several kernels and counts once) */
+int impg_gpu_partition_counter(const impg_gpu_partition_t *, const char *key, int64_t *value);
+void impg_gpu_partition_destroy(impg_gpu_partition_t *);
+
 /* ---- synthetic workload generators (SplitMix64) ----- */
 /* Fills records / ops for `n_records` synthetic alignments (200-op CIGARs by
  * default).  Call with ops == NULL to size: *n_ops_out receives the op count. */
