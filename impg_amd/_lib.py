@@ -186,6 +186,8 @@ SYMBOLS = [
     ("impg_gpu_index_hop_profile", C.c_int, [_P, _P, C.c_size_t, C.c_int, C.POINTER(C.c_size_t)]),
     ("impg_gpu_regions_create", C.c_int, [_P, C.c_uint32, C.c_int, C.c_int, C.POINTER(_P)]),
     ("impg_gpu_regions_apply", C.c_int, [_P, _P, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("impg_gpu_regions_apply_device", C.c_int, [_P, _P, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, _P, C.c_size_t,
+                                                C.POINTER(C.c_size_t)]),
     ("impg_gpu_regions_last_rows", C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("impg_gpu_regions_get", C.c_int, [_P, C.c_int, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("impg_gpu_regions_select", C.c_int, [_P, C.c_int, C.c_char_p, _P, C.c_int64, _P, C.c_size_t, C.POINTER(C.c_size_t)]),

@@ -450,6 +450,23 @@ int impg_gpu_regions_apply(impg_gpu_regions_t *r, const impg_gpu_interval_t *row
   P_CATCH
 }
 
+int impg_gpu_regions_apply_device(impg_gpu_regions_t *r, const impg_gpu_interval_t *d_rows, size_t n_rows, int32_t merge_distance,
+                                  int32_t min_missing_size, int32_t min_boundary_distance, impg_gpu_partition_row_t *out_rows, size_t cap,
+                                  size_t *n_out) {
+  P_TRY
+  if (!r || !n_out || (!d_rows && n_rows) || (!out_rows && cap)) throw Error{IMPG_E_INVALID, "null argument"};
+  if (r->on_host) throw Error{IMPG_E_INVALID, "rows in device memory need a device-state object (on_host = 0)"};
+  if (merge_distance < 0) throw Error{IMPG_E_INVALID, "merge_distance < 0 (--no-merge) is not supported"};
+  if (n_rows >= (1ull << 30)) throw Error{IMPG_E_UNSUPPORTED, "more than 2^30 rows in one window"};
+  r->last.clear();
+  IMPG_HIP(hipSetDevice(r->d->device));
+  r->d->apply(d_rows, (uint32_t)n_rows, merge_distance, min_missing_size, min_boundary_distance, r->last);
+  copy_rows(r->last, out_rows, cap);
+  *n_out = r->last.size();
+  return IMPG_OK;
+  P_CATCH
+}
+
 int impg_gpu_regions_last_rows(const impg_gpu_regions_t *r, impg_gpu_partition_row_t *out_rows, size_t cap, size_t *n_out) {
   P_TRY
   if (!r || !n_out || (!out_rows && cap)) throw Error{IMPG_E_INVALID, "null argument"};

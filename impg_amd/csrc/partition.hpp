@@ -45,7 +45,8 @@ struct DeviceRegions {
   uint32_t n_mask = 0, n_missing = 0;
   bool mask_has_empty = false;
   SelSummary longest;                        // of the current missing table (the totals are read on demand)
-  DevBuf totals;                             // u64[n_seq]
+  DevBuf totals[2];                          // u64[n_seq] each: missing bases per sequence; a window writes the other one
+  int t_cur = 0;                             // ... and it becomes current together with the tables, or not at all
   uint64_t launches = 0;                     // kernel launches + rocPRIM calls issued (a library sort or scan is several kernels and counts once)
   // scratch
   DevBuf key_a, key_b, val_a, val_b, mk, pm, head, pos, a_key, a_hi, b_lo, b_hi, c_key, c_hi, e_key, e_hi, s_a, s_first, s_cnt,

@@ -28,7 +28,9 @@
 //   8 missing minus the new mask: stage 5's kernels on the missing table, then the merge at 0 (what missing.insert does
 //     with touching pieces, :1300, :1309); a sequence whose set empties simply has no ranges (:1313-1316)
 //   9 selection: atomic max of (length << 32 | range index) -- the table is ordered by (sequence, start), so the index
-//     breaks ties as max_by does (:739-744) -- and the missing bases per sequence
+//     breaks ties as max_by does (:739-744) -- and the missing bases per sequence, summed into the one of two buffers
+//     that is not current
+// Nothing a window writes is current before its header is read: a refused row (norm_kernel) drops tables and sums alike.
 // The host learns two things per window besides the output rows: the number of segments of stage 5 (to size stage 6) and
 // a nine-word header (counts, flags, the longest missing range).
 #include <hip/hip_runtime.h>
@@ -60,6 +62,15 @@ __device__ __forceinline__ uint32_t lower_start(const int2 *__restrict__ r, uint
   while (lo < hi) {
     const uint32_t mid = (lo + hi) >> 1;
     if (r[mid].x < p) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+// number of ranges of r[0..n) with start <= p (p may be INT32_MAX: no p + 1)
+__device__ __forceinline__ uint32_t upper_start(const int2 *__restrict__ r, uint32_t n, int32_t p) {
+  uint32_t lo = 0, hi = n;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (r[mid].x <= p) lo = mid + 1; else hi = mid;
   }
   return lo;
 }
@@ -270,7 +281,7 @@ __global__ __launch_bounds__(256) void mask_merge_kernel(const uint32_t *__restr
     const uint32_t g = i - n_old;
     const uint32_t s = key_seq(a_key[g]);
     const uint32_t ma = m_off[s], mn = m_off[s + 1] - ma;
-    const uint32_t rank = ma + lower_start(m_rng + ma, mn, b_lo[g] + 1);  // old ranges of lower sequences, and of s with start <= lo
+    const uint32_t rank = ma + upper_start(m_rng + ma, mn, b_lo[g]);  // old ranges of lower sequences, and of s with start <= lo
     out_key[g + rank] = make_key(s, b_lo[g]);
     out_hi[g + rank] = b_hi[g];
   }
@@ -401,10 +412,12 @@ DeviceRegions::DeviceRegions(int device_, const int64_t *seq_len, uint32_t n_seq
   std::vector<int32_t> L(n_seq);
   std::vector<uint32_t> xo(n_seq + 1, 0), mo(n_seq + 1, 0);
   std::vector<int32_t> xr;
+  std::vector<u64> tot(n_seq, 0);
   int64_t best = -1;
   for (uint32_t q = 0; q < n_seq; q++) {
     L[q] = (int32_t)std::min<int64_t>(std::max<int64_t>(seq_len[q], 0), INT32_MAX);
     if (L[q] > 0) {
+      tot[q] = (u64)L[q];
       xr.push_back(0); xr.push_back(L[q]);
       if (L[q] >= best) { best = L[q]; longest.any = true; longest.seq = q; longest.lo = 0; longest.hi = L[q]; }
     }
@@ -413,12 +426,13 @@ DeviceRegions::DeviceRegions(int device_, const int64_t *seq_len, uint32_t n_seq
   n_missing = (uint32_t)(xr.size() / 2);
   auto need = [](DevBuf &b, size_t bytes) { b.reserve(std::max<size_t>(bytes, 256)); };
   need(len, (size_t)n_seq * 4);
-  need(totals, (size_t)n_seq * 8);
+  for (int k = 0; k < 2; k++) need(totals[k], (size_t)n_seq * 8);
   need(ctr, C_WORDS * 4);
   for (int k = 0; k < 2; k++) { need(m_off[k], ((size_t)n_seq + 1) * 4); need(x_off[k], ((size_t)n_seq + 1) * 4); }
   need(m_rng[0], 256); need(x_rng[0], xr.size() * 4);
   // the state is built once on the host -- lengths, an empty mask, missing = every sequence -- and lives in HBM from here on
   if (n_seq) IMPG_HIP(hipMemcpyAsync(len.p, L.data(), (size_t)n_seq * 4, hipMemcpyHostToDevice, stream));
+  if (n_seq) IMPG_HIP(hipMemcpyAsync(totals[0].p, tot.data(), (size_t)n_seq * 8, hipMemcpyHostToDevice, stream));
   IMPG_HIP(hipMemcpyAsync(m_off[0].p, mo.data(), ((size_t)n_seq + 1) * 4, hipMemcpyHostToDevice, stream));
   IMPG_HIP(hipMemcpyAsync(x_off[0].p, xo.data(), ((size_t)n_seq + 1) * 4, hipMemcpyHostToDevice, stream));
   if (!xr.empty()) IMPG_HIP(hipMemcpyAsync(x_rng[0].p, xr.data(), xr.size() * 4, hipMemcpyHostToDevice, stream));
@@ -447,7 +461,7 @@ void DeviceRegions::apply(const impg_gpu_interval_t *d_rows, uint32_t n, int32_t
   const unsigned end_bit = 32 + bits_for(n_seq);
   uint32_t *c = ctr.as<uint32_t>();
   const uint32_t n_old = n_mask, n_x = n_missing;
-  const int mo = m_cur, xo = x_cur, mn = m_cur ^ 1, xn = x_cur ^ 1;
+  const int mo = m_cur, xo = x_cur, mn = m_cur ^ 1, xn = x_cur ^ 1, tn = t_cur ^ 1;
   // 1
   op.need(key_a, (size_t)2 * n * 8); op.need(key_b, (size_t)2 * n * 8); op.need(val_a, (size_t)2 * n * 4); op.need(val_b, (size_t)2 * n * 4);
   IMPG_HIP(hipMemsetAsync(c + C_HDR, 0, H_WORDS * 4, s));
@@ -519,19 +533,21 @@ void DeviceRegions::apply(const impg_gpu_interval_t *d_rows, uint32_t n, int32_t
                                                                                     x_off[xn].as<uint32_t>(), x_rng[xn].as<int2>(), c + C_HDR, H_NMISS, -1);
   launches += 3;
   // 9
-  IMPG_HIP(hipMemsetAsync(totals.p, 0, std::max<size_t>((size_t)n_seq * 8, 8), s));
+  IMPG_HIP(hipMemsetAsync(totals[tn].p, 0, std::max<size_t>((size_t)n_seq * 8, 8), s));
   IMPG_HIP(hipMemsetAsync(c + C_BEST, 0, 8, s));
-  select_kernel<<<cdiv(xs_ub, 256), 256, 0, s>>>(key_a.as<u64>(), val_a.as<int32_t>(), xs_ub, c + C_NMISS, (u64 *)(c + C_BEST), totals.as<u64>());
+  select_kernel<<<cdiv(xs_ub, 256), 256, 0, s>>>(key_a.as<u64>(), val_a.as<int32_t>(), xs_ub, c + C_NMISS, (u64 *)(c + C_BEST), totals[tn].as<u64>());
   op.need(out_rows, (size_t)sg * sizeof(PIv));
   finish_kernel<<<cdiv(sg, 256), 256, 0, s>>>(key_a.as<u64>(), val_a.as<int32_t>(), (const u64 *)(c + C_BEST), c, o_key.as<u64>(), o_hi.as<int32_t>(),
                                               sg, out_rows.as<PIv>());
   launches += 4;
   IMPG_HIP(hipMemcpyAsync(h_hdr, c + C_HDR, H_WORDS * 4, hipMemcpyDeviceToHost, s));
   IMPG_HIP(hipStreamSynchronize(s));
-  // (a refused row leaves the state as it was: the tables just built are dropped)
+  // (a refused row leaves the state as it was: the tables and the sums just built are dropped, all of them in the
+  // buffers that are not current)
   if (h_hdr[H_ERR]) throw Error{IMPG_E_INVALID, "a row names an unknown sequence or has a negative coordinate"};
   m_cur = mn;
   x_cur = xn;
+  t_cur = tn;
   n_mask = h_hdr[H_NMASK];
   n_missing = h_hdr[H_NMISS];
   mask_has_empty = h_hdr[H_EMPTY] != 0;
@@ -563,13 +579,7 @@ void DeviceRegions::summary(SelSummary &s, bool want_totals) {
   if (!want_totals) return;
   s.total.assign(n_seq, 0);
   if (!n_seq) return;
-  if (launches == 0) {  // no window yet: every sequence is missing whole
-    std::vector<int32_t> L(n_seq);
-    IMPG_HIP(hipMemcpy(L.data(), len.p, (size_t)n_seq * 4, hipMemcpyDeviceToHost));
-    for (uint32_t q = 0; q < n_seq; q++) s.total[q] = L[q];
-    return;
-  }
-  IMPG_HIP(hipMemcpyAsync(s.total.data(), totals.p, (size_t)n_seq * 8, hipMemcpyDeviceToHost, stream));
+  IMPG_HIP(hipMemcpyAsync(s.total.data(), totals[t_cur].p, (size_t)n_seq * 8, hipMemcpyDeviceToHost, stream));
   IMPG_HIP(hipStreamSynchronize(stream));
 }
 

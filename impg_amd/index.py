@@ -670,15 +670,22 @@ class Regions:
         _lib.check(_lib.lib().impg_gpu_regions_create(sl.ctypes.data, sl.size, int(on_host), device, C.byref(h)))
         self._h = h
 
-    def apply(self, rows, merge_distance, min_missing_size=3000, min_boundary_distance=3000):
-        """One window's update on rows (INTERVAL_DTYPE); returns the window's [(seq_id, start, end)]."""
+    def apply(self, rows, merge_distance, min_missing_size=3000, min_boundary_distance=3000, device_ptr=None, n=None):
+        """One window's update on rows (INTERVAL_DTYPE); returns the window's [(seq_id, start, end)].  device_ptr / n:
+        the rows are already on the device (impg_gpu_regions_apply_device)."""
+        k = C.c_size_t(0)
+        if device_ptr is not None:
+            cap = max(16, 2 * n)
+            out = np.zeros(cap, dtype=_lib.PARTITION_ROW_DTYPE)
+            _lib.check(_lib.lib().impg_gpu_regions_apply_device(self._h, device_ptr, n, merge_distance, min_missing_size,
+                                                                min_boundary_distance, out.ctypes.data, cap, C.byref(k)))
+            return self._rows(out, k.value)
         a = np.ascontiguousarray(rows, dtype=_lib.INTERVAL_DTYPE)
         cap = max(16, 2 * a.size)
         out = np.zeros(cap, dtype=_lib.PARTITION_ROW_DTYPE)
-        n = C.c_size_t(0)
         _lib.check(_lib.lib().impg_gpu_regions_apply(self._h, a.ctypes.data, a.size, merge_distance, min_missing_size,
-                                                     min_boundary_distance, out.ctypes.data, cap, C.byref(n)))
-        return self._rows(out, n.value)
+                                                     min_boundary_distance, out.ctypes.data, cap, C.byref(k)))
+        return self._rows(out, k.value)
 
     def _rows(self, out, n):
         """The first n rows of `out`, or -- more than it holds -- the rows the object kept, fetched whole."""

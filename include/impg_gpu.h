@@ -607,6 +607,13 @@ int impg_gpu_regions_create(const int64_t *seq_len, uint32_t n_seq, int on_host,
 int impg_gpu_regions_apply(impg_gpu_regions_t *, const impg_gpu_interval_t *rows, size_t n_rows, int32_t merge_distance,
                            int32_t min_missing_size, int32_t min_boundary_distance, impg_gpu_partition_row_t *out_rows, size_t cap,
                            size_t *n_out);
+/* The same on rows that already lie in the object's device's memory, as a session's window applies its query's rows
+ * (device state only; whatever wrote the rows has completed).  Nothing reads them on the host: a row with a sequence id
+ * >= n_seq or a negative coordinate is found by the kernels, the call returns IMPG_E_INVALID and the state -- both
+ * tables and everything select answers from -- is what it was before the call. */
+int impg_gpu_regions_apply_device(impg_gpu_regions_t *, const impg_gpu_interval_t *d_rows, size_t n_rows, int32_t merge_distance,
+                                  int32_t min_missing_size, int32_t min_boundary_distance, impg_gpu_partition_row_t *out_rows,
+                                  size_t cap, size_t *n_out);
 int impg_gpu_regions_last_rows(const impg_gpu_regions_t *, impg_gpu_partition_row_t *out_rows, size_t cap, size_t *n_out);
 /* which = IMPG_REGIONS_MASKED / _MISSING: off_out[n_seq + 1], and the first min(cap, total) ranges as (start, end)
  * pairs; *n_ranges = total.  ranges_out may be NULL with cap 0 to size. */

@@ -103,9 +103,13 @@ class Ref:
                 if r[1] < min_boundary:
                     self.count["boundary_extensions"] += r[1] > 0
                     zero = r[1] > 0
+                    if zero:
+                        self.seen.add("boundary_to_zero")
                     r[1] = 0
                 if self.lens[r[0]] - r[2] < min_boundary:
                     self.count["boundary_extensions"] += r[2] < self.lens[r[0]]
+                    if r[2] < self.lens[r[0]]:
+                        self.seen.add("boundary_to_len")
                     r[2] = self.lens[r[0]]
                 r.append(zero)
             for s in {r[0] for r in v}:
@@ -158,6 +162,8 @@ class Ref:
         for _, start, end in ivs:  # step 3
             for xs, xe in ext:
                 if (xe >= start and xs <= start) or (xs <= end and xe >= end):
+                    if xs < start and xe > end:  # one extension moves both ends: it covers the interval whole
+                        self.seen.add("extension_covers_interval")
                     start = min(start, xs)
                     end = max(end, xe)
             buf.append((start, end))
@@ -396,3 +402,169 @@ def random_windows(rng, lens, n_windows, max_rows=200):
                 rows.append(r)
         out.append(rows)
     return out
+
+
+# ---- small, collision-dense universes: nesting, touching and equal coordinates in nearly every window -------------------
+I32_MAX = 2 ** 31 - 1
+DENSE_N_SEQ = (1, 2, 3, 4, 7, 8)
+DENSE_D, DENSE_MIN_MISSING, DENSE_MIN_BOUNDARY = (0, 1, 3, 100), (0, 1, 5, 1000), (0, 1, 4, 1000)
+DENSE_VARIANTS = {"plain": dict(zero_len=False, big=False), "zero_len": dict(zero_len=True, big=False),
+                  "big": dict(zero_len=False, big=True)}
+# what a variant's seeds together must have met (dense_reference); the zero-length variant adds ZERO_LEN_REACH
+DENSE_REACH = ["fragment_extension", "extension_covers_interval", "boundary_to_zero", "boundary_to_len", "both_to_zero", "split",
+               "inside_mask", "equal_mask", "touching", "emptied_everywhere"]
+ZERO_LEN_REACH = "zero_length_mask_range"
+
+
+def dense_case(seed, *, zero_len=False, big=False, n_windows=12):
+    """(lens, (d, min_missing, min_boundary), windows): 1-8 sequences of 1-64 bases, 1-8 rows a window with both
+    coordinates uniform in [0, len], parameters from 0 to beyond every length.  zero_len: rows with q_first == q_last are
+    kept.  big: every length is 2^31 - 1 and every coordinate within 64 of either end."""
+    rng = np.random.default_rng([int(seed), int(zero_len), int(big)])
+    n_seq = int(rng.choice(DENSE_N_SEQ))
+    lens = [I32_MAX] * n_seq if big else [int(x) for x in rng.integers(1, 65, n_seq)]
+    params = tuple(int(rng.choice(c)) for c in (DENSE_D, DENSE_MIN_MISSING, DENSE_MIN_BOUNDARY))
+
+    def coord(s):
+        if not big:
+            return int(rng.integers(0, lens[s] + 1))
+        off = int(rng.integers(0, 65))
+        return off if rng.random() < 0.5 else lens[s] - off
+
+    windows = []
+    for _ in range(n_windows):
+        rows = []
+        for _ in range(int(rng.integers(1, 9))):
+            s = int(rng.integers(0, n_seq))
+            a, b = coord(s), coord(s)
+            while a == b and not zero_len:
+                a, b = coord(s), coord(s)
+            rows.append((s, a, b))
+        windows.append(rows)
+    return lens, params, windows
+
+
+def ref_tables(ref):
+    """(masked, missing) of a Ref.  A sequence of length 0 starts outside the missing map in both implementations
+    (include/impg_gpu.h), where the reference keeps the range (0, 0) until a row touches it: that range is left out."""
+    missing = ref.missing.table()
+    for s, n in enumerate(ref.lens):
+        if n == 0:
+            missing[s] = []
+    return ref.masked.table(), missing
+
+
+def ref_steps(ref, windows, params, window_size, names=None, modes=("longest", "total")):
+    """Apply the windows to `ref`; per window (rows, output rows, masked, missing, {mode: select(mode)}), for replay()."""
+    steps = []
+    for rows in windows:
+        out = ref.apply(rows, *params)
+        masked, missing = ref_tables(ref)
+        steps.append((rows, params, out, masked, missing, {m: ref.select(m, window_size, names) for m in modes}))
+    return steps
+
+
+def replay(reg, steps, window_size, names=None):
+    """A Regions object against the recorded steps of a Ref: rows, both tables and the selections after every window."""
+    for k, (rows, params, out, masked, missing, sel) in enumerate(steps):
+        assert reg.apply(rows_array(rows), *params) == out, (k, params, rows[:8])
+        assert reg.get("masked") == masked, (k, params, rows[:8])
+        assert reg.get("missing") == missing, (k, params, rows[:8])
+        for mode, want in sel.items():
+            assert reg.select(mode, window_size, names) == want, (k, mode, params, rows[:8])
+
+
+def dense_reference(seeds, *, zero_len=False, big=False):
+    """Ref over dense_case(seed) of every seed: ([(seed, lens, window size, steps)], what the seeds reached together).
+    The window size is the longest length, one window a range: on 2^31 - 1 bases a small one enumerates 10^8 windows."""
+    cases, reached = [], set()
+    for seed in seeds:
+        lens, params, windows = dense_case(seed, zero_len=zero_len, big=big)
+        ref = Ref(lens)
+        steps = []
+        for k, rows in enumerate(windows):
+            if all(ref.missing.get(s) is None for s in range(len(lens))):
+                reached.add("emptied_everywhere")  # every missing set has emptied, and a further window is applied
+            steps += ref_steps(ref, [rows], params, max(lens))
+            if any(a == z for v in steps[-1][3].values() for a, z in v):
+                reached.add(ZERO_LEN_REACH)
+        reached |= ref.seen
+        reached |= {name for name, key in (("fragment_extension", "extensions"), ("split", "splits")) if ref.count[key]}
+        cases.append((seed, lens, max(lens), steps))
+    return cases, reached
+
+
+def sparse_case(n_seq):
+    """Many sequences, few of them touched, a few of length 0 (rows on those are (s, 0, 0))."""
+    rng = np.random.default_rng([77, n_seq])
+    lens = [int(x) for x in rng.integers(1, 400, n_seq)]
+    for s in range(3, n_seq, 61):
+        lens[s] = 0
+    hot = sorted({0, n_seq // 2, n_seq - 1, min(3, n_seq - 1)} | {int(x) for x in rng.integers(0, n_seq, 3)})
+    windows = []
+    for _ in range(6):
+        rows = []
+        for _ in range(int(rng.integers(1, 7))):
+            s = hot[int(rng.integers(0, len(hot)))]
+            a, b = (int(x) for x in rng.integers(0, lens[s] + 1, 2))
+            if a != b or lens[s] == 0:
+                rows.append((s, a, b))
+        windows.append(rows or [(0, 0, lens[0])])
+    return lens, (1, 5, 4), windows
+
+
+def row_count_case(n):
+    """n rows that stay n intervals (d = 0, gaps of 3), in random order and strand on two sequences: a fresh mask
+    (n_old = 0), n intervals each split by the warm one, 2n fragment extensions, then n intervals swallowed whole.
+    [(rows, params)] per window."""
+    rng = np.random.default_rng([78, n])
+    lens = [8 * ((n + 1) // 2) + 20] * 2
+
+    def rows(a, b):
+        out = [(i % 2, 8 * (i // 2) + a, 8 * (i // 2) + b) for i in range(n)]
+        out = [r if rng.random() < 0.7 else (r[0], r[2], r[1]) for r in out]
+        return [out[i] for i in rng.permutation(n)]
+
+    first = rows(1, 3)
+    return lens, [(first, (0, 0, 0)), (rows(2, 5), (0, 0, 0)), (rows(7, 8), (0, 3, 0)), (first, (0, 0, 0))]
+
+
+def piece_count_case():
+    """Windows whose subtraction of the old mask leaves exactly the stated number of pieces (none of them touch, so the
+    window's output has as many rows): (lens, params, [(rows, pieces)])."""
+    return [100, 100], (0, 0, 0), [([(0, 10, 20), (0, 30, 40)], 2), ([(0, 12, 18)], 0), ([(0, 15, 25)], 1), ([(0, 5, 28)], 2),
+                                   ([(0, 30, 40)], 0), ([(1, 7, 9)], 1), ([(0, 0, 50), (1, 0, 9)], 4)]
+
+
+def clamp_case():
+    """(lengths as given, lengths as both implementations keep them, params, windows at the clamped end; the last has
+    a zero-length row at 2^31 - 1 itself behind a mask range of its sequence)."""
+    e = I32_MAX
+    return [2 ** 33, 100], [e, 100], (0, 5, 4), [[(0, e - 10, e - 6)], [(0, e - 30, e - 20), (0, e - 3, e)], [(0, e - 50, e - 40), (0, e, e)],
+                                                [(0, e, e - 100)]]
+
+
+TIE_NAMES = ["S%d#%d#c%d" % (k % 5, k % 3, k) for k in range(40)]
+
+
+def tie_case():
+    """40 sequences of 1000 bases, every row a whole hundred: the missing ranges, the sequences' sums and the groups'
+    sums tie all the time."""
+    rng = np.random.default_rng(79)
+    windows = []
+    for _ in range(12):
+        windows.append([(int(s), 100 * int(j), 100 * int(j) + 100) for s, j in zip(rng.integers(0, 40, 10), rng.integers(0, 10, 10))])
+    return [1000] * 40, (0, 0, 0), windows
+
+
+REFUSAL_NAMES = ["A#1#c", "B#1#c", "B#2#c"]
+
+
+def refusal_case(fresh):
+    """(lens, params, windows applied first, valid rows of the refused call, a window for afterwards).  The valid rows
+    alone would move the winner of `total`, `sample` and `haplotype` to another sequence or group."""
+    lens = [1000, 900, 800]
+    if fresh:  # sums 1000 / 900 / 800; the valid rows alone: 50 / 900 / 800
+        return lens, (0, 0, 0), [], [(0, 0, 950)], [(1, 100, 300)]
+    # sums 500 / 800 / 800; the valid rows alone: 500 / 100 / 100
+    return lens, (0, 0, 0), [[(0, 0, 500)], [(1, 100, 200)]], [(1, 200, 900), (2, 0, 700)], [(2, 100, 300)]

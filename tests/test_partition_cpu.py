@@ -128,3 +128,53 @@ def test_rows_beyond_the_callers_buffer_are_kept():
     assert n.value == 13 and [tuple(int(x) for x in r) for r in small] == want[:2]
     assert reg._rows(small, n.value) == want               # fetched whole; the state moved on once
     assert reg.get("masked") == ref.masked.table() and reg.get("missing") == ref.missing.table()
+
+
+# ---- small, collision-dense universes (the inputs of tests/test_gpu_partition_algebra.py, proven here without a GPU) ----
+DENSE_SEEDS = range(150)
+
+
+@pytest.mark.parametrize("variant", list(pr.DENSE_VARIANTS))
+def test_dense_universes(variant):
+    """check_steps' comparison plus the selections, after each of 12 windows of 150 seeds; what the seeds must have
+    reached is asserted from the restatement alone, before the twin is looked at."""
+    cases, reached = pr.dense_reference(DENSE_SEEDS, **pr.DENSE_VARIANTS[variant])
+    want = pr.DENSE_REACH + ([pr.ZERO_LEN_REACH] if variant == "zero_len" else [])
+    assert [c for c in want if c not in reached] == []
+    for seed, lens, w, steps in cases:
+        pr.replay(impg_amd.Regions(lens, on_host=True), steps, w)
+
+
+@pytest.mark.parametrize("n_seq", [1, 2, 255, 256, 257, 1024])
+def test_sparse_universes(n_seq):
+    lens, params, windows = pr.sparse_case(n_seq)
+    assert n_seq < 4 or lens.count(0) >= 1
+    pr.replay(impg_amd.Regions(lens, on_host=True), pr.ref_steps(pr.Ref(lens), windows, params, max(lens)), max(lens))
+
+
+@pytest.mark.parametrize("n", [1, 255, 256, 257, 513])
+def test_row_counts(n):
+    lens, windows = pr.row_count_case(n)
+    ref = pr.Ref(lens)
+    steps = [st for rows, params in windows for st in pr.ref_steps(ref, [rows], params, lens[0])]
+    assert [len(st[2]) for st in steps] == [n, n, n, 0]  # fresh, each split by the mask, each extended, each swallowed
+    assert ref.count["extensions"] == 2 * n - min(n, 2)  # (the last interval of a sequence is far from its end)
+    pr.replay(impg_amd.Regions(lens, on_host=True), steps, lens[0])
+
+
+def test_piece_counts_and_clamped_length():
+    lens, params, windows = pr.piece_count_case()
+    steps = pr.ref_steps(pr.Ref(lens), [rows for rows, _ in windows], params, 100)
+    assert [len(st[2]) for st in steps] == [pieces for _, pieces in windows]
+    pr.replay(impg_amd.Regions(lens, on_host=True), steps, 100)
+    given, kept, params, windows = pr.clamp_case()
+    reg = impg_amd.Regions(given, on_host=True)
+    assert reg.get("missing")[0] == [(0, pr.I32_MAX)]
+    pr.replay(reg, pr.ref_steps(pr.Ref(kept), windows, params, pr.I32_MAX), pr.I32_MAX)
+
+
+def test_dense_ties():
+    lens, params, windows = pr.tie_case()
+    modes = ("longest", "total", "sample", "haplotype")
+    for w in (1000, 300):
+        pr.replay(impg_amd.Regions(lens, on_host=True), pr.ref_steps(pr.Ref(lens), windows, params, w, pr.TIE_NAMES, modes), w, pr.TIE_NAMES)
