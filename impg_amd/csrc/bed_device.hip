@@ -19,12 +19,11 @@
 //             span merged before it (else the run's first row's): main.rs:12535-12547 unrolled.
 #include <hip/hip_runtime.h>
 
-#include <rocprim/device/device_scan.hpp>
-
 #include <algorithm>
 #include <functional>
 #include <string>
 
+#include "device_prims.hpp"
 #include "engine.hpp"
 
 namespace impg {
@@ -48,11 +47,6 @@ __global__ __launch_bounds__(256) void gap_keys_kernel(Rows R, uint32_t n, unsig
   k32[i] = ord_u32(f ? c.x : -c.x);  // q.first ascending on '+', descending on '-' (main.rs:12893-12901)
   k64[i] = ((((unsigned long long)R.q[i] << seq_bits | R.qid[i]) << seq_bits | R.tid[i]) << 1) | (f ? 1ull : 0ull);
   idx[i] = i;
-}
-__global__ __launch_bounds__(256) void gather_u64_by_kernel(const unsigned long long *__restrict__ src, const uint32_t *__restrict__ idx,
-                                                            uint32_t n, unsigned long long *__restrict__ dst) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i < n) dst[i] = src[idx[i]];
 }
 __device__ __forceinline__ uint32_t uf_find(uint32_t *parent, uint32_t x) {
   uint32_t p = parent[x];
@@ -94,10 +88,6 @@ __global__ __launch_bounds__(256) void gap_link_kernel(Rows R, const uint32_t *_
     const bool t_forward = f ? B.z > A.z : B.w < A.w;
     if (t_forward && t_gap <= d) uf_unite(parent, ia, ib);
   }
-}
-__global__ __launch_bounds__(256) void iota_u32_kernel(uint32_t *v, uint32_t n) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i < n) v[i] = i;
 }
 // the chain's bounding box, gathered at its root (the box itself is order-independent)
 __global__ __launch_bounds__(256) void gap_box_kernel(Rows R, uint32_t n, uint32_t *__restrict__ parent, int4 *__restrict__ box,
@@ -321,13 +311,13 @@ uint32_t device_bed_rows(Engine &E, const impg_gpu_index &ix, uint32_t n_ranges,
   if (merge_distance >= 0 && n > 1) {
     gap_keys_kernel<<<cdiv(n, 256), 256, 0, s>>>(R, n, seq_bits, k32a.as<uint32_t>(), k64a.as<unsigned long long>(), ia.as<uint32_t>());
     launch_sort_u32(tmp.p, tmp.cap, k32a.as<uint32_t>(), k32b.as<uint32_t>(), ia.as<uint32_t>(), ib.as<uint32_t>(), n, s, 0, 32);
-    gather_u64_by_kernel<<<cdiv(n, 256), 256, 0, s>>>(k64a.as<unsigned long long>(), ib.as<uint32_t>(), n, k64b.as<unsigned long long>());
+    prims::gather_kernel<<<cdiv(n, 256), 256, 0, s>>>(k64a.as<unsigned long long>(), ib.as<uint32_t>(), n, k64b.as<unsigned long long>());
     launch_sort_pairs(tmp.p, tmp.cap, k64b.as<unsigned long long>(), k64a.as<unsigned long long>(), ib.as<uint32_t>(), ia.as<uint32_t>(), n,
                       q_bits + 2 * seq_bits + 1, s);
     // sorted: keys in k64a, perm in ia
     DevBuf parent, box, root_flag, root_pos;
     parent.reserve(nb4); box.reserve((size_t)n * 16); root_flag.reserve(nb4); root_pos.reserve(nb4);
-    iota_u32_kernel<<<cdiv(n, 256), 256, 0, s>>>(parent.as<uint32_t>(), n);
+    prims::iota_kernel<<<cdiv(n, 256), 256, 0, s>>>(parent.as<uint32_t>(), n);
     gap_link_kernel<<<cdiv(n, 256), 256, 0, s>>>(R, ia.as<uint32_t>(), k64a.as<unsigned long long>(), n, merge_distance, parent.as<uint32_t>());
     IMPG_HIP(hipMemcpyAsync(box.p, rc.p, (size_t)n * 16, hipMemcpyDeviceToDevice, s));
     gap_box_kernel<<<cdiv(n, 256), 256, 0, s>>>(R, n, parent.as<uint32_t>(), box.as<int4>(), root_flag.as<uint32_t>());
@@ -348,7 +338,7 @@ uint32_t device_bed_rows(Engine &E, const impg_gpu_index &ix, uint32_t n_ranges,
     DevBuf k64c;
     k64c.reserve(nb8);
     launch_sort_pairs(tmp.p, tmp.cap, k64a.as<unsigned long long>(), k64c.as<unsigned long long>(), ia.as<uint32_t>(), ib.as<uint32_t>(), m, 33, s);
-    gather_u64_by_kernel<<<cdiv(m, 256), 256, 0, s>>>(k64b.as<unsigned long long>(), ib.as<uint32_t>(), m, k64a.as<unsigned long long>());
+    prims::gather_kernel<<<cdiv(m, 256), 256, 0, s>>>(k64b.as<unsigned long long>(), ib.as<uint32_t>(), m, k64a.as<unsigned long long>());
     launch_sort_pairs(tmp.p, tmp.cap, k64a.as<unsigned long long>(), k64c.as<unsigned long long>(), ib.as<uint32_t>(), ia.as<uint32_t>(), m,
                       q_bits + seq_bits, s);
     // sorted: keys in k64c, perm in ia
@@ -358,13 +348,8 @@ uint32_t device_bed_rows(Engine &E, const impg_gpu_index &ix, uint32_t n_ranges,
     (void)E.scan(seg_head.as<uint32_t>(), seg_id.as<uint32_t>(), m);
     axis_val_kernel<<<cdiv(m, 256), 256, 0, s>>>(cur, ia.as<uint32_t>(), seg_head.as<uint32_t>(), seg_id.as<uint32_t>(), m, val.as<unsigned long long>());
     {
-      size_t sb = 0;
-      IMPG_HIP(rocprim::inclusive_scan(nullptr, sb, val.as<unsigned long long>(), pmax.as<unsigned long long>(), m,
-                                       rocprim::maximum<unsigned long long>(), s));
       DevBuf stmp;
-      stmp.reserve(std::max<size_t>(sb, 256));
-      IMPG_HIP(rocprim::inclusive_scan(stmp.p, sb, val.as<unsigned long long>(), pmax.as<unsigned long long>(), m,
-                                       rocprim::maximum<unsigned long long>(), s));
+      prims::inclusive_max(stmp, val.as<unsigned long long>(), pmax.as<unsigned long long>(), m, s);
       IMPG_HIP(hipStreamSynchronize(s));  // (stmp dies here)
     }
     axis_run_heads_kernel<<<cdiv(m, 256), 256, 0, s>>>(cur, ia.as<uint32_t>(), seg_head.as<uint32_t>(), pmax.as<unsigned long long>(), m, merge_distance,
@@ -376,11 +361,8 @@ uint32_t device_bed_rows(Engine &E, const impg_gpu_index &ix, uint32_t n_ranges,
     head_of.reserve((size_t)m * 4);
     if (merge_strands) {
       head_pos_kernel<<<cdiv(m, 256), 256, 0, s>>>(run_head.as<uint32_t>(), m, seg_id.as<uint32_t>());
-      size_t sb = 0;
-      IMPG_HIP(rocprim::inclusive_scan(nullptr, sb, seg_id.as<uint32_t>(), head_of.as<uint32_t>(), m, rocprim::maximum<uint32_t>(), s));
       DevBuf stmp;
-      stmp.reserve(std::max<size_t>(sb, 256));
-      IMPG_HIP(rocprim::inclusive_scan(stmp.p, sb, seg_id.as<uint32_t>(), head_of.as<uint32_t>(), m, rocprim::maximum<uint32_t>(), s));
+      prims::inclusive_max(stmp, seg_id.as<uint32_t>(), head_of.as<uint32_t>(), m, s);
       IMPG_HIP(hipStreamSynchronize(s));
     }
     axis_emit_kernel<<<cdiv(m, 256), 256, 0, s>>>(cur, ia.as<uint32_t>(), run_head.as<uint32_t>(), run_pos.as<uint32_t>(), pmax.as<unsigned long long>(),
@@ -442,10 +424,7 @@ void device_bed_text(Engine &E, const impg_gpu_index &ix, const DevBuf &rows, ui
   len.reserve((size_t)n_rows * 4);
   off.reserve((size_t)(n_rows + 1) * 8);
   text_len_kernel<<<cdiv(n_rows, 256), 256, 0, s>>>(rows.as<BedRow>(), n_rows, t, len.as<uint32_t>());
-  size_t sb = 0;
-  IMPG_HIP(rocprim::exclusive_scan(nullptr, sb, len.as<uint32_t>(), off.as<unsigned long long>(), 0ull, n_rows, rocprim::plus<unsigned long long>(), s));
-  stmp.reserve(std::max<size_t>(sb, 256));
-  IMPG_HIP(rocprim::exclusive_scan(stmp.p, sb, len.as<uint32_t>(), off.as<unsigned long long>(), 0ull, n_rows, rocprim::plus<unsigned long long>(), s));
+  prims::exclusive_sum(stmp, len.as<uint32_t>(), off.as<unsigned long long>(), n_rows, s);
   // piece boundaries: whole rows, at most PIECE bytes each; found on the host from a sampled copy of the offsets
   constexpr size_t PIECE = 256ull << 20;
   std::vector<unsigned long long> h_off(n_rows);

@@ -17,8 +17,6 @@
 // as the checker: tests/test_gpu_parity.py::test_device_build_matches_host_build compares the saved bytes.
 #include <hip/hip_runtime.h>
 
-#include <rocprim/device/device_scan.hpp>
-
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -27,6 +25,7 @@
 #include <functional>
 #include <thread>
 
+#include "device_prims.hpp"
 #include "kernels.hpp"
 
 namespace impg {
@@ -458,10 +457,7 @@ bool build_index_device(impg_gpu_index &ix, const impg_gpu_record_t *records, si
   if (n_records) {
     entry_counts_kernel<<<cdiv(n_records, 256), 256, 0, s>>>(d_rec.as<impg_gpu_record_t>(), (uint32_t)n_records, bidirectional ? 1 : 0, dev_owner, shard,
                                                              cnt.as<uint32_t>());
-    size_t sb = 0;
-    IMPG_HIP(rocprim::exclusive_scan(nullptr, sb, cnt.as<uint32_t>(), pos.as<uint32_t>(), 0u, n_records, rocprim::plus<uint32_t>(), s));
-    tmp.reserve(std::max<size_t>(sb, 256));
-    IMPG_HIP(rocprim::exclusive_scan(tmp.p, sb, cnt.as<uint32_t>(), pos.as<uint32_t>(), 0u, n_records, rocprim::plus<uint32_t>(), s));
+    prims::exclusive_sum(tmp, cnt.as<uint32_t>(), pos.as<uint32_t>(), n_records, s);
     entry_keys_kernel<<<cdiv(n_records, 256), 256, 0, s>>>(d_rec.as<impg_gpu_record_t>(), (uint32_t)n_records, bidirectional ? 1 : 0, dev_owner, shard,
                                                            pos.as<uint32_t>(), key.as<unsigned long long>(), val.as<uint32_t>());
   }
@@ -476,10 +472,7 @@ bool build_index_device(impg_gpu_index &ix, const impg_gpu_record_t *records, si
   uint64_t n_ext = 0;
   if (n_entries) {
     ext_counts_kernel<<<cdiv(n_entries, 256), 256, 0, s>>>(d_rec.as<impg_gpu_record_t>(), val2.as<uint32_t>(), (uint32_t)n_entries, ext_cnt.as<uint32_t>());
-    size_t sb = 0;
-    IMPG_HIP(rocprim::exclusive_scan(nullptr, sb, ext_cnt.as<uint32_t>(), ext_off.as<unsigned long long>(), 0ull, n_entries, rocprim::plus<unsigned long long>(), s));
-    tmp.reserve(std::max<size_t>(sb, 256));
-    IMPG_HIP(rocprim::exclusive_scan(tmp.p, sb, ext_cnt.as<uint32_t>(), ext_off.as<unsigned long long>(), 0ull, n_entries, rocprim::plus<unsigned long long>(), s));
+    prims::exclusive_sum(tmp, ext_cnt.as<uint32_t>(), ext_off.as<unsigned long long>(), n_entries, s);
     unsigned long long last_off = 0;
     uint32_t last_cnt = 0;
     IMPG_HIP(hipMemcpyAsync(&last_off, ext_off.as<unsigned long long>() + (n_entries - 1), 8, hipMemcpyDeviceToHost, s));
@@ -498,12 +491,7 @@ bool build_index_device(impg_gpu_index &ix, const impg_gpu_record_t *records, si
                                                         (uint32_t)n_entries, ix.blob(10)->as<uint32_t>(), ix.blob(9)->as<Entry>(),
                                                         ix.blob(11)->as<uint32_t>(), ix.blob(1)->as<int32_t>(), ix.blob(2)->as<int32_t>(),
                                                         ix.blob(3)->as<int32_t>(), maxin.as<unsigned long long>());
-    size_t sb = 0;
-    IMPG_HIP(rocprim::inclusive_scan(nullptr, sb, maxin.as<unsigned long long>(), maxout.as<unsigned long long>(), n_entries,
-                                     rocprim::maximum<unsigned long long>(), s));
-    tmp.reserve(std::max<size_t>(sb, 256));
-    IMPG_HIP(rocprim::inclusive_scan(tmp.p, sb, maxin.as<unsigned long long>(), maxout.as<unsigned long long>(), n_entries,
-                                     rocprim::maximum<unsigned long long>(), s));
+    prims::inclusive_max(tmp, maxin.as<unsigned long long>(), maxout.as<unsigned long long>(), n_entries, s);
     pmax_kernel<<<cdiv(n_entries, 256), 256, 0, s>>>(maxout.as<unsigned long long>(), (uint32_t)n_entries, ix.blob(4)->as<int32_t>());
   }
   lap("entries + columns");
@@ -683,10 +671,7 @@ uint64_t tokenize_on_device(ParsedPaf &pp, int device, DevBuf &d_ops) {
     hipStream_t s = nullptr;
     cigar_count_kernel<<<cdiv(n, 4), 256, 0, s>>>(d_text.as<char>(), d_boff.as<unsigned long long>(), d_blen.as<uint32_t>(), (uint32_t)n,
                                                   d_cnt.as<uint32_t>(), d_bad.as<uint32_t>());
-    size_t sb = 0;
-    IMPG_HIP(rocprim::exclusive_scan(nullptr, sb, d_cnt.as<uint32_t>(), d_off.as<unsigned long long>(), 0ull, n, rocprim::plus<unsigned long long>(), s));
-    tmp.reserve(std::max<size_t>(sb, 256));
-    IMPG_HIP(rocprim::exclusive_scan(tmp.p, sb, d_cnt.as<uint32_t>(), d_off.as<unsigned long long>(), 0ull, n, rocprim::plus<unsigned long long>(), s));
+    prims::exclusive_sum(tmp, d_cnt.as<uint32_t>(), d_off.as<unsigned long long>(), n, s);
     IMPG_HIP(hipMemcpyAsync(cnt.data(), d_cnt.p, n * 4, hipMemcpyDeviceToHost, s));
     IMPG_HIP(hipMemcpyAsync(off.data(), d_off.p, n * 8, hipMemcpyDeviceToHost, s));
     uint32_t bad = 0;

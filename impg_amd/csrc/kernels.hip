@@ -20,8 +20,8 @@
 #include <hip/hip_runtime.h>
 
 #include <cstring>
-#include <rocprim/device/device_radix_sort.hpp>
 
+#include "device_prims.hpp"
 #include "impg_internal.hpp"
 #include "kernels.hpp"
 
@@ -571,9 +571,6 @@ __global__ __launch_bounds__(256) void run_lengths_kernel(const uint32_t *__rest
 // what each home rank sent); the block goes above the window bits, so the order is block by block and a block's
 // pairs stay together.
 // where a range's window will be in the entry array, estimated from the record alone (the lookup order's key)
-#ifndef IMPG_ORDER_KEY_F64
-#define IMPG_ORDER_KEY_F64 1
-#endif
 __device__ __forceinline__ uint32_t order_key(const SegDesc *__restrict__ seg, const int32_t *__restrict__ seq_len, uint32_t n_seq,
                                               uint32_t target_id, int32_t start) {
   if (target_id >= n_seq) return 0u;
@@ -585,7 +582,7 @@ __device__ __forceinline__ uint32_t order_key(const SegDesc *__restrict__ seg, c
     // floor(st * n / len): a 64-bit integer division is a long sequence per record; in double precision the product is
     // exact below 2^53 (a 31-bit start, a segment of < 2^22 entries), the quotient correctly rounded, and a quotient that
     // is no integer lies at least 1 / len from one -- so the truncation is the integer division's result
-    if (IMPG_ORDER_KEY_F64 && d.y < (1u << 22)) rel = (uint64_t)((double)st * (double)d.y / (double)(uint32_t)len);
+    if (d.y < (1u << 22)) rel = (uint64_t)((double)st * (double)d.y / (double)(uint32_t)len);
     else rel = (uint64_t)st * d.y / (uint64_t)(uint32_t)len;
   }
   return d.x + (uint32_t)min(rel, (uint64_t)(d.y ? d.y - 1u : 0u));
@@ -926,11 +923,8 @@ __global__ __launch_bounds__(256) void scan_apply(const uint32_t *__restrict__ i
 // per range are small); prefixes are 64-bit, the offsets written are their low 32 bits and *total is exact.
 // (n < 2^32 - 4096, like the three-kernel form: a tile's lane offsets are 32-bit; the engine's counts stay far below.)
 // The three kernels above read the counts twice and ran the level's 8 x 10^7-range scan at 2.3 TB/s (282 + 89 + 72 us);
-// IMPG_SCAN_LOOKBACK = 0 brings them back.
+// they remain the path for pointers that are not 16-byte aligned.
 // ---------------------------------------------------------------------------
-#ifndef IMPG_SCAN_LOOKBACK
-#define IMPG_SCAN_LOOKBACK 1
-#endif
 constexpr uint32_t LB_ITEMS = 16, LB_BLOCK = 256, LB_TILE = LB_ITEMS * LB_BLOCK;
 constexpr unsigned long long LB_FLAG_SUM = 1ull << 62, LB_FLAG_INCL = 2ull << 62, LB_VALUE = (1ull << 62) - 1ull;
 __global__ __launch_bounds__(LB_BLOCK) void scan_lookback_kernel(const uint32_t *__restrict__ in, uint32_t *__restrict__ out, uint32_t n,
@@ -1021,7 +1015,7 @@ __global__ __launch_bounds__(LB_BLOCK) void scan_lookback_kernel(const uint32_t 
 
 void launch_exclusive_scan(const uint32_t *d_in, uint32_t *d_out, uint32_t n, unsigned long long *d_bsum,
                            unsigned long long *d_total, hipStream_t s) {
-  if (IMPG_SCAN_LOOKBACK && ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_out)) & 15u) == 0u) {
+  if (((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_out)) & 15u) == 0u) {
     const uint32_t nt = std::max<uint32_t>((n + LB_TILE - 1) / LB_TILE, 1u);
     IMPG_HIP(hipMemsetAsync(d_bsum, 0, ((size_t)nt + 1) * sizeof(unsigned long long), s));
     scan_lookback_kernel<<<nt, LB_BLOCK, 0, s>>>(d_in, d_out, n, d_bsum, nt, d_total);
@@ -1420,24 +1414,16 @@ __device__ unsigned long long g_phase_clk[16];
 #define PHASE_ARG
 #define PHASE_PASS
 #endif
-#ifdef IMPG_PROJECT_WAVES  // (experiments: force the register allocation that gives this many waves per SIMD)
-#define PROJECT_OCCUPANCY __attribute__((amdgpu_waves_per_eu(IMPG_PROJECT_WAVES, IMPG_PROJECT_WAVES)))
-#else
-#define PROJECT_OCCUPANCY
-#endif
 constexpr uint32_t PROJ_BLOCK = IMPG_PROJ_BLOCK, PROJ_WAVES = PROJ_BLOCK / 64u;
 // LDS copies of entries and prefix lines (project_staged_kernel) are padded so that lanes reading the same word of
 // different entries / lines do not meet on one bank: the strides are 4 banks (16 bytes) off a multiple of the 32.
 constexpr uint32_t STG_ENT_STRIDE = 20u;                                   // words per staged entry (16 + 4)
 constexpr uint32_t STG_LINE_STRIDE = TILE_WORDS + 4u;                      // words per staged prefix line
 constexpr uint32_t STG_REC_STRIDE = INLINE_TILES * STG_LINE_STRIDE + 4u;   // words per staged record (8 lines)
-// project_entries_kernel (IMPG_ENT_CP_LDS, round 5): the entry's words 4 .. 15 -- the record totals and the seven inline
+// project_entries_kernel (round 5): the entry's words 4 .. 15 -- the record totals and the seven inline
 // checkpoints -- also sit behind the wave's LDS record, and a chunk's lanes read them from there (two broadcast reads)
 // instead of comparing against scalar registers: held in scalars they were the registers the allocator spilled (the
 // kernel runs at its 102-SGPR limit), and every chunk fetched them back with fourteen v_readlane.
-#ifndef IMPG_ENT_CP_LDS
-#define IMPG_ENT_CP_LDS 1
-#endif
 constexpr uint32_t ENT_CP_OFF = INLINE_TILES * STG_LINE_STRIDE;           // where the entry's checkpoint words sit in the wave's LDS record
 // One (range, entry) pair: project_overlapping_interval's PAF branch (impg.rs:1260-1312) for the range [f_start, f_end)
 // against entry eidx.  ok: the projection exists (and passes the identity filter); qid / res: its query sequence and
@@ -1501,7 +1487,7 @@ __device__ __forceinline__ void project_core(const DeviceIndexView &v, uint4 e0,
     c.m = (n + TILE_OPS - 1) / TILE_OPS;
     c.totT = e1.w;
     c.totQ = e2.x;
-    if (IMPG_ENT_CP_LDS && STAGED && ORIENT >= 0) {
+    if (STAGED && ORIENT >= 0) {
       // (record totals off the wave's LDS record too: as scalars they were two more of the spilled registers, fetched back
       // ten times a chunk)
       c.totT = st_pfx[ENT_CP_OFF + 3u];
@@ -1534,7 +1520,7 @@ __device__ __forceinline__ void project_core(const DeviceIndexView &v, uint4 e0,
       if (ORIENT >= 0 || c.m <= INLINE_TILES) {  // (a known orientation is only handed in for a record of at most INLINE_TILES tiles)
         // the seven inline slots hold P[1..m-1], P[m] = totT, then INT_MAX (index_build.cpp); P[8] is totT when m = 8
         uint4 p2 = e2, p3 = e3;
-        if (IMPG_ENT_CP_LDS && STAGED && ORIENT >= 0) {
+        if (STAGED && ORIENT >= 0) {
           const uint4 *cp = reinterpret_cast<const uint4 *>(__builtin_assume_aligned(st_pfx, 16)) + ENT_CP_OFF / 4u;
           p2 = cp[1];
           p3 = cp[2];
@@ -1822,9 +1808,8 @@ __device__ __forceinline__ uint32_t select_bit64(uint32_t lo, uint32_t hi, uint3
 __device__ __forceinline__ void put_ordered_row(const OrderedOut &o, uint32_t d, uint32_t qid, uint32_t tid, bool ok, int32_t qs, int32_t qe,
                                                 int32_t ts, int32_t te) {
   const bool on = ok && !(o.min_output_length >= 0 && abs(qe - qs) < o.min_output_length);
-#ifdef IMPG_ORD_NOSTORE  // (experiment: the kernel without its row stores)
-  if (!(qs == -0x7FFFFFF0 && te == 0x7FFFFFF1)) return;
-#endif
+  // (with the row stores compiled out the ordered step went 51.03 -> 47.0 ms, project 31.95 -> 28.5: what the stores cost;
+  // that build arm is removed, see DESIGN_HISTORY and profiles/r6_ordered_rows_ab.log)
   // (24 bytes at an 8-byte boundary: a 16-byte and an 8-byte store.  A row is a line of its own among 10^9 and every store
   // instruction of a wave touches 64 lines -- ~12 ms of the headline's final level per such instruction, measured; rows of
   // one aligned 32-byte sector cost the same: it is the scattered store, not a read-modify-write)
@@ -1953,7 +1938,7 @@ __device__ __forceinline__ void count_accepted(uint32_t mine, unsigned long long
 // VGPRs / 7 waves: 36.5 ms against 33.6.  The kernel is bound by a shared pipe (the vector-memory path, see DESIGN
 // 5.2), not by the latency of any one read.)
 template <bool TRANSITIVE, int MODE>
-__global__ __launch_bounds__(PROJ_BLOCK) PROJECT_OCCUPANCY void project_kernel(DeviceIndexView v, const FrontierRec *__restrict__ fr,
+__global__ __launch_bounds__(PROJ_BLOCK) void project_kernel(DeviceIndexView v, const FrontierRec *__restrict__ fr,
                                                       const uint32_t *__restrict__ pair_range,
                                                       const uint32_t *__restrict__ pair_entry, uint32_t n_pairs,
                                                       HitArrays h, unsigned long long *__restrict__ accepted,
@@ -2125,17 +2110,12 @@ __device__ __forceinline__ uint32_t project_places(const DeviceIndexView &v, con
   }
   return n_ok;
 }
-#ifdef IMPG_STG_WAVES  // (experiments: force the register allocation that gives this many waves per SIMD)
-#define STG_OCCUPANCY __attribute__((amdgpu_waves_per_eu(IMPG_STG_WAVES, IMPG_STG_WAVES)))
-#else
-#define STG_OCCUPANCY
-#endif
 // MASKS: the level's pairs are named by the count pass's hit masks (WindowLists with tile_first, a counting run's final
 // level); else by the emit pass's list pair_entry[place] (slots by place, kernels.hpp).  Either way a block takes
 // STG_RANGES consecutive ranges of the lookup order and all their places -- wl.pair_off[], the windows and the
 // ranges' (start, end) go to LDS first, so a place finds its range, its entry and the range's ends without leaving the CU.
 template <bool TRANSITIVE, bool MASKS, int OUT = OUT_SLOTS>
-__global__ __launch_bounds__(STG_THREADS) STG_OCCUPANCY void project_staged_kernel(DeviceIndexView v, const uint32_t *__restrict__ pair_entry,
+__global__ __launch_bounds__(STG_THREADS) void project_staged_kernel(DeviceIndexView v, const uint32_t *__restrict__ pair_entry,
                                                       uint32_t n_pairs, HitArrays h, unsigned long long *__restrict__ accepted,
                                                       uint32_t *__restrict__ err_flag, int regroup, WindowLists wl) {
   // (XCD-contiguous mapping as in project_kernel)
@@ -2262,12 +2242,8 @@ __global__ __launch_bounds__(STG_THREADS) STG_OCCUPANCY void project_staged_kern
 // Ranges whose window is wider than the mask (their pairs are listed by the wave-per-range emit) are projected at the
 // end from that list; a block whose pairs are few for the entries they touch takes project_places (nothing staged).
 // ---------------------------------------------------------------------------
-// IMPG_ENT_GROUP_SKIP = 1: an entry's enumeration only looks at the groups of 64 ranges whose masks can name it (one LDS read and
-// a ballot pick one or two of the eight).  Measured, round 5: 21.7 -> 21.8-22.1 ms -- the eight unrolled ballots overlap with
-// the record's LDS traffic and cost less than the loop that replaces them.  0 (the default): all eight.
-#ifndef IMPG_ENT_GROUP_SKIP
-#define IMPG_ENT_GROUP_SKIP 0
-#endif
+// (Round 5, measured and removed, see DESIGN_HISTORY: an enumeration that only looked at the one or two groups of 64 ranges whose
+// masks can name the entry ran 21.7 -> 21.8-22.1 ms -- the eight unrolled ballots overlap with the record's LDS traffic.)
 #ifndef IMPG_ENT_RANGES
 #define IMPG_ENT_RANGES 512
 #endif
@@ -2276,12 +2252,9 @@ __global__ __launch_bounds__(STG_THREADS) STG_OCCUPANCY void project_staged_kern
 #endif
 constexpr uint32_t ENT_RANGES = IMPG_ENT_RANGES;                          // ranges (consecutive in the lookup order) per block
 constexpr uint32_t ENT_THREADS = IMPG_ENT_THREADS, ENT_WAVES = ENT_THREADS / 64u;
-// IMPG_ENT_E0_LDS: a chunk's lanes also take the entry's coordinates (words 0 .. 3) from the LDS copy, as vector registers:
+// A chunk's lanes also take the entry's coordinates (words 0 .. 3) from the LDS copy, as vector registers:
 // an add or a compare with a scalar operand issues at half the rate of one on vector registers (profiles/r3_issue_rate.json),
 // and four more scalars are free.  Projection of a headline step 19.1 -> 18.7 ms on the same box.
-#ifndef IMPG_ENT_E0_LDS
-#define IMPG_ENT_E0_LDS 1
-#endif
 constexpr uint32_t ENT_REC_STRIDE = ENT_CP_OFF + 16u;                     // words of a wave's LDS record (8 padded lines, then the entry: words 4 .. 15, 0 .. 3)
 static_assert((ENT_RANGES & (ENT_RANGES - 1u)) == 0u && ENT_RANGES % ENT_THREADS == 0 && ENT_THREADS % 64u == 0, "whole turns of the block over its ranges");
 constexpr uint32_t ENT_REC_V4 = ENT_WAVES * ENT_REC_STRIDE / 4u, ENT_LIST_V4 = ENT_WAVES * ENT_RANGES * 2u / 16u;
@@ -2292,11 +2265,6 @@ static_assert((ENT_REC_V4 + ENT_LIST_V4) * 4u >= 5u * ENT_THREADS + ENT_WAVES, "
 // 19.2 at 5, 18.8 at 6 (the block's 24 KB of LDS allow no more).
 #ifndef IMPG_ENT_WAVES
 #define IMPG_ENT_WAVES 6
-#endif
-#if IMPG_ENT_WAVES > 0
-#define ENT_OCCUPANCY __attribute__((amdgpu_waves_per_eu(IMPG_ENT_WAVES, IMPG_ENT_WAVES)))
-#else
-#define ENT_OCCUPANCY
 #endif
 // (Round 5, measured and dropped: a fast path without the second candidate test -- the neighbouring op chosen up front by two
 // comparisons when the located op only touches the threshold, ~2 % of ends; the 0.1 % of pairs that still fail listed in
@@ -2317,7 +2285,7 @@ __device__ __forceinline__ void project_entry_chunk(const DeviceIndexView &v, ui
     res.found = res.any = false;
     res.pqs = res.pts = res.pqe = res.pte = -1;
     uint32_t qid = HIT_NONE;
-    if (IMPG_ENT_E0_LDS && IMPG_ENT_CP_LDS && ORIENT >= 0) {
+    if (ORIENT >= 0) {
       e0 = reinterpret_cast<const uint4 *>(__builtin_assume_aligned(rec, 16))[ENT_CP_OFF / 4u + 3u];
       asm volatile("" : "+v"(e0.x), "+v"(e0.y), "+v"(e0.z), "+v"(e0.w));
     }
@@ -2360,7 +2328,8 @@ struct EntSlices {
   int phase;
 };
 template <bool TRANSITIVE, int MODE, int OUT>
-__global__ __launch_bounds__(ENT_THREADS) ENT_OCCUPANCY void project_entries_kernel(DeviceIndexView v, const uint32_t *__restrict__ pair_entry, uint32_t n_pairs,
+__global__ __launch_bounds__(ENT_THREADS) __attribute__((amdgpu_waves_per_eu(IMPG_ENT_WAVES, IMPG_ENT_WAVES)))
+void project_entries_kernel(DeviceIndexView v, const uint32_t *__restrict__ pair_entry, uint32_t n_pairs,
                                                       HitArrays h, unsigned long long *__restrict__ accepted,
                                                       uint32_t *__restrict__ err_flag, int regroup, WindowLists wl, double min_identity, EntSlices sl) {
   const uint32_t per_xcd = gridDim.x >> 3;
@@ -2382,9 +2351,6 @@ __global__ __launch_bounds__(ENT_THREADS) ENT_OCCUPANCY void project_entries_ker
   constexpr bool ordered = OUT == OUT_ROWS;
   constexpr bool qs = OUT == OUT_QS;  // slots as {query id, the range's place} pairs in h.qid (a kept fused level)
   constexpr bool WIDE_LISTED = ordered;  // windows wider than the hit mask: listed (pair_entry, in visit order) or by the window test
-#if IMPG_ENT_GROUP_SKIP
-  __shared__ int2 st_grp[ENT_RANGES / 64u];  // per 64 ranges: the first and the last entry their masks name
-#endif
   __shared__ uint32_t st_nwide, st_alloc, st_next;
   __shared__ uint32_t wred[2u * ENT_WAVES];
   __shared__ uint32_t wcnt[ENT_WAVES];
@@ -2428,16 +2394,6 @@ __global__ __launch_bounds__(ENT_THREADS) ENT_OCCUPANCY void project_entries_ker
         emax = max(emax, ghi);
       }
     }
-#if IMPG_ENT_GROUP_SKIP
-    {  // the 64 ranges this wave has just loaded are one group of the enumeration below
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        glo = min(glo, (uint32_t)__shfl_xor((int)glo, o));
-        ghi = max(ghi, (uint32_t)__shfl_xor((int)ghi, o));
-      }
-      if (l == 0) st_grp[t >> 6] = make_int2((int32_t)glo, (int32_t)ghi);  // (an empty group: lo > hi, nothing lies between)
-    }
-#endif
   }
   {
 #pragma unroll
@@ -2520,7 +2476,7 @@ __global__ __launch_bounds__(ENT_THREADS) ENT_OCCUPANCY void project_entries_ker
       // this entry's record into the wave's LDS record (the previous entry's reads are done: their results were used)
       __builtin_amdgcn_wave_barrier();
       st_rec[wv][(l >> 3) * (STG_LINE_STRIDE / 4u) + (l & 7u)] = lc;
-      if (IMPG_ENT_CP_LDS && l < 4u) st_rec[wv][ENT_CP_OFF / 4u + ((l + 3u) & 3u)] = cq;  // (words 4 .. 15, then 0 .. 3)
+      if (l < 4u) st_rec[wv][ENT_CP_OFF / 4u + ((l + 3u) & 3u)] = cq;  // (words 4 .. 15, then 0 .. 3)
       uint4 e0, e1, e2, e3;
       e0.x = IMPG_RDL(cq.x, 0); e0.y = IMPG_RDL(cq.y, 0); e0.z = IMPG_RDL(cq.z, 0); e0.w = IMPG_RDL(cq.w, 0);
       e1.x = IMPG_RDL(cq.x, 1); e1.y = IMPG_RDL(cq.y, 1); e1.z = IMPG_RDL(cq.z, 1); e1.w = IMPG_RDL(cq.w, 1);
@@ -2539,20 +2495,9 @@ __global__ __launch_bounds__(ENT_THREADS) ENT_OCCUPANCY void project_entries_ker
       uint32_t cnt = 0;
       // (what the count pass tested a wide window's entries with -- ends[] / ends_t[] -- from the entry's own words: no load)
       const int32_t e_end = TRANSITIVE ? ((int32_t)e0.x < (int32_t)e0.y ? (int32_t)e0.y : (-2147483647 - 1)) : (int32_t)e0.y;
-#if IMPG_ENT_GROUP_SKIP
-      // (in the lookup order a block's 512 ranges climb through its ~50 entries: one or two of the eight groups of 64 can
-      // name a given entry at all -- found with one LDS read and a ballot; the other groups' masks are not looked at)
-      const int2 gb = st_grp[l & (ENT_RANGES / 64u - 1u)];
-      uint32_t groups = (uint32_t)__ballot(l < ENT_RANGES / 64u && eidx >= (uint32_t)gb.x && eidx <= (uint32_t)gb.y);
-#pragma unroll 1
-      for (; groups; groups &= groups - 1u) {
-        const uint32_t q = (uint32_t)__builtin_ctz(groups);
-        const uint32_t r = q * 64u + l;
-#else
 #pragma unroll
       for (uint32_t q = 0; q < ENT_RANGES / 64u; q++) {
         const uint32_t r = q * 64u + l;
-#endif
         bool hit = false;
         if (r < nr) {
           const uint4 w = st_win[r];
@@ -3286,17 +3231,8 @@ __device__ __forceinline__ uint32_t lower_bound_start(const int2 *a, uint32_t n,
 #define IMPG_VU_LDS_CAP 12
 #endif
 constexpr uint32_t VU_LDS_CAP = IMPG_VU_LDS_CAP;
-// IMPG_VW_WINDOWS = 1: every hit of a batch that meets no earlier one takes its turn at once (replay_hits_wave).  Exact -- the
-// suite and the config-5 tiling test are green with it -- and measured SLOWER: config 5, 4 000 windows, update 629 -> 1 045 ms.
-// Two passes over a ~1 000-range list per batch and 5 KB more LDS a wave (10 waves a CU instead of 17) cost more than the ~25
-// hits a batch it frees from the sequential part save.  0 (the default): round 3's two classes.
-#ifndef IMPG_VW_WINDOWS
-#define IMPG_VW_WINDOWS 0
-#endif
-#ifndef IMPG_VW_WINDOW
-#define IMPG_VW_WINDOW 4   // ranges a hit may start in / swallow and still take its turn on a private copy
-#endif
-[[maybe_unused]] constexpr uint32_t VW_WINDOW = IMPG_VW_WINDOW;
+// (Measured and removed, see DESIGN_HISTORY: every hit of a batch that meets no earlier one taking its turn at once was exact and
+// 1.66x slower -- config 5, 4 000 windows, update 629 -> 1 045 ms; 5 KB more LDS a wave left 10 waves a CU instead of 17.)
 // groups whose list can outgrow this get a whole wave (visited_update_wave_kernel below)
 // two sizes of LDS working set (9 KB: 17 waves per CU; 32 KB: 5): groups with few hits and a short list take the small one
 #ifndef IMPG_VW_TINY
@@ -3454,16 +3390,12 @@ __device__ __forceinline__ int2 list_range(global_list_t p, uint32_t i) {
 #ifndef IMPG_VU_WAVES
 #define IMPG_VU_WAVES 6
 #endif
-#if IMPG_VU_WAVES > 0
-#define VU_OCCUPANCY __attribute__((amdgpu_waves_per_eu(IMPG_VU_WAVES, IMPG_VU_WAVES)))
-#else
-#define VU_OCCUPANCY
-#endif
 // (the listed form's 32 KB column allows two waves whatever the allocator does: the target is the dense form's)
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wpass-failed"
 template <uint32_t CAP, bool LISTED>  // CAP: entries of a lane's LDS column; LISTED: the groups of list[0 .. *n_list), grid-strided
-__global__ __launch_bounds__(64) VU_OCCUPANCY void visited_update_kernel(const unsigned long long *__restrict__ svals,
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(IMPG_VU_WAVES, IMPG_VU_WAVES)))
+void visited_update_kernel(const unsigned long long *__restrict__ svals,
                                                             const int32_t *__restrict__ seq_len,
                                                             const unsigned long long *__restrict__ gkey,
                                                             const uint32_t *__restrict__ gstart,
@@ -3700,55 +3632,30 @@ template <class L> __device__ __forceinline__ uint32_t wave_lower_bound(const L 
   const uint32_t idx = lo + lane;
   return lo + (uint32_t)__popcll(__ballot(idx < hi && R.x(idx) < s));
 }
-// (Round 5: four chunks of 64 per round trip.  A chunk was read, waited for and written before the next was read -- eight
-// dependent LDS round trips to make room in the middle of a 1 000-range list, most of a sequential hit's ~1 200 clocks.
-// The chunks of one round neither read what another of them writes -- going down, chunk j writes [b_j + 1, t_j + 1) and
-// the chunks below it read below b_j -- so all four are requested, then all four stored; IMPG_VW_SHIFT_CHUNKS = 1 is the old loop.)
-#ifndef IMPG_VW_WINDOW_TURN
-#define IMPG_VW_WINDOW_TURN 1  // a sequential hit's turn on one 64-range read of the list (replay_hits_wave); 0: round 3's loops
-#endif
-#ifndef IMPG_VW_SHIFT_CHUNKS
-#define IMPG_VW_SHIFT_CHUNKS 1  // (4: measured on config 5, 4 000 windows: update 629-634 -> 644 ms -- the shifts are not what a sequential hit waits for)
-#endif
-constexpr uint32_t VW_SHIFT_CHUNKS = IMPG_VW_SHIFT_CHUNKS;
+// (Round 5, measured and removed, see DESIGN_HISTORY: four chunks of 64 requested per round trip, then all four stored, instead
+// of a chunk at a time -- config 5, 4 000 windows: update 629-634 -> 644 ms; the shifts are not what a sequential hit waits for.)
 template <class L> __device__ __forceinline__ void wave_shift_up(const L &R, uint32_t pos, uint32_t len) {  // [pos, len) -> [pos+1, len+1)
   const uint32_t lane = lane_id();
   for (uint32_t top = len; top > pos;) {
-    int32_t vx[VW_SHIFT_CHUNKS], vy[VW_SHIFT_CHUNKS];
-    uint32_t at[VW_SHIFT_CHUNKS];
-    bool on[VW_SHIFT_CHUNKS];
-#pragma unroll
-    for (uint32_t c = 0; c < VW_SHIFT_CHUNKS; c++) {
-      const uint32_t base = top > pos + 64u ? top - 64u : pos;
-      at[c] = base + lane;
-      on[c] = at[c] < top;
-      vx[c] = 0; vy[c] = 0;
-      if (on[c]) { vx[c] = R.x(at[c]); vy[c] = R.y(at[c]); }
-      top = base;  // (an exhausted range leaves top == pos: the remaining chunks of the round are empty)
-    }
+    const uint32_t base = top > pos + 64u ? top - 64u : pos;
+    const uint32_t at = base + lane;
+    const bool on = at < top;
+    int32_t vx = 0, vy = 0;
+    if (on) { vx = R.x(at); vy = R.y(at); }
+    top = base;
     order_point(R);
-#pragma unroll
-    for (uint32_t c = 0; c < VW_SHIFT_CHUNKS; c++)
-      if (on[c]) { R.x(at[c] + 1) = vx[c]; R.y(at[c] + 1) = vy[c]; }
+    if (on) { R.x(at + 1) = vx; R.y(at + 1) = vy; }
     order_point(R);
   }
 }
 template <class L> __device__ __forceinline__ void wave_shift_down(const L &R, uint32_t from, uint32_t len, uint32_t k) {  // [from, len) -> [from-k, len-k)
   const uint32_t lane = lane_id();
-  for (uint32_t base = from; base < len; base += 64u * VW_SHIFT_CHUNKS) {
-    int32_t vx[VW_SHIFT_CHUNKS], vy[VW_SHIFT_CHUNKS];
-#pragma unroll
-    for (uint32_t c = 0; c < VW_SHIFT_CHUNKS; c++) {
-      const uint32_t i = base + c * 64u + lane;
-      vx[c] = 0; vy[c] = 0;
-      if (i < len) { vx[c] = R.x(i); vy[c] = R.y(i); }
-    }
+  for (uint32_t base = from; base < len; base += 64u) {
+    const uint32_t i = base + lane;
+    int32_t vx = 0, vy = 0;
+    if (i < len) { vx = R.x(i); vy = R.y(i); }
     order_point(R);
-#pragma unroll
-    for (uint32_t c = 0; c < VW_SHIFT_CHUNKS; c++) {
-      const uint32_t i = base + c * 64u + lane;
-      if (i < len) { R.x(i - k) = vx[c]; R.y(i - k) = vy[c]; }
-    }
+    if (i < len) { R.x(i - k) = vx; R.y(i - k) = vy; }
     order_point(R);
   }
 }
@@ -3954,10 +3861,8 @@ __device__ __forceinline__ uint32_t replay_hits_wave(const L &R, uint32_t len, c
                                                      uint32_t &t_next, uint32_t list_cap) {
   const bool writer = lane_id() == 0;
   const uint32_t lane = lane_id();
-#if !IMPG_VW_WINDOWS
   __shared__ uint32_t iso_point[64];
   const int32_t iso_margin = max(mdbr, 0) + 1;
-#endif
   uint32_t t0 = t_next;
   for (; t0 < n; t0 += 64u) {
     if (len + 64u > list_cap) break;  // (a batch adds at most 64 ranges: the caller moves the list somewhere bigger)
@@ -3965,148 +3870,6 @@ __device__ __forceinline__ uint32_t replay_hits_wave(const L &R, uint32_t len, c
     // uncovered piece and leaves the list as it is (impg.rs:314-343), and the list only ever grows.  Deep levels of
     // a saturating closure are almost all such hits: every lane tests one hit of the batch against the list as it
     // stands, and only the others take their turn in the sequential replay below.
-#if IMPG_VW_WINDOWS
-    // ---- round 5: every hit that meets no EARLIER hit of its batch takes its turn at once -------------------------------
-    // A hit's turn reads and writes a handful of neighbouring ranges and nothing else: the range before its lower bound
-    // (proximity test, impg.rs:2513-2545; the walk's first range, :305-313), the ranges that start inside it (the walk,
-    // the insert, the ranges merge_forward swallows, :314-368) and the first range that starts beyond it (where the walk,
-    // the second proximity test and the merge stop) -- list positions [lb - 1, ub], lb = first range starting at or after
-    // the hit's start, ub = first range starting beyond its end.  Two hits whose position intervals are disjoint cannot
-    // tell in which order they were replayed; so every uncovered hit whose interval meets that of no EARLIER uncovered hit
-    // of the batch (a later one it meets waits: that one needs this one's result) is replayed NOW, by its own lane, with
-    // the reference's own code (replay_one) on a private copy of its <= W + 2 ranges, and the list is rebuilt once for
-    // all of them: the copied stretches taken out (one ascending pass), room made for what they became (one descending
-    // pass), the private lists written back.  What is left -- hits behind an earlier one they meet, hits on more than W
-    // ranges, hits the clamps touch -- takes its turn in the sequential part below, in order.  (Round 3's two classes,
-    // hits that meet no range at all and hits that grow exactly one, were the cases ub - lb = 0 and most of = 1: 57 % of
-    // the uncovered hits of a deep level; a list of ~1 000 ranges on 5 Mb under 5-10 kb hits has most hits on two or three.)
-    constexpr uint32_t W = VW_WINDOW, PRIV = VW_WINDOW + 4u;
-    __shared__ int32_t priv_x[PRIV * 64u], priv_y[PRIV * 64u];
-    __shared__ uint32_t s_os[64], s_ol[64], s_cr[64], s_cn[64], s_cpos[64];
-    unsigned long long todo;
-    int32_t rs = 0, re = 0;  // this lane's hit of the batch (the sequential part below reads them lane to lane)
-    {
-      bool need = false, plain = false;
-      uint32_t lb = 0, ub = 0;
-      if (t0 + lane < n) {
-        const unsigned long long iv = svals[st + t0 + lane];
-        rs = (int32_t)(uint32_t)(iv >> 32); re = (int32_t)(uint32_t)iv;
-        const int32_t s0 = max(rs, 0), e0 = min(re, sequence_length);
-        const uint32_t p0 = list_lower_bound(R, len, s0);
-        // (a hit that the clamps leave empty or inverted -- a length-0 set of a masked batch -- takes the literal path)
-        const bool covered = s0 < e0 && ((p0 < len && R.x(p0) == s0 && R.y(p0) >= e0) || (p0 > 0 && R.y(p0 - 1) >= e0));
-        need = !covered;
-        plain = need && rs >= 0 && re <= sequence_length && rs < re && re < 0x7FFFFFFF;
-        if (plain) { lb = p0; ub = list_lower_bound(R, len, re + 1); }
-      }
-      todo = __ballot(need);
-      // the hit's interval of list positions, closed, not clamped (-1 and len stand for "before the first" / "behind the
-      // last range": two hits in front of the whole list meet there); a hit the clamps touch meets everything
-      const int32_t blo = plain ? (int32_t)lb - 1 : (int32_t)0x80000000, bhi = plain ? (int32_t)ub : 0x7FFFFFFF;
-      bool earlier = false;
-      for (unsigned long long left = todo; left; left &= left - 1ull) {
-        const uint32_t j = (uint32_t)__ffsll((long long)left) - 1u;
-        const int32_t lo_j = __builtin_amdgcn_readlane(blo, j), hi_j = __builtin_amdgcn_readlane(bhi, j);
-        if (j < lane && lo_j <= bhi && blo <= hi_j) earlier = true;
-      }
-      const bool par = plain && ub - lb <= W && !earlier;
-      const unsigned long long pm = __ballot(par);
-      if (pm) {
-        const uint32_t k = (uint32_t)__popcll(pm);
-        // the private copy and the hit's turn on it
-        const uint32_t bs = (uint32_t)max(blo, 0), be = min((uint32_t)bhi + 1u, len), ol = par ? be - bs : 0u;
-        const ListInLds Q{priv_x + lane, priv_y + lane};
-        uint32_t pl = ol, pn = 0;
-        int32_t qx0 = 0, qx1 = 0, qx2 = 0, qx3 = 0, qx4 = 0, qx5 = 0, qy0 = 0, qy1 = 0, qy2 = 0, qy3 = 0, qy4 = 0, qy5 = 0;  // its pieces: at most W + 2
-        static_assert(VW_WINDOW + 2u <= 6u, "a hit's pieces are held in six register pairs");
-        if (par) {
-          for (uint32_t i = 0; i < ol; i++) { Q.x(i) = R.x(bs + i); Q.y(i) = R.y(bs + i); }
-          replay_one(Q, pl, rs, re, sequence_length, min_transitive_len, mdbr,
-                     [&](int32_t a, int32_t b) {
-                       if (pn == 0) { qx0 = a; qy0 = b; } else if (pn == 1) { qx1 = a; qy1 = b; } else if (pn == 2) { qx2 = a; qy2 = b; }
-                       else if (pn == 3) { qx3 = a; qy3 = b; } else if (pn == 4) { qx4 = a; qy4 = b; } else { qx5 = a; qy5 = b; }
-                       pn += 1;
-                     }, [] {});
-        }
-        {  // the pieces, in any order (they are sorted afterwards)
-          const uint32_t inc = wave_incl_scan(pn);
-          const uint32_t at = np + inc - pn;
-          if (pn > 0) P[at] = make_int2(qx0, qy0);
-          if (pn > 1) P[at + 1u] = make_int2(qx1, qy1);
-          if (pn > 2) P[at + 2u] = make_int2(qx2, qy2);
-          if (pn > 3) P[at + 3u] = make_int2(qx3, qy3);
-          if (pn > 4) P[at + 4u] = make_int2(qx4, qy4);
-          if (pn > 5) P[at + 5u] = make_int2(qx5, qy5);
-          np += (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
-        }
-        // the copied stretches in list order (their intervals are disjoint: ranked by where they start)
-        uint32_t rank = 0;
-        for (unsigned long long left = pm; left; left &= left - 1ull) {
-          const uint32_t j = (uint32_t)__ffsll((long long)left) - 1u;
-          rank += __builtin_amdgcn_readlane(blo, j) < blo ? 1u : 0u;
-        }
-        __syncthreads();  // (the arrays may still be read by the previous batch)
-        if (par) { s_os[rank] = bs; s_ol[rank] = ol; s_cn[rank] = pl; }
-        __syncthreads();
-        {
-          const uint32_t o = lane < k ? s_ol[lane] : 0u, nl = lane < k ? s_cn[lane] : 0u;
-          const uint32_t cr = wave_incl_scan(o), cn = wave_incl_scan(nl);
-          __syncthreads();
-          if (lane < k) { s_cr[lane] = cr; s_cn[lane] = cn; s_cpos[lane] = s_os[lane] - (cr - o); }
-          __syncthreads();
-        }
-        const uint32_t removed = s_cr[k - 1u], added = s_cn[k - 1u];
-        // (number of entries of the ascending array a[0 .. k) that are <= v)
-        auto count_le = [&](const uint32_t *a, uint32_t v) -> uint32_t {
-          uint32_t lo = 0, hi = k;
-          while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (a[mid] <= v) lo = mid + 1u; else hi = mid; }
-          return lo;
-        };
-        // pass A, ascending: the copied stretches out, what stays moves down by what was taken out before it
-        for (uint32_t base = s_os[0]; base < len; base += 64u) {
-          const uint32_t i = base + lane;
-          const bool on = i < len;
-          int32_t vx = 0, vy = 0;
-          uint32_t dst = 0;
-          bool keep = false;
-          if (on) {
-            vx = R.x(i); vy = R.y(i);
-            const uint32_t j = count_le(s_os, i);
-            keep = j == 0u || i >= s_os[j - 1u] + s_ol[j - 1u];
-            dst = i - (j ? s_cr[j - 1u] : 0u);
-          }
-          order_point(R);
-          if (keep) { R.x(dst) = vx; R.y(dst) = vy; }
-          order_point(R);
-        }
-        const uint32_t len_c = len - removed;
-        // pass B, descending: room for what the stretches became
-        for (uint32_t top = len_c; top > s_cpos[0];) {
-          const uint32_t base = top > s_cpos[0] + 64u ? top - 64u : s_cpos[0];
-          const uint32_t c = base + lane;
-          const bool on = c < top;
-          int32_t vx = 0, vy = 0;
-          uint32_t dst = 0;
-          if (on) {
-            vx = R.x(c); vy = R.y(c);
-            const uint32_t j = count_le(s_cpos, c);
-            dst = c + (j ? s_cn[j - 1u] : 0u);
-          }
-          order_point(R);
-          if (on) { R.x(dst) = vx; R.y(dst) = vy; }
-          order_point(R);
-          top = base;
-        }
-        if (par) {
-          const uint32_t at = s_cpos[rank] + (s_cn[rank] - pl);
-          for (uint32_t i = 0; i < pl; i++) { R.x(at + i) = Q.x(i); R.y(at + i) = Q.y(i); }
-        }
-        order_point(R);
-        len = len_c + added;
-        todo &= ~pm;
-      }
-    }
-#else
     unsigned long long todo;
     int32_t rs = 0, re = 0;  // this lane's hit of the batch (the sequential part below reads them lane to lane)
     VW_T(vw0);
@@ -4258,7 +4021,6 @@ __device__ __forceinline__ uint32_t replay_hits_wave(const L &R, uint32_t len, c
       VW_T(vw3);
       VW_ADD(2, vw3 - vw2);
     }
-#endif
     VW_ADD(8, __popcll(todo));
     while (todo) {
     VW_T(vs0);
@@ -4267,7 +4029,6 @@ __device__ __forceinline__ uint32_t replay_hits_wave(const L &R, uint32_t len, c
     // (from the lane that loaded it: a second read of svals here was a global-memory round trip per replayed hit)
     int32_t start = __builtin_amdgcn_readlane(rs, tl), end = __builtin_amdgcn_readlane(re, tl);
     uint32_t pos = wave_lower_bound(R, len, start);
-#if IMPG_VW_WINDOW_TURN
     // Round 5: a sequential hit's turn on ONE read of the list.  Everything the turn looks at -- the range before the hit's
     // lower bound (proximity test, the walk's first range, the insert's extension), the ranges that start inside the
     // hit (the walk's gaps, the ranges merge_forward swallows) and the first one beyond -- is the 64 ranges from pos - 1:
@@ -4343,7 +4104,6 @@ __device__ __forceinline__ uint32_t replay_hits_wave(const L &R, uint32_t len, c
         continue;
       }
     }
-#endif
     if (mdbr > 0) {  // impg.rs:2513-2545
       bool should_add = true;
       if (pos > 0 && abs(start - R.y(pos - 1)) < mdbr) should_add = false;
@@ -5573,16 +5333,12 @@ void launch_update_keys(const FrontierRec *fr, const uint32_t *pair_range, uint3
   update_keys_kernel<<<cdiv(n_pairs, 256), 256, 0, s>>>(fr, pair_range, n_pairs, h, keys, vals, n_active);
 }
 size_t sort_pairs_scratch_bytes(uint32_t n) {
-  size_t bytes = 0;
-  (void)rocprim::radix_sort_pairs<rocprim::default_config, const unsigned long long *, unsigned long long *,
-                                  const uint32_t *, uint32_t *>(nullptr, bytes, nullptr, nullptr, nullptr, nullptr, n, 0, 64,
-                                                                (hipStream_t)0);
-  return bytes;
+  return prims::radix_sort_pairs_bytes<const unsigned long long *, unsigned long long *, const uint32_t *, uint32_t *>(n, 0, 64);
 }
 void launch_sort_pairs(void *tmp, size_t tmp_bytes, const unsigned long long *kin, unsigned long long *kout,
                        const uint32_t *vin, uint32_t *vout, uint32_t n, unsigned end_bit, hipStream_t s) {
   if (!n) return;
-  IMPG_HIP(rocprim::radix_sort_pairs(tmp, tmp_bytes, kin, kout, vin, vout, n, 0, end_bit, s));
+  prims::radix_sort_pairs(tmp, tmp_bytes, kin, kout, vin, vout, n, 0, end_bit, s);
 }
 bool seg_group_fits(uint32_t n_seq) { return n_seq <= SEG_MAX_SEQ; }
 size_t seg_group_bins_bytes(uint32_t n_queries, uint32_t n_seq, uint32_t parts) {
@@ -5799,15 +5555,12 @@ void launch_dfs_compact(const uint32_t *gstart, const uint32_t *cnt, const uint3
                                                                        key_out, st_out, en_out, depth_out);
 }
 size_t sort_u32_scratch_bytes(uint32_t n) {
-  size_t bytes = 0;
-  (void)rocprim::radix_sort_pairs<rocprim::default_config, const uint32_t *, uint32_t *, const uint32_t *, uint32_t *>(
-      nullptr, bytes, nullptr, nullptr, nullptr, nullptr, n, 0, 32, (hipStream_t)0);
-  return bytes;
+  return prims::radix_sort_pairs_bytes<const uint32_t *, uint32_t *, const uint32_t *, uint32_t *>(n, 0, 32);
 }
 void launch_sort_u32(void *tmp, size_t tmp_bytes, const uint32_t *kin, uint32_t *kout, const uint32_t *vin, uint32_t *vout,
                      uint32_t n, hipStream_t s, unsigned begin_bit, unsigned end_bit) {
   if (!n) return;
-  IMPG_HIP(rocprim::radix_sort_pairs(tmp, tmp_bytes, kin, kout, vin, vout, n, begin_bit, end_bit, s));
+  prims::radix_sort_pairs(tmp, tmp_bytes, kin, kout, vin, vout, n, begin_bit, end_bit, s);
 }
 
 // ---------------------------------------------------------------------------
@@ -6034,17 +5787,13 @@ void launch_order_sort(uint32_t *keys, uint32_t *key_tmp, uint32_t *perm_out, ui
   }
 }
 size_t sort_u64v_scratch_bytes(uint32_t n) {
-  size_t bytes = 0;
-  (void)rocprim::radix_sort_pairs<rocprim::default_config, const unsigned long long *, unsigned long long *,
-                                  const unsigned long long *, unsigned long long *>(nullptr, bytes, nullptr, nullptr, nullptr,
-                                                                                    nullptr, n, 0, 64, (hipStream_t)0);
-  return bytes;
+  return prims::radix_sort_pairs_bytes<const unsigned long long *, unsigned long long *, const unsigned long long *, unsigned long long *>(n, 0, 64);
 }
 void launch_sort_u64v(void *tmp, size_t tmp_bytes, const unsigned long long *kin, unsigned long long *kout,
                       const unsigned long long *vin, unsigned long long *vout, uint32_t n, hipStream_t s, unsigned end_bit,
                       unsigned begin_bit) {
   if (!n) return;
-  IMPG_HIP(rocprim::radix_sort_pairs(tmp, tmp_bytes, kin, kout, vin, vout, n, begin_bit, end_bit, s));
+  prims::radix_sort_pairs(tmp, tmp_bytes, kin, kout, vin, vout, n, begin_bit, end_bit, s);
 }
 void launch_compact_fill(const unsigned long long *keys, uint32_t n, uint32_t table, unsigned long long *key_out,
                          unsigned long long *src_out, hipStream_t s) {

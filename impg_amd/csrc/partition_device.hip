@@ -35,11 +35,9 @@
 // a nine-word header (counts, flags, the longest missing range).
 #include <hip/hip_runtime.h>
 
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-
 #include <algorithm>
 
+#include "device_prims.hpp"
 #include "partition.hpp"
 
 namespace impg {
@@ -367,33 +365,17 @@ inline unsigned bits_for(uint32_t v) {  // bits that hold 0..v
 struct Ops {
   DeviceRegions &R;
   hipStream_t s;
-  void need(DevBuf &b, size_t bytes) { b.reserve(std::max<size_t>(bytes, 256)); }
-  void excl_scan(const uint32_t *in, uint32_t *out, size_t n) {
-    size_t sb = 0;
-    IMPG_HIP(rocprim::exclusive_scan(nullptr, sb, in, out, 0u, n, rocprim::plus<uint32_t>(), s));
-    need(R.tmp, sb);
-    IMPG_HIP(rocprim::exclusive_scan(R.tmp.p, sb, in, out, 0u, n, rocprim::plus<uint32_t>(), s));
-    R.launches++;
-  }
-  void max_scan(const u64 *in, u64 *out, size_t n) {
-    size_t sb = 0;
-    IMPG_HIP(rocprim::inclusive_scan(nullptr, sb, in, out, n, rocprim::maximum<u64>(), s));
-    need(R.tmp, sb);
-    IMPG_HIP(rocprim::inclusive_scan(R.tmp.p, sb, in, out, n, rocprim::maximum<u64>(), s));
-    R.launches++;
-  }
+  void excl_scan(const uint32_t *in, uint32_t *out, size_t n) { prims::exclusive_sum(R.tmp, in, out, n, s); R.launches++; }
+  void max_scan(const u64 *in, u64 *out, size_t n) { prims::inclusive_max(R.tmp, in, out, n, s); R.launches++; }
   // stable; keys of [0, 32 + seq bits)
   void sort(const u64 *kin, u64 *kout, const int32_t *vin, int32_t *vout, size_t n, unsigned end_bit) {
-    size_t sb = 0;
-    IMPG_HIP(rocprim::radix_sort_pairs(nullptr, sb, kin, kout, vin, vout, n, 0u, end_bit, s));
-    need(R.tmp, sb);
-    IMPG_HIP(rocprim::radix_sort_pairs(R.tmp.p, sb, kin, kout, vin, vout, n, 0u, end_bit, s));
+    prims::radix_sort_pairs(R.tmp, kin, kout, vin, vout, n, 0u, end_bit, s);
     R.launches++;
   }
   // runs of a sorted list of *d_n (<= n_ub) items: out[*d_n_out]
   void merge(const u64 *key, const int32_t *hi, uint32_t n_ub, const uint32_t *d_n, int32_t d, u64 *out_key, int32_t *out_hi, uint32_t *d_n_out) {
-    need(R.mk, (size_t)n_ub * 8); need(R.pm, (size_t)n_ub * 8);
-    need(R.head, ((size_t)n_ub + 1) * 4); need(R.pos, ((size_t)n_ub + 1) * 4);
+    prims::grow(R.mk, (size_t)n_ub * 8); prims::grow(R.pm, (size_t)n_ub * 8);
+    prims::grow(R.head, ((size_t)n_ub + 1) * 4); prims::grow(R.pos, ((size_t)n_ub + 1) * 4);
     maxkey_kernel<<<cdiv(n_ub, 256), 256, 0, s>>>(key, hi, n_ub, d_n, R.mk.as<u64>());
     max_scan(R.mk.as<u64>(), R.pm.as<u64>(), n_ub);
     head_kernel<<<cdiv((size_t)n_ub + 1, 256), 256, 0, s>>>(key, R.pm.as<u64>(), n_ub, d_n, d, R.head.as<uint32_t>());
@@ -424,12 +406,12 @@ DeviceRegions::DeviceRegions(int device_, const int64_t *seq_len, uint32_t n_seq
     xo[q + 1] = (uint32_t)(xr.size() / 2);
   }
   n_missing = (uint32_t)(xr.size() / 2);
-  auto need = [](DevBuf &b, size_t bytes) { b.reserve(std::max<size_t>(bytes, 256)); };
-  need(len, (size_t)n_seq * 4);
-  for (int k = 0; k < 2; k++) need(totals[k], (size_t)n_seq * 8);
-  need(ctr, C_WORDS * 4);
-  for (int k = 0; k < 2; k++) { need(m_off[k], ((size_t)n_seq + 1) * 4); need(x_off[k], ((size_t)n_seq + 1) * 4); }
-  need(m_rng[0], 256); need(x_rng[0], xr.size() * 4);
+  using prims::grow;
+  grow(len, (size_t)n_seq * 4);
+  for (int k = 0; k < 2; k++) grow(totals[k], (size_t)n_seq * 8);
+  grow(ctr, C_WORDS * 4);
+  for (int k = 0; k < 2; k++) { grow(m_off[k], ((size_t)n_seq + 1) * 4); grow(x_off[k], ((size_t)n_seq + 1) * 4); }
+  grow(m_rng[0], 256); grow(x_rng[0], xr.size() * 4);
   // the state is built once on the host -- lengths, an empty mask, missing = every sequence -- and lives in HBM from here on
   if (n_seq) IMPG_HIP(hipMemcpyAsync(len.p, L.data(), (size_t)n_seq * 4, hipMemcpyHostToDevice, stream));
   if (n_seq) IMPG_HIP(hipMemcpyAsync(totals[0].p, tot.data(), (size_t)n_seq * 8, hipMemcpyHostToDevice, stream));
@@ -463,24 +445,24 @@ void DeviceRegions::apply(const impg_gpu_interval_t *d_rows, uint32_t n, int32_t
   const uint32_t n_old = n_mask, n_x = n_missing;
   const int mo = m_cur, xo = x_cur, mn = m_cur ^ 1, xn = x_cur ^ 1, tn = t_cur ^ 1;
   // 1
-  op.need(key_a, (size_t)2 * n * 8); op.need(key_b, (size_t)2 * n * 8); op.need(val_a, (size_t)2 * n * 4); op.need(val_b, (size_t)2 * n * 4);
+  prims::grow(key_a, (size_t)2 * n * 8); prims::grow(key_b, (size_t)2 * n * 8); prims::grow(val_a, (size_t)2 * n * 4); prims::grow(val_b, (size_t)2 * n * 4);
   IMPG_HIP(hipMemsetAsync(c + C_HDR, 0, H_WORDS * 4, s));
   norm_kernel<<<cdiv(n, 256), 256, 0, s>>>(d_rows, n, n_seq, key_a.as<u64>(), val_a.as<int32_t>(), c);
   op.sort(key_a.as<u64>(), key_b.as<u64>(), val_a.as<int32_t>(), val_b.as<int32_t>(), n, end_bit);
   // 2
-  op.need(a_key, (size_t)n * 8); op.need(a_hi, (size_t)n * 4);
+  prims::grow(a_key, (size_t)n * 8); prims::grow(a_hi, (size_t)n * 4);
   op.merge(key_b.as<u64>(), val_b.as<int32_t>(), n, c + C_N, d, a_key.as<u64>(), a_hi.as<int32_t>(), c + C_M);
   // 3 + 4
-  op.need(b_lo, (size_t)n * 4); op.need(b_hi, (size_t)n * 4);
+  prims::grow(b_lo, (size_t)n * 4); prims::grow(b_hi, (size_t)n * 4);
   extend_cand_kernel<<<cdiv(n, 256), 256, 0, s>>>(a_key.as<u64>(), a_hi.as<int32_t>(), n, c + C_M, len.as<int32_t>(), x_off[xo].as<uint32_t>(),
                                                   x_rng[xo].as<int2>(), min_boundary, min_missing, n_seq, b_lo.as<int32_t>(), b_hi.as<int32_t>(),
                                                   key_a.as<u64>(), val_a.as<int32_t>(), c);
   op.sort(key_a.as<u64>(), key_b.as<u64>(), val_a.as<int32_t>(), val_b.as<int32_t>(), (size_t)2 * n, end_bit);
   count_valid_kernel<<<cdiv((size_t)2 * n, 256), 256, 0, s>>>(key_b.as<u64>(), 2 * n, n_seq, c + C_CAND);
-  op.need(e_key, (size_t)2 * n * 8); op.need(e_hi, (size_t)2 * n * 4);
+  prims::grow(e_key, (size_t)2 * n * 8); prims::grow(e_hi, (size_t)2 * n * 4);
   op.merge(key_b.as<u64>(), val_b.as<int32_t>(), 2 * n, c + C_CAND, 0, e_key.as<u64>(), e_hi.as<int32_t>(), c + C_EXT);
   // 5
-  op.need(s_a, ((size_t)n + 1) * 4); op.need(s_first, ((size_t)n + 1) * 4); op.need(s_cnt, ((size_t)n + 1) * 4); op.need(s_off, ((size_t)n + 1) * 4);
+  prims::grow(s_a, ((size_t)n + 1) * 4); prims::grow(s_first, ((size_t)n + 1) * 4); prims::grow(s_cnt, ((size_t)n + 1) * 4); prims::grow(s_off, ((size_t)n + 1) * 4);
   apply_count_kernel<<<cdiv((size_t)n + 1, 256), 256, 0, s>>>(a_key.as<u64>(), n, c + C_M, b_lo.as<int32_t>(), b_hi.as<int32_t>(), e_key.as<u64>(),
                                                                e_hi.as<int32_t>(), c + C_EXT, m_off[mo].as<uint32_t>(), m_rng[mo].as<int2>(),
                                                                s_a.as<uint32_t>(), s_first.as<uint32_t>(), s_cnt.as<uint32_t>());
@@ -492,8 +474,8 @@ void DeviceRegions::apply(const impg_gpu_interval_t *d_rows, uint32_t n, int32_t
   if (n_seg >= (1u << 30)) throw Error{IMPG_E_UNSUPPORTED, "a window leaves more than 2^30 pieces"};
   // 6
   const uint32_t sg = std::max(n_seg, 1u);
-  op.need(t_key, (size_t)sg * 8); op.need(t_hi, (size_t)sg * 4); op.need(n_key, (size_t)sg * 8); op.need(n_hi, (size_t)sg * 4);
-  op.need(o_key, (size_t)sg * 8); op.need(o_hi, (size_t)sg * 4);
+  prims::grow(t_key, (size_t)sg * 8); prims::grow(t_hi, (size_t)sg * 4); prims::grow(n_key, (size_t)sg * 8); prims::grow(n_hi, (size_t)sg * 4);
+  prims::grow(o_key, (size_t)sg * 8); prims::grow(o_hi, (size_t)sg * 4);
   piece_write_kernel<<<cdiv(sg, 256), 256, 0, s>>>(a_key.as<u64>(), b_lo.as<int32_t>(), b_hi.as<int32_t>(), n, s_a.as<uint32_t>(),
                                                     s_first.as<uint32_t>(), s_off.as<uint32_t>(), m_rng[mo].as<int2>(), sg, t_key.as<u64>(),
                                                     t_hi.as<int32_t>(), c + C_SEG);
@@ -504,31 +486,31 @@ void DeviceRegions::apply(const impg_gpu_interval_t *d_rows, uint32_t n, int32_t
   op.merge(sk, sh, sg, c + C_SEG, 0, o_key.as<u64>(), o_hi.as<int32_t>(), c + C_OUT);
   // 7
   const uint32_t comb = n_old + n;
-  op.need(c_key, (size_t)comb * 8); op.need(c_hi, (size_t)comb * 4);
-  op.need(key_a, (size_t)comb * 8); op.need(val_a, (size_t)comb * 4);
+  prims::grow(c_key, (size_t)comb * 8); prims::grow(c_hi, (size_t)comb * 4);
+  prims::grow(key_a, (size_t)comb * 8); prims::grow(val_a, (size_t)comb * 4);
   mask_merge_kernel<<<cdiv(comb, 256), 256, 0, s>>>(m_off[mo].as<uint32_t>(), m_rng[mo].as<int2>(), n_old, n_seq, a_key.as<u64>(), b_lo.as<int32_t>(),
                                                     b_hi.as<int32_t>(), n, c + C_M, c_key.as<u64>(), c_hi.as<int32_t>(), c + C_COMB);
   op.merge(c_key.as<u64>(), c_hi.as<int32_t>(), comb, c + C_COMB, 0, key_a.as<u64>(), val_a.as<int32_t>(), c + C_NMASK);
-  op.need(m_rng[mn], (size_t)comb * 8);
+  prims::grow(m_rng[mn], (size_t)comb * 8);
   table_kernel<<<cdiv(std::max<size_t>(comb, (size_t)n_seq + 1), 256), 256, 0, s>>>(key_a.as<u64>(), val_a.as<int32_t>(), comb, c + C_NMASK, n_seq,
                                                                                    m_off[mn].as<uint32_t>(), m_rng[mn].as<int2>(), c + C_HDR, H_NMASK, H_EMPTY);
   launches += 2;
   // 8
   const uint32_t xs_ub = std::max<uint32_t>(2 * n_x + comb, 1);
   const uint32_t nx1 = std::max(n_x, 1u);
-  op.need(key_b, (size_t)nx1 * 8); op.need(b_lo, (size_t)nx1 * 4); op.need(b_hi, (size_t)nx1 * 4);
-  op.need(s_a, ((size_t)n_x + 1) * 4); op.need(s_first, ((size_t)n_x + 1) * 4); op.need(s_cnt, ((size_t)n_x + 1) * 4); op.need(s_off, ((size_t)n_x + 1) * 4);
+  prims::grow(key_b, (size_t)nx1 * 8); prims::grow(b_lo, (size_t)nx1 * 4); prims::grow(b_hi, (size_t)nx1 * 4);
+  prims::grow(s_a, ((size_t)n_x + 1) * 4); prims::grow(s_first, ((size_t)n_x + 1) * 4); prims::grow(s_cnt, ((size_t)n_x + 1) * 4); prims::grow(s_off, ((size_t)n_x + 1) * 4);
   missing_count_kernel<<<cdiv((size_t)n_x + 1, 256), 256, 0, s>>>(x_off[xo].as<uint32_t>(), x_rng[xo].as<int2>(), n_x, n_seq, m_off[mn].as<uint32_t>(),
                                                                   m_rng[mn].as<int2>(), key_b.as<u64>(), b_lo.as<int32_t>(), b_hi.as<int32_t>(),
                                                                   s_a.as<uint32_t>(), s_first.as<uint32_t>(), s_cnt.as<uint32_t>());
   op.excl_scan(s_cnt.as<uint32_t>(), s_off.as<uint32_t>(), (size_t)n_x + 1);
-  op.need(c_key, (size_t)xs_ub * 8); op.need(c_hi, (size_t)xs_ub * 4);
-  op.need(key_a, (size_t)xs_ub * 8); op.need(val_a, (size_t)xs_ub * 4);
+  prims::grow(c_key, (size_t)xs_ub * 8); prims::grow(c_hi, (size_t)xs_ub * 4);
+  prims::grow(key_a, (size_t)xs_ub * 8); prims::grow(val_a, (size_t)xs_ub * 4);
   piece_write_kernel<<<cdiv(xs_ub, 256), 256, 0, s>>>(key_b.as<u64>(), b_lo.as<int32_t>(), b_hi.as<int32_t>(), n_x, s_a.as<uint32_t>(),
                                                        s_first.as<uint32_t>(), s_off.as<uint32_t>(), m_rng[mn].as<int2>(), xs_ub, c_key.as<u64>(),
                                                        c_hi.as<int32_t>(), c + C_XSEG);
   op.merge(c_key.as<u64>(), c_hi.as<int32_t>(), xs_ub, c + C_XSEG, 0, key_a.as<u64>(), val_a.as<int32_t>(), c + C_NMISS);
-  op.need(x_rng[xn], (size_t)xs_ub * 8);
+  prims::grow(x_rng[xn], (size_t)xs_ub * 8);
   table_kernel<<<cdiv(std::max<size_t>(xs_ub, (size_t)n_seq + 1), 256), 256, 0, s>>>(key_a.as<u64>(), val_a.as<int32_t>(), xs_ub, c + C_NMISS, n_seq,
                                                                                     x_off[xn].as<uint32_t>(), x_rng[xn].as<int2>(), c + C_HDR, H_NMISS, -1);
   launches += 3;
@@ -536,7 +518,7 @@ void DeviceRegions::apply(const impg_gpu_interval_t *d_rows, uint32_t n, int32_t
   IMPG_HIP(hipMemsetAsync(totals[tn].p, 0, std::max<size_t>((size_t)n_seq * 8, 8), s));
   IMPG_HIP(hipMemsetAsync(c + C_BEST, 0, 8, s));
   select_kernel<<<cdiv(xs_ub, 256), 256, 0, s>>>(key_a.as<u64>(), val_a.as<int32_t>(), xs_ub, c + C_NMISS, (u64 *)(c + C_BEST), totals[tn].as<u64>());
-  op.need(out_rows, (size_t)sg * sizeof(PIv));
+  prims::grow(out_rows, (size_t)sg * sizeof(PIv));
   finish_kernel<<<cdiv(sg, 256), 256, 0, s>>>(key_a.as<u64>(), val_a.as<int32_t>(), (const u64 *)(c + C_BEST), c, o_key.as<u64>(), o_hi.as<int32_t>(),
                                               sg, out_rows.as<PIv>());
   launches += 4;

@@ -22,10 +22,9 @@
 //   scatter   row of slot k of record r = dest[r] + pos[k] - pos[first slot of r]
 #include <hip/hip_runtime.h>
 
-#include <rocprim/device/device_scan.hpp>
-
 #include <algorithm>
 
+#include "device_prims.hpp"
 #include "engine.hpp"
 
 namespace impg {
@@ -87,15 +86,6 @@ __global__ __launch_bounds__(256) void level_records_kernel(const FrontierRec *_
   if (r >= n_fr) return;
   rec_q[r] = fr[r].qidx;
   rec_cnt[r] = rec_cnt[r] - rec_start[r];  // (rec_cnt held the end; a record without slots has 0 - 0)
-}
-__global__ __launch_bounds__(256) void iota_kernel(uint32_t *v, uint32_t n) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i < n) v[i] = i;
-}
-__global__ __launch_bounds__(256) void gather_kernel(const uint32_t *__restrict__ src, const uint32_t *__restrict__ idx, uint32_t n,
-                                                     uint32_t *__restrict__ dst) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i < n) dst[i] = src[idx[i]];
 }
 // sorted records -> rec_dest (back at the record's own index) and the ranges' first rows
 __global__ __launch_bounds__(256) void record_dest_kernel(const uint32_t *__restrict__ sq, const uint32_t *__restrict__ sidx,
@@ -237,11 +227,11 @@ void plan_rows(Engine &E, uint32_t n_ranges, const impg_gpu_params_t &p, std::ve
     rb += L->n_frontier;
   }
   // ---- range-major order (stable: emission order within a range) -----------------------------------------------------
-  iota_kernel<<<cdiv(R, 256), 256, 0, s>>>(idx.as<uint32_t>(), (uint32_t)R);
+  prims::iota_kernel<<<cdiv(R, 256), 256, 0, s>>>(idx.as<uint32_t>(), (uint32_t)R);
   const size_t tb = sort_u32_scratch_bytes((uint32_t)R);
   tmp.reserve(tb);
   launch_sort_u32(tmp.p, tb, rq, sq.as<uint32_t>(), idx.as<uint32_t>(), sidx.as<uint32_t>(), (uint32_t)R, s, 0, bits_for(n_ranges));
-  gather_kernel<<<cdiv(R, 256), 256, 0, s>>>(rc, sidx.as<uint32_t>(), (uint32_t)R, scnt.as<uint32_t>());
+  prims::gather_kernel<<<cdiv(R, 256), 256, 0, s>>>(rc, sidx.as<uint32_t>(), (uint32_t)R, scnt.as<uint32_t>());
   const uint64_t total = E.scan(scnt.as<uint32_t>(), sdest.as<uint32_t>(), (uint32_t)R);
   if (total != n_rows) throw Error{IMPG_E_INVALID, "internal: result rows and records disagree"};
   record_dest_kernel<<<cdiv(R, 256), 256, 0, s>>>(sq.as<uint32_t>(), sidx.as<uint32_t>(), sdest.as<uint32_t>(), scnt.as<uint32_t>(), (uint32_t)R,
@@ -277,12 +267,9 @@ uint64_t build_row_cigars(Engine &E, std::vector<std::unique_ptr<LevelBufs>> &le
     IMPG_HIP(hipMemsetAsync(coff.p, 0, 8, s));
     return 0;
   }
-  size_t sb = 0;
-  IMPG_HIP(rocprim::exclusive_scan(nullptr, sb, clen.as<uint32_t>(), coff.as<unsigned long long>(), 0ull, pl.n_rows, rocprim::plus<unsigned long long>(), s));
   DevBuf stmp;
   stmp.pool = &E.level_pool;
-  stmp.reserve(std::max<size_t>(sb, 256));
-  IMPG_HIP(rocprim::exclusive_scan(stmp.p, sb, clen.as<uint32_t>(), coff.as<unsigned long long>(), 0ull, pl.n_rows, rocprim::plus<unsigned long long>(), s));
+  prims::exclusive_sum(stmp, clen.as<uint32_t>(), coff.as<unsigned long long>(), pl.n_rows, s);
   unsigned long long last_off = 0;
   uint32_t last_len = 0;
   IMPG_HIP(hipMemcpyAsync(&last_off, coff.as<unsigned long long>() + (pl.n_rows - 1), 8, hipMemcpyDeviceToHost, s));
