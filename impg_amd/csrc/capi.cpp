@@ -48,6 +48,8 @@ static void engine_options(impg_gpu_index &ix, Engine *e) {
   e->seg_parts_force = ix.opt_seg_parts;
   e->seg_stats = ix.seg_stats;
   e->proj_stats = ix.proj_stats;
+  e->update_stats = ix.opt_update_stats;
+  e->upd_stats = ix.upd_stats;
 }
 EngineLease::EngineLease(impg_gpu_index &ix_) : ix(ix_) {
   std::unique_lock<std::mutex> lk(ix.eng_m);
@@ -613,6 +615,8 @@ int impg_gpu_set_option(impg_gpu_index_t *ix, const char *key, int64_t value) {
   } else if (k == "filter_covered") {  // visited update: hits covered by the old list dropped before the replay (0 off, 1 always, 2 auto; results identical)
     if (value < 0 || value > 2) throw Error{IMPG_E_INVALID, "filter_covered is 0, 1 or 2"};
     ix->opt_filter_covered = (int)value;
+  } else if (k == "update_stats") {  // visited update: every level's groups per tier and rare path counted into the update_* counters (0 off, default; 1: one small copy per level)
+    ix->opt_update_stats = value != 0;
   } else if (k == "free_slot_order") {  // counting runs lay their slots out in projection order (1, default) or keep the reference order (0)
     ix->opt_free_slots = value != 0;
   } else if (k == "debug_fail_owner" || k == "debug_fail_home") {  // tests: (rank + 1) << 16 | hop (sharded indexes; 0 = off)
@@ -663,6 +667,14 @@ int impg_gpu_get_counter(const impg_gpu_index_t *ix, const char *key, int64_t *v
   else if (k == "project_entries_rows_levels") *value_out = (int64_t)ix->proj_stats[PROJ_ARM_ENTRIES_ROWS].load();
   else if (k == "project_entries_ident_levels") *value_out = (int64_t)ix->proj_stats[PROJ_ARM_ENTRIES_IDENT].load();
   else if (k == "project_tp_levels") *value_out = (int64_t)ix->proj_stats[PROJ_ARM_TP].load();
+  else if (k == "update_lane_groups") *value_out = (int64_t)ix->upd_stats[UPD_LANE].load();
+  else if (k == "update_mid_groups") *value_out = (int64_t)ix->upd_stats[UPD_MID].load();
+  else if (k == "update_wave_tiny_groups") *value_out = (int64_t)ix->upd_stats[UPD_WAVE_TINY].load();
+  else if (k == "update_wave_small_groups") *value_out = (int64_t)ix->upd_stats[UPD_WAVE_SMALL].load();
+  else if (k == "update_wave_large_groups") *value_out = (int64_t)ix->upd_stats[UPD_WAVE_LARGE].load();
+  else if (k == "update_inplace_groups") *value_out = (int64_t)ix->upd_stats[UPD_INPLACE].load();
+  else if (k == "update_tiled_sort_groups") *value_out = (int64_t)ix->upd_stats[UPD_TILED_SORT].load();
+  else if (k == "update_lane_spill_groups") *value_out = (int64_t)ix->upd_stats[UPD_LANE_SPILL].load();
   else throw Error{IMPG_E_INVALID, "unknown counter " + k};
   return IMPG_OK;
   IMPG_CATCH

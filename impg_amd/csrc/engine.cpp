@@ -29,7 +29,7 @@ Engine::Engine(int device) {
   IMPG_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
   for (DevBuf *b : {&ord_offsets, &ord_rows}) b->pool = &level_pool;  // (handed over to the caller's result)
   win_se.pool = &level_pool;  // (handed over to a kept fused level as its frontier: a pooled block like the level's others)
-  counters.reserve(128);  // (words 0..7: the counters of a run; 8..11: the list lengths and work counters of the update)
+  counters.reserve(128);  // (words 0..7: the counters of a run; 8..13: the update's list lengths, work and reach counters; 14, 15: scan2's totals)
   acc_slots.reserve(COUNT_BYTES);
   act_slots.reserve(COUNT_BYTES);
   IMPG_HIP(hipHostMalloc((void **)&h_counters, 64, hipHostMallocDefault));
@@ -329,9 +329,9 @@ void Engine::scan2(const uint32_t *in_a, uint32_t *out_a, const uint32_t *in_b, 
   if (n) {
     scan_tmp.reserve(scan_scratch_bytes(n));
     scan_tmp2.reserve(scan_scratch_bytes(n));
-    launch_exclusive_scan(in_a, out_a, n, scan_tmp.as<unsigned long long>(), counters.as<unsigned long long>() + 12, stream);
-    launch_exclusive_scan(in_b, out_b, n, scan_tmp2.as<unsigned long long>(), counters.as<unsigned long long>() + 13, stream);
-    IMPG_HIP(hipMemcpyAsync(h_counters, counters.as<uint64_t>() + 12, 16, hipMemcpyDeviceToHost, stream));
+    launch_exclusive_scan(in_a, out_a, n, scan_tmp.as<unsigned long long>(), counters.as<unsigned long long>() + 14, stream);
+    launch_exclusive_scan(in_b, out_b, n, scan_tmp2.as<unsigned long long>(), counters.as<unsigned long long>() + 15, stream);
+    IMPG_HIP(hipMemcpyAsync(h_counters, counters.as<uint64_t>() + 14, 16, hipMemcpyDeviceToHost, stream));
   }
   if (n_extra) IMPG_HIP(hipMemcpyAsync(h_counters + 2, d_extra, (size_t)n_extra * 4, hipMemcpyDeviceToHost, stream));
   IMPG_HIP(hipStreamSynchronize(stream));
@@ -793,8 +793,21 @@ uint32_t Engine::update(const DeviceIndexView &v, const FrontierRec *fr, LevelBu
                             vt->off.as<uint32_t>(), poff.as<uint32_t>(), n_groups, p.min_transitive_len,
                             p.min_distance_between_ranges, vt->ranges.as<int2>(), vt->len.as<uint32_t>(),
                             pieces.as<int2>(), n_pieces.as<uint32_t>(), cap.as<uint32_t>(), pcap.as<uint32_t>(), big_list.as<uint32_t>(),
-                            (uint32_t *)(counters.as<uint64_t>() + 8), stream);
+                            (uint32_t *)(counters.as<uint64_t>() + 8), update_stats && upd_stats, stream);
       uint64_t nn = scan(n_pieces.as<uint32_t>(), foff.as<uint32_t>(), n_groups);
+      if (update_stats && upd_stats && n_groups) {  // (the scan has waited for the update: its words are final)
+        IMPG_HIP(hipMemcpyAsync(h_counters, counters.as<uint64_t>() + 8, VU_NBIG_WORDS * 4, hipMemcpyDeviceToHost, stream));
+        IMPG_HIP(hipStreamSynchronize(stream));
+        const uint32_t *w = reinterpret_cast<const uint32_t *>(h_counters), *reach = w + VU_REACH_BASE;
+        upd_stats[UPD_LANE] += n_groups - (w[0] + w[1] + w[2] + w[6]);
+        upd_stats[UPD_MID] += w[6];
+        upd_stats[UPD_WAVE_TINY] += w[2];
+        upd_stats[UPD_WAVE_SMALL] += w[0];
+        upd_stats[UPD_WAVE_LARGE] += w[1];
+        upd_stats[UPD_INPLACE] += reach[VU_REACH_INPLACE];
+        upd_stats[UPD_TILED_SORT] += reach[VU_REACH_TILED_SORT];
+        upd_stats[UPD_LANE_SPILL] += reach[VU_REACH_LANE_SPILL];
+      }
       if (nn >= 0xFFFFFFF0ull) { if (split_ok) throw SplitBatch{}; throw Error{IMPG_E_UNSUPPORTED, "frontier exceeds 2^32 ranges"}; }
       n_next = (uint32_t)nn;
       next_frontier.reserve(std::max<size_t>((size_t)n_next * sizeof(FrontierRec), 256));

@@ -126,6 +126,7 @@ struct Engine {
   DevBuf win_se, tile_first;       // the ranges' (start, end) by place; first range of every projection tile
   int filter_covered = 0;          // option "filter_covered": hits covered by their group's old list dropped before the replay (0 off: it bought nothing on config 5, where hits are covered by the list as it GROWS, not as the level found it; 1 always, 2 long groups)
   uint64_t covered_dropped = 0;    // ... how many that was, over the engine's life (tuning aid)
+  bool update_stats = false;       // option "update_stats": a level's update copies its list lengths and reach counters home (impg_gpu_index::upd_stats)
   DevBuf m_dest, m_qid, m_coords, m_pe, m_sa, m_sn, m_so, m_sr;  // 5-key sort: destination + double buffers
   // projection order (locality): ranges sorted by window position, their slots listed in that order
   DevBuf wide_n, wide_list;  // ranges whose window is wider than the lane-per-range emit pass takes
@@ -240,6 +241,7 @@ struct Engine {
   DevBuf seg_run, seg_q, seg_bins, seg_tot;  // update by segments: run bounds per frontier range; first / last range, active hits and output offset per query
   std::atomic<uint64_t> *seg_stats = nullptr;  // the handle's counters (impg_gpu_index::seg_stats), or null
   std::atomic<uint64_t> *proj_stats = nullptr;  // ... and its levels per projection kernel (impg_gpu_index::proj_stats, by ProjArm)
+  std::atomic<uint64_t> *upd_stats = nullptr;  // ... and its groups per tier / rare path of the visited update (by UpdStat; option update_stats)
   void count_arm(int arm) { if (proj_stats && arm >= 0 && arm < PROJ_ARMS) proj_stats[arm]++; }
   uint32_t seg_parts_force = 0;  // option "segment_parts": every level that groups by segments cuts its queries into this many slices (0: by size)
   bool seg_group = true;  // option "segment_groups": the update's hits grouped query by query instead of by the library's radix sort

@@ -437,6 +437,7 @@ struct impg_gpu_index {
   bool opt_regroup = true;
   bool opt_fuse_final = true;
   int opt_filter_covered = 0;
+  bool opt_update_stats = false;  // option "update_stats" (Engine::update_stats)
   int opt_walk = 1;
   uint32_t opt_walk_members = 0;  // option "walk_members" (Engine::walk_members)
   bool opt_seg_group = true;      // option "segment_groups" (Engine::seg_group)
@@ -450,6 +451,8 @@ struct impg_gpu_index {
   mutable std::atomic<uint64_t> seg_stats[3] = {};
   // ... and which kernel projected each level (by impg::ProjArm: launch_project's return value, counted by the engine)
   mutable std::atomic<uint64_t> proj_stats[8] = {};
+  // ... and, under option update_stats, the groups each tier of the visited update took and the rare paths they reached (by impg::UpdStat)
+  mutable std::atomic<uint64_t> upd_stats[8] = {};
   impg::ShardCtx *shard = nullptr;    // set: this index is one rank's shard; queries are collective calls
   impg::Cluster *cluster = nullptr;   // set: this handle fronts n_dev shards in this process (no arrays of its own)
   impg_gpu_index();

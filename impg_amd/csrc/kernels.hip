@@ -3407,7 +3407,8 @@ void visited_update_kernel(const unsigned long long *__restrict__ svals,
                                                             int32_t min_transitive_len, int32_t mdbr,
                                                             int2 *__restrict__ new_ranges, uint32_t *__restrict__ new_len,
                                                             int2 *__restrict__ pieces, uint32_t *__restrict__ n_pieces,
-                                                            const uint32_t *__restrict__ list, const uint32_t *__restrict__ n_list) {
+                                                            const uint32_t *__restrict__ list, const uint32_t *__restrict__ n_list,
+                                                            uint32_t *__restrict__ reach) {
   __shared__ int32_t lds_x[CAP * 64], lds_y[CAP * 64];
   const uint32_t n_items = LISTED ? *n_list : n_groups;
   for (uint32_t item0 = blockIdx.x * 64u; item0 < n_items; item0 += gridDim.x * 64u) {  // (one trip unless LISTED)
@@ -3563,6 +3564,11 @@ void visited_update_kernel(const unsigned long long *__restrict__ svals,
   if (mine) {
     new_len[g] = len;
     n_pieces[g] = np;
+  }
+  {  // (option update_stats, else reach is null: the groups whose pieces met the list in the column and moved to their global slice --
+     // a few per cent of a headline level's waves hold one, and 10^5 atomics on one word cost the update 1.6 ms when they were unconditional: headline workload, 20 steps, three runs each on one MI355X, update stage 6.07 -> 7.69 ms a step)
+    const unsigned long long sp = __ballot(fast && spilled);
+    if (reach && sp && threadIdx.x == 0) atomicAdd(reach + VU_REACH_LANE_SPILL, (uint32_t)__popcll(sp));
   }
 #ifdef IMPG_VU_CLOCKS
   VU_MARK(7);
@@ -4187,7 +4193,7 @@ __global__ __launch_bounds__(64) void visited_update_wave_kernel(const unsigned 
                                                                  int32_t min_transitive_len,
                                                                  int32_t mdbr, int2 *__restrict__ new_ranges,
                                                                  uint32_t *__restrict__ new_len, int2 *__restrict__ pieces,
-                                                                 uint32_t *__restrict__ n_pieces) {
+                                                                 uint32_t *__restrict__ n_pieces, uint32_t *__restrict__ reach) {
   // The capacities group_prepare sized (old length + hits, + 2 x hits for the pieces) are worst cases; what a group
   // really needs is usually a fraction (hits pile up on the same regions and merge).  The list therefore starts in
   // LDS whatever its worst case and moves to its global slice only if it really outgrows the buffer; the pieces go
@@ -4234,8 +4240,10 @@ __global__ __launch_bounds__(64) void visited_update_wave_kernel(const unsigned 
       for (uint32_t i = lane; i < len; i += 64u) R[i] = src[i];
     }
     __syncthreads();
-    if (t_next < n)  // the list outgrew the buffer (or never fitted): the rest of the replay in place
+    if (t_next < n) {  // the list outgrew the buffer (or never fitted): the rest of the replay in place
+      if (reach && lane == 0) atomicAdd(reach + VU_REACH_INPLACE, 1u);  // (option update_stats)
       len = replay_hits_wave(ListInPlace{R}, len, svals, st, n, sequence_length, min_transitive_len, mdbr, P, np, t_next, 0xFFFFFFFFu);
+    }
     __syncthreads();
     // next-depth ranges of the group: sorted by start, overlapping / contiguous ones merged (impg.rs:2568-2584)
     VW_T(vwp0);
@@ -4247,6 +4255,7 @@ __global__ __launch_bounds__(64) void visited_update_wave_kernel(const unsigned 
       wave_sort_pieces(S, np);
     } else {
       constexpr uint32_t TS = CAP >= 4096u ? 4096u : CAP >= 1024u ? 1024u : 128u;  // the largest power of two the buffer holds
+      if (reach && lane == 0) atomicAdd(reach + VU_REACH_TILED_SORT, 1u);  // (option update_stats)
       wave_sort_pieces_tiled<TS>(P, np, lds);
     }
     VW_T(vwp1);
@@ -5422,30 +5431,32 @@ void launch_visited_update(const unsigned long long *svals, const int32_t *seq_l
                            const int2 *const *old_src, const uint32_t *noff, const uint32_t *poff,
                            uint32_t n_groups, int32_t min_transitive_len, int32_t mdbr, int2 *new_ranges,
                            uint32_t *new_len, int2 *pieces, uint32_t *n_pieces, const uint32_t *cap, const uint32_t *pcap,
-                           uint32_t *big_list, uint32_t *n_big, hipStream_t s) {
+                           uint32_t *big_list, uint32_t *n_big, bool count_reach, hipStream_t s) {
   if (!n_groups) return;
-  (void)hipMemsetAsync(n_big, 0, 32, s);  // three list lengths, three work counters, the mid list's length
+  // three list lengths, three work counters, the mid list's length, a spare word, the reach counters (VU_REACH_*)
+  (void)hipMemsetAsync(n_big, 0, VU_NBIG_WORDS * 4, s);
+  uint32_t *reach = count_reach ? n_big + VU_REACH_BASE : nullptr;
   big_groups_kernel<<<cdiv(n_groups, BG_THREADS * BG_PER_THREAD), BG_THREADS, 0, s>>>(cap, pcap, n_groups, big_list, n_big);
   const unsigned long long *srcs = reinterpret_cast<const unsigned long long *>(old_src);
   visited_update_kernel<VU_LDS_CAP, false><<<cdiv(n_groups, 64), 64, 0, s>>>(svals, seq_len, gkey, gstart, glen, srcs, cap, noff, poff, n_groups,
                                                                              min_transitive_len, mdbr, new_ranges, new_len, pieces, n_pieces,
-                                                                             nullptr, nullptr);
+                                                                             nullptr, nullptr, reach);
   // the listed groups: as many blocks as stay resident (their number is on the device), each striding over the list
   const uint32_t mid_blocks = std::min<uint32_t>(cdiv(n_groups, 64), 256u * std::min(32u, (160u * 1024u) / (VU_MID_CAP * 64u * 8u)));
   visited_update_kernel<VU_MID_CAP, true><<<mid_blocks, 64, 0, s>>>(svals, seq_len, gkey, gstart, glen, srcs, cap, noff, poff, n_groups,
                                                                     min_transitive_len, mdbr, new_ranges, new_len, pieces, n_pieces,
-                                                                    big_list + 2u * (size_t)n_groups, n_big + 6);
+                                                                    big_list + 2u * (size_t)n_groups, n_big + 6, reach);
   // one wave per big group, grid-strided over however many there are (the count stays on the device)
   const uint32_t blocks = std::min<uint32_t>(n_groups, 256u * std::min(32u, (160u * 1024u) / (VW_CAP_SMALL * 8u)));
   visited_update_wave_kernel<VW_CAP_SMALL><<<blocks, 64, 0, s>>>(
       svals, seq_len, gkey, gstart, glen, old_src, cap, noff, poff, big_list, n_big, n_big + 3, 0u, min_transitive_len, mdbr, new_ranges,
-      new_len, pieces, n_pieces);
+      new_len, pieces, n_pieces, reach);
   visited_update_wave_kernel<VW_CAP_TINY, true><<<std::min<uint32_t>(n_groups, 256u * 32u), 64, 0, s>>>(
       svals, seq_len, gkey, gstart, glen, old_src, cap, noff, poff, big_list + n_groups, n_big + 2, n_big + 5, 0u, min_transitive_len, mdbr, new_ranges,
-      new_len, pieces, n_pieces);
+      new_len, pieces, n_pieces, reach);
   visited_update_wave_kernel<VW_CAP_LARGE><<<std::min<uint32_t>(n_groups, 256u * 5u), 64, 0, s>>>(
       svals, seq_len, gkey, gstart, glen, old_src, cap, noff, poff, big_list, n_big + 1, n_big + 4, n_groups, min_transitive_len, mdbr,
-      new_ranges, new_len, pieces, n_pieces);
+      new_ranges, new_len, pieces, n_pieces, reach);
 }
 void launch_covered_flags(const unsigned long long *svals, const uint32_t *head, const uint32_t *gid,
                           const unsigned long long *gkey, const int2 *const *old_src, const uint32_t *cap, const uint32_t *glen,

@@ -161,6 +161,15 @@ enum ProjArm : int {
   PROJ_ARMS
 };
 static_assert(PROJ_ARMS == sizeof(impg_gpu_index::proj_stats) / sizeof(impg_gpu_index::proj_stats[0]), "one counter per arm");
+// the visited update's groups by the kernel that took them, and the rare paths they reached (impg_gpu_get_counter "update_*")
+enum UpdStat {
+  UPD_LANE = 0, UPD_MID, UPD_WAVE_TINY, UPD_WAVE_SMALL, UPD_WAVE_LARGE,  // big_groups_kernel's tiers
+  UPD_INPLACE,     // wave kernel: the replay finished (or ran) in place on the group's global slice
+  UPD_TILED_SORT,  // wave kernel: more pieces than the LDS buffer holds (wave_sort_pieces_tiled)
+  UPD_LANE_SPILL,  // lane kernels: pieces and list met in the LDS column, the pieces moved to their global slice
+  UPD_STATS
+};
+static_assert(UPD_STATS == sizeof(impg_gpu_index::upd_stats) / sizeof(impg_gpu_index::upd_stats[0]), "one counter per path");
 int launch_project(const DeviceIndexView &v, const FrontierRec *fr, const uint32_t *pair_range,
                    const uint32_t *pair_entry, uint32_t n_pairs, bool transitive, HitArrays h,
                    unsigned long long *accepted, uint32_t *err_flag, double min_identity, const SliceArrays *slices,
@@ -202,12 +211,17 @@ void launch_table_qoff(const unsigned long long *keys, uint32_t n_groups, uint32
 void launch_group_prepare(const VisitedTables &vt, const unsigned long long *gkey, const uint32_t *gstart,
                           uint32_t n_groups, uint32_t n_active, uint32_t *glen, const int2 **old_src,
                           uint32_t *cap, uint32_t *pcap, hipStream_t s);
+// n_big: VU_NBIG_WORDS words, cleared by the launch.  [0] [1] [2] [6]: the groups listed for the wave kernel's small, large
+// and tiny working set and for the listed lane kernel (big_groups_kernel); [3..5] the wave kernels' work counters; from
+// VU_REACH_BASE on, the reach counters only the rare paths bump, and only under count_reach (option update_stats): groups whose replay ran in
+// place on the global slice, groups whose pieces took wave_sort_pieces_tiled, lane groups whose pieces left the LDS column
+constexpr uint32_t VU_NBIG_WORDS = 12, VU_REACH_BASE = 8, VU_REACH_INPLACE = 0, VU_REACH_TILED_SORT = 1, VU_REACH_LANE_SPILL = 2;
 void launch_visited_update(const unsigned long long *svals, const int32_t *seq_len,
                            const unsigned long long *gkey, const uint32_t *gstart, const uint32_t *glen,
                            const int2 *const *old_src, const uint32_t *noff, const uint32_t *poff,
                            uint32_t n_groups, int32_t min_transitive_len, int32_t mdbr, int2 *new_ranges,
                            uint32_t *new_len, int2 *pieces, uint32_t *n_pieces, const uint32_t *cap, const uint32_t *pcap,
-                           uint32_t *big_list, uint32_t *n_big, hipStream_t s);
+                           uint32_t *big_list, uint32_t *n_big, bool count_reach, hipStream_t s);
 // hits covered by their group's old list dropped before the replay (kernels.hip "covered_flags")
 void launch_covered_flags(const unsigned long long *svals, const uint32_t *head, const uint32_t *gid,
                           const unsigned long long *gkey, const int2 *const *old_src, const uint32_t *cap, const uint32_t *glen,

@@ -428,7 +428,11 @@ class GpuImpg:
         launch): "project_lane_levels" (project_kernel), "project_staged_levels", "project_staged_rows_levels"
         (project_staged_kernel, listed pairs / ordered rows), "project_entries_slots_levels",
         "project_entries_qs_levels", "project_entries_rows_levels", "project_entries_ident_levels"
-        (project_entries_kernel by output / the identity filter), "project_tp_levels" (tracepoint index)."""
+        (project_entries_kernel by output / the identity filter), "project_tp_levels" (tracepoint index).  Under
+        set_option("update_stats", 1), the visited update's groups per tier -- "update_lane_groups",
+        "update_mid_groups", "update_wave_tiny_groups", "update_wave_small_groups", "update_wave_large_groups" -- and
+        per rare path: "update_inplace_groups" (replay on the global slice), "update_tiled_sort_groups" (more pieces
+        than the LDS buffer), "update_lane_spill_groups" (a lane's pieces left its LDS column)."""
         v = C.c_int64(0)
         check(lib().impg_gpu_get_counter(self._h, key.encode(), C.byref(v)))
         return v.value

@@ -238,7 +238,11 @@ int impg_gpu_set_option(impg_gpu_index_t *, const char *key, int64_t value);
  * last grid-form launch (1: not the grid form); how the visited updates grouped their hits: "segment_sliced_levels" =
  * levels whose queries were cut into slices of their frontier ranges, "segment_retries" = levels counted a second time
  * because one query held more hits than a wave should take, "segment_library_levels" = levels that went through the
- * library's radix sort instead. */
+ * library's radix sort instead.  With option "update_stats" = 1 (0, the default: nothing is copied or counted) every
+ * level's visited update also counts its (query, sequence) groups by the kernel that took them -- "update_lane_groups",
+ * "update_mid_groups", "update_wave_tiny_groups", "update_wave_small_groups", "update_wave_large_groups" -- and by the
+ * rare path they reached: "update_inplace_groups" (the replay ran on the group's global slice), "update_tiled_sort_groups"
+ * (more pieces than the LDS buffer holds), "update_lane_spill_groups" (a lane's pieces left its LDS column). */
 int impg_gpu_get_counter(const impg_gpu_index_t *, const char *key, int64_t *value_out);
 /* Large result arrays live in pinned host blocks that are recycled through a process-wide pool (at most
  * IMPG_PINNED_POOL_BYTES, default 6 GiB, are kept when results are freed).  Gives pooled blocks back to the system
