@@ -51,22 +51,8 @@ static void engine_options(impg_gpu_index &ix, Engine *e) {
   e->update_stats = ix.opt_update_stats;
   e->upd_stats = ix.upd_stats;
 }
-EngineLease::EngineLease(impg_gpu_index &ix_) : ix(ix_) {
-  std::unique_lock<std::mutex> lk(ix.eng_m);
-  for (;;) {
-    if (!ix.eng_free.empty()) { e = ix.eng_free.back(); ix.eng_free.pop_back(); break; }
-    if ((int)ix.engines.size() < ix.max_engines) {
-      ix.engines.emplace_back(new Engine(ix.device));
-      e = ix.engines.back().get();
-      break;
-    }
-    ix.eng_cv.wait(lk);
-  }
-  engine_options(ix, e);
-}
-// An engine for a handle that keeps it (a partition session): never waits -- null when every engine is out.
-Engine *try_lease_engine(impg_gpu_index &ix) {
-  std::unique_lock<std::mutex> lk(ix.eng_m);
+// The free engine used last, else a new one while the handle may have more; null: every engine is out.  (eng_m held.)
+static Engine *take_or_create(impg_gpu_index &ix) {
   Engine *e = nullptr;
   if (!ix.eng_free.empty()) { e = ix.eng_free.back(); ix.eng_free.pop_back(); }
   else if ((int)ix.engines.size() < ix.max_engines) {
@@ -76,36 +62,25 @@ Engine *try_lease_engine(impg_gpu_index &ix) {
   engine_options(ix, e);
   return e;
 }
-void return_engine(impg_gpu_index &ix, Engine *e) {
+EngineLease::EngineLease(impg_gpu_index &ix_) : ix(ix_) {
+  std::unique_lock<std::mutex> lk(ix.eng_m);
+  while (!(e = take_or_create(ix))) ix.eng_cv.wait(lk);
+}
+// An engine for a handle that keeps it (a partition session): never waits -- null when every engine is out.
+Engine *try_lease_engine(impg_gpu_index &ix) {
+  std::unique_lock<std::mutex> lk(ix.eng_m);
+  return take_or_create(ix);
+}
+void return_engine(impg_gpu_index &ix, Engine *e) {  // the lease's end: what belonged to it ends here (engine.hpp)
   e->remote = nullptr;
   e->masked = false;
   e->subset_on = false;
-  e->on_kernels_done = nullptr;  // (the row stream's hook captures its caller's locals: never past the lease)
-  e->keep_any_order = false;
-  e->ordered_rows = false;
   std::lock_guard<std::mutex> lk(ix.eng_m);
   ix.eng_free.push_back(e);
   ix.eng_cv.notify_one();
 }
-void return_engine(impg_gpu_index &ix, Engine *e);
 EngineLease::~EngineLease() { return_engine(ix, e); }
 }  // namespace impg
-
-#define IMPG_TRY try {
-#define IMPG_CATCH                                  \
-  }                                                 \
-  catch (const impg::Error &e) {                    \
-    impg::set_error(e.msg);                         \
-    return e.code;                                  \
-  }                                                 \
-  catch (const std::bad_alloc &) {                  \
-    impg::set_error("host out of memory");          \
-    return IMPG_E_OOM;                              \
-  }                                                 \
-  catch (const std::exception &e) {                 \
-    impg::set_error(std::string("internal: ") + e.what()); \
-    return IMPG_E_INVALID;                          \
-  }
 
 namespace impg {
 
@@ -148,7 +123,7 @@ namespace impg {
 // enqueued, ahead of the copies (whoever takes turns on the GPU may let the next one in while the rows cross PCIe)
 void assemble_results(Engine &E, const impg_gpu_range_t *h_ranges, uint32_t n, const impg_gpu_params_t &p,
                       std::vector<std::unique_ptr<LevelBufs>> &levels, DevBuf &self_dev, impg_gpu_results &res, uint64_t max_rows,
-                      hipEvent_t kernels_done) {
+                      hipEvent_t kernels_done, const std::function<void()> &on_kernels_done) {
   hipStream_t s = E.stream;
   res.ranges.assign(h_ranges, h_ranges + n);
   res.has_cigar = p.store_cigar != 0;
@@ -181,12 +156,81 @@ void assemble_results(Engine &E, const impg_gpu_range_t *h_ranges, uint32_t n, c
     IMPG_HIP(hipMemcpyAsync(res.cigar_off.data(), coff.p, (nr + 1) * 8, hipMemcpyDeviceToHost, s));
     if (n_ops) IMPG_HIP(hipMemcpyAsync(res.cigar_ops.data(), cpool.p, n_ops * 4, hipMemcpyDeviceToHost, s));
   }
-  if (kernels_done) { IMPG_HIP(hipEventSynchronize(kernels_done)); if (E.on_kernels_done) E.on_kernels_done(); }
+  if (kernels_done) { IMPG_HIP(hipEventSynchronize(kernels_done)); if (on_kernels_done) on_kernels_done(); }
   IMPG_HIP(hipStreamSynchronize(s));
   levels.clear();
   res.offsets.resize((size_t)n + 1);
   for (size_t q = 0; q <= n; q++) res.offsets[q] = off32[q];
   res.projected = E.last_projected;
+}
+
+const impg_gpu_range_t *upload_ranges(DevBuf &dst, const impg_gpu_range_t *ranges, size_t n, const hipStream_t *async_on) {
+  dst.reserve(std::max<size_t>(n * sizeof(impg_gpu_range_t), 256));
+  if (n && async_on) IMPG_HIP(hipMemcpyAsync(dst.p, ranges, n * sizeof(impg_gpu_range_t), hipMemcpyHostToDevice, *async_on));
+  else if (n) IMPG_HIP(hipMemcpy(dst.p, ranges, n * sizeof(impg_gpu_range_t), hipMemcpyHostToDevice));
+  return dst.as<impg_gpu_range_t>();
+}
+
+StatSinks::StatSinks(DevBuf &cnt, DevBuf &ck, bool want_count, bool want_cksum, size_t n, const hipStream_t *async_on) {
+  auto zeroed = [&](DevBuf &b) {
+    b.reserve(std::max<size_t>(n * 8, 256));
+    if (async_on) IMPG_HIP(hipMemsetAsync(b.p, 0, n * 8, *async_on));
+    else IMPG_HIP(hipMemset(b.p, 0, std::max<size_t>(n * 8, 8)));
+    return b.as<unsigned long long>();
+  };
+  if (want_count) count = zeroed(cnt);
+  if (want_cksum) cksum = zeroed(ck);
+}
+void StatSinks::home(uint64_t *per_range_count, uint64_t *per_range_checksum, size_t n) const {
+  if (per_range_count && n) IMPG_HIP(hipMemcpy(per_range_count, count, n * 8, hipMemcpyDeviceToHost));
+  if (per_range_checksum && n) IMPG_HIP(hipMemcpy(per_range_checksum, cksum, n * 8, hipMemcpyDeviceToHost));
+}
+
+bool run_chunk_rows(const impg_gpu_index &ix, Engine &E, const impg_gpu_range_t *d_ranges, const impg_gpu_range_t *h_ranges, size_t b,
+                    size_t e, const impg_gpu_params_t &p, impg_gpu_results &part, std::mutex *gpu_turn, uint64_t max_rows,
+                    hipEvent_t kernels_done, const std::function<void()> &on_kernels_done) {
+  std::vector<std::unique_ptr<LevelBufs>> levels;
+  DevBuf self_dev;
+  self_dev.pool = &E.level_pool;
+  const auto c0 = std::chrono::steady_clock::now();
+  {
+    const auto turn = take_turn(gpu_turn);
+    RunSpec rs(d_ranges + b, (uint32_t)(e - b), p);
+    rs.keep = &levels;
+    rs.self_out = &self_dev;
+    E.run(ix, rs);
+  }
+  const auto c1 = std::chrono::steady_clock::now();
+  if (e == b) return false;
+  assemble_results(E, h_ranges + b, (uint32_t)(e - b), p, levels, self_dev, part, max_rows, kernels_done, on_kernels_done);
+  part.run_s = std::chrono::duration<double>(c1 - c0).count();
+  part.assemble_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - c1).count();
+  return true;
+}
+
+bool run_chunk_bed(const impg_gpu_index &ix, Engine &E, const impg_gpu_range_t *d_ranges, const impg_gpu_range_t *h_ranges,
+                   const char *const *range_names, size_t b, size_t e, const impg_gpu_params_t &p, int32_t merge_distance,
+                   const std::function<void(const char *, size_t)> &sink, double *seconds3, std::mutex *gpu_turn) {
+  std::vector<std::unique_ptr<LevelBufs>> levels;
+  DevBuf self_dev, rows;
+  self_dev.pool = &E.level_pool;
+  const auto turn = take_turn(gpu_turn);
+  const auto c0 = std::chrono::steady_clock::now();
+  RunSpec rs(d_ranges + b, (uint32_t)(e - b), p);
+  rs.keep = &levels;
+  rs.self_out = &self_dev;
+  E.run(ix, rs);
+  const auto c1 = std::chrono::steady_clock::now();
+  if (e == b) return false;
+  const uint32_t n_rows = device_bed_rows(E, ix, (uint32_t)(e - b), p, merge_distance, levels, self_dev, rows);
+  const auto c2 = std::chrono::steady_clock::now();
+  device_bed_text(E, ix, rows, n_rows, (uint32_t)(e - b), bed_range_names(ix, h_ranges, range_names, b, e),
+                  p.original_sequence_coordinates != 0, sink);
+  const auto c3 = std::chrono::steady_clock::now();
+  seconds3[0] += std::chrono::duration<double>(c1 - c0).count();
+  seconds3[1] += std::chrono::duration<double>(c2 - c1).count();
+  seconds3[2] += std::chrono::duration<double>(c3 - c2).count();
+  return true;
 }
 
 }  // namespace impg
@@ -214,42 +258,52 @@ template <class F> void for_chunks(Engine &E, size_t n, F fn) {
 }  // namespace
 
 namespace {
-// The trait's rows from the per-query walk (Engine::run_walk).  A handful of queries write into generous fixed
-// regions of one pool and are done in one launch; a batch (or a query that outgrows its region) is counted first and
-// walked again with every query's rows at their final place -- the walk is deterministic, so the second pass writes
-// exactly what the first counted.
-bool walk_query(impg_gpu_index &ix, Engine &E, const impg_gpu_range_t *h_ranges, uint32_t n, const impg_gpu_params_t &p, impg_gpu_results &res) {
+// The per-query walk (Engine::run_walk) with its rows kept, over the n ranges in E.ranges_dev.  Every query writes into
+// its region of W.rows (base[q], cap[q] rows); if one outgrew its region the queries are walked again with every
+// query's rows at their final place, back to back -- the walk is deterministic, so the second pass writes exactly what
+// the first counted (`exact` is then set).  cnt[q]: the rows of query q.  false: the walk did not take the batch.
+bool walk_two_pass(impg_gpu_index &ix, Engine &E, uint32_t n, const impg_gpu_params_t &p, Engine::WalkRows &W,
+                   std::vector<unsigned long long> &base, std::vector<uint32_t> &cap, std::vector<uint32_t> &cnt, bool &exact) {
   hipStream_t s = E.stream;
-  Engine::WalkRows W;
   for (DevBuf *b : {&W.rows, &W.base, &W.cap, &W.n_rows}) b->pool = &E.level_pool;
   W.base.reserve(std::max<size_t>((size_t)n * 8, 256)); W.cap.reserve(std::max<size_t>((size_t)n * 4, 256));
   W.n_rows.reserve(std::max<size_t>((size_t)n * 4, 256));
-  std::vector<unsigned long long> base(n);
-  std::vector<uint32_t> cap(n), cnt(n);
-  const bool optimistic = n <= Engine::SMALL_RANGES;
-  const uint32_t each = optimistic ? (1u << 17) : 0u;
-  for (uint32_t q = 0; q < n; q++) { base[q] = (unsigned long long)q * each; cap[q] = each; }
-  auto pass = [&](uint64_t total_rows) {
+  cnt.assign(n, 0);
+  auto pass = [&]() {
+    uint64_t total_rows = 0;
+    for (uint32_t q = 0; q < n; q++) total_rows += cap[q];
     W.rows.reserve(std::max<size_t>(total_rows * sizeof(impg_gpu_interval_t), 256));
     IMPG_HIP(hipMemcpyAsync(W.base.p, base.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
     IMPG_HIP(hipMemcpyAsync(W.cap.p, cap.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
     return E.run_walk(ix, E.ranges_dev.as<impg_gpu_range_t>(), n, p, nullptr, nullptr, nullptr, &W, cnt.data());  // (cnt: the rows every query wrote)
   };
-  if (!pass((uint64_t)n * each)) return false;
+  exact = false;
+  if (!pass()) return false;
   bool fits = true;
-  uint64_t total = 0;
-  for (uint32_t q = 0; q < n; q++) { fits = fits && cnt[q] <= cap[q]; total += cnt[q]; }
+  for (uint32_t q = 0; q < n; q++) fits = fits && cnt[q] <= cap[q];
+  if (fits) return true;
+  uint64_t at = 0;
+  for (uint32_t q = 0; q < n; q++) { base[q] = at; cap[q] = cnt[q]; at += cnt[q]; }
+  const std::vector<uint32_t> want = cnt;
+  if (!pass()) return false;
+  if (cnt != want) throw Error{IMPG_E_INVALID, "internal: the walk's second pass disagrees with its first"};
+  exact = true;
+  return true;
+}
+// The trait's rows from the per-query walk.  A handful of queries write into generous fixed regions of one pool and are
+// done in one launch; a batch is counted first (regions of no rows) and walked again.
+bool walk_query(impg_gpu_index &ix, Engine &E, uint32_t n, const impg_gpu_params_t &p, impg_gpu_results &res) {
+  hipStream_t s = E.stream;
+  Engine::WalkRows W;
+  const uint32_t each = n <= Engine::SMALL_RANGES ? (1u << 17) : 0u;
+  std::vector<unsigned long long> base(n);
+  std::vector<uint32_t> cap(n, each), cnt;
+  for (uint32_t q = 0; q < n; q++) base[q] = (unsigned long long)q * each;
   bool contiguous = false;
-  if (!fits) {
-    uint64_t at = 0;
-    for (uint32_t q = 0; q < n; q++) { base[q] = at; cap[q] = cnt[q]; at += cnt[q]; }
-    const std::vector<uint32_t> want = cnt;
-    if (!pass(total)) return false;
-    if (cnt != want) throw Error{IMPG_E_INVALID, "internal: the walk's second pass disagrees with its first"};
-    contiguous = true;
-  }
+  if (!walk_two_pass(ix, E, n, p, W, base, cap, cnt, contiguous)) return false;
+  uint64_t total = 0;
   res.offsets.assign((size_t)n + 1, 0);
-  for (uint32_t q = 0; q < n; q++) res.offsets[q + 1] = res.offsets[q] + cnt[q];
+  for (uint32_t q = 0; q < n; q++) { res.offsets[q + 1] = res.offsets[q] + cnt[q]; total += cnt[q]; }
   res.intervals.resize(total, true);
   const impg_gpu_interval_t *d_rows = W.rows.as<impg_gpu_interval_t>();
   if (contiguous) {
@@ -264,7 +318,6 @@ bool walk_query(impg_gpu_index &ix, Engine &E, const impg_gpu_range_t *h_ranges,
   ix.result_rows_to_host += total;
   res.has_cigar = false;
   res.projected = E.last_projected;
-  (void)h_ranges;
   return true;
 }
 }  // namespace
@@ -277,39 +330,27 @@ uint32_t query_rows_device(impg_gpu_index &ix, Engine &E, const impg_gpu_range_t
                            const impg_gpu_interval_t *&d_rows, bool &walked) {
   hipStream_t s = E.stream;
   walked = false;
-  E.ranges_dev.reserve(256);
-  IMPG_HIP(hipMemcpyAsync(E.ranges_dev.p, &range, sizeof range, hipMemcpyHostToDevice, s));
+  upload_ranges(E.ranges_dev, &range, 1, &s);
   if (E.walk_applicable(ix, 1, p)) {
     Engine::WalkRows W;
-    for (DevBuf *b : {&W.rows, &W.base, &W.cap, &W.n_rows}) b->pool = &E.level_pool;
-    W.base.reserve(256); W.cap.reserve(256); W.n_rows.reserve(256);
-    unsigned long long base = 0;
-    uint32_t cap = 1u << 17, cnt = 0;
-    auto pass = [&]() {
-      W.rows.reserve(std::max<size_t>((size_t)cap * sizeof(impg_gpu_interval_t), 256));
-      IMPG_HIP(hipMemcpyAsync(W.base.p, &base, 8, hipMemcpyHostToDevice, s));
-      IMPG_HIP(hipMemcpyAsync(W.cap.p, &cap, 4, hipMemcpyHostToDevice, s));
-      return E.run_walk(ix, E.ranges_dev.as<impg_gpu_range_t>(), 1, p, nullptr, nullptr, nullptr, &W, &cnt);
-    };
-    bool ok = pass();
-    if (ok && cnt > cap) {
-      const uint32_t want = cnt;
-      cap = cnt;
-      ok = pass();
-      if (ok && cnt != want) throw Error{IMPG_E_INVALID, "internal: the walk's second pass disagrees with its first"};
-    }
-    if (ok) {
+    std::vector<unsigned long long> base(1, 0);
+    std::vector<uint32_t> cap(1, 1u << 17), cnt;
+    bool exact;
+    if (walk_two_pass(ix, E, 1, p, W, base, cap, cnt, exact)) {
       rows.adopt(W.rows);
       d_rows = rows.as<impg_gpu_interval_t>();
       walked = true;
-      return cnt;
+      return cnt[0];
     }
   }
   std::vector<std::unique_ptr<LevelBufs>> levels;
   DevBuf self_dev;
   self_dev.pool = &E.level_pool;
   try {
-    E.run(ix, E.ranges_dev.as<impg_gpu_range_t>(), 1, p, &levels, nullptr, nullptr, nullptr, &self_dev);
+    RunSpec rs(E.ranges_dev.as<impg_gpu_range_t>(), 1, p);
+    rs.keep = &levels;
+    rs.self_out = &self_dev;
+    E.run(ix, rs);
   } catch (const SplitBatch &) {
     throw Error{IMPG_E_UNSUPPORTED, "a single range exceeds the pair budget"};
   }
@@ -692,55 +733,53 @@ int impg_gpu_visit_rank(uint32_t n, int order_policy, uint32_t *rank_out) {
 
 }  // extern "C"
 namespace impg {
-// masked_regions -> the engine's device tables (EngineLease clears the flag when the call ends)
+// masked_regions -> the engine's device tables (the lease's end clears the flag)
 void apply_mask(Engine &E, const impg_gpu_index &ix, const impg_gpu_mask_t *m, const impg_gpu_params_t &p) {
-  {
-    if (!m) return;
-    if (!p.transitive) throw Error{IMPG_E_INVALID, "masked_regions belong to the transitive queries"};
-    const uint32_t n_seq = ix.view.n_seq;
-    if (m->n_seqs && (!m->seq_id || !m->sequence_length || !m->range_off)) throw Error{IMPG_E_INVALID, "null mask array"};
-    const uint64_t total = m->n_seqs ? m->range_off[m->n_seqs] : 0;
-    if (total >= 0xFFFFFFF0ull) throw Error{IMPG_E_UNSUPPORTED, "mask exceeds 2^32 ranges"};
-    if (total && !m->ranges) throw Error{IMPG_E_INVALID, "null mask array"};
-    std::vector<uint32_t> off(n_seq + 1, 0);
-    // a sequence absent from the map: Impg starts its set with length 0 (visited_entry, impg.rs:2048-2053), MultiImpg
-    // with the real length (multi_impg.rs:919-922) except for the query's own target (entry().or_default(), :827-830)
-    std::vector<int32_t> init_len(n_seq, 0), touch_len(n_seq, 0);
-    bool has_empty = false;
-    if (p.multi_impg) for (uint32_t s = 0; s < n_seq; s++) touch_len[s] = (int32_t)std::min<int64_t>(std::max<int64_t>(ix.seq.lens[s], 0), INT32_MAX);
-    for (uint32_t i = 0; i < m->n_seqs; i++) {
-      const uint32_t s = m->seq_id[i];
-      if (s >= n_seq) throw Error{IMPG_E_INVALID, "mask names an unknown sequence id"};
-      if (i && s <= m->seq_id[i - 1]) throw Error{IMPG_E_INVALID, "mask sequence ids must be strictly ascending"};
-      if (m->range_off[i + 1] < m->range_off[i]) throw Error{IMPG_E_INVALID, "mask offsets must not decrease"};
-      off[s + 1] = (uint32_t)(m->range_off[i + 1] - m->range_off[i]);
-      init_len[s] = touch_len[s] = m->sequence_length[i];
-      for (uint64_t k = m->range_off[i]; k < m->range_off[i + 1]; k++) {
-        const int32_t a = m->ranges[2 * k], b = m->ranges[2 * k + 1];
-        if (a > b || (k > m->range_off[i] && a <= m->ranges[2 * k - 1]))  // SortedRanges invariant (impg.rs:330-368)
-          throw Error{IMPG_E_INVALID, "mask ranges must be sorted, disjoint and non-touching"};
-        has_empty = has_empty || a == b;
-      }
+  if (!m) return;
+  if (!p.transitive) throw Error{IMPG_E_INVALID, "masked_regions belong to the transitive queries"};
+  const uint32_t n_seq = ix.view.n_seq;
+  if (m->n_seqs && (!m->seq_id || !m->sequence_length || !m->range_off)) throw Error{IMPG_E_INVALID, "null mask array"};
+  const uint64_t total = m->n_seqs ? m->range_off[m->n_seqs] : 0;
+  if (total >= 0xFFFFFFF0ull) throw Error{IMPG_E_UNSUPPORTED, "mask exceeds 2^32 ranges"};
+  if (total && !m->ranges) throw Error{IMPG_E_INVALID, "null mask array"};
+  std::vector<uint32_t> off(n_seq + 1, 0);
+  // a sequence absent from the map: Impg starts its set with length 0 (visited_entry, impg.rs:2048-2053), MultiImpg
+  // with the real length (multi_impg.rs:919-922) except for the query's own target (entry().or_default(), :827-830)
+  std::vector<int32_t> init_len(n_seq, 0), touch_len(n_seq, 0);
+  bool has_empty = false;
+  if (p.multi_impg) for (uint32_t s = 0; s < n_seq; s++) touch_len[s] = (int32_t)std::min<int64_t>(std::max<int64_t>(ix.seq.lens[s], 0), INT32_MAX);
+  for (uint32_t i = 0; i < m->n_seqs; i++) {
+    const uint32_t s = m->seq_id[i];
+    if (s >= n_seq) throw Error{IMPG_E_INVALID, "mask names an unknown sequence id"};
+    if (i && s <= m->seq_id[i - 1]) throw Error{IMPG_E_INVALID, "mask sequence ids must be strictly ascending"};
+    if (m->range_off[i + 1] < m->range_off[i]) throw Error{IMPG_E_INVALID, "mask offsets must not decrease"};
+    off[s + 1] = (uint32_t)(m->range_off[i + 1] - m->range_off[i]);
+    init_len[s] = touch_len[s] = m->sequence_length[i];
+    for (uint64_t k = m->range_off[i]; k < m->range_off[i + 1]; k++) {
+      const int32_t a = m->ranges[2 * k], b = m->ranges[2 * k + 1];
+      if (a > b || (k > m->range_off[i] && a <= m->ranges[2 * k - 1]))  // SortedRanges invariant (impg.rs:330-368)
+        throw Error{IMPG_E_INVALID, "mask ranges must be sorted, disjoint and non-touching"};
+      has_empty = has_empty || a == b;
     }
-    for (uint32_t s = 0; s < n_seq; s++) off[s + 1] += off[s];
-    // m->ranges is already in sequence-id order
-    E.mask_off.reserve((size_t)(n_seq + 1) * 4);
-    E.mask_ranges.reserve(std::max<size_t>(total * 8, 256));
-    E.mask_init_len.reserve(std::max<size_t>((size_t)n_seq * 4, 256));
-    E.mask_touch_len.reserve(std::max<size_t>((size_t)n_seq * 4, 256));
-    IMPG_HIP(hipMemcpy(E.mask_off.p, off.data(), (size_t)(n_seq + 1) * 4, hipMemcpyHostToDevice));
-    ix.mask_table_uploads++;
-    if (total) { IMPG_HIP(hipMemcpy(E.mask_ranges.p, m->ranges, total * 8, hipMemcpyHostToDevice)); ix.mask_table_uploads++; }
-    if (n_seq) {
-      IMPG_HIP(hipMemcpy(E.mask_init_len.p, init_len.data(), (size_t)n_seq * 4, hipMemcpyHostToDevice));
-      IMPG_HIP(hipMemcpy(E.mask_touch_len.p, touch_len.data(), (size_t)n_seq * 4, hipMemcpyHostToDevice));
-      ix.mask_table_uploads += 2;
-    }
-    E.masked = true;
-    E.mask_has_empty = has_empty;
-    E.mask_ranges_total = total;
-    E.mask_lists = m->n_seqs;
   }
+  for (uint32_t s = 0; s < n_seq; s++) off[s + 1] += off[s];
+  // m->ranges is already in sequence-id order
+  E.mask_off.reserve((size_t)(n_seq + 1) * 4);
+  E.mask_ranges.reserve(std::max<size_t>(total * 8, 256));
+  E.mask_init_len.reserve(std::max<size_t>((size_t)n_seq * 4, 256));
+  E.mask_touch_len.reserve(std::max<size_t>((size_t)n_seq * 4, 256));
+  IMPG_HIP(hipMemcpy(E.mask_off.p, off.data(), (size_t)(n_seq + 1) * 4, hipMemcpyHostToDevice));
+  ix.mask_table_uploads++;
+  if (total) { IMPG_HIP(hipMemcpy(E.mask_ranges.p, m->ranges, total * 8, hipMemcpyHostToDevice)); ix.mask_table_uploads++; }
+  if (n_seq) {
+    IMPG_HIP(hipMemcpy(E.mask_init_len.p, init_len.data(), (size_t)n_seq * 4, hipMemcpyHostToDevice));
+    IMPG_HIP(hipMemcpy(E.mask_touch_len.p, touch_len.data(), (size_t)n_seq * 4, hipMemcpyHostToDevice));
+    ix.mask_table_uploads += 2;
+  }
+  E.masked = true;
+  E.mask_has_empty = has_empty;
+  E.mask_ranges_total = total;
+  E.mask_lists = m->n_seqs;
 }
 void apply_subset(Engine &E, const impg_gpu_index &ix, const uint8_t *subset_keep) {
   if (!subset_keep) return;
@@ -784,11 +823,10 @@ int impg_gpu_query_batch_filtered(impg_gpu_index_t *ix, const impg_gpu_range_t *
       return IMPG_OK;
     }
   }
-  E.ranges_dev.reserve(std::max<size_t>(n * sizeof(impg_gpu_range_t), 256));
-  if (n) IMPG_HIP(hipMemcpyAsync(E.ranges_dev.p, ranges, n * sizeof(impg_gpu_range_t), hipMemcpyHostToDevice, E.stream));
+  const impg_gpu_range_t *d_ranges = upload_ranges(E.ranges_dev, ranges, n, &E.stream);
   if (n < (1ull << 31) && E.walk_applicable(*ix, (uint32_t)n, *params)) {  // small transitive batches, DFS batches: one launch
     const auto c0 = std::chrono::steady_clock::now();
-    if (walk_query(*ix, E, ranges, (uint32_t)n, *params, *res)) {
+    if (walk_query(*ix, E, (uint32_t)n, *params, *res)) {
       res->run_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - c0).count();
       res->ranges.assign(ranges, ranges + n);
       *out = res.release();
@@ -798,17 +836,9 @@ int impg_gpu_query_batch_filtered(impg_gpu_index_t *ix, const impg_gpu_range_t *
   }
   res->offsets.assign(1, 0);
   for_chunks(E, n, [&](size_t b, size_t e) {
-    std::vector<std::unique_ptr<LevelBufs>> levels;
-    DevBuf self_dev;
-    self_dev.pool = &E.level_pool;
-    const auto c0 = std::chrono::steady_clock::now();
-    E.run(*ix, E.ranges_dev.as<impg_gpu_range_t>() + b, (uint32_t)(e - b), *params, &levels, nullptr, nullptr, nullptr, &self_dev);
-    const auto c1 = std::chrono::steady_clock::now();
     impg_gpu_results part;
-    assemble_results(E, ranges + b, (uint32_t)(e - b), *params, levels, self_dev, part);
+    run_chunk_rows(*ix, E, d_ranges, ranges, b, e, *params, part);
     ix->result_rows_to_host += part.intervals.size();
-    part.run_s = std::chrono::duration<double>(c1 - c0).count();
-    part.assemble_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - c1).count();
     append_results(*res, part);
   });
   res->ranges.assign(ranges, ranges + n);
@@ -896,8 +926,7 @@ int impg_gpu_query_batch_stream(impg_gpu_index_t *ix, const impg_gpu_range_t *ra
       Engine &E = *lease;
       apply_mask(E, *ix, mask, *params);
       apply_subset(E, *ix, subset_keep);
-      E.ranges_dev.reserve(std::max<size_t>(n * sizeof(impg_gpu_range_t), 256));
-      if (n) IMPG_HIP(hipMemcpyAsync(E.ranges_dev.p, ranges, n * sizeof(impg_gpu_range_t), hipMemcpyHostToDevice, E.stream));
+      const impg_gpu_range_t *d_ranges = upload_ranges(E.ranges_dev, ranges, n, &E.stream);
       struct Ev {  // (an event of the call's own: the engine recycles its pool run by run)
         hipEvent_t e = nullptr;
         Ev() { IMPG_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); }
@@ -919,23 +948,12 @@ int impg_gpu_query_batch_stream(impg_gpu_index_t *ix, const impg_gpu_range_t *ra
         while (!todo.empty()) {
           const auto [pb, pe] = todo.back();
           todo.pop_back();
-          std::unique_lock<std::mutex> turn(sh.gpu);
-          bool released = false;
-          E.on_kernels_done = [&]() { if (!released) { released = true; turn.unlock(); } };
+          std::unique_lock<std::mutex> turn(sh.gpu);  // passed on once the chunk's kernels have run: its copies overlap the other engine's kernels
           try {
-            std::vector<std::unique_ptr<LevelBufs>> levels;
-            DevBuf self_dev;
-            self_dev.pool = &E.level_pool;
-            const auto c0 = std::chrono::steady_clock::now();
-            E.run(*ix, E.ranges_dev.as<impg_gpu_range_t>() + pb, (uint32_t)(pe - pb), *params, &levels, nullptr, nullptr, nullptr, &self_dev);
-            const auto c1 = std::chrono::steady_clock::now();
             part.offsets.clear(); part.intervals.clear(); part.cigar_off.clear(); part.cigar_ops.clear();
-            assemble_results(E, ranges + pb, (uint32_t)(pe - pb), *params, levels, self_dev, part, max_rows, done);
+            run_chunk_rows(*ix, E, d_ranges, ranges, pb, pe, *params, part, nullptr, max_rows, done, [&]() { turn.unlock(); });
             ix->result_rows_to_host += part.intervals.size();
-            part.run_s = std::chrono::duration<double>(c1 - c0).count();
-            part.assemble_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - c1).count();
           } catch (const SplitBatch &) {
-            E.on_kernels_done = nullptr;
             if (pe - pb <= 1) throw Error{IMPG_E_UNSUPPORTED, "a single range exceeds the pair budget"};
             const size_t mid = pb + (pe - pb) / 2;
             {  // (the chunks still to be dealt start at the size that fitted: a split costs the run that found it out)
@@ -946,8 +964,7 @@ int impg_gpu_query_batch_stream(impg_gpu_index_t *ix, const impg_gpu_range_t *ra
             todo.push_back({pb, mid});
             continue;
           }
-          E.on_kernels_done = nullptr;
-          if (!released) turn.unlock();
+          if (turn.owns_lock()) turn.unlock();
           // in range order: this chunk's turn comes when every earlier chunk has been handed over
           std::unique_lock<std::mutex> lk(sh.m);
           sh.cv.wait(lk, [&] { return sh.stop || sh.deliver_seq == seq; });
@@ -994,33 +1011,22 @@ void impg_gpu_results_free(impg_gpu_results_t *r) { delete r; }
 
 static int stats_impl(impg_gpu_index_t *ix, Engine &E, const impg_gpu_range_t *d_ranges, size_t n, const impg_gpu_params_t *params,
                       uint64_t *per_range_count, uint64_t *per_range_checksum, impg_gpu_stats_t *stats) {
-  unsigned long long *dc = nullptr, *dk = nullptr;
-  if (per_range_count) {
-    E.stat_count.reserve(std::max<size_t>(n * 8, 256));
-    IMPG_HIP(hipMemsetAsync(E.stat_count.p, 0, n * 8, E.stream));
-    dc = E.stat_count.as<unsigned long long>();
-  }
-  if (per_range_checksum) {
-    E.stat_cksum.reserve(std::max<size_t>(n * 8, 256));
-    IMPG_HIP(hipMemsetAsync(E.stat_cksum.p, 0, n * 8, E.stream));
-    dk = E.stat_cksum.as<unsigned long long>();
-  }
+  const StatSinks sinks(E.stat_count, E.stat_cksum, per_range_count, per_range_checksum, n, &E.stream);
   impg_gpu_stats_t tot;
   memset(&tot, 0, sizeof tot);
   for_chunks(E, n, [&](size_t b, size_t e) {
     impg_gpu_stats_t st;
+    RunSpec rs(d_ranges + b, (uint32_t)(e - b), *params);
+    rs.stats = &st;
+    sinks.aim(rs, b);
     // a split retry must not double-count the slice
-    if (dc) IMPG_HIP(hipMemsetAsync(dc + b, 0, (e - b) * 8, E.stream));
-    if (dk) IMPG_HIP(hipMemsetAsync(dk + b, 0, (e - b) * 8, E.stream));
-    E.run(*ix, d_ranges + b, (uint32_t)(e - b), *params, nullptr, dc ? dc + b : nullptr, dk ? dk + b : nullptr, &st, nullptr);
-    tot.projected += st.projected; tot.pairs += st.pairs; tot.frontier_ranges += st.frontier_ranges;
-    tot.levels = std::max(tot.levels, st.levels);
-    tot.ms_total += st.ms_total; tot.ms_lookup += st.ms_lookup; tot.ms_project += st.ms_project; tot.ms_update += st.ms_update;
-    tot.project_launches += st.project_launches;
+    if (rs.d_count) IMPG_HIP(hipMemsetAsync(rs.d_count, 0, (e - b) * 8, E.stream));
+    if (rs.d_cksum) IMPG_HIP(hipMemsetAsync(rs.d_cksum, 0, (e - b) * 8, E.stream));
+    E.run(*ix, rs);
+    add_stats(tot, st);
   });
   if (stats) *stats = tot;
-  if (per_range_count && n) IMPG_HIP(hipMemcpy(per_range_count, dc, n * 8, hipMemcpyDeviceToHost));
-  if (per_range_checksum && n) IMPG_HIP(hipMemcpy(per_range_checksum, dk, n * 8, hipMemcpyDeviceToHost));
+  sinks.home(per_range_count, per_range_checksum, n);
   return IMPG_OK;
 }
 
@@ -1034,9 +1040,7 @@ int impg_gpu_query_batch_stats(impg_gpu_index_t *ix, const impg_gpu_range_t *ran
   IMPG_HIP(hipSetDevice(ix->device));
   EngineLease lease(*ix);
   Engine &E = *lease;
-  E.ranges_dev.reserve(std::max<size_t>(n * sizeof(impg_gpu_range_t), 256));
-  if (n) IMPG_HIP(hipMemcpyAsync(E.ranges_dev.p, ranges, n * sizeof(impg_gpu_range_t), hipMemcpyHostToDevice, E.stream));
-  return stats_impl(ix, E, E.ranges_dev.as<impg_gpu_range_t>(), n, params, per_range_count, per_range_checksum, stats);
+  return stats_impl(ix, E, upload_ranges(E.ranges_dev, ranges, n, &E.stream), n, params, per_range_count, per_range_checksum, stats);
   IMPG_CATCH
 }
 
@@ -1127,12 +1131,7 @@ int impg_gpu_query_batch_device(impg_gpu_index_t *ix, const impg_gpu_range_t *ra
   h->params = *params;
   h->n = n;
   h->layout = layout;
-  const impg_gpu_range_t *d_ranges = ranges;
-  if (!ranges_on_device) {
-    E.ranges_dev.reserve(std::max<size_t>(n * sizeof(impg_gpu_range_t), 256));
-    if (n) IMPG_HIP(hipMemcpyAsync(E.ranges_dev.p, ranges, n * sizeof(impg_gpu_range_t), hipMemcpyHostToDevice, E.stream));
-    d_ranges = E.ranges_dev.as<impg_gpu_range_t>();
-  }
+  const impg_gpu_range_t *d_ranges = ranges_on_device ? ranges : upload_ranges(E.ranges_dev, ranges, n, &E.stream);
   impg_gpu_stats_t tot;
   memset(&tot, 0, sizeof tot);
   for_chunks(E, n, [&](size_t b, size_t e) {
@@ -1142,14 +1141,15 @@ int impg_gpu_query_batch_device(impg_gpu_index_t *ix, const impg_gpu_range_t *ra
     impg_gpu_stats_t st;
     DevBuf self_dev;
     self_dev.pool = &E.level_pool;
+    RunSpec rs(d_ranges + b, (uint32_t)(e - b), *params);
+    rs.keep = &c.levels;
+    rs.stats = &st;
+    rs.self_out = layout != IMPG_ROWS_ATTRIBUTED ? &self_dev : nullptr;
     // attributed: a slot names its frontier record (pair_range), so the final level may be fused like a counting run's;
     // ordered: every level's slots are runs in visit order, placed below
-    E.keep_any_order = layout == IMPG_ROWS_ATTRIBUTED;
-    E.ordered_rows = layout == IMPG_ROWS_ORDERED_SLOTS;  // rows placed slot by slot, the fused final level's by its own kernel
-    try {
-      E.run(*ix, d_ranges + b, (uint32_t)(e - b), *params, &c.levels, nullptr, nullptr, &st, layout != IMPG_ROWS_ATTRIBUTED ? &self_dev : nullptr);
-    } catch (...) { E.keep_any_order = E.ordered_rows = false; throw; }
-    E.keep_any_order = E.ordered_rows = false;
+    rs.keep_any_order = layout == IMPG_ROWS_ATTRIBUTED;
+    rs.ordered_rows = layout == IMPG_ROWS_ORDERED_SLOTS;  // rows placed slot by slot, the fused final level's by its own kernel
+    E.run(*ix, rs);
     if (layout == IMPG_ROWS_ORDERED_SLOTS) {
       c.rows.adopt(E.ord_rows);
       c.offsets.adopt(E.ord_offsets);
@@ -1174,10 +1174,7 @@ int impg_gpu_query_batch_device(impg_gpu_index_t *ix, const impg_gpu_range_t *ra
       c.n_rows = pl.n_rows;
       c.levels.clear();
     }
-    tot.projected += st.projected; tot.pairs += st.pairs; tot.frontier_ranges += st.frontier_ranges;
-    tot.levels = std::max(tot.levels, st.levels);
-    tot.ms_total += st.ms_total; tot.ms_lookup += st.ms_lookup; tot.ms_project += st.ms_project; tot.ms_update += st.ms_update;
-    tot.project_launches += st.project_launches;
+    add_stats(tot, st);
     h->chunks.push_back(std::move(cp));
   });
   for (size_t c = 0; c < h->chunks.size(); c++) {
@@ -1323,26 +1320,10 @@ void bed_batch(impg_gpu_index_t *ix, const impg_gpu_range_t *ranges, size_t n, c
   EngineLease lease(*ix);
   Engine &E = *lease;
   apply_subset(E, *ix, subset_keep);
-  E.ranges_dev.reserve(std::max<size_t>(n * sizeof(impg_gpu_range_t), 256));
-  if (n) IMPG_HIP(hipMemcpyAsync(E.ranges_dev.p, ranges, n * sizeof(impg_gpu_range_t), hipMemcpyHostToDevice, E.stream));
-  double t_engine = 0, t_merge = 0, t_text = 0;
-  for_chunks(E, n, [&](size_t b, size_t e) {
-    const auto c0 = std::chrono::steady_clock::now();
-    std::vector<std::unique_ptr<LevelBufs>> levels;
-    DevBuf self_dev, rows;
-    self_dev.pool = &E.level_pool;
-    E.run(*ix, E.ranges_dev.as<impg_gpu_range_t>() + b, (uint32_t)(e - b), p, &levels, nullptr, nullptr, nullptr, &self_dev);
-    const auto c1 = std::chrono::steady_clock::now();
-    const uint32_t n_rows = device_bed_rows(E, *ix, (uint32_t)(e - b), p, merge_distance, levels, self_dev, rows);
-    const auto c2 = std::chrono::steady_clock::now();
-    const std::vector<std::string> rn = bed_range_names(*ix, ranges, range_names, b, e);
-    device_bed_text(E, *ix, rows, n_rows, (uint32_t)(e - b), rn, p.original_sequence_coordinates != 0, sink);
-    const auto c3 = std::chrono::steady_clock::now();
-    t_engine += std::chrono::duration<double>(c1 - c0).count();
-    t_merge += std::chrono::duration<double>(c2 - c1).count();
-    t_text += std::chrono::duration<double>(c3 - c2).count();
-  });
-  if (seconds3) { seconds3[0] = t_engine; seconds3[1] = t_merge; seconds3[2] = t_text; }
+  const impg_gpu_range_t *d_ranges = upload_ranges(E.ranges_dev, ranges, n, &E.stream);
+  double t3[3] = {0, 0, 0};  // engine, merge, text
+  for_chunks(E, n, [&](size_t b, size_t e) { run_chunk_bed(*ix, E, d_ranges, ranges, range_names, b, e, p, merge_distance, sink, t3); });
+  if (seconds3) for (int k = 0; k < 3; k++) seconds3[k] = t3[k];
 }
 }  // namespace
 

@@ -426,7 +426,7 @@ uint64_t Engine::expand(const DeviceIndexView &v, const FrontierRec *fr, uint32_
   expand_n_fr = n_fr;
   bool fused = by_place && fuse_final && emit_by_lanes(v) && !v.tp_mode;
   if (by_place) win_se.reserve(std::max<size_t>((size_t)n_fr * sizeof(FrontierRec), 256));
-  const bool ordered = ordered_rows && !raw;
+  const bool ordered = run_modes.ordered_rows && !raw;
   if (ordered) { L.slot_ref.reserve(std::max<size_t>((size_t)n_fr * 4, 256)); ord_cnt.reserve(std::max<size_t>((size_t)n_fr * 4, 256)); }
   launch_lookup_count(v, fr, n_fr, transitive, d_perm, cnt.as<uint32_t>(), win.as<uint4>(), wide_n.as<uint32_t>(),
                       wide_list.as<uint32_t>(), stream, by_place, by_place ? win_se.as<FrontierRec>() : nullptr,
@@ -910,12 +910,23 @@ void Engine::check_params(const impg_gpu_params_t &p) {
   if (p.transitive && p.max_depth > 65535) throw Error{IMPG_E_INVALID, "max_depth is a u16 in the reference"};
 }
 
-// The batch driver.  d_ranges: device array of n ranges.  If `keep` is non-null
-// every level's buffers are appended to it (full-results mode); otherwise the
-// level scratch is reused.  count/cksum: optional device arrays [n] of u64.
-void Engine::run(const impg_gpu_index &ix, const impg_gpu_range_t *d_ranges, uint32_t n, const impg_gpu_params_t &p,
-                 std::vector<std::unique_ptr<LevelBufs>> *keep, unsigned long long *d_count,
-                 unsigned long long *d_cksum, impg_gpu_stats_t *st, DevBuf *self_out) {
+// The batch driver (the request: RunSpec, engine.hpp).
+void Engine::run(const impg_gpu_index &ix, const RunSpec &spec) {
+  const impg_gpu_range_t *d_ranges = spec.d_ranges;
+  const uint32_t n = spec.n;
+  const impg_gpu_params_t &p = spec.p;
+  std::vector<std::unique_ptr<LevelBufs>> *keep = spec.keep;
+  unsigned long long *d_count = spec.d_count, *d_cksum = spec.d_cksum;
+  impg_gpu_stats_t *st = spec.stats;
+  DevBuf *self_out = spec.self_out;
+  // the modes are the engine's for as long as this run lasts, whichever way it ends (SplitBatch and Error included)
+  struct ModesScope {
+    RunModes &m;
+    ~ModesScope() { m = RunModes{}; }
+  } modes_scope{run_modes};
+  run_modes = spec;
+  const bool ordered_rows = spec.ordered_rows;
+  RemoteRows *const remote_rows = spec.remote_rows;
   check_params(p);
   // (the identity filter on an index built without its identity lines: they are built now, once)
   if (p.min_identity == p.min_identity && ix.lacks_identity_lines()) const_cast<impg_gpu_index &>(ix).ensure_identity_lines();
@@ -958,7 +969,7 @@ void Engine::run(const impg_gpu_index &ix, const impg_gpu_range_t *d_ranges, uin
   }
   if (transitive && (p.dfs || multi)) {  // one worklist pop at a time per query
     ev_next = 0;
-    run_dfs(ix, d_ranges, n, p, keep, d_count, d_cksum, st, self_out);
+    run_dfs(ix, spec);
     return;
   }
 
@@ -1006,7 +1017,7 @@ void Engine::run(const impg_gpu_index &ix, const impg_gpu_range_t *d_ranges, uin
     if (owners_keep) remote_rows->level = depth;
     // (kept levels too when their reader takes the slots in any order and finds a slot's frontier record through
     // pair_range -- the rows left in HBM, impg_gpu_query_batch_device's attributed layout: keep_any_order)
-    fuse_final = fuse_allowed && last && (!keep || keep_any_order || ordered_rows) && !remote;
+    fuse_final = fuse_allowed && last && (!keep || spec.keep_any_order || ordered_rows) && !remote;
     // (per-range counts / checksums of a fused level cost two atomics per hit -- its slots are in entry order, a range's
     // are no run -- which a deep closure's final level, 10^4+ ranges a query, does not earn back: config 5 with counts
     // 2.8 s per 4 000 windows fused, 1.4 s not)
@@ -1124,9 +1135,14 @@ void Engine::compact_tables() {
 // the visited update runs for all of them, and the stacks are re-sorted and merged
 // (impg.rs:2289-2304).  A query's pops happen in the reference's order; queries
 // are independent, so interleaving them changes nothing.
-void Engine::run_dfs(const impg_gpu_index &ix, const impg_gpu_range_t *d_ranges, uint32_t n, const impg_gpu_params_t &p,
-                     std::vector<std::unique_ptr<LevelBufs>> *keep, unsigned long long *d_count, unsigned long long *d_cksum,
-                     impg_gpu_stats_t *st, DevBuf *self_out) {
+void Engine::run_dfs(const impg_gpu_index &ix, const RunSpec &spec) {
+  const impg_gpu_range_t *d_ranges = spec.d_ranges;
+  const uint32_t n = spec.n;
+  const impg_gpu_params_t &p = spec.p;
+  std::vector<std::unique_ptr<LevelBufs>> *keep = spec.keep;
+  unsigned long long *d_count = spec.d_count, *d_cksum = spec.d_cksum;
+  impg_gpu_stats_t *st = spec.stats;
+  DevBuf *self_out = spec.self_out;
   const DeviceIndexView &v = ix.view;
   hipEvent_t t0 = event(), t1 = event();
   IMPG_HIP(hipEventRecord(t0, stream));

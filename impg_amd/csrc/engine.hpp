@@ -16,7 +16,7 @@ struct LevelBufs {  // one BFS level: its frontier and its hit slots
   DevBuf sl_a, sl_n, sl_off, sl_rem, slice_pos, slice_pool;
   uint64_t slice_total = 0;
   uint32_t n_frontier = 0, n_pairs = 0;
-  // ordered rows placed by slot (Engine::ordered_rows): the level's slots per frontier record -- counts, then their exclusive
+  // ordered rows placed by slot (RunModes::ordered_rows): the level's slots per frontier record -- counts, then their exclusive
   // scan -- in frontier order, and per query where the level's rows start relative to the scan (kernels.hip "Ordered rows")
   DevBuf slot_ref, lvbase, run_start;
   bool qs_interleaved = false;  // qid holds {query id, source} pairs, 8 bytes a slot (a kept fused level); pair_range is not written
@@ -52,6 +52,41 @@ struct Expander {
   // need_hits: somebody at home reads the slots (update, counts, rows); need_rows: including the target columns
   virtual HopResult hop(Engine &home, const DeviceIndexView &v, const FrontierRec *fr, uint32_t n_fr, bool transitive,
                         LevelBufs &L, impg_gpu_stats_t *st, bool need_hits, bool need_rows, bool alive) = 0;
+};
+
+// The rows form of a sharded index (sharded.cpp rank_rows): the final level of the walk stays with the ranks that
+// project it.  With `keep`: the kept levels then take their blocks from `pool` (they belong to the caller's handle, not
+// to the engine), the last hop routes its records tagged range_base + their range index -- their range in the
+// collective batch -- and nothing comes home from it; what this rank projects in that hop, as an owner, for whichever
+// home, lands in `parts` (one level per slice, frontier[].qidx = the collective range).
+struct RemoteRows {
+  std::vector<std::unique_ptr<LevelBufs>> *parts;
+  BufPool *pool;  // where every kept level's blocks come from (the rank index's rows_pool)
+  uint64_t range_base;
+  uint32_t level;  // depth of the final level (set by run())
+};
+// How a run treats the levels it keeps.  All off by default; they hold for one Engine::run and no longer.
+struct RunModes {
+  // the kept levels' slots may come in any order, as long as pair_range names every slot's frontier record (a kept
+  // final level may then be fused like a counting run's)
+  bool keep_any_order = false;
+  // Ordered rows placed by slot (with `keep`): the batch's rows grouped by range in the reference's emission order,
+  // every SLOT at its final place (a None projection stays as a hole row) -- so that where a row goes follows from the
+  // lookups' counts alone and the fused final level can write its rows itself.  After run(): ord_rows[ord_total]
+  // (impg_gpu_interval_t), ord_offsets[n + 1].
+  bool ordered_rows = false;
+  RemoteRows *remote_rows = nullptr;
+};
+// One request to Engine::run: the batch, where its results go (every sink optional), and its modes.
+struct RunSpec : RunModes {
+  const impg_gpu_range_t *d_ranges;  // device array of n ranges
+  uint32_t n;
+  const impg_gpu_params_t &p;
+  std::vector<std::unique_ptr<LevelBufs>> *keep = nullptr;  // every level's buffers are appended (full results); null: the level scratch is reused
+  unsigned long long *d_count = nullptr, *d_cksum = nullptr;  // device arrays [n]: per-range counts / checksums
+  impg_gpu_stats_t *stats = nullptr;
+  DevBuf *self_out = nullptr;  // transitive: the self intervals
+  RunSpec(const impg_gpu_range_t *d_ranges_, uint32_t n_, const impg_gpu_params_t &p_) : d_ranges(d_ranges_), n(n_), p(p_) {}
 };
 
 struct Engine {
@@ -95,7 +130,6 @@ struct Engine {
   // five-key sort walk the reference's slot order.)
   bool free_slot_order = false;
   bool free_slots_allowed = true;  // option "free_slot_order" (A/B runs)
-  std::function<void()> on_kernels_done;  // the row stream: called by assemble_results once the chunk's kernels have run (the copies follow)
   bool regroup_pairs = true;       // option "regroup_entries": a projection block sorts its 256 pairs by entry first
   // A counting run's final level (max_depth reached, or a plain query): no update follows and no row is kept, so nothing
   // reads its slots in order -- the projection kernel enumerates the pairs from the count pass's windows and the emit
@@ -103,14 +137,7 @@ struct Engine {
   bool fuse_allowed = true;        // option "fuse_final_level" (A/B runs)
   bool fuse_final = false, fuse_need_ranges = false, fuse_range_places = false;
   bool last_range_places = false;  // the last expand wrote places of the lookup order into pair_range (a kept fused level)
-  // set by the caller around run(): the kept levels' slots may come in any order, as long as pair_range names every
-  // slot's frontier record (a kept final level may then be fused like a counting run's)
-  bool keep_any_order = false;
-  // Ordered rows placed by slot (set by the caller around run(), with `keep`): the batch's rows grouped by range in the
-  // reference's emission order, every SLOT at its final place (a None projection stays as a hole row) -- so that where a
-  // row goes follows from the lookups' counts alone and the fused final level can write its rows itself.  After run():
-  // ord_rows[ord_total] (impg_gpu_interval_t), ord_offsets[n + 1].
-  bool ordered_rows = false;
+  // ordered rows placed by slot (RunModes::ordered_rows)
   DevBuf ord_acc, ord_offsets, ord_rows, ord_dest, ord_vpos, ord_cnt;
   uint64_t ord_total = 0;
   bool ord_offsets_done = false;
@@ -165,18 +192,8 @@ struct Engine {
   void post_expand(const FrontierRec *fr, uint32_t n_fr, LevelBufs &L, const uint32_t *d_pair_off, uint32_t *tie_idx,
                    const uint32_t *tie_rank, SliceArrays sl);
   Expander *remote = nullptr;  // set: frontiers are expanded on the owning shards
-  // The rows form of a sharded index (sharded.cpp rank_rows): the final level of the walk stays with the ranks that
-  // project it.  Set by the caller around run(), with `keep`: the kept levels then take their blocks from `pool` (they
-  // belong to the caller's handle, not to this engine), the last hop routes its records tagged range_base + their range
-  // index -- their range in the collective batch -- and nothing comes home from it; what this rank projects in that hop,
-  // as an owner, for whichever home, lands in `parts` (one level per slice, frontier[].qidx = the collective range).
-  struct RemoteRows {
-    std::vector<std::unique_ptr<LevelBufs>> *parts;
-    BufPool *pool;  // where every kept level's blocks come from (the rank index's rows_pool)
-    uint64_t range_base;
-    uint32_t level;  // depth of the final level (set by run())
-  };
-  RemoteRows *remote_rows = nullptr;
+  // the modes of the run in flight, for expand / hop / Expander::hop (all off outside Engine::run)
+  const RunModes &modes() const { return run_modes; }
   HopResult hop(const DeviceIndexView &v, const FrontierRec *fr, uint32_t n_fr, bool transitive, LevelBufs &L,
                 impg_gpu_stats_t *st, bool need_hits, bool need_rows, bool alive);
   uint32_t update(const DeviceIndexView &v, const FrontierRec *fr, LevelBufs &L, uint32_t n_queries,
@@ -186,17 +203,15 @@ struct Engine {
   // scratch of the DFS driver / table compaction
   DevBuf dk_a, dk_b, ds_a, ds_b, de_a, de_b, dd_a, dd_b, d_flag2, d_pos2, d_popdepth, d_popsel, d_perm, d_perm2, d_k32, d_k32b,
       d_src, d_src2, d_ckey, d_ckey2;
-  void run_dfs(const impg_gpu_index &ix, const impg_gpu_range_t *d_ranges, uint32_t n, const impg_gpu_params_t &p,
-               std::vector<std::unique_ptr<LevelBufs>> *keep, unsigned long long *d_count, unsigned long long *d_cksum,
-               impg_gpu_stats_t *st, DevBuf *self_out);
+  void run_dfs(const impg_gpu_index &ix, const RunSpec &spec);
   void finish_run(impg_gpu_stats_t *st, hipEvent_t t0, hipEvent_t t1);
   static void check_params(const impg_gpu_params_t &p);
   // level -1 of a transitive batch: visited table 0, self intervals, frontier 0
   uint32_t begin_transitive(const DeviceIndexView &v, const impg_gpu_range_t *d_ranges, uint32_t n,
                             const impg_gpu_params_t &p, FrontierRec *d_self, DevBuf &frontier_out);
-  // masked_regions of the batch in flight (capi sets these around Engine::run): CSR over the sequence ids, the
-  // sequence length a set starts with at level -1 / on first touch (visited_entry, impg.rs:2041-2055)
-  // subset filter of the batch in flight: keep[sequence id] on the device (null = none), and the batch's ranges
+  // masked_regions of the lease (see EngineLease): CSR over the sequence ids, the sequence length a set starts with at
+  // level -1 / on first touch (visited_entry, impg.rs:2041-2055)
+  // subset filter of the lease: keep[sequence id] on the device (null = none), and the batch's ranges
   // (a hit on the query's own target always stays)
   DevBuf subset_keep;
   bool subset_on = false;
@@ -213,9 +228,7 @@ struct Engine {
   uint64_t stage_launches = 0;
   DevBuf stage_next;       // next frontier produced by the last stage_update
   uint32_t stage_next_n = 0, stage_queries = 0;
-  void run(const impg_gpu_index &ix, const impg_gpu_range_t *d_ranges, uint32_t n, const impg_gpu_params_t &p,
-           std::vector<std::unique_ptr<LevelBufs>> *keep, unsigned long long *d_count, unsigned long long *d_cksum,
-           impg_gpu_stats_t *st, DevBuf *self_out);
+  void run(const impg_gpu_index &ix, const RunSpec &spec);
   // Impg::query of a small batch (the trait's per-call shape) as one chain of launches and one synchronisation;
   // false = not applicable (too many candidate pairs): the caller takes the general path
   static constexpr uint32_t SMALL_RANGES = 64, SMALL_PAIRS = 1u << 18;
@@ -251,6 +264,9 @@ struct Engine {
   char *small_out = nullptr;   // pinned + mapped: header, rows, the rows' ranges (written by the device)
   void *small_out_dev = nullptr;
   size_t small_out_cap = 0;
+
+ private:
+  RunModes run_modes;  // run()'s copy of its request's modes, cleared on every way out of it
 };
 
 // owner: null = one shard holds everything; else owner[target id] = the shard that holds the target's entries
@@ -259,7 +275,12 @@ void build_index(impg_gpu_index &ix, const impg_gpu_record_t *records, size_t n_
                  uint32_t shard, uint32_t n_shards, const uint32_t *owner, const TpInput *tp = nullptr,
                  const EntryPlan *plan = nullptr);
 
-struct EngineLease {  // an engine of the index for the duration of one call (capi.cpp)
+// An engine of the index for the duration of one call (capi.cpp).  What a call hangs on its engine beyond one run --
+// `masked` / mask_*, `subset_on` / subset_keep, `remote` -- belongs to the LEASE: whoever takes the engine sets it
+// (apply_mask, apply_subset, run_lanes; a partition session points the mask at its own tables while it holds its
+// engine), and return_engine, the lease's end, is the one place that ends it.  What holds for one run only travels in
+// the run's RunSpec and is never written on the engine by a caller.
+struct EngineLease {
   impg_gpu_index &ix;
   Engine *e = nullptr;
   explicit EngineLease(impg_gpu_index &ix);
@@ -270,15 +291,70 @@ struct EngineLease {  // an engine of the index for the duration of one call (ca
 };
 
 // ---- shared by capi.cpp and sharded.cpp --------------------------------------------------------------
+// the body of an extern "C" entry point: nothing unwinds across the ABI, every failure becomes its status code
+#define IMPG_TRY try {
+#define IMPG_CATCH                                          \
+  }                                                         \
+  catch (const impg::Error &e) {                            \
+    impg::set_error(e.msg);                                 \
+    return e.code;                                          \
+  }                                                         \
+  catch (const std::bad_alloc &) {                          \
+    impg::set_error("host out of memory");                  \
+    return IMPG_E_OOM;                                      \
+  }                                                         \
+  catch (const std::exception &e) {                         \
+    impg::set_error(std::string("internal: ") + e.what());  \
+    return IMPG_E_INVALID;                                  \
+  }
 void require_device(int device);
 std::unique_ptr<impg_gpu_index> make_index(const impg_gpu_record_t *records, size_t n_records, const uint32_t *ops,
                                            size_t n_ops, const int64_t *seq_len, uint32_t n_seq, int bidirectional,
                                            int order_policy, int device, uint32_t shard, uint32_t n_shards,
                                            const HostSeqIndex *seq, const std::vector<uint64_t> *file_first,
                                            const uint32_t *owner);
+// on_kernels_done: called once kernels_done has passed (the copies follow)
 void assemble_results(Engine &E, const impg_gpu_range_t *h_ranges, uint32_t n, const impg_gpu_params_t &p,
                       std::vector<std::unique_ptr<LevelBufs>> &levels, DevBuf &self_dev, impg_gpu_results &res,
-                      uint64_t max_rows = ~0ull, hipEvent_t kernels_done = nullptr);
+                      uint64_t max_rows = ~0ull, hipEvent_t kernels_done = nullptr,
+                      const std::function<void()> &on_kernels_done = nullptr);
+// A call's ranges on the device: `dst` grown to hold them and filled, asynchronously on *async_on or, when that is
+// null, by a blocking copy.  Returns dst's array.
+const impg_gpu_range_t *upload_ranges(DevBuf &dst, const impg_gpu_range_t *ranges, size_t n, const hipStream_t *async_on);
+// sums of a call's runs (chunks, lanes): work and time add up, the depth is the deepest run's
+inline void add_stats(impg_gpu_stats_t &tot, const impg_gpu_stats_t &st) {
+  tot.projected += st.projected; tot.pairs += st.pairs; tot.frontier_ranges += st.frontier_ranges;
+  tot.levels = std::max(tot.levels, st.levels);
+  tot.ms_total += st.ms_total; tot.ms_lookup += st.ms_lookup; tot.ms_project += st.ms_project; tot.ms_update += st.ms_update;
+  tot.project_launches += st.project_launches;
+  tot.ms_exchange += st.ms_exchange;
+}
+// The per-range counts / checksums of a counting call on the device (null: not asked for): zeroed in `cnt` / `ck` on
+// *async_on or, when that is null, by blocking memsets; home() copies what was asked for to the caller's arrays.
+struct StatSinks {
+  unsigned long long *count = nullptr, *cksum = nullptr;
+  StatSinks(DevBuf &cnt, DevBuf &ck, bool want_count, bool want_cksum, size_t n, const hipStream_t *async_on);
+  void aim(RunSpec &rs, size_t b) const { rs.d_count = count ? count + b : nullptr; rs.d_cksum = cksum ? cksum + b : nullptr; }
+  void home(uint64_t *per_range_count, uint64_t *per_range_checksum, size_t n) const;
+};
+// a turn on the GPU, where callers take turns (null: nobody to take turns with -- the lock owns nothing)
+inline std::unique_lock<std::mutex> take_turn(std::mutex *gpu_turn) {
+  return gpu_turn ? std::unique_lock<std::mutex>(*gpu_turn) : std::unique_lock<std::mutex>();
+}
+// One chunk of a full-results call: ranges [b, e) of the call's device / host arrays through the batch engine with
+// every level kept, then the trait's rows in `part` (assemble_results), run_s and assemble_s taken.  false: an empty
+// chunk -- a rank of a sharded batch that only took part in the hops; nothing is assembled.
+// gpu_turn (optional): whoever takes turns on the GPU; held over the run and released before the assembly (run_s
+// includes the wait for it).  max_rows / kernels_done / on_kernels_done: assemble_results'.
+bool run_chunk_rows(const impg_gpu_index &ix, Engine &E, const impg_gpu_range_t *d_ranges, const impg_gpu_range_t *h_ranges, size_t b,
+                    size_t e, const impg_gpu_params_t &p, impg_gpu_results &part, std::mutex *gpu_turn = nullptr,
+                    uint64_t max_rows = ~0ull, hipEvent_t kernels_done = nullptr,
+                    const std::function<void()> &on_kernels_done = nullptr);
+// Its sibling for BED: the run, both merges and the text on the device (bed_device.hip); the three stages' seconds are
+// added to seconds3.  gpu_turn is held through the text.  false: an empty chunk, as above (no time is added).
+bool run_chunk_bed(const impg_gpu_index &ix, Engine &E, const impg_gpu_range_t *d_ranges, const impg_gpu_range_t *h_ranges,
+                   const char *const *range_names, size_t b, size_t e, const impg_gpu_params_t &p, int32_t merge_distance,
+                   const std::function<void(const char *, size_t)> &sink, double *seconds3, std::mutex *gpu_turn = nullptr);
 // ---- result rows on the device (rows_device.hip) ---------------------------------------------------------------
 // Where every emitted slot of a chunk goes among the chunk's result rows (grouped by range, emission order within).
 struct RowPlan {

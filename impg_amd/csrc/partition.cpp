@@ -373,22 +373,6 @@ struct impg_gpu_partition {
   }
 };
 
-#define P_TRY try {
-#define P_CATCH                                             \
-  }                                                         \
-  catch (const impg::Error &e) {                            \
-    impg::set_error(e.msg);                                 \
-    return e.code;                                          \
-  }                                                         \
-  catch (const std::bad_alloc &) {                          \
-    impg::set_error("host out of memory");                  \
-    return IMPG_E_OOM;                                      \
-  }                                                         \
-  catch (const std::exception &e) {                         \
-    impg::set_error(std::string("internal: ") + e.what());  \
-    return IMPG_E_INVALID;                                  \
-  }
-
 static void regions_init(impg_gpu_regions &r, const int64_t *seq_len, uint32_t n_seq, bool on_host, int device, hipStream_t s) {
   r.on_host = on_host;
   r.len.resize(n_seq);
@@ -424,13 +408,13 @@ static void regions_windows(impg_gpu_regions &r, int selection, const std::strin
 extern "C" {
 
 int impg_gpu_regions_create(const int64_t *seq_len, uint32_t n_seq, int on_host, int device, impg_gpu_regions_t **out) {
-  P_TRY
+  IMPG_TRY
   if (!out || (!seq_len && n_seq)) throw Error{IMPG_E_INVALID, "null argument"};
   auto r = std::make_unique<impg_gpu_regions>();
   regions_init(*r, seq_len, n_seq, on_host != 0, device, nullptr);
   *out = r.release();
   return IMPG_OK;
-  P_CATCH
+  IMPG_CATCH
 }
 
 static void copy_rows(const std::vector<PIv> &v, impg_gpu_partition_row_t *out, size_t cap) {
@@ -440,20 +424,20 @@ static void copy_rows(const std::vector<PIv> &v, impg_gpu_partition_row_t *out, 
 int impg_gpu_regions_apply(impg_gpu_regions_t *r, const impg_gpu_interval_t *rows, size_t n_rows, int32_t merge_distance,
                            int32_t min_missing_size, int32_t min_boundary_distance, impg_gpu_partition_row_t *out_rows, size_t cap,
                            size_t *n_out) {
-  P_TRY
+  IMPG_TRY
   if (!r || !n_out || (!rows && n_rows) || (!out_rows && cap)) throw Error{IMPG_E_INVALID, "null argument"};
   r->last.clear();
   regions_apply(*r, rows, n_rows, merge_distance, min_missing_size, min_boundary_distance, r->last);
   copy_rows(r->last, out_rows, cap);
   *n_out = r->last.size();
   return IMPG_OK;
-  P_CATCH
+  IMPG_CATCH
 }
 
 int impg_gpu_regions_apply_device(impg_gpu_regions_t *r, const impg_gpu_interval_t *d_rows, size_t n_rows, int32_t merge_distance,
                                   int32_t min_missing_size, int32_t min_boundary_distance, impg_gpu_partition_row_t *out_rows, size_t cap,
                                   size_t *n_out) {
-  P_TRY
+  IMPG_TRY
   if (!r || !n_out || (!d_rows && n_rows) || (!out_rows && cap)) throw Error{IMPG_E_INVALID, "null argument"};
   if (r->on_host) throw Error{IMPG_E_INVALID, "rows in device memory need a device-state object (on_host = 0)"};
   if (merge_distance < 0) throw Error{IMPG_E_INVALID, "merge_distance < 0 (--no-merge) is not supported"};
@@ -464,20 +448,20 @@ int impg_gpu_regions_apply_device(impg_gpu_regions_t *r, const impg_gpu_interval
   copy_rows(r->last, out_rows, cap);
   *n_out = r->last.size();
   return IMPG_OK;
-  P_CATCH
+  IMPG_CATCH
 }
 
 int impg_gpu_regions_last_rows(const impg_gpu_regions_t *r, impg_gpu_partition_row_t *out_rows, size_t cap, size_t *n_out) {
-  P_TRY
+  IMPG_TRY
   if (!r || !n_out || (!out_rows && cap)) throw Error{IMPG_E_INVALID, "null argument"};
   copy_rows(r->last, out_rows, cap);
   *n_out = r->last.size();
   return IMPG_OK;
-  P_CATCH
+  IMPG_CATCH
 }
 
 int impg_gpu_regions_get(impg_gpu_regions_t *r, int which, uint64_t *off_out, int32_t *ranges_out, size_t cap, size_t *n_ranges) {
-  P_TRY
+  IMPG_TRY
   if (!r || !off_out || !n_ranges || (!ranges_out && cap)) throw Error{IMPG_E_INVALID, "null argument"};
   if (which != IMPG_REGIONS_MASKED && which != IMPG_REGIONS_MISSING) throw Error{IMPG_E_INVALID, "which: masked or missing"};
   const size_t n_seq = r->len.size();
@@ -498,12 +482,12 @@ int impg_gpu_regions_get(impg_gpu_regions_t *r, int which, uint64_t *off_out, in
   *n_ranges = flat.size() / 2;
   if (cap) memcpy(ranges_out, flat.data(), std::min(cap, flat.size() / 2) * 8);
   return IMPG_OK;
-  P_CATCH
+  IMPG_CATCH
 }
 
 int impg_gpu_regions_select(impg_gpu_regions_t *r, int selection, const char *separator, const char *const *names, int64_t window_size,
                             impg_gpu_range_t *windows_out, size_t cap, size_t *n) {
-  P_TRY
+  IMPG_TRY
   if (!r || !n || (!windows_out && cap)) throw Error{IMPG_E_INVALID, "null argument"};
   std::vector<std::string> nm;
   if (names) for (size_t q = 0; q < r->len.size(); q++) nm.push_back(names[q] ? names[q] : "");
@@ -512,7 +496,7 @@ int impg_gpu_regions_select(impg_gpu_regions_t *r, int selection, const char *se
   for (size_t i = 0; i < w.size() && i < cap; i++) windows_out[i] = w[i];
   *n = w.size();
   return IMPG_OK;
-  P_CATCH
+  IMPG_CATCH
 }
 
 void impg_gpu_regions_free(impg_gpu_regions_t *r) {
@@ -522,7 +506,7 @@ void impg_gpu_regions_free(impg_gpu_regions_t *r) {
 
 int impg_gpu_partition_starting_windows(const uint32_t *seq_ids, size_t n, const int64_t *seq_len, uint32_t n_seq, int64_t window_size,
                                         impg_gpu_range_t *windows_out, size_t cap, size_t *n_out) {
-  P_TRY
+  IMPG_TRY
   if (!n_out || (!seq_ids && n) || (!seq_len && n_seq) || (!windows_out && cap)) throw Error{IMPG_E_INVALID, "null argument"};
   std::vector<int32_t> len(n_seq);
   for (uint32_t q = 0; q < n_seq; q++) len[q] = (int32_t)std::min<int64_t>(std::max<int64_t>(seq_len[q], 0), INT32_MAX);
@@ -531,7 +515,7 @@ int impg_gpu_partition_starting_windows(const uint32_t *seq_ids, size_t n, const
   for (size_t i = 0; i < w.size() && i < cap; i++) windows_out[i] = w[i];
   *n_out = w.size();
   return IMPG_OK;
-  P_CATCH
+  IMPG_CATCH
 }
 
 static void to_parts(const impg_gpu_partition_row_t *rows, const uint64_t *pnum, size_t n, std::vector<Partition> &parts) {
@@ -543,7 +527,7 @@ static void to_parts(const impg_gpu_partition_row_t *rows, const uint64_t *pnum,
 }
 
 int impg_gpu_partition_rehome(impg_gpu_partition_row_t *rows, uint64_t *partition_num, size_t n) {
-  P_TRY
+  IMPG_TRY
   if ((!rows || !partition_num) && n) throw Error{IMPG_E_INVALID, "null argument"};
   std::vector<Partition> parts;
   to_parts(rows, partition_num, n, parts);
@@ -555,12 +539,12 @@ int impg_gpu_partition_rehome(impg_gpu_partition_row_t *rows, uint64_t *partitio
       partition_num[k++] = p.first;
     }
   return IMPG_OK;
-  P_CATCH
+  IMPG_CATCH
 }
 
 int impg_gpu_partition_bed_text(const impg_gpu_partition_row_t *rows, const uint64_t *partition_num, size_t n, const char *const *names,
                                 uint32_t n_seq, char **text, size_t *len) {
-  P_TRY
+  IMPG_TRY
   if (!text || ((!rows || !partition_num) && n) || (!names && n_seq)) throw Error{IMPG_E_INVALID, "null argument"};
   std::vector<std::string> nm(n_seq);
   for (uint32_t q = 0; q < n_seq; q++) nm[q] = names[q] ? names[q] : "";
@@ -568,12 +552,12 @@ int impg_gpu_partition_bed_text(const impg_gpu_partition_row_t *rows, const uint
   to_parts(rows, partition_num, n, parts);
   *text = dup_text(single_file_text(parts, nm), len);
   return IMPG_OK;
-  P_CATCH
+  IMPG_CATCH
 }
 
 int impg_gpu_partition_create(impg_gpu_index_t *ix, const impg_gpu_params_t *params, const impg_gpu_partition_opts_t *opts,
                               const uint32_t *starting_seq_ids, size_t n_starting, impg_gpu_partition_t **out) {
-  P_TRY
+  IMPG_TRY
   if (!ix || !params || !opts || !out || (!starting_seq_ids && n_starting)) throw Error{IMPG_E_INVALID, "null argument"};
   if (ix->shard || ix->cluster) throw Error{IMPG_E_UNSUPPORTED, "partition on a sharded index is not built"};
   if (!params->transitive) throw Error{IMPG_E_INVALID, "partition runs the transitive queries (params.transitive = 1)"};
@@ -605,7 +589,7 @@ int impg_gpu_partition_create(impg_gpu_index_t *ix, const impg_gpu_params_t *par
   }
   *out = p.release();
   return IMPG_OK;
-  P_CATCH
+  IMPG_CATCH
 }
 
 static void next_windows(impg_gpu_partition &p, std::vector<impg_gpu_range_t> &w) {
@@ -614,7 +598,7 @@ static void next_windows(impg_gpu_partition &p, std::vector<impg_gpu_range_t> &w
 }
 
 int impg_gpu_partition_next_windows(impg_gpu_partition_t *p, impg_gpu_range_t *windows_out, size_t cap, size_t *n) {
-  P_TRY
+  IMPG_TRY
   if (!p || !n || (!windows_out && cap)) throw Error{IMPG_E_INVALID, "null argument"};
   std::vector<impg_gpu_range_t> w;
   next_windows(*p, w);
@@ -624,7 +608,7 @@ int impg_gpu_partition_next_windows(impg_gpu_partition_t *p, impg_gpu_range_t *w
   p->have_pending = false;
   p->pending.clear();
   return IMPG_OK;
-  P_CATCH
+  IMPG_CATCH
 }
 
 namespace {
@@ -699,7 +683,7 @@ void window(impg_gpu_partition &p, const impg_gpu_range_t &w, std::vector<PIv> &
 }  // namespace
 
 int impg_gpu_partition_window(impg_gpu_partition_t *p, const impg_gpu_range_t *w, impg_gpu_partition_row_t *rows_out, size_t cap, size_t *n_out) {
-  P_TRY
+  IMPG_TRY
   if (!p || !w || !n_out || (!rows_out && cap)) throw Error{IMPG_E_INVALID, "null argument"};
   p->regions.last.clear();
   window(*p, *w, p->regions.last);
@@ -707,11 +691,11 @@ int impg_gpu_partition_window(impg_gpu_partition_t *p, const impg_gpu_range_t *w
   *n_out = p->regions.last.size();
   if (!p->regions.last.empty()) p->c_partitions++;
   return IMPG_OK;
-  P_CATCH
+  IMPG_CATCH
 }
 
 int impg_gpu_partition_run(impg_gpu_partition_t *p, const char *folder, int separate_files, char **text, size_t *len, uint64_t *n_partitions) {
-  P_TRY
+  IMPG_TRY
   if (!p) throw Error{IMPG_E_INVALID, "null argument"};
   if (p->ix->seq.names.size() != p->regions.len.size()) throw Error{IMPG_E_INVALID, "BED text needs an index with sequence names"};
   std::vector<Partition> parts;
@@ -743,13 +727,13 @@ int impg_gpu_partition_run(impg_gpu_partition_t *p, const char *folder, int sepa
   }
   if (n_partitions) *n_partitions = num;
   return IMPG_OK;
-  P_CATCH
+  IMPG_CATCH
 }
 
 impg_gpu_regions_t *impg_gpu_partition_regions(impg_gpu_partition_t *p) { return p ? &p->regions : nullptr; }
 
 int impg_gpu_partition_counter(const impg_gpu_partition_t *p, const char *key, int64_t *value) {
-  P_TRY
+  IMPG_TRY
   if (!p || !key || !value) throw Error{IMPG_E_INVALID, "null argument"};
   const std::string k = key;
   if (k == "windows") *value = p->c_windows;
@@ -760,7 +744,7 @@ int impg_gpu_partition_counter(const impg_gpu_partition_t *p, const char *key, i
   else if (k == "step_launches") *value = p->regions.d ? (int64_t)p->regions.d->launches : 0;
   else throw Error{IMPG_E_INVALID, "unknown counter: " + k};
   return IMPG_OK;
-  P_CATCH
+  IMPG_CATCH
 }
 
 void impg_gpu_partition_destroy(impg_gpu_partition_t *p) { delete p; }

@@ -186,7 +186,7 @@ struct ShardedExpander : Expander {
   // (the final level of a rows batch: a slice is expanded into a level of its own, blocks of the rank's rows pool, and kept
   // with a copy of the records its source[] indexes -- places of the lookup order where the fused level wrote them: the
   // records in that order, win_se)
-  void keep_slice(Engine &E, const FrontierRec *sub, std::unique_ptr<LevelBufs> K, Engine::RemoteRows &rr) {
+  void keep_slice(Engine &E, const FrontierRec *sub, std::unique_ptr<LevelBufs> K, RemoteRows &rr) {
     const size_t bytes = (size_t)K->n_frontier * sizeof(FrontierRec);
     K->frontier.reserve(std::max<size_t>(bytes, 256));
     IMPG_HIP(hipMemcpyAsync(K->frontier.p, E.last_range_places ? E.win_se.p : (const void *)sub, bytes, hipMemcpyDeviceToDevice, E.stream));
@@ -197,7 +197,7 @@ struct ShardedExpander : Expander {
                 impg_gpu_stats_t *st, bool need_hits, bool need_rows, bool alive) override {
     const int W = comm->world, me = comm->rank;
     // the final hop of a rows batch (every rank is in it at the same point): owners keep what they project
-    Engine::RemoteRows *rr = need_hits ? nullptr : E.remote_rows;
+    RemoteRows *rr = need_hits ? nullptr : E.modes().remote_rows;
     hipStream_t s = E.stream;
     const size_t K = (size_t)W + 1;
     std::vector<uint64_t> mine(K, 0), mat(K * W);
@@ -630,47 +630,29 @@ template <class P, class F> void run_lanes(impg_gpu_index &ix, size_t n, P prep,
   if (auto e = first_cause(errs)) std::rethrow_exception(e);  // (the lane that failed first, not the lowest-numbered one)
 }
 
-void add_stats(impg_gpu_stats_t &tot, const impg_gpu_stats_t &st) {
-  tot.projected += st.projected; tot.pairs += st.pairs; tot.frontier_ranges += st.frontier_ranges;
-  tot.levels = std::max(tot.levels, st.levels);
-  tot.ms_total += st.ms_total; tot.ms_lookup += st.ms_lookup; tot.ms_project += st.ms_project; tot.ms_update += st.ms_update;
-  tot.project_launches += st.project_launches;
-  tot.ms_exchange += st.ms_exchange;
-}
+// the turn on the GPU a lane's chunk takes (one lane: nobody to take turns with)
+std::mutex *lane_turn(ShardCtx &S) { return S.comm->lanes.size() > 1 ? &S.gpu_turn : nullptr; }
 
 // one rank's part of a collective counting batch
 void rank_stats(impg_gpu_index &ix, const impg_gpu_range_t *ranges, bool on_device, size_t n, const impg_gpu_params_t &p,
                 uint64_t *per_range_count, uint64_t *per_range_checksum, impg_gpu_stats_t *stats) {
   IMPG_HIP(hipSetDevice(ix.device));
   DevBuf d_ranges, d_cnt, d_ck;
-  const impg_gpu_range_t *dr = ranges;
-  if (!on_device) {
-    check_ranges(ranges, n);
-    d_ranges.reserve(std::max<size_t>(n * sizeof(impg_gpu_range_t), 256));
-    if (n) IMPG_HIP(hipMemcpy(d_ranges.p, ranges, n * sizeof(impg_gpu_range_t), hipMemcpyHostToDevice));
-    dr = d_ranges.as<impg_gpu_range_t>();
-  }
-  unsigned long long *dc = nullptr, *dk = nullptr;
-  if (per_range_count) {
-    d_cnt.reserve(std::max<size_t>(n * 8, 256));
-    IMPG_HIP(hipMemset(d_cnt.p, 0, std::max<size_t>(n * 8, 8)));
-    dc = d_cnt.as<unsigned long long>();
-  }
-  if (per_range_checksum) {
-    d_ck.reserve(std::max<size_t>(n * 8, 256));
-    IMPG_HIP(hipMemset(d_ck.p, 0, std::max<size_t>(n * 8, 8)));
-    dk = d_ck.as<unsigned long long>();
-  }
+  if (!on_device) check_ranges(ranges, n);
+  const impg_gpu_range_t *dr = on_device ? ranges : upload_ranges(d_ranges, ranges, n, nullptr);
+  const StatSinks sinks(d_cnt, d_ck, per_range_count, per_range_checksum, n, nullptr);
   ShardCtx &S = *ix.shard;
   std::vector<impg_gpu_stats_t> per_lane(S.comm->lanes.size());
   for (auto &x : per_lane) memset(&x, 0, sizeof x);
   for (auto &x : S.lanes) x->exchange_s = 0;
   run_lanes(ix, n, [](Engine &) {}, [&](size_t l, Engine &E, size_t b, size_t e) {
     impg_gpu_stats_t st;
+    RunSpec rs(dr + b, (uint32_t)(e - b), p);
+    rs.stats = &st;
+    sinks.aim(rs, b);
     {
-      std::unique_lock<std::mutex> turn(S.gpu_turn, std::defer_lock);
-      if (S.comm->lanes.size() > 1) turn.lock();
-      E.run(ix, dr + b, (uint32_t)(e - b), p, nullptr, dc ? dc + b : nullptr, dk ? dk + b : nullptr, &st, nullptr);
+      const auto turn = take_turn(lane_turn(S));
+      E.run(ix, rs);
     }
     add_stats(per_lane[l], st);
   });
@@ -681,8 +663,7 @@ void rank_stats(impg_gpu_index &ix, const impg_gpu_range_t *ranges, bool on_devi
     add_stats(tot, per_lane[l]);
   }
   if (stats) *stats = tot;
-  if (per_range_count && n) IMPG_HIP(hipMemcpy(per_range_count, dc, n * 8, hipMemcpyDeviceToHost));
-  if (per_range_checksum && n) IMPG_HIP(hipMemcpy(per_range_checksum, dk, n * 8, hipMemcpyDeviceToHost));
+  sinks.home(per_range_count, per_range_checksum, n);
 }
 
 // one rank's part of a collective full-results batch
@@ -691,8 +672,7 @@ void rank_query(impg_gpu_index &ix, const impg_gpu_range_t *ranges, size_t n, co
   IMPG_HIP(hipSetDevice(ix.device));
   check_ranges(ranges, n);
   DevBuf d_ranges;
-  d_ranges.reserve(std::max<size_t>(n * sizeof(impg_gpu_range_t), 256));
-  if (n) IMPG_HIP(hipMemcpy(d_ranges.p, ranges, n * sizeof(impg_gpu_range_t), hipMemcpyHostToDevice));
+  const impg_gpu_range_t *dr = upload_ranges(d_ranges, ranges, n, nullptr);
   const size_t chunk = shard_chunk(ix, n);
   std::vector<std::unique_ptr<impg_gpu_results>> parts((n + chunk - 1) / chunk + 1);
   std::atomic<uint64_t> served{0};  // projections done here for other ranks' records during chunks this rank had no ranges for
@@ -700,22 +680,9 @@ void rank_query(impg_gpu_index &ix, const impg_gpu_range_t *ranges, size_t n, co
     apply_mask(E, ix, mask, p);  // every lane's lease carries the batch's mask / filter
     apply_subset(E, ix, subset_keep);
   }, [&](size_t, Engine &E, size_t b, size_t e) {
-    std::vector<std::unique_ptr<LevelBufs>> levels;
-    DevBuf self_dev;
-    self_dev.pool = &E.level_pool;
-    const auto c0 = std::chrono::steady_clock::now();
-    {
-      std::unique_lock<std::mutex> turn(ix.shard->gpu_turn, std::defer_lock);
-      if (ix.shard->comm->lanes.size() > 1) turn.lock();
-      E.run(ix, d_ranges.as<impg_gpu_range_t>() + b, (uint32_t)(e - b), p, &levels, nullptr, nullptr, nullptr, &self_dev);
-    }
-    const auto c1 = std::chrono::steady_clock::now();
-    if (e == b) { served += E.last_projected; return; }  // an empty chunk: this rank only took part in the hops
     auto part = std::make_unique<impg_gpu_results>();
-    assemble_results(E, ranges + b, (uint32_t)(e - b), p, levels, self_dev, *part);
-    part->run_s = std::chrono::duration<double>(c1 - c0).count();
-    part->assemble_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - c1).count();
-    parts[b / chunk] = std::move(part);
+    if (run_chunk_rows(ix, E, dr, ranges, b, e, p, *part, lane_turn(*ix.shard))) parts[b / chunk] = std::move(part);
+    else served += E.last_projected;  // an empty chunk: this rank only took part in the hops
   });
   res.offsets.assign(1, 0);
   for (auto &pt : parts)
@@ -730,32 +697,18 @@ void rank_bed(impg_gpu_index &ix, const impg_gpu_range_t *ranges, size_t n, cons
   IMPG_HIP(hipSetDevice(ix.device));
   check_ranges(ranges, n);
   DevBuf d_ranges;
-  d_ranges.reserve(std::max<size_t>(n * sizeof(impg_gpu_range_t), 256));
-  if (n) IMPG_HIP(hipMemcpy(d_ranges.p, ranges, n * sizeof(impg_gpu_range_t), hipMemcpyHostToDevice));
+  const impg_gpu_range_t *dr = upload_ranges(d_ranges, ranges, n, nullptr);
   const size_t chunk = shard_chunk(ix, n);
   chunks_out.assign((n + chunk - 1) / chunk + 1, std::string());
   std::mutex tm;
   double t3[3] = {0, 0, 0};
   run_lanes(ix, n, [&](Engine &E) { apply_subset(E, ix, subset_keep); }, [&](size_t, Engine &E, size_t b, size_t e) {
-    std::vector<std::unique_ptr<LevelBufs>> levels;
-    DevBuf self_dev, rows;
-    self_dev.pool = &E.level_pool;
-    std::unique_lock<std::mutex> turn(ix.shard->gpu_turn, std::defer_lock);
-    if (ix.shard->comm->lanes.size() > 1) turn.lock();
-    const auto c0 = std::chrono::steady_clock::now();
-    E.run(ix, d_ranges.as<impg_gpu_range_t>() + b, (uint32_t)(e - b), p, &levels, nullptr, nullptr, nullptr, &self_dev);
-    const auto c1 = std::chrono::steady_clock::now();
-    if (e == b) return;  // an empty chunk: this rank only took part in the hops
-    const uint32_t n_rows = device_bed_rows(E, ix, (uint32_t)(e - b), p, merge_distance, levels, self_dev, rows);
-    const auto c2 = std::chrono::steady_clock::now();
     std::string &out = chunks_out[b / chunk];
-    device_bed_text(E, ix, rows, n_rows, (uint32_t)(e - b), bed_range_names(ix, ranges, range_names, b, e), p.original_sequence_coordinates != 0,
-                    [&](const char *t, size_t k) { out.append(t, k); });
-    const auto c3 = std::chrono::steady_clock::now();
+    double dt[3] = {0, 0, 0};
+    run_chunk_bed(ix, E, dr, ranges, range_names, b, e, p, merge_distance, [&](const char *t, size_t k) { out.append(t, k); }, dt,
+                  lane_turn(*ix.shard));
     std::lock_guard<std::mutex> lk(tm);
-    t3[0] += std::chrono::duration<double>(c1 - c0).count();
-    t3[1] += std::chrono::duration<double>(c2 - c1).count();
-    t3[2] += std::chrono::duration<double>(c3 - c2).count();
+    for (int k = 0; k < 3; k++) t3[k] += dt[k];
   });
   if (seconds3) for (int k = 0; k < 3; k++) seconds3[k] = t3[k];
 }
@@ -813,13 +766,8 @@ void rank_rows(impg_gpu_index &ix, const impg_gpu_range_t *ranges, bool on_devic
   IMPG_HIP(hipSetDevice(ix.device));
   R.ix = &ix; R.device = ix.device; R.offset = offset; R.n = n; R.total = total;
   DevBuf d_ranges;
-  const impg_gpu_range_t *dr = ranges;
-  if (!on_device) {
-    check_ranges(ranges, n);
-    d_ranges.reserve(std::max<size_t>(n * sizeof(impg_gpu_range_t), 256));
-    if (n) IMPG_HIP(hipMemcpy(d_ranges.p, ranges, n * sizeof(impg_gpu_range_t), hipMemcpyHostToDevice));
-    dr = d_ranges.as<impg_gpu_range_t>();
-  }
+  if (!on_device) check_ranges(ranges, n);
+  const impg_gpu_range_t *dr = on_device ? ranges : upload_ranges(d_ranges, ranges, n, nullptr);
   ShardCtx &S = *ix.shard;
   // (the rows of a big batch are tens of GB: their blocks go back to the pool when the handle is freed and are the next
   // call's -- a fresh hipMalloc of them costs more than the batch)
@@ -831,22 +779,16 @@ void rank_rows(impg_gpu_index &ix, const impg_gpu_range_t *ranges, bool on_devic
   for (auto &x : S.lanes) x->exchange_s = 0;
   run_lanes(ix, n, [](Engine &) {}, [&](size_t l, Engine &E, size_t b, size_t e) {
     std::vector<std::unique_ptr<LevelBufs>> levels, owned;
-    Engine::RemoteRows rr{&owned, &ix.rows_pool, offset + b, 0};
+    RemoteRows rr{&owned, &ix.rows_pool, offset + b, 0};
     impg_gpu_stats_t st;
+    RunSpec rs(dr + b, (uint32_t)(e - b), p);
+    rs.keep = &levels;
+    rs.stats = &st;
+    rs.keep_any_order = true;
+    rs.remote_rows = &rr;
     {
-      std::unique_lock<std::mutex> turn(S.gpu_turn, std::defer_lock);
-      if (n_lanes > 1) turn.lock();
-      E.keep_any_order = true;
-      E.remote_rows = &rr;
-      try {
-        E.run(ix, dr + b, (uint32_t)(e - b), p, &levels, nullptr, nullptr, &st, nullptr);
-      } catch (...) {
-        E.keep_any_order = false;
-        E.remote_rows = nullptr;
-        throw;
-      }
-      E.keep_any_order = false;
-      E.remote_rows = nullptr;
+      const auto turn = take_turn(lane_turn(S));
+      E.run(ix, rs);
     }
     add_stats(per_lane[l], st);
     for (size_t k = 0; k < levels.size(); k++)
@@ -1058,22 +1000,6 @@ int sharded_query_batch(impg_gpu_index &ix, const impg_gpu_range_t *ranges, size
 }  // namespace impg
 
 using namespace impg;
-
-#define IMPG_TRY try {
-#define IMPG_CATCH                                          \
-  }                                                         \
-  catch (const impg::Error &e) {                            \
-    impg::set_error(e.msg);                                 \
-    return e.code;                                          \
-  }                                                         \
-  catch (const std::bad_alloc &) {                          \
-    impg::set_error("host out of memory");                  \
-    return IMPG_E_OOM;                                      \
-  }                                                         \
-  catch (const std::exception &e) {                         \
-    impg::set_error(std::string("internal: ") + e.what());  \
-    return IMPG_E_INVALID;                                  \
-  }
 
 namespace {
 std::unique_ptr<impg_gpu_index> make_rank_index(const impg_gpu_record_t *records, size_t n_records, const uint32_t *ops, size_t n_ops,

@@ -135,6 +135,18 @@ def test_sharded_device_rows_edges(tmp_path):
     check_rows(g, single, c, rl, kw, [0])
     check_rows(g, single, c, rl, dict(), [0])
     g.set_option("pair_budget", 1 << 28)
+    # every lane's engine has just run in the rows mode (the final level left with its owners): a full-results call on the
+    # same engines brings every final-level hit home -- on this handle, and on one of two ranks x two lanes
+    g2 = impg_amd.GpuImpg.from_paf(path, devices=[0, 0], lanes=2)
+    g2.set_option("pair_budget", 1024)
+    g2.query_batch_device(rl, impg_amd.make_params(**kw)).free()
+    g2.set_option("pair_budget", 1 << 28)
+    for h in (g, g2):
+        for kw2 in (dict(), kw):
+            h.query_batch_device(rl, impg_amd.make_params(**kw2)).free()  # (rows mode once more, then the rows at home)
+            res = h.query_batch(rl, impg_amd.make_params(**kw2))
+            for i, (t, s, e) in enumerate(rl):
+                assert res[i].tolist() == c.query(t, s, e, **kw2).tolist(), (kw2, i)
 
 
 def test_sharded_device_rows_tracepoints():
