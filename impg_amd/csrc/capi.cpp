@@ -50,6 +50,8 @@ static void engine_options(impg_gpu_index &ix, Engine *e) {
   e->proj_stats = ix.proj_stats;
   e->update_stats = ix.opt_update_stats;
   e->upd_stats = ix.upd_stats;
+  e->wide_emit = WideEmit{ix.opt_wide_cap, ix.opt_wide_bins, ix.opt_lookup_stats};
+  e->lk_stats = ix.lk_stats;
 }
 // The free engine used last, else a new one while the handle may have more; null: every engine is out.  (eng_m held.)
 static Engine *take_or_create(impg_gpu_index &ix) {
@@ -658,6 +660,14 @@ int impg_gpu_set_option(impg_gpu_index_t *ix, const char *key, int64_t value) {
     ix->opt_filter_covered = (int)value;
   } else if (k == "update_stats") {  // visited update: every level's groups per tier and rare path counted into the update_* counters (0 off, default; 1: one small copy per level)
     ix->opt_update_stats = value != 0;
+  } else if (k == "lookup_stats") {  // lookup: every level's wide windows counted by the path that emitted them into the lookup_wide_* counters (0 off, default; 1: one small copy per level)
+    ix->opt_lookup_stats = value != 0;
+  } else if (k == "wide_emit_cap") {  // hits lookup_emit_wide_kernel sorts in one LDS pass (4096, default; testing; results identical)
+    if (value < 64 || value > (long long)WIDE_CAP) throw Error{IMPG_E_INVALID, "wide_emit_cap is 64 .. 4096"};
+    ix->opt_wide_cap = (uint32_t)value;
+  } else if (k == "wide_emit_bins") {  // rank bins it groups a window's hits by beyond that (1024, default; testing; results identical)
+    if (value < 2 || value > (long long)WIDE_BINS) throw Error{IMPG_E_INVALID, "wide_emit_bins is 2 .. 1024"};
+    ix->opt_wide_bins = (uint32_t)value;
   } else if (k == "free_slot_order") {  // counting runs lay their slots out in projection order (1, default) or keep the reference order (0)
     ix->opt_free_slots = value != 0;
   } else if (k == "debug_fail_owner" || k == "debug_fail_home") {  // tests: (rank + 1) << 16 | hop (sharded indexes; 0 = off)
@@ -697,6 +707,7 @@ int impg_gpu_get_counter(const impg_gpu_index_t *ix, const char *key, int64_t *v
   if (k == "walk_launches") *value_out = (int64_t)ix->walk_launches.load();
   else if (k == "walk_fallbacks") *value_out = (int64_t)ix->walk_fallbacks.load();
   else if (k == "walk_members") *value_out = (int64_t)ix->walk_last_members.load();
+  else if (k == "small_batches") *value_out = (int64_t)ix->small_batches.load();
   else if (k == "segment_sliced_levels") *value_out = (int64_t)ix->seg_stats[0].load();
   else if (k == "segment_retries") *value_out = (int64_t)ix->seg_stats[1].load();
   else if (k == "segment_library_levels") *value_out = (int64_t)ix->seg_stats[2].load();
@@ -716,6 +727,11 @@ int impg_gpu_get_counter(const impg_gpu_index_t *ix, const char *key, int64_t *v
   else if (k == "update_inplace_groups") *value_out = (int64_t)ix->upd_stats[UPD_INPLACE].load();
   else if (k == "update_tiled_sort_groups") *value_out = (int64_t)ix->upd_stats[UPD_TILED_SORT].load();
   else if (k == "update_lane_spill_groups") *value_out = (int64_t)ix->upd_stats[UPD_LANE_SPILL].load();
+  else if (k == "lookup_wide_windows") *value_out = (int64_t)ix->lk_stats[LK_WIDE].load();
+  else if (k == "lookup_wide_single") *value_out = (int64_t)ix->lk_stats[LK_SINGLE].load();
+  else if (k == "lookup_wide_grouped") *value_out = (int64_t)ix->lk_stats[LK_GROUPED].load();
+  else if (k == "lookup_wide_group_passes") *value_out = (int64_t)ix->lk_stats[LK_GROUP_PASSES].load();
+  else if (k == "lookup_wide_overflow") *value_out = (int64_t)ix->lk_stats[LK_OVERFLOW].load();
   else throw Error{IMPG_E_INVALID, "unknown counter " + k};
   return IMPG_OK;
   IMPG_CATCH

@@ -74,11 +74,14 @@ bool Engine::run_small(const impg_gpu_index &ix, const impg_gpu_range_t *h_range
   IMPG_HIP(hipMemsetAsync(acc_slots.p, 0, COUNT_BYTES, stream));
   const FrontierRec *fr = frontier_a.as<FrontierRec>();
   launch_ranges_to_frontier(ranges_dev.as<impg_gpu_range_t>(), n, frontier_a.as<FrontierRec>(), (uint32_t *)(counters.as<uint64_t>() + 5), stream);
-  launch_lookup_count(v, fr, n, false, nullptr, cnt.as<uint32_t>(), win.as<uint4>(), wide_n.as<uint32_t>(), wide_list.as<uint32_t>(), stream);
+  const bool lk = wide_emit.count_reach && lk_stats;
+  launch_lookup_count(v, fr, n, false, nullptr, cnt.as<uint32_t>(), win.as<uint4>(), wide_n.as<uint32_t>(), wide_list.as<uint32_t>(), stream,
+                      false, nullptr, nullptr, lk);
   uint32_t *d_total = reinterpret_cast<uint32_t *>(counters.as<uint64_t>() + 3);
   launch_small_scan(cnt.as<uint32_t>(), n, pair_off.as<uint32_t>(), d_total, stream);
   launch_lookup_emit(v, fr, n, false, pair_off.as<uint32_t>(), win.as<uint4>(), L.pair_range.as<uint32_t>(), pair_entry.as<uint32_t>(),
-                     nullptr, nullptr, ProjList{nullptr, nullptr, nullptr}, wide_n.as<uint32_t>(), wide_list.as<uint32_t>(), stream);
+                     nullptr, nullptr, ProjList{nullptr, nullptr, nullptr}, wide_n.as<uint32_t>(), wide_list.as<uint32_t>(), stream, false, false,
+                     WideEmit{wide_emit.cap, wide_emit.bins, lk});
   HitArrays h{L.qid.as<uint32_t>(), L.coords.as<int4>()};
   count_arm(launch_project(v, fr, L.pair_range.as<uint32_t>(), pair_entry.as<uint32_t>(), B, false, h, acc_slots.as<unsigned long long>(),
                            (uint32_t *)(counters.as<uint64_t>() + 2), min_identity, nullptr, ProjList{nullptr, nullptr, nullptr}, stream, d_total));
@@ -88,6 +91,7 @@ bool Engine::run_small(const impg_gpu_index &ix, const impg_gpu_range_t *h_range
   launch_small_pack(fr, L.pair_range.as<uint32_t>(), d_total, B, h, (const uint32_t *)(counters.as<uint64_t>() + 2),
                     acc_slots.as<unsigned long long>(), od, d_rows, d_rr, stream);
   IMPG_HIP(hipStreamSynchronize(stream));
+  count_wide_paths(v, n);
   struct Hdr { uint32_t n_pairs, err, p0, p1; unsigned long long accepted; };
   const Hdr *hd = reinterpret_cast<const Hdr *>(small_out);
   if (hd->err & 2) throw Error{IMPG_E_INVALID, "Projection resulted in negative query coordinates"};
@@ -113,6 +117,7 @@ bool Engine::run_small(const impg_gpu_index &ix, const impg_gpu_range_t *h_range
   res.has_cigar = false;
   res.projected = hd->accepted;
   last_projected = hd->accepted;
+  ix.small_batches++;
   return true;
 }
 
@@ -401,6 +406,20 @@ void Engine::projection_offsets(const uint32_t *d_perm, uint32_t n_fr, const uin
   d_offp = lo_offp.as<uint32_t>();
 }
 
+// option lookup_stats: the level's wide windows by the path that emitted them, from wide_n's words (one small copy, one wait)
+void Engine::count_wide_paths(const DeviceIndexView &v, uint32_t n) {
+  if (!(wide_emit.count_reach && lk_stats) || !n || !emit_by_lanes(v)) return;
+  uint32_t w[LK_WORDS];
+  IMPG_HIP(hipMemcpyAsync(w, wide_n.p, sizeof w, hipMemcpyDeviceToHost, stream));
+  IMPG_HIP(hipStreamSynchronize(stream));
+  const uint32_t *reach = w + LK_REACH_BASE;
+  lk_stats[LK_WIDE] += w[0];
+  lk_stats[LK_OVERFLOW] += w[1];
+  lk_stats[LK_SINGLE] += reach[LK_REACH_SINGLE];
+  lk_stats[LK_GROUPED] += reach[LK_REACH_GROUPED];
+  lk_stats[LK_GROUP_PASSES] += reach[LK_REACH_PASSES];
+}
+
 // lookup + projection of one frontier; fills L (pair_range, hit arrays), returns #pairs
 uint64_t Engine::expand(const DeviceIndexView &v, const FrontierRec *fr, uint32_t n_fr, bool transitive, LevelBufs &L,
                         impg_gpu_stats_t *st, bool raw, const RecordBlocks *blocks) {
@@ -425,12 +444,14 @@ uint64_t Engine::expand(const DeviceIndexView &v, const FrontierRec *fr, uint32_
   L.placed = false;
   expand_n_fr = n_fr;
   bool fused = by_place && fuse_final && emit_by_lanes(v) && !v.tp_mode;
+  const bool lk = wide_emit.count_reach && lk_stats;
+  const WideEmit we{wide_emit.cap, wide_emit.bins, lk};
   if (by_place) win_se.reserve(std::max<size_t>((size_t)n_fr * sizeof(FrontierRec), 256));
   const bool ordered = run_modes.ordered_rows && !raw;
   if (ordered) { L.slot_ref.reserve(std::max<size_t>((size_t)n_fr * 4, 256)); ord_cnt.reserve(std::max<size_t>((size_t)n_fr * 4, 256)); }
   launch_lookup_count(v, fr, n_fr, transitive, d_perm, cnt.as<uint32_t>(), win.as<uint4>(), wide_n.as<uint32_t>(),
                       wide_list.as<uint32_t>(), stream, by_place, by_place ? win_se.as<FrontierRec>() : nullptr,
-                      ordered && by_place ? ord_cnt.as<uint32_t>() : nullptr);
+                      ordered && by_place ? ord_cnt.as<uint32_t>() : nullptr, lk);
   uint64_t P = scan(cnt.as<uint32_t>(), pair_off.as<uint32_t>(), n_fr);
   if (P > pair_budget || P >= 0xFFFFFFF0ull) {
     if (split_ok) throw SplitBatch{};
@@ -457,7 +478,7 @@ uint64_t Engine::expand(const DeviceIndexView &v, const FrontierRec *fr, uint32_
     tile_first.reserve(((size_t)(P + 255) / 256 + 1) * 4);
     if (!staged) launch_tile_first(cnt.as<uint32_t>(), pair_off.as<uint32_t>(), n_fr, tile_first.as<uint32_t>(), stream);
     launch_lookup_emit(v, fr, n_fr, transitive, pair_off.as<uint32_t>(), win.as<uint4>(), L.pair_range.as<uint32_t>(),
-                       pair_entry.as<uint32_t>(), d_perm, nullptr, pl, wide_n.as<uint32_t>(), wide_list.as<uint32_t>(), stream, true, true);
+                       pair_entry.as<uint32_t>(), d_perm, nullptr, pl, wide_n.as<uint32_t>(), wide_list.as<uint32_t>(), stream, true, true, we);
     wlists = WindowLists{tile_first.as<uint32_t>(), pair_off.as<uint32_t>(), win.as<uint4>(), win_se.as<FrontierRec>(), d_perm, n_fr,
                          fuse_need_ranges && !direct ? L.pair_range.as<uint32_t>() : nullptr, 1u, fuse_range_places ? 1u : 0u};
     last_range_places = fuse_need_ranges && fuse_range_places && !direct;
@@ -486,7 +507,7 @@ uint64_t Engine::expand(const DeviceIndexView &v, const FrontierRec *fr, uint32_
     }
   } else if (by_place) {
     launch_lookup_emit(v, fr, n_fr, transitive, pair_off.as<uint32_t>(), win.as<uint4>(), L.pair_range.as<uint32_t>(),
-                       pair_entry.as<uint32_t>(), d_perm, nullptr, pl, wide_n.as<uint32_t>(), wide_list.as<uint32_t>(), stream, true);
+                       pair_entry.as<uint32_t>(), d_perm, nullptr, pl, wide_n.as<uint32_t>(), wide_list.as<uint32_t>(), stream, true, false, we);
     // (which range owns which places, for the staged projection of a dense level)
     wlists = WindowLists{nullptr, pair_off.as<uint32_t>(), win.as<uint4>(), win_se.as<FrontierRec>(), d_perm, n_fr, nullptr, 0u, 0u};
   } else {
@@ -496,8 +517,9 @@ uint64_t Engine::expand(const DeviceIndexView &v, const FrontierRec *fr, uint32_
     const bool entry_slots = store_cigar || multi || !pl.slot;
     launch_lookup_emit(v, fr, n_fr, transitive, pair_off.as<uint32_t>(), win.as<uint4>(), L.pair_range.as<uint32_t>(),
                        entry_slots ? pair_entry.as<uint32_t>() : nullptr, pl.slot ? d_perm : nullptr, d_offp, pl,
-                       wide_n.as<uint32_t>(), wide_list.as<uint32_t>(), stream);
+                       wide_n.as<uint32_t>(), wide_list.as<uint32_t>(), stream, false, false, we);
   }
+  count_wide_paths(v, n_fr);
   IMPG_HIP(hipEventRecord(e1, stream));
   HitArrays h = direct ? HitArrays{nullptr, nullptr} : hit_arrays(L, L.n_pairs);
   SliceArrays sl{nullptr, nullptr, nullptr, nullptr};

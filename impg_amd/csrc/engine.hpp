@@ -157,6 +157,9 @@ struct Engine {
   DevBuf m_dest, m_qid, m_coords, m_pe, m_sa, m_sn, m_so, m_sr;  // 5-key sort: destination + double buffers
   // projection order (locality): ranges sorted by window position, their slots listed in that order
   DevBuf wide_n, wide_list;  // ranges whose window is wider than the lane-per-range emit pass takes
+  WideEmit wide_emit;        // options "wide_emit_cap" / "wide_emit_bins"; count_reach = option "lookup_stats": a level's lookup copies its list lengths and reach counters home (impg_gpu_index::lk_stats)
+  std::atomic<uint64_t> *lk_stats = nullptr;  // the handle's lookup_wide_* counters (by LookupStat), or null
+  void count_wide_paths(const DeviceIndexView &v, uint32_t n);  // after a level's launch_lookup_emit; nothing without the option
   DevBuf lo_key, lo_key2, lo_idx, lo_perm, lo_cnt, lo_off, lo_offp, slot_of;
   uint32_t locality_min = 4096;  // frontier ranges below which the reordering is not worth its launches (0 = never reorder)
   const uint32_t *stage_perm = nullptr;  // lookup order of the last stage_count call

@@ -438,11 +438,14 @@ struct impg_gpu_index {
   bool opt_fuse_final = true;
   int opt_filter_covered = 0;
   bool opt_update_stats = false;  // option "update_stats" (Engine::update_stats)
+  bool opt_lookup_stats = false;  // option "lookup_stats" (Engine::wide_emit.count_reach)
+  uint32_t opt_wide_cap = 4096, opt_wide_bins = 1024;  // options "wide_emit_cap" / "wide_emit_bins" (Engine::wide_emit)
   int opt_walk = 1;
   uint32_t opt_walk_members = 0;  // option "walk_members" (Engine::walk_members)
   bool opt_seg_group = true;      // option "segment_groups" (Engine::seg_group)
   uint32_t opt_seg_parts = 0;     // option "segment_parts" (Engine::seg_parts_force)
   mutable std::atomic<uint64_t> walk_launches{0}, walk_fallbacks{0}, walk_last_members{1};  // impg_gpu_get_counter
+  mutable std::atomic<uint64_t> small_batches{0};  // ... and the batches Engine::run_small answered
   // ... and how the visited updates of its batches grouped their hits: levels cut into slices, levels counted a second time
   // for one huge query, levels that went to the library sort ([0], [1], [2]; Engine::update)
   // host <-> device traffic of the masked queries, counted where the copies are issued: mask tables uploaded (apply_mask,
@@ -453,6 +456,8 @@ struct impg_gpu_index {
   mutable std::atomic<uint64_t> proj_stats[8] = {};
   // ... and, under option update_stats, the groups each tier of the visited update took and the rare paths they reached (by impg::UpdStat)
   mutable std::atomic<uint64_t> upd_stats[8] = {};
+  // ... and, under option lookup_stats, the lookup's wide windows by the path that emitted them (by impg::LookupStat)
+  mutable std::atomic<uint64_t> lk_stats[5] = {};
   impg::ShardCtx *shard = nullptr;    // set: this index is one rank's shard; queries are collective calls
   impg::Cluster *cluster = nullptr;   // set: this handle fronts n_dev shards in this process (no arrays of its own)
   impg_gpu_index();

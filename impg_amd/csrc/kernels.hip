@@ -173,7 +173,7 @@ __global__ __launch_bounds__(256) void lookup_count_lane_kernel(DeviceIndexView 
   if (cnt_ref) cnt_ref[r] = c;
   win[o] = make_uint4(lo, ub, (uint32_t)mask, (uint32_t)(mask >> 32));
   if (se) se[o] = f;  // (the whole record at the range's place: the projection reads its ends there, a kept level its range and target)
-  // windows too wide for the lane-per-range emit pass (dense targets) are listed for the wave-per-range one
+  // windows too wide for the lane-per-range emit pass (dense targets) are listed for lookup_count_wide_kernel and the block-per-range emit
   if (deferred) wide_list[atomicAdd(wide_n, 1u)] = o;
 }
 // ... and the wide windows' counts: a wave per listed window, 64 entries a round
@@ -218,8 +218,8 @@ __global__ __launch_bounds__(256) void lookup_emit_kernel(DeviceIndexView v, con
                                                           const uint32_t *__restrict__ list_n,
                                                           const uint32_t *__restrict__ place_perm) {
   // place_perm (optional): items, win[] and pair_off[] are indexed by PLACE in the lookup order; the range is place_perm[place]
-  // list (optional): process only these ranges -- the ones whose window is wider than
-  // lookup_emit_lane_kernel takes, collected by the count pass
+  // list (optional): process only these items -- the overflow list of lookup_emit_wide_kernel: wide windows in which one
+  // rank bin alone holds more hits than that kernel's buffer.  (Without a list: every range, when emit_by_lanes() says no.)
   const uint32_t wave = (blockIdx.x * 256u + threadIdx.x) >> 6;
   const uint32_t nwaves = (gridDim.x * 256u) >> 6;
   const unsigned lane = lane_id();
@@ -350,16 +350,18 @@ __global__ __launch_bounds__(256) void lookup_emit_kernel(DeviceIndexView v, con
 // K1b-wide: the listed wide windows (dense targets, repeat hot spots: `bench.py --workload skewed` has windows of thousands of
 // entries), a BLOCK per range: the window's hits are collected as (visit rank, entry) keys in LDS, sorted there (bitonic), and
 // written out in visit order -- O(W + H log^2 H) per range.  (The wave-per-range kernel above ranks every hit against every
-// other with a readlane loop, O(W x H): 98 % of a skewed step, 3.2 s.)  More than WIDE_CAP hits: the range goes onto
-// the overflow list and the kernel above takes it.
-constexpr uint32_t WIDE_CAP = 4096, WIDE_BINS = 1024;
+// other with a readlane loop, O(W x H): 98 % of a skewed step, 3.2 s.)  More than WIDE_CAP hits: rank bins gathered into
+// groups, a pass per group; one bin alone beyond WIDE_CAP: the range goes onto the overflow list and the kernel above takes it.
+// (cap / bins: WIDE_CAP / WIDE_BINS, or what options wide_emit_cap / wide_emit_bins lower them to -- the LDS arrays keep their
+// compiled size.  reach: null, or the level's LK_REACH_* words (option lookup_stats), bumped by one thread per window.)
 template <bool TRANSITIVE>
 __global__ __launch_bounds__(256) void lookup_emit_wide_kernel(DeviceIndexView v, const FrontierRec *__restrict__ fr, uint32_t n,
                                                                const uint32_t *__restrict__ pair_off, const uint4 *__restrict__ win,
                                                                uint32_t *__restrict__ pair_range, uint32_t *__restrict__ pair_entry,
                                                                const uint32_t *__restrict__ offp, ProjList pl, const uint32_t *__restrict__ list,
                                                                const uint32_t *__restrict__ list_n, const uint32_t *__restrict__ place_perm,
-                                                               uint32_t *__restrict__ over_list, uint32_t *__restrict__ over_n) {
+                                                               uint32_t *__restrict__ over_list, uint32_t *__restrict__ over_n,
+                                                               uint32_t cap, uint32_t bins, uint32_t *__restrict__ reach) {
   __shared__ unsigned long long keys[WIDE_CAP];
   __shared__ uint32_t hist[WIDE_BINS];
   __shared__ uint16_t gb[WIDE_BINS + 2];  // group g = rank bins [gb[g], gb[g + 1])
@@ -377,10 +379,10 @@ __global__ __launch_bounds__(256) void lookup_emit_wide_kernel(DeviceIndexView v
     // a hit's sort key: its visit rank (its place in the window under the sorted order policy), below `dom`
     const uint32_t dom = v.sorted_order ? ub - lo : max(v.max_seg, 1u);
     uint32_t shift = 0;
-    while ((dom >> shift) > WIDE_BINS) shift++;
-    if (dom >> shift == WIDE_BINS && (dom & ((1u << shift) - 1u))) shift++;  // (every key >> shift below WIDE_BINS)
+    while ((dom >> shift) > bins) shift++;
+    if (dom >> shift == bins && (dom & ((1u << shift) - 1u))) shift++;  // (every key >> shift below bins)
     // the window's hits whose rank bin lies in [b0, b1), in visit order, to the range's slots from `at` on; returns their number
-    // (or more than WIDE_CAP, nothing written: the caller splits the bins)
+    // (or more than cap, nothing written: the caller splits the bins)
     auto emit_bins = [&](uint32_t b0, uint32_t b1, uint32_t at) -> uint32_t {
       if (tid == 0) s_cnt = 0u;
       __syncthreads();
@@ -398,11 +400,11 @@ __global__ __launch_bounds__(256) void lookup_emit_wide_kernel(DeviceIndexView v
         if (lane_id() == 0 && m) wb = atomicAdd(&s_cnt, (uint32_t)__popcll(m));
         wb = (uint32_t)__builtin_amdgcn_readfirstlane((int)wb);
         const uint32_t pos = wb + (uint32_t)__popcll(m & lanemask_lt());
-        if (hit && pos < WIDE_CAP) keys[pos] = ((unsigned long long)rk << 32) | i;
+        if (hit && pos < cap) keys[pos] = ((unsigned long long)rk << 32) | i;
       }
       __syncthreads();
       const uint32_t H = s_cnt;
-      if (H > WIDE_CAP) return H;
+      if (H > cap) return H;
       uint32_t P2 = 64u;
       while (P2 < H) P2 <<= 1;
       for (uint32_t k = H + tid; k < P2; k += 256u) keys[k] = ~0ull;
@@ -427,11 +429,14 @@ __global__ __launch_bounds__(256) void lookup_emit_wide_kernel(DeviceIndexView v
       __syncthreads();
       return H;
     };
-    const uint32_t H = emit_bins(0u, WIDE_BINS, 0u);
-    if (H <= WIDE_CAP) continue;
+    const uint32_t H = emit_bins(0u, bins, 0u);
+    if (H <= cap) {
+      if (reach && tid == 0) atomicAdd(reach + LK_REACH_SINGLE, 1u);  // (option lookup_stats)
+      continue;
+    }
     // more hits than the buffer takes (a thousand-fold repeat): the rank bins' histogram, bins gathered into groups of at most
-    // WIDE_CAP hits, a collect-sort-write pass per group -- the window is read once more per group
-    for (uint32_t b = tid; b < WIDE_BINS; b += 256u) hist[b] = 0u;
+    // cap hits, a collect-sort-write pass per group -- the window is read once more per group
+    for (uint32_t b = tid; b < bins; b += 256u) hist[b] = 0u;
     __syncthreads();
     for (uint32_t base = lo; base < ub; base += 256u) {
       const uint32_t i = base + tid;
@@ -442,14 +447,14 @@ __global__ __launch_bounds__(256) void lookup_emit_wide_kernel(DeviceIndexView v
       uint32_t ng = 0, acc = 0;
       bool bad = false;
       gb[0] = 0;
-      for (uint32_t b = 0; b < WIDE_BINS; b++) {
+      for (uint32_t b = 0; b < bins; b++) {
         const uint32_t c = hist[b];
-        bad = bad || c > WIDE_CAP;
-        if (acc + c > WIDE_CAP) { ng++; gb[ng] = (uint16_t)b; acc = 0; }
+        bad = bad || c > cap;
+        if (acc + c > cap) { ng++; gb[ng] = (uint16_t)b; acc = 0; }
         acc += c;
       }
       ng++;
-      gb[ng] = (uint16_t)WIDE_BINS;
+      gb[ng] = (uint16_t)bins;
       s_ng = bad ? 0u : ng;
     }
     __syncthreads();
@@ -459,6 +464,7 @@ __global__ __launch_bounds__(256) void lookup_emit_wide_kernel(DeviceIndexView v
       __syncthreads();
       continue;
     }
+    if (reach && tid == 0) { atomicAdd(reach + LK_REACH_GROUPED, 1u); atomicAdd(reach + LK_REACH_PASSES, ng); }  // (option lookup_stats)
     uint32_t at = 0;
     for (uint32_t g = 0; g < ng; g++) at += emit_bins(gb[g], gb[g + 1u], at);
   }
@@ -5007,12 +5013,12 @@ static inline uint32_t wave_grid(uint32_t n_items) {  // one wave per item, 4 wa
 
 void launch_lookup_count(const DeviceIndexView &v, const FrontierRec *fr, uint32_t n, bool transitive, const uint32_t *perm,
                          uint32_t *cnt, uint4 *win, uint32_t *wide_n, uint32_t *wide_list, hipStream_t s, bool by_place, FrontierRec *se,
-                         uint32_t *cnt_ref) {
+                         uint32_t *cnt_ref, bool count_reach) {
   if (!n) return;
   const bool lanes = emit_by_lanes(v);
   const int bp = by_place && perm ? 1 : 0;
   if (!bp) se = nullptr;
-  if (lanes) IMPG_HIP(hipMemsetAsync(wide_n, 0, 8, s));  // (the wide list's length, and its overflow list's: launch_lookup_emit)
+  if (lanes) IMPG_HIP(hipMemsetAsync(wide_n, 0, count_reach ? LK_WORDS * 4 : 8, s));  // (the wide list's length, and its overflow list's: launch_lookup_emit; option lookup_stats: the reach words too)
   if (transitive) lookup_count_lane_kernel<true><<<cdiv(n, 256), 256, 0, s>>>(v, fr, n, perm, cnt, win, wide_n, lanes ? wide_list : nullptr, bp, se, cnt_ref);
   else lookup_count_lane_kernel<false><<<cdiv(n, 256), 256, 0, s>>>(v, fr, n, perm, cnt, win, wide_n, lanes ? wide_list : nullptr, bp, se, cnt_ref);
   if (lanes) {  // the listed (wide) windows' counts; the list's length stays on the device: a grid of at most 8 192 waves strides over it
@@ -5134,12 +5140,13 @@ void launch_tile_first(const uint32_t *cnt, const uint32_t *pair_off, uint32_t n
 void launch_lookup_emit(const DeviceIndexView &v, const FrontierRec *fr, uint32_t n, bool transitive,
                         const uint32_t *pair_off, const uint4 *win, uint32_t *pair_range, uint32_t *pair_entry,
                         const uint32_t *perm, const uint32_t *offp, ProjList pl, const uint32_t *wide_n,
-                        const uint32_t *wide_list, hipStream_t s, bool by_place, bool wide_only) {
+                        const uint32_t *wide_list, hipStream_t s, bool by_place, bool wide_only, WideEmit we) {
   if (!n) return;
   const int bp = by_place && perm ? 1 : 0;
   const uint32_t *pp = bp ? perm : nullptr;
-  // windows of <= 64 entries: lane per range; the rest (dense targets), or everything if a rank could
-  // overflow the packed sort key: wave per range
+  // windows of <= 64 entries: lane per range; the rest (dense targets): block per range, and wave per range only for the
+  // windows the block kernel hands on (one rank bin with more hits than its buffer) -- or for everything, if a rank could
+  // overflow the packed sort key
   const bool lanes = emit_by_lanes(v);
   if (lanes && !wide_only) {
     if (transitive) lookup_emit_lane_kernel<true><<<cdiv(n, 64), 64, 0, s>>>(v, n, pair_off, win, pair_range, pair_entry, perm, offp, pl, bp);
@@ -5150,9 +5157,10 @@ void launch_lookup_emit(const DeviceIndexView &v, const FrontierRec *fr, uint32_
     // LDS; a range with more hits than its buffer takes goes onto the overflow list (behind the wide list's n entries; its
     // count is wide_n[1], zeroed with wide_n[0] by the count pass) for the wave-per-range kernel
     uint32_t *over_list = const_cast<uint32_t *>(wide_list) + n, *over_n = const_cast<uint32_t *>(wide_n) + 1;
+    uint32_t *reach = we.count_reach ? const_cast<uint32_t *>(wide_n) + LK_REACH_BASE : nullptr;  // (zeroed by the count pass)
     const uint32_t gw = std::min(n, 4096u);
-    if (transitive) lookup_emit_wide_kernel<true><<<gw, 256, 0, s>>>(v, fr, n, pair_off, win, pair_range, pair_entry, offp, pl, wide_list, wide_n, pp, over_list, over_n);
-    else lookup_emit_wide_kernel<false><<<gw, 256, 0, s>>>(v, fr, n, pair_off, win, pair_range, pair_entry, offp, pl, wide_list, wide_n, pp, over_list, over_n);
+    if (transitive) lookup_emit_wide_kernel<true><<<gw, 256, 0, s>>>(v, fr, n, pair_off, win, pair_range, pair_entry, offp, pl, wide_list, wide_n, pp, over_list, over_n, we.cap, we.bins, reach);
+    else lookup_emit_wide_kernel<false><<<gw, 256, 0, s>>>(v, fr, n, pair_off, win, pair_range, pair_entry, offp, pl, wide_list, wide_n, pp, over_list, over_n, we.cap, we.bins, reach);
     const uint32_t g = std::min(wave_grid(n), 256u);
     if (transitive) lookup_emit_kernel<true><<<g, 256, 0, s>>>(v, fr, n, pair_off, win, pair_range, pair_entry, offp, pl, over_list, over_n, pp);
     else lookup_emit_kernel<false><<<g, 256, 0, s>>>(v, fr, n, pair_off, win, pair_range, pair_entry, offp, pl, over_list, over_n, pp);

@@ -51,10 +51,23 @@ struct VisitedTables {
   const int2 *mask_ranges;
 };
 
+// wide_n: LK_WORDS words.  [0] the length of the wide list (windows wider than the count pass's 64-bit hit mask), [1] that of its
+// overflow list (windows lookup_emit_wide_kernel hands to lookup_emit_kernel), both cleared by the count pass; from LK_REACH_BASE
+// on, the reach counters lookup_emit_wide_kernel bumps, once per window and only under count_reach (option lookup_stats):
+// windows sorted in one LDS pass, windows split into rank-bin groups, the collect-sort-write passes of those
+constexpr uint32_t LK_WORDS = 8, LK_REACH_BASE = 2, LK_REACH_SINGLE = 0, LK_REACH_GROUPED = 1, LK_REACH_PASSES = 2;
+// lookup_emit_wide_kernel's key buffer and rank bins (the size of its LDS arrays) ...
+constexpr uint32_t WIDE_CAP = 4096, WIDE_BINS = 1024;
+// ... and what a launch uses of them (options wide_emit_cap / wide_emit_bins: testing; results identical)
+struct WideEmit { uint32_t cap = WIDE_CAP, bins = WIDE_BINS; bool count_reach = false; };
+// the lookup's wide windows by the path that emitted them (impg_gpu_get_counter "lookup_wide_*"; option lookup_stats)
+enum LookupStat { LK_WIDE = 0, LK_SINGLE, LK_GROUPED, LK_GROUP_PASSES, LK_OVERFLOW, LK_STATS };
+static_assert(LK_STATS == sizeof(impg_gpu_index::lk_stats) / sizeof(impg_gpu_index::lk_stats[0]), "one counter per path");
 void launch_lookup_count(const DeviceIndexView &v, const FrontierRec *fr, uint32_t n, bool transitive, const uint32_t *perm,
                          uint32_t *cnt, uint4 *win, uint32_t *wide_n, uint32_t *wide_list, hipStream_t s, bool by_place = false,
                          FrontierRec *se = nullptr /* by_place: the ranges' records at their places (the projection reads the ends there) */,
-                         uint32_t *cnt_ref = nullptr /* by_place: the counts in FRONTIER order too (ordered rows) */);
+                         uint32_t *cnt_ref = nullptr /* by_place: the counts in FRONTIER order too (ordered rows) */,
+                         bool count_reach = false /* wide_n's reach words cleared too */);
 // visit position of every hit of the windows of <= 64 entries, by place: vpos[pair_off[i] + k] for range i's k-th hit in index order
 // (dest: the ranges' first rows, computed by the same kernel: dest[place] = offsets[query] + lvbase[query] + slot_ref[range])
 struct OrdDestArgs { const FrontierRec *frp; const uint32_t *perm, *slot_ref, *offsets, *lvbase; uint32_t *dest; };
@@ -118,7 +131,7 @@ struct ProjList {
 void launch_lookup_emit(const DeviceIndexView &v, const FrontierRec *fr, uint32_t n, bool transitive,
                         const uint32_t *pair_off, const uint4 *win, uint32_t *pair_range, uint32_t *pair_entry,
                         const uint32_t *perm, const uint32_t *offp, ProjList pl, const uint32_t *wide_n,
-                        const uint32_t *wide_list, hipStream_t s, bool by_place = false, bool wide_only = false);
+                        const uint32_t *wide_list, hipStream_t s, bool by_place = false, bool wide_only = false, WideEmit we = WideEmit{});
 constexpr uint32_t ROUTE_WORLD_MAX = 1024;
 void launch_route_keys(const FrontierRec *fr, uint32_t n, uint32_t world, const uint32_t *owner, uint32_t n_seq, uint32_t *key,
                        uint32_t *idx, unsigned long long *hist, hipStream_t s);

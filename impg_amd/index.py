@@ -423,7 +423,8 @@ class GpuImpg:
         check(lib().impg_gpu_set_option(self._h, key.encode(), int(value)))
 
     def counter(self, key):
-        """impg_gpu_get_counter: "walk_launches", "walk_fallbacks", "walk_members"; "segment_sliced_levels",
+        """impg_gpu_get_counter: "walk_launches", "walk_fallbacks", "walk_members"; "small_batches" (plain batches the
+        small-batch path answered); "segment_sliced_levels",
         "segment_retries", "segment_library_levels"; and the levels projected per kernel (counted on the host, per
         launch): "project_lane_levels" (project_kernel), "project_staged_levels", "project_staged_rows_levels"
         (project_staged_kernel, listed pairs / ordered rows), "project_entries_slots_levels",
@@ -432,7 +433,11 @@ class GpuImpg:
         set_option("update_stats", 1), the visited update's groups per tier -- "update_lane_groups",
         "update_mid_groups", "update_wave_tiny_groups", "update_wave_small_groups", "update_wave_large_groups" -- and
         per rare path: "update_inplace_groups" (replay on the global slice), "update_tiled_sort_groups" (more pieces
-        than the LDS buffer), "update_lane_spill_groups" (a lane's pieces left its LDS column)."""
+        than the LDS buffer), "update_lane_spill_groups" (a lane's pieces left its LDS column).  Under
+        set_option("lookup_stats", 1), the lookup's windows of more than 64 entries: "lookup_wide_windows" (listed by
+        the count pass), "lookup_wide_single" (sorted in one LDS pass), "lookup_wide_grouped" (split into rank-bin
+        groups), "lookup_wide_group_passes" (the passes those took), "lookup_wide_overflow" (handed to the
+        wave-per-range kernel: one rank bin alone beyond the buffer)."""
         v = C.c_int64(0)
         check(lib().impg_gpu_get_counter(self._h, key.encode(), C.byref(v)))
         return v.value

@@ -223,6 +223,9 @@ int impg_gpu_index_approximate(const impg_gpu_index_t *);
  * stable radix sort; results are identical either way) and "segment_parts" (0, the default: a query whose level holds
  * more hits than one wave should take is cut into slices of its frontier ranges, as many as the level's size asks for;
  * N = that many slices on every level that groups by segments -- for tests; results are identical),
+ * "wide_emit_cap" (64 .. 4096, the default) and "wide_emit_bins" (2 .. 1024, the default): the hits the lookup sorts in one
+ * pass for a window of more than 64 entries, and the rank bins it groups a window's hits by beyond that -- for tests;
+ * results are identical,
  * "fuse_final_level" (1, the default: the final level of such a run -- no update follows, no row is kept --
  * takes its (range, entry) pairs straight from the lookup's per-range windows inside the projection kernel; the emit
  * pass and its pair lists are skipped; counts and checksums are identical either way).
@@ -235,14 +238,19 @@ int impg_gpu_set_option(impg_gpu_index_t *, const char *key, int64_t value);
  * answered): "walk_launches" = per-query walk launches that answered their batch (walk_device.inc: DFS batches, small
  * depth-limited BFS batches incl. masked ones -- the shape of partition.rs:359-391), "walk_fallbacks" = launches whose
  * batch the batch engine had to run again (a query outgrew its slab), "walk_members" = workgroups per query of the
- * last grid-form launch (1: not the grid form); how the visited updates grouped their hits: "segment_sliced_levels" =
+ * last grid-form launch (1: not the grid form), "small_batches" = plain batches of <= 64 ranges answered by the one-chain
+ * small-batch path; how the visited updates grouped their hits: "segment_sliced_levels" =
  * levels whose queries were cut into slices of their frontier ranges, "segment_retries" = levels counted a second time
  * because one query held more hits than a wave should take, "segment_library_levels" = levels that went through the
  * library's radix sort instead.  With option "update_stats" = 1 (0, the default: nothing is copied or counted) every
  * level's visited update also counts its (query, sequence) groups by the kernel that took them -- "update_lane_groups",
  * "update_mid_groups", "update_wave_tiny_groups", "update_wave_small_groups", "update_wave_large_groups" -- and by the
  * rare path they reached: "update_inplace_groups" (the replay ran on the group's global slice), "update_tiled_sort_groups"
- * (more pieces than the LDS buffer holds), "update_lane_spill_groups" (a lane's pieces left its LDS column). */
+ * (more pieces than the LDS buffer holds), "update_lane_spill_groups" (a lane's pieces left its LDS column).  With option
+ * "lookup_stats" = 1 (0, the default: nothing is copied or counted) every level's lookup counts its windows of more than 64
+ * entries: "lookup_wide_windows" (all of them), "lookup_wide_single" (hits sorted in one pass), "lookup_wide_grouped" (hits
+ * split into groups of rank bins), "lookup_wide_group_passes" (the passes those took), "lookup_wide_overflow" (one rank bin
+ * alone beyond the buffer: handed to the wave-per-range kernel). */
 int impg_gpu_get_counter(const impg_gpu_index_t *, const char *key, int64_t *value_out);
 /* Large result arrays live in pinned host blocks that are recycled through a process-wide pool (at most
  * IMPG_PINNED_POOL_BYTES, default 6 GiB, are kept when results are freed).  Gives pooled blocks back to the system

@@ -258,13 +258,19 @@ def test_min_gap_compressed_identity(tmp_path, seed, weird, max_ops):
 @pytest.mark.parametrize("n", [150, 380, 470, 560, 700, 950])
 def test_visit_order_network_widths(tmp_path, n):
     """lookup_emit_lane sorts a window's hits into visit order with a network pruned to the wave's widest window (32 / 40 /
-    48 / 64 places, kernels.hip emit_sort): coverage swept so that the windows pass through every width and into the
-    wave-per-range kernel beyond 64."""
+    48 / 64 places, kernels.hip emit_sort): coverage swept so that the windows pass through every width and, beyond 64, onto
+    the wide list -- lookup_count_wide_kernel and the block-per-window lookup_emit_wide_kernel, which sorts each of them in one
+    pass here (no window holds 4 096 hits, none goes on to the overflow list).  The widest window has 28 and 52 entries for
+    n = 150 and 380 (nothing listed) and 74 .. 142 from n = 470 on (9 .. 262 of the 300 plain windows are wider than 64)."""
     text, names = random_paf(300 + n, n, n_seq=2, seq_len=40000, max_ops=120, self_aln=True)
     g, c = both(tmp_path, text)
+    g.set_option("lookup_stats", 1)
     ranges = random_ranges(n, 300, 2, 40000, max_len=1000)
     assert_same(g, c, ranges)
+    assert (g.counter("lookup_wide_windows") > 0) == (n >= 470), n
     assert_same(g, c, ranges[:80], transitive=True, max_depth=2, min_transitive_len=30)
+    wide, single, over = (g.counter("lookup_wide_" + k) for k in ("windows", "single", "overflow"))
+    assert (wide > 0 or n < 470) and single == wide and over == 0, (n, wide, single, over)
 
 
 def test_identity_threshold_on_the_border(tmp_path):
