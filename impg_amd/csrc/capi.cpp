@@ -205,6 +205,7 @@ bool run_chunk_rows(const impg_gpu_index &ix, Engine &E, const impg_gpu_range_t 
   const auto c1 = std::chrono::steady_clock::now();
   if (e == b) return false;
   assemble_results(E, h_ranges + b, (uint32_t)(e - b), p, levels, self_dev, part, max_rows, kernels_done, on_kernels_done);
+  part.approximate = ix.tp_mode;
   part.run_s = std::chrono::duration<double>(c1 - c0).count();
   part.assemble_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - c1).count();
   return true;
@@ -402,6 +403,7 @@ void append_results(impg_gpu_results &res, impg_gpu_results &part) {
   if (res.offsets.empty()) res.offsets.assign(1, 0);
   if (part.offsets.empty()) part.offsets.assign(1, 0);
   const uint64_t base = res.intervals.size();
+  res.approximate = res.approximate || part.approximate;
   if (part.has_cigar) {
     res.has_cigar = true;
     if (res.cigar_off.empty()) res.cigar_off.assign((size_t)1, (uint64_t)0);
@@ -668,6 +670,12 @@ int impg_gpu_set_option(impg_gpu_index_t *ix, const char *key, int64_t value) {
   } else if (k == "wide_emit_bins") {  // rank bins it groups a window's hits by beyond that (1024, default; testing; results identical)
     if (value < 2 || value > (long long)WIDE_BINS) throw Error{IMPG_E_INVALID, "wide_emit_bins is 2 .. 1024"};
     ix->opt_wide_bins = (uint32_t)value;
+  } else if (k == "approximate_cigar") {
+    // store_cigar on a tracepoint index: 0 (default) refused; 1 every row carries the approximate mode's CIGAR, [matches '=']
+    // [mismatches 'X'] with a zero count left out (impg.rs:1479-1486) -- statistics, not an alignment: the lengths do not
+    // add up to the row's coordinates.  No effect on a CIGAR index; a run-time setting, not saved with the index.
+    if (value != 0 && value != 1) throw Error{IMPG_E_INVALID, "approximate_cigar is 0 or 1"};
+    ix->opt_approx_cigar = value != 0;  // (a multi-GPU handle hands it to its ranks with every batch: sharded_query_batch)
   } else if (k == "free_slot_order") {  // counting runs lay their slots out in projection order (1, default) or keep the reference order (0)
     ix->opt_free_slots = value != 0;
   } else if (k == "debug_fail_owner" || k == "debug_fail_home") {  // tests: (rank + 1) << 16 | hop (sharded indexes; 0 = off)
@@ -831,6 +839,7 @@ int impg_gpu_query_batch_filtered(impg_gpu_index_t *ix, const impg_gpu_range_t *
   apply_mask(E, *ix, mask, *params);
   apply_subset(E, *ix, subset_keep);
   auto res = std::make_unique<impg_gpu_results>();
+  res->approximate = ix->tp_mode;  // (run_small and the walk step aside on a tracepoint index: the object below is the one returned)
   if (n && n <= Engine::SMALL_RANGES && !params->transitive) {  // the per-call shape: one chain of launches, one sync
     const auto c0 = std::chrono::steady_clock::now();
     if (E.run_small(*ix, ranges, (uint32_t)n, *params, *res)) {

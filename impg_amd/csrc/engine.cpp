@@ -956,8 +956,10 @@ void Engine::run(const impg_gpu_index &ix, const RunSpec &spec) {
   split_ok = n > 1 && !remote;  // (ranks of a sharded batch stay in lock step: no re-splitting)
   min_identity = p.min_identity;
   store_cigar = p.store_cigar != 0 && keep != nullptr;  // slices are only materialised for full results
-  if (store_cigar && ix.tp_mode)
-    throw Error{IMPG_E_UNSUPPORTED, "store_cigar is not offered on a tracepoint index (the approximate mode has no CIGAR to slice)"};
+  // (the approximate mode's CIGAR is two sums, "N= MX" -- impg.rs:1479-1486 --, not an alignment: a caller asks for it by option)
+  if (store_cigar && ix.tp_mode && !ix.opt_approx_cigar)
+    throw Error{IMPG_E_UNSUPPORTED, "store_cigar on a tracepoint index needs option approximate_cigar = 1 (the approximate mode's "
+                                    "CIGAR is a pair of match / mismatch counts, not an alignment)"};
   multi = p.multi_impg != 0;
   // (kept levels too: the device-side row placement, rows_device.hip, only needs a record's slots to be one run)
   free_slot_order = free_slots_allowed;
@@ -1094,6 +1096,7 @@ void Engine::finish_run(impg_gpu_stats_t *st, hipEvent_t t0, hipEvent_t t1) {
   IMPG_HIP(hipMemcpy(hc, counters.p, 48, hipMemcpyDeviceToHost));
   if (hc[5]) throw Error{IMPG_E_INVALID, "query range must satisfy start < end"};  // (a run that scanned nothing)
   if (hc[2] & 2) throw Error{IMPG_E_INVALID, "Projection resulted in negative query coordinates"};  // the reference panics (impg.rs:1509-1514)
+  if (hc[2] & 4) throw Error{IMPG_E_INVALID, "CIGAR operation length exceeds 29 bits"};  // approximate CIGAR; the reference panics (impg.rs:88)
   if (hc[2]) throw Error{IMPG_E_INVALID, "an alignment hit by the query has no CIGAR (missing cg:Z tag)"};
   hc[1] = read_slots(acc_slots);
   if (st) {

@@ -439,6 +439,7 @@ struct impg_gpu_index {
   int opt_filter_covered = 0;
   bool opt_update_stats = false;  // option "update_stats" (Engine::update_stats)
   bool opt_lookup_stats = false;  // option "lookup_stats" (Engine::wide_emit.count_reach)
+  bool opt_approx_cigar = false;  // option "approximate_cigar": store_cigar on a tracepoint index returns the approximate CIGAR (Engine::run)
   uint32_t opt_wide_cap = 4096, opt_wide_bins = 1024;  // options "wide_emit_cap" / "wide_emit_bins" (Engine::wide_emit)
   int opt_walk = 1;
   uint32_t opt_walk_members = 0;  // option "walk_members" (Engine::walk_members)
@@ -469,6 +470,7 @@ struct impg_gpu_results {
   impg::HostArr<impg_gpu_interval_t> intervals;
   std::vector<impg_gpu_range_t> ranges;
   bool has_cigar = false;
+  bool approximate = false;  // rows of a tracepoint index: a CIGAR here is the approximate mode's pair of counts (paf_out.cpp)
   impg::HostArr<uint64_t> cigar_off;  // [intervals+1] when has_cigar
   impg::HostArr<uint32_t> cigar_ops;
   uint64_t projected = 0;

@@ -2637,13 +2637,17 @@ __device__ __forceinline__ int32_t tp_refine(int32_t query_pos, int32_t query_de
   }
   return min(max(refined, lo), hi);
 }
-template <bool TRANSITIVE>
+// CIGAR (option approximate_cigar under store_cigar): an accepted slot also leaves the reference's approximate CIGAR
+// "N= MX" (impg.rs:1476-1483) in `sl` -- a = matches, off = mismatches, n = how many of the two are positive, rem = 0 --
+// for slice_write_tp_kernel; the slot arrays then go through everything a CIGAR index's slices go through.
+template <bool TRANSITIVE, bool CIGAR = false>
 __global__ __launch_bounds__(256) void project_tp_kernel(DeviceIndexView v, const FrontierRec *__restrict__ fr,
                                                          const uint32_t *__restrict__ pair_range,
                                                          const uint32_t *__restrict__ pair_entry, uint32_t n_pairs,
                                                          HitArrays h, unsigned long long *__restrict__ accepted,
                                                          uint32_t *__restrict__ err_flag, double min_identity, int use_ident,
-                                                         ProjList pl, const uint32_t *__restrict__ n_pairs_dev) {
+                                                         ProjList pl, const uint32_t *__restrict__ n_pairs_dev,
+                                                         SliceArrays sl = SliceArrays{nullptr, nullptr, nullptr, nullptr}) {
   if (n_pairs_dev) n_pairs = *n_pairs_dev;
   const uint32_t per_xcd = gridDim.x >> 3;
   const uint32_t lblock = (blockIdx.x & 7u) * per_xcd + (blockIdx.x >> 3);  // one contiguous eighth of the pair list per XCD
@@ -2696,8 +2700,9 @@ __global__ __launch_bounds__(256) void project_tp_kernel(DeviceIndexView v, cons
         seg(bl0, bl1, ppos, pdelta, sstart, send, asd);
         const int32_t refined_last = tp_refine(ppos, pdelta, sstart, min(send, re), asd, false, qlo, qhi);
         bool keep = true;
-        if (use_ident) {  // the approximate CIGAR "M= X X" (impg.rs:1476-1491)
-          const int64_t mm = (int64_t)bl1.z - bf0.z, xx = (int64_t)bl1.w - bf0.w;
+        int64_t mm = 0, xx = 0;  // the approximate CIGAR "M= X X" (impg.rs:1476-1491): one pair of sums for the filter and the ops
+        if (CIGAR || use_ident) { mm = (int64_t)bl1.z - bf0.z; xx = (int64_t)bl1.w - bf0.w; }
+        if (use_ident) {
           const int64_t total = mm + xx;
           const double ident = total == 0 ? 0.0 : (double)mm / (double)total;
           keep = !(ident < min_identity);
@@ -2708,6 +2713,15 @@ __global__ __launch_bounds__(256) void project_tp_kernel(DeviceIndexView v, cons
           out = make_int4(swap_q ? refined_last : refined_first, swap_q ? refined_first : refined_last, rs, re);
           qid = e1.x;
           ok = true;
+          if (CIGAR) {
+            // a length CigarOp::new cannot hold (the reference panics, impg.rs:88): the run fails, no op is cut short
+            const bool fits = mm <= (int64_t)OP_LEN_MASK && xx <= (int64_t)OP_LEN_MASK;
+            if (!fits) atomicOr(err_flag, 4u);
+            sl.a[p] = (uint32_t)mm;
+            sl.off[p] = (int32_t)xx;
+            sl.n[p] = fits ? (mm > 0 ? 1u : 0u) + (xx > 0 ? 1u : 0u) : 0u;
+            sl.rem[p] = 0;
+          }
         }
       }
     }
@@ -2757,6 +2771,18 @@ __global__ __launch_bounds__(64) void slice_write_kernel(DeviceIndexView v, cons
   const int32_t fo = sl.off[p], lr = sl.rem[p];
   if (fo > 0) o[0] = (o[0] & (7u << 29)) | (uint32_t)((int32_t)(o[0] & OP_LEN_MASK) - fo);
   if (lr < 0) o[n - 1] = (o[n - 1] & (7u << 29)) | (uint32_t)((int32_t)(o[n - 1] & OP_LEN_MASK) + lr);
+}
+
+// ... on a tracepoint index (option approximate_cigar): the slot's one or two ops from the sums project_tp_kernel<., true>
+// left in sl -- [matches '='] if positive, then [mismatches 'X'] if positive (impg.rs:1479-1486).  A lane per slot.
+__global__ __launch_bounds__(256) void slice_write_tp_kernel(HitArrays h, SliceArrays sl, uint32_t n_pairs,
+                                                             const uint32_t *__restrict__ off, uint32_t *__restrict__ out) {
+  const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+  if (p >= n_pairs || h.qid[p] == HIT_NONE || sl.n[p] == 0u) return;
+  const uint32_t mm = sl.a[p], xx = (uint32_t)sl.off[p];
+  uint32_t *o = out + off[p];
+  if (mm) *o++ = mm | (0u << 29);
+  if (xx) *o = xx | (1u << 29);
 }
 
 // ---------------------------------------------------------------------------
@@ -5258,6 +5284,13 @@ int launch_project(const DeviceIndexView &v, const FrontierRec *fr, const uint32
   const bool two_walks = !v.pfx && !slices;
   if (v.tp_mode) {  // tracepoint index: every projection is the approximate one
     const uint32_t gt = (cdiv(n_pairs, 256) + 7u) & ~7u;
+    if (slices) {  // store_cigar under option approximate_cigar: the approximate CIGAR's two sums stay with the slot
+      if (transitive) project_tp_kernel<true, true><<<gt, 256, 0, s>>>(v, fr, pair_range, pair_entry, n_pairs, h, accepted, err_flag,
+                                                                       ident ? min_identity : 0.0, ident ? 1 : 0, pl, n_pairs_dev, *slices);
+      else project_tp_kernel<false, true><<<gt, 256, 0, s>>>(v, fr, pair_range, pair_entry, n_pairs, h, accepted, err_flag,
+                                                             ident ? min_identity : 0.0, ident ? 1 : 0, pl, n_pairs_dev, *slices);
+      return PROJ_ARM_TP;
+    }
     if (transitive) project_tp_kernel<true><<<gt, 256, 0, s>>>(v, fr, pair_range, pair_entry, n_pairs, h, accepted, err_flag,
                                                                ident ? min_identity : 0.0, ident ? 1 : 0, pl, n_pairs_dev);
     else project_tp_kernel<false><<<gt, 256, 0, s>>>(v, fr, pair_range, pair_entry, n_pairs, h, accepted, err_flag,
@@ -5333,7 +5366,9 @@ void launch_slice_counts(HitArrays h, SliceArrays sl, uint32_t n_pairs, uint32_t
 }
 void launch_slice_write(const DeviceIndexView &v, const uint32_t *pair_entry, HitArrays h, SliceArrays sl, uint32_t n_pairs,
                         const uint32_t *off, uint32_t *out, hipStream_t s) {
-  if (n_pairs) slice_write_kernel<<<cdiv(n_pairs, 64), 64, 0, s>>>(v, pair_entry, h, sl, n_pairs, off, out);
+  if (!n_pairs) return;
+  if (v.tp_mode) slice_write_tp_kernel<<<cdiv(n_pairs, 256), 256, 0, s>>>(h, sl, n_pairs, off, out);
+  else slice_write_kernel<<<cdiv(n_pairs, 64), 64, 0, s>>>(v, pair_entry, h, sl, n_pairs, off, out);
 }
 void launch_hit_stats(const FrontierRec *fr, uint32_t n_fr, const uint32_t *pair_range, uint32_t n_pairs, HitArrays h,
                       int32_t min_output_length, bool skip_same_target, unsigned long long *rstat, unsigned long long *count,

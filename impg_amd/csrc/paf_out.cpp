@@ -215,6 +215,11 @@ void put_u(std::string &s, unsigned long long v) {
 void render_paf(const impg_gpu_results &res, const impg_gpu_index &ix, const char *const *range_names,
                 const impg_gpu_params_t &p, int32_t merge_distance, bool bedpe, std::vector<std::string> &parts) {
   if (!res.has_cigar) throw Error{IMPG_E_INVALID, "PAF / BEDPE output needs results queried with store_cigar = 1"};
+  // Approximate mode prints bed or bedpe (main.rs:7387-7397): its CIGAR is two counts (impg.rs:1479-1486), no alignment to
+  // print as cg:Z.  BEDPE merges and rates those rows with the code below, as output_results_bedpe does (main.rs:11894-11987).
+  if (res.approximate && !bedpe)
+    throw Error{IMPG_E_UNSUPPORTED, "PAF output of approximate-mode results: the reference offers bed and bedpe there (their CIGAR "
+                                    "is a pair of match / mismatch counts, not an alignment)"};
   const size_t nr = res.offsets.size() - 1;
   parts.assign(nr, std::string());
   std::atomic<size_t> next{0};

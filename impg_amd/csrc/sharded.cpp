@@ -972,6 +972,7 @@ int sharded_query_batch(impg_gpu_index &ix, const impg_gpu_range_t *ranges, size
                         const impg_gpu_mask_t *mask, const uint8_t *subset_keep, impg_gpu_results **out) {
   if (mask && !p.transitive) throw Error{IMPG_E_INVALID, "masked_regions belong to the transitive queries"};
   auto res = std::make_unique<impg_gpu_results>();
+  res->approximate = ix.tp_mode;
   if (!ix.cluster) {
     rank_query(ix, ranges, n, p, mask, subset_keep, *res);
     *out = res.release();
@@ -983,7 +984,8 @@ int sharded_query_batch(impg_gpu_index &ix, const impg_gpu_range_t *ranges, size
   split_blocks(n, W, cut);
   std::vector<impg_gpu_results> parts(W);
   for (auto &r : C.ranks) { r->opt_chunk_ranges = ix.opt_chunk_ranges; r->opt_pair_budget = ix.opt_pair_budget; r->opt_locality_min = ix.opt_locality_min;
-                            r->opt_debug_fail_owner = ix.opt_debug_fail_owner; r->opt_debug_fail_home = ix.opt_debug_fail_home; r->opt_lane_schedule = ix.opt_lane_schedule; }
+                            r->opt_debug_fail_owner = ix.opt_debug_fail_owner; r->opt_debug_fail_home = ix.opt_debug_fail_home; r->opt_lane_schedule = ix.opt_lane_schedule;
+                            r->opt_approx_cigar = ix.opt_approx_cigar; }  // (every shard's engine reads its own rank's handle: Engine::run)
   on_every_rank(C, [&](size_t r) { rank_query(*C.ranks[r], ranges + cut[r], cut[r + 1] - cut[r], p, mask, subset_keep, parts[r]); });
   res->offsets.assign(1, 0);
   double run_s = 0, asm_s = 0;

@@ -85,7 +85,8 @@ class QueryResults:
 
     def paf(self, range_names=None, merge_distance=0, params=None, fmt="paf"):
         """output_results_paf / output_results_bedpe over every range (main.rs:11894-12103); the batch
-        must have been queried with store_cigar = True."""
+        must have been queried with store_cigar = True.  Results of a tracepoint index print as "bedpe" only
+        (the reference refuses "paf" in approximate mode, main.rs:7387-7397)."""
         L = lib()
         p = params or make_params(store_cigar=True)
         arr = None
@@ -290,7 +291,10 @@ class GpuImpg:
     def from_tracepoints(cls, records, tracepoints, seq_len, query_deltas=None, diffs=None, fastga=False, trace_spacing=0,
                          max_complexity=0, bidirectional=True, order=_lib.ORDER_COITREES, device=0, devices=None, lanes=2):
         """impg_gpu_index_create_tracepoints: an index over tracepoint alignments (.1aln / .tpa content handed over as
-        arrays); every query on it runs in approximate mode (approximate_mode = true of the trait)."""
+        arrays); every query on it runs in approximate mode (approximate_mode = true of the trait).  store_cigar is
+        refused on it until set_option("approximate_cigar", 1): a row's CIGAR is then the reference's approximate one,
+        [matches '='] [mismatches 'X'] with a zero count left out (impg.rs:1479-1486) -- counts, not an alignment --,
+        and QueryResults.paf(fmt="bedpe") prints what `impg query --approximate -o bedpe` prints."""
         rec = np.ascontiguousarray(records, dtype=_lib.TP_RECORD_DTYPE)
         tp = np.ascontiguousarray(tracepoints, dtype=np.int32)
         qd = None if query_deltas is None else np.ascontiguousarray(query_deltas, dtype=np.int32)

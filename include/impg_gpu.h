@@ -125,7 +125,14 @@ int impg_gpu_index_create_files(const impg_gpu_record_t *records, size_t n_recor
  * segment statistics ("N= MX").  Per alignment the index keeps prefix sums of the four per-segment quantities, so
  * a projection is two binary searches instead of a scan.  Tracepoints and query deltas must be non-negative (they
  * are in files FASTGA / the tracepoints crate write; the reference takes abs() of the former in places) and sum
- * below 2^31 per alignment: IMPG_E_UNSUPPORTED otherwise.  store_cigar is not offered (IMPG_E_UNSUPPORTED); the
+ * below 2^31 per alignment: IMPG_E_UNSUPPORTED otherwise.  store_cigar is IMPG_E_UNSUPPORTED until option
+ * "approximate_cigar" is set to 1 (impg_gpu_set_option).  Every row's CIGAR is then the one
+ * project_overlapping_interval_fast returns (impg.rs:1479-1486): [matches '='] if positive, then [mismatches 'X'] if
+ * positive -- 0, 1 or 2 ops, the very sums the identity filter sees.  They are statistics, not an alignment: their
+ * lengths do not add up to the row's coordinates, which is why a caller has to ask.  The self interval keeps its
+ * [(end - start) '='].  A sum of 2^29 or more does not fit a CigarOp (the reference panics, impg.rs:88): IMPG_E_INVALID.
+ * impg_gpu_query, impg_gpu_query_batch / _masked / _filtered / _stream take it, on one GPU, a multi-GPU handle and
+ * rank processes; impg_gpu_query_batch_device stays without store_cigar.  The
  * exact mode of these files needs the sequences and a WFA realignment and stays with the host. */
 typedef struct {
   uint32_t query_id, target_id;
@@ -228,7 +235,10 @@ int impg_gpu_index_approximate(const impg_gpu_index_t *);
  * results are identical,
  * "fuse_final_level" (1, the default: the final level of such a run -- no update follows, no row is kept --
  * takes its (range, entry) pairs straight from the lookup's per-range windows inside the projection kernel; the emit
- * pass and its pair lists are skipped; counts and checksums are identical either way).
+ * pass and its pair lists are skipped; counts and checksums are identical either way),
+ * "approximate_cigar" (0, the default: store_cigar on a tracepoint index is IMPG_E_UNSUPPORTED; 1: its rows carry the
+ * approximate mode's CIGAR -- see impg_gpu_index_create_tracepoints.  No effect on an index built from CIGARs.  A
+ * run-time setting: impg_gpu_index_save does not write it; a multi-GPU handle hands it to its shards).
  * Actions rather than settings, so that a process's FIRST call costs what its later ones do: "prewarm_result_bytes" = N
  * pins a host block of N bytes into the result pool now (a 5 GB result pins its block inside the first call
  * otherwise, ~0.3-1 s); "prewarm_walk" = 1 / 2 allocates the per-query walk's slabs (1: the per-call / small-batch BFS
@@ -487,7 +497,12 @@ int impg_gpu_query_batch_bed_fd(impg_gpu_index_t *, const impg_gpu_range_t *rang
  *      merge: contiguity, identical overlap, gaps <= -d) + output_results_paf /
  *      output_results_bedpe with gi:f / bi:f (main.rs:7472-7496, :11894-12103,
  *      :12563-12845, :13014-13180).  The results must come from a query with
- *      store_cigar = 1.  *text is malloc'ed; free() it. ------------------------ */
+ *      store_cigar = 1.  *text is malloc'ed; free() it.
+ *      Results of a tracepoint index (option "approximate_cigar") print as IMPG_OUT_BEDPE -- what `impg query
+ *      --approximate -o bedpe` prints: the same merge and the same gi:f / bi:f, fed with the two-count CIGARs --
+ *      and are IMPG_E_UNSUPPORTED as IMPG_OUT_PAF, a format the reference refuses in approximate mode
+ *      (main.rs:7387-7397).  A range holding a row without ops is IMPG_E_UNSUPPORTED in either kind of
+ *      index (the reference merges such a range by gaps alone, main.rs:11905-11910: not built). ---- */
 #define IMPG_OUT_PAF 0
 #define IMPG_OUT_BEDPE 1
 int impg_gpu_results_paf(const impg_gpu_results_t *, const impg_gpu_index_t *,
