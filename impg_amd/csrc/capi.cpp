@@ -34,23 +34,13 @@ namespace impg {
 // handle from several host threads (the trait is Send + Sync: rayon workers share the index) each take their
 // own engine: up to max_engines run side by side, further callers wait for one to come back.
 static void engine_options(impg_gpu_index &ix, Engine *e) {
-  e->pair_budget = ix.opt_pair_budget;
-  e->chunk_ranges = ix.opt_chunk_ranges;
-  e->locality_min = ix.opt_locality_min;
-  e->free_slots_allowed = ix.opt_free_slots;
-  e->regroup_pairs = ix.opt_regroup;
-  e->fuse_allowed = ix.opt_fuse_final;
-  e->filter_covered = ix.opt_filter_covered;
-  e->walk_allowed = ix.opt_walk != 0 && !getenv("IMPG_NO_WALK");
-  e->walk_bfs = ix.opt_walk == 2;  // (the environment switch runs a whole test suite on the batch engine)
-  e->walk_members = ix.opt_walk_members;
-  e->seg_group = ix.opt_seg_group;
-  e->seg_parts_force = ix.opt_seg_parts;
+  const Options &o = e->opt = ix.opt;
+  e->walk_allowed = o.walk_kernel != 0 && !getenv("IMPG_NO_WALK");
+  e->walk_bfs = o.walk_kernel == 2;  // (the environment switch runs a whole test suite on the batch engine)
+  e->wide_emit = WideEmit{(uint32_t)o.wide_emit_cap, (uint32_t)o.wide_emit_bins, o.lookup_stats != 0};
   e->seg_stats = ix.seg_stats;
   e->proj_stats = ix.proj_stats;
-  e->update_stats = ix.opt_update_stats;
   e->upd_stats = ix.upd_stats;
-  e->wide_emit = WideEmit{ix.opt_wide_cap, ix.opt_wide_bins, ix.opt_lookup_stats};
   e->lk_stats = ix.lk_stats;
 }
 // The free engine used last, else a new one while the handle may have more; null: every engine is out.  (eng_m held.)
@@ -243,7 +233,7 @@ namespace {
 // budget (SplitBatch) is retried at half the size.  Queries are independent, so
 // any split by ranges gives identical results.
 template <class F> void for_chunks(Engine &E, size_t n, F fn) {
-  size_t chunk = E.chunk_ranges ? E.chunk_ranges : n;
+  size_t chunk = E.opt.chunk_ranges ? (size_t)E.opt.chunk_ranges : n;
   if (chunk == 0) chunk = 1;
   size_t b = 0;
   while (b < n) {
@@ -499,14 +489,14 @@ int impg_gpu_index_create_from_paf(const char *const *paths, int n_paths, int bi
   ParsedPaf pp;
   std::vector<std::string> ps(paths, paths + n_paths);
   const auto t0 = std::chrono::steady_clock::now();
-  const bool timing = getenv("IMPG_BUILD_TIMING") != nullptr;
+  const bool timing = build_switches().timing;
   auto lap = [&](const char *what, std::chrono::steady_clock::time_point from) {
     if (timing) fprintf(stderr, "[build] %-28s %.3f s\n", what, std::chrono::duration<double>(std::chrono::steady_clock::now() - from).count());
   };
   // The CIGAR text is tokenised on the device (parse_cigar_to_delta, impg.rs:2935-2950 -> cigar_tokens_kernel): the
   // host only splits lines and fields, the text crosses PCIe once and the ops never exist on the host.  Inputs whose
   // text and ops would not fit next to the index they become (or IMPG_BUILD_HOST=1) are tokenised by the host parser.
-  bool raw = getenv("IMPG_BUILD_HOST") == nullptr;
+  bool raw = !build_switches().host_build;
   if (raw) {
     uint64_t bytes = 0;
     for (auto &p : ps) {
@@ -626,124 +616,64 @@ int impg_gpu_index_approximate(const impg_gpu_index_t *ix) {
 
 uint64_t impg_gpu_host_pool_trim(uint64_t keep_bytes) { return (uint64_t)impg::pinned_trim((size_t)keep_bytes); }
 
+// (options.hpp is host-only and spells these limits out: they are the kernels')
+static_assert(option_row("walk_members")->hi == WALK_MAX_MEMBERS && option_row("wide_emit_cap")->hi == WIDE_CAP && option_row("wide_emit_bins")->hi == WIDE_BINS,
+              "the option table's limits are the kernels' capacities");
+
 int impg_gpu_set_option(impg_gpu_index_t *ix, const char *key, int64_t value) {
   IMPG_TRY
   if (!ix || !key) throw Error{IMPG_E_INVALID, "null argument"};
-  std::string k(key);
-  if (k == "pair_budget") {
-    if (value < 1024 || value >= 0xFFFFFFF0ll) throw Error{IMPG_E_INVALID, "pair_budget out of range"};
-    ix->opt_pair_budget = (uint64_t)value;
-  } else if (k == "chunk_ranges") {
-    if (value < 0 || value >= (1ll << 31)) throw Error{IMPG_E_INVALID, "chunk_ranges out of range"};
-    ix->opt_chunk_ranges = (uint32_t)value;
-  } else if (k == "locality_min") {  // frontier size from which the projection runs in window order (0 = never)
-    if (value < 0 || value >= (1ll << 31)) throw Error{IMPG_E_INVALID, "locality_min out of range"};
-    ix->opt_locality_min = (uint32_t)value;
-  } else if (k == "device_rows_pool_bytes") {  // HBM an engine keeps between impg_gpu_query_batch_device calls (freed slot arrays, reused by the next call)
-    if (value < 0) throw Error{IMPG_E_INVALID, "device_rows_pool_bytes must not be negative"};
-    ix->opt_device_rows_pool = (uint64_t)value;
-  } else if (k == "fuse_final_level") {  // a counting run's final level enumerates its pairs from the count pass's windows: no emit pass (results identical)
-    ix->opt_fuse_final = value != 0;
-  } else if (k == "regroup_entries") {  // projection blocks regroup their pairs by entry before reading the index (results identical)
-    ix->opt_regroup = value != 0;
-  } else if (k == "walk_kernel") {  // the per-query walk (walk_device.inc): 0 never, 1 DFS batches of any size and depth-limited BFS batches of <= 64 ranges (default), 2 every BFS batch of <= 64 ranges
-    if (value < 0 || value > 2) throw Error{IMPG_E_INVALID, "walk_kernel is 0, 1 or 2"};
-    ix->opt_walk = (int)value;
-  } else if (k == "segment_groups") {  // the update's hits grouped query by query (1, default) or by the library's radix sort (0); results identical
-    ix->opt_seg_group = value != 0;
-  } else if (k == "segment_parts") {  // slices a query's hits are grouped in: 0 = from the level's size (default), n = that many on every level that groups by segments (testing; results identical)
-    if (value < 0 || value > 4096) throw Error{IMPG_E_INVALID, "segment_parts is 0 .. 4096"};
-    ix->opt_seg_parts = (uint32_t)value;
-  } else if (k == "walk_members") {  // workgroups per query of the walk's grid form (depth-limited BFS, <= 64 ranges): 0 = as many as fit (<= 32), 1 = no grid form
-    if (value < 0 || value > (long long)WALK_MAX_MEMBERS) throw Error{IMPG_E_INVALID, "walk_members is 0 .. 64"};
-    ix->opt_walk_members = (uint32_t)value;
-  } else if (k == "filter_covered") {  // visited update: hits covered by the old list dropped before the replay (0 off, 1 always, 2 auto; results identical)
-    if (value < 0 || value > 2) throw Error{IMPG_E_INVALID, "filter_covered is 0, 1 or 2"};
-    ix->opt_filter_covered = (int)value;
-  } else if (k == "update_stats") {  // visited update: every level's groups per tier and rare path counted into the update_* counters (0 off, default; 1: one small copy per level)
-    ix->opt_update_stats = value != 0;
-  } else if (k == "lookup_stats") {  // lookup: every level's wide windows counted by the path that emitted them into the lookup_wide_* counters (0 off, default; 1: one small copy per level)
-    ix->opt_lookup_stats = value != 0;
-  } else if (k == "wide_emit_cap") {  // hits lookup_emit_wide_kernel sorts in one LDS pass (4096, default; testing; results identical)
-    if (value < 64 || value > (long long)WIDE_CAP) throw Error{IMPG_E_INVALID, "wide_emit_cap is 64 .. 4096"};
-    ix->opt_wide_cap = (uint32_t)value;
-  } else if (k == "wide_emit_bins") {  // rank bins it groups a window's hits by beyond that (1024, default; testing; results identical)
-    if (value < 2 || value > (long long)WIDE_BINS) throw Error{IMPG_E_INVALID, "wide_emit_bins is 2 .. 1024"};
-    ix->opt_wide_bins = (uint32_t)value;
-  } else if (k == "approximate_cigar") {
-    // store_cigar on a tracepoint index: 0 (default) refused; 1 every row carries the approximate mode's CIGAR, [matches '=']
-    // [mismatches 'X'] with a zero count left out (impg.rs:1479-1486) -- statistics, not an alignment: the lengths do not
-    // add up to the row's coordinates.  No effect on a CIGAR index; a run-time setting, not saved with the index.
-    if (value != 0 && value != 1) throw Error{IMPG_E_INVALID, "approximate_cigar is 0 or 1"};
-    ix->opt_approx_cigar = value != 0;  // (a multi-GPU handle hands it to its ranks with every batch: sharded_query_batch)
-  } else if (k == "free_slot_order") {  // counting runs lay their slots out in projection order (1, default) or keep the reference order (0)
-    ix->opt_free_slots = value != 0;
-  } else if (k == "debug_fail_owner" || k == "debug_fail_home") {  // tests: (rank + 1) << 16 | hop (sharded indexes; 0 = off)
-    if (value < 0 || value > 0xFFFFFFFFll) throw Error{IMPG_E_INVALID, "debug_fail_* out of range"};
-    (k == "debug_fail_owner" ? ix->opt_debug_fail_owner : ix->opt_debug_fail_home) = (uint32_t)value;
-  } else if (k == "lane_schedule") {  // tests: forced lane start / hand-over order of a sharded batch (0 = off)
-    if (value < 0) throw Error{IMPG_E_INVALID, "lane_schedule out of range"};
-    ix->opt_lane_schedule = (uint64_t)value;
-  } else if (k == "prewarm_result_bytes") {
-    // A pinned host block of this size goes into the library's pool now (host_mem.cpp), so that a process's FIRST
-    // result-returning call copies into a recycled block like every later one (pinning 5 GB costs ~0.3-1 s, inside the
-    // call otherwise).  Blocks beyond IMPG_PINNED_POOL_BYTES (6 GiB) are not kept: ask for what the calls return.
-    if (value < 0) throw Error{IMPG_E_INVALID, "prewarm_result_bytes is a size"};
-    if (value) {
-      size_t cap = 0;
-      void *b = pinned_take((size_t)value, cap);
-      pinned_give(b, cap);
-    }
-  } else if (k == "prewarm_walk") {
-    // The per-query walk's slabs (walk_device.inc) exist before the first call that needs them: 1 = the 64 slabs of the
-    // per-call / small-batch BFS shape, 2 = also the DFS batch's slabs (~15 GB: one per resident wave).
-    if (value < 0 || value > 2) throw Error{IMPG_E_INVALID, "prewarm_walk is 0, 1 or 2"};
-    if (value && !ix->shard && !ix->cluster) {
-      IMPG_HIP(hipSetDevice(ix->device));
-      EngineLease lease(*ix);
-      lease->reserve_walk_slabs(*ix, value >= 2);
-    }
-  } else throw Error{IMPG_E_INVALID, "unknown option " + k};
+  const OptionRow *row = option_row(key);
+  if (!row) throw Error{IMPG_E_INVALID, std::string("unknown option ") + key};
+  if (!option_store(ix->opt, *row, value)) throw Error{IMPG_E_INVALID, row->refusal};
+  if (row->member || !value) return IMPG_OK;
+  // the two keys that act instead of storing (options.hpp)
+  if (!strcmp(key, "prewarm_result_bytes")) {
+    size_t cap = 0;
+    void *b = pinned_take((size_t)value, cap);
+    pinned_give(b, cap);
+  } else if (!ix->shard && !ix->cluster) {  // prewarm_walk
+    IMPG_HIP(hipSetDevice(ix->device));
+    EngineLease lease(*ix);
+    lease->reserve_walk_slabs(*ix, value >= 2);
+  }
   return IMPG_OK;
   IMPG_CATCH
 }
+const char *impg_gpu_option_key(size_t i) { return i < N_OPTIONS ? OPTION_TABLE[i].key : nullptr; }
+
+// impg_gpu_get_counter: every key and the atomic of the handle it reads
+struct CounterRow { const char *key; const std::atomic<uint64_t> &(*at)(const impg_gpu_index &); };
+#define CTR(key, member) {key, [](const impg_gpu_index &ix) -> const std::atomic<uint64_t> & { return ix.member; }}
+static const CounterRow COUNTER_TABLE[] = {
+    CTR("walk_launches", walk_launches), CTR("walk_fallbacks", walk_fallbacks), CTR("walk_members", walk_last_members), CTR("small_batches", small_batches),
+    CTR("segment_sliced_levels", seg_stats[0]), CTR("segment_retries", seg_stats[1]), CTR("segment_library_levels", seg_stats[2]),
+    CTR("project_lane_levels", proj_stats[PROJ_ARM_LANE]), CTR("project_staged_levels", proj_stats[PROJ_ARM_STAGED]),
+    CTR("project_staged_rows_levels", proj_stats[PROJ_ARM_STAGED_ROWS]), CTR("project_entries_slots_levels", proj_stats[PROJ_ARM_ENTRIES_SLOTS]),
+    CTR("project_entries_qs_levels", proj_stats[PROJ_ARM_ENTRIES_QS]), CTR("project_entries_rows_levels", proj_stats[PROJ_ARM_ENTRIES_ROWS]),
+    CTR("project_entries_ident_levels", proj_stats[PROJ_ARM_ENTRIES_IDENT]), CTR("project_tp_levels", proj_stats[PROJ_ARM_TP]),
+    CTR("update_lane_groups", upd_stats[UPD_LANE]), CTR("update_mid_groups", upd_stats[UPD_MID]), CTR("update_wave_tiny_groups", upd_stats[UPD_WAVE_TINY]),
+    CTR("update_wave_small_groups", upd_stats[UPD_WAVE_SMALL]), CTR("update_wave_large_groups", upd_stats[UPD_WAVE_LARGE]),
+    CTR("update_inplace_groups", upd_stats[UPD_INPLACE]), CTR("update_tiled_sort_groups", upd_stats[UPD_TILED_SORT]),
+    CTR("update_lane_spill_groups", upd_stats[UPD_LANE_SPILL]),
+    CTR("lookup_wide_windows", lk_stats[LK_WIDE]), CTR("lookup_wide_single", lk_stats[LK_SINGLE]), CTR("lookup_wide_grouped", lk_stats[LK_GROUPED]),
+    CTR("lookup_wide_group_passes", lk_stats[LK_GROUP_PASSES]), CTR("lookup_wide_overflow", lk_stats[LK_OVERFLOW]),
+};
+#undef CTR
+constexpr size_t N_COUNTERS = sizeof(COUNTER_TABLE) / sizeof(COUNTER_TABLE[0]);
 
 int impg_gpu_get_counter(const impg_gpu_index_t *ix, const char *key, int64_t *value_out) {
   IMPG_TRY
   if (!ix || !key || !value_out) throw Error{IMPG_E_INVALID, "null argument"};
-  const std::string k = key;
-  if (k == "walk_launches") *value_out = (int64_t)ix->walk_launches.load();
-  else if (k == "walk_fallbacks") *value_out = (int64_t)ix->walk_fallbacks.load();
-  else if (k == "walk_members") *value_out = (int64_t)ix->walk_last_members.load();
-  else if (k == "small_batches") *value_out = (int64_t)ix->small_batches.load();
-  else if (k == "segment_sliced_levels") *value_out = (int64_t)ix->seg_stats[0].load();
-  else if (k == "segment_retries") *value_out = (int64_t)ix->seg_stats[1].load();
-  else if (k == "segment_library_levels") *value_out = (int64_t)ix->seg_stats[2].load();
-  else if (k == "project_lane_levels") *value_out = (int64_t)ix->proj_stats[PROJ_ARM_LANE].load();
-  else if (k == "project_staged_levels") *value_out = (int64_t)ix->proj_stats[PROJ_ARM_STAGED].load();
-  else if (k == "project_staged_rows_levels") *value_out = (int64_t)ix->proj_stats[PROJ_ARM_STAGED_ROWS].load();
-  else if (k == "project_entries_slots_levels") *value_out = (int64_t)ix->proj_stats[PROJ_ARM_ENTRIES_SLOTS].load();
-  else if (k == "project_entries_qs_levels") *value_out = (int64_t)ix->proj_stats[PROJ_ARM_ENTRIES_QS].load();
-  else if (k == "project_entries_rows_levels") *value_out = (int64_t)ix->proj_stats[PROJ_ARM_ENTRIES_ROWS].load();
-  else if (k == "project_entries_ident_levels") *value_out = (int64_t)ix->proj_stats[PROJ_ARM_ENTRIES_IDENT].load();
-  else if (k == "project_tp_levels") *value_out = (int64_t)ix->proj_stats[PROJ_ARM_TP].load();
-  else if (k == "update_lane_groups") *value_out = (int64_t)ix->upd_stats[UPD_LANE].load();
-  else if (k == "update_mid_groups") *value_out = (int64_t)ix->upd_stats[UPD_MID].load();
-  else if (k == "update_wave_tiny_groups") *value_out = (int64_t)ix->upd_stats[UPD_WAVE_TINY].load();
-  else if (k == "update_wave_small_groups") *value_out = (int64_t)ix->upd_stats[UPD_WAVE_SMALL].load();
-  else if (k == "update_wave_large_groups") *value_out = (int64_t)ix->upd_stats[UPD_WAVE_LARGE].load();
-  else if (k == "update_inplace_groups") *value_out = (int64_t)ix->upd_stats[UPD_INPLACE].load();
-  else if (k == "update_tiled_sort_groups") *value_out = (int64_t)ix->upd_stats[UPD_TILED_SORT].load();
-  else if (k == "update_lane_spill_groups") *value_out = (int64_t)ix->upd_stats[UPD_LANE_SPILL].load();
-  else if (k == "lookup_wide_windows") *value_out = (int64_t)ix->lk_stats[LK_WIDE].load();
-  else if (k == "lookup_wide_single") *value_out = (int64_t)ix->lk_stats[LK_SINGLE].load();
-  else if (k == "lookup_wide_grouped") *value_out = (int64_t)ix->lk_stats[LK_GROUPED].load();
-  else if (k == "lookup_wide_group_passes") *value_out = (int64_t)ix->lk_stats[LK_GROUP_PASSES].load();
-  else if (k == "lookup_wide_overflow") *value_out = (int64_t)ix->lk_stats[LK_OVERFLOW].load();
-  else throw Error{IMPG_E_INVALID, "unknown counter " + k};
-  return IMPG_OK;
+  for (const CounterRow &c : COUNTER_TABLE)
+    if (!strcmp(c.key, key)) {
+      *value_out = (int64_t)c.at(*ix).load();
+      return IMPG_OK;
+    }
+  throw Error{IMPG_E_INVALID, std::string("unknown counter ") + key};
   IMPG_CATCH
 }
+const char *impg_gpu_counter_key(size_t i) { return i < N_COUNTERS ? COUNTER_TABLE[i].key : nullptr; }
 
 int impg_gpu_visit_rank(uint32_t n, int order_policy, uint32_t *rank_out) {
   IMPG_TRY
@@ -1151,7 +1081,7 @@ int impg_gpu_query_batch_device(impg_gpu_index_t *ix, const impg_gpu_range_t *ra
   Engine &E = **h->lease;
   // (the slot arrays of a big batch are tens of GB: they go back to the engine's pool when the handle is freed and are
   // the next call's -- the pool's default cap would hipFree / hipMalloc them call after call)
-  E.level_pool.max_held = std::max<size_t>(E.level_pool.max_held, (size_t)ix->opt_device_rows_pool);
+  E.level_pool.max_held = std::max<size_t>(E.level_pool.max_held, (size_t)ix->opt.device_rows_pool_bytes);
   h->ix = ix;
   h->params = *params;
   h->n = n;

@@ -143,7 +143,7 @@ bool Engine::walk_applicable(const impg_gpu_index &ix, uint32_t n, const impg_gp
   return p.max_depth >= 2 && walk_group_size(ix, n, p) >= 2;
 }
 uint32_t Engine::walk_group_size(const impg_gpu_index &ix, uint32_t n, const impg_gpu_params_t &p) const {
-  if (p.dfs || p.max_depth < 2 || n > SMALL_RANGES || walk_members == 1) return 1;
+  if (p.dfs || p.max_depth < 2 || n > SMALL_RANGES || opt.walk_members == 1) return 1;
   int cus = 256;
   (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ix.device);
   // every workgroup of the launch must be resident (the members wait for each other): one 1024-thread workgroup per CU --
@@ -157,7 +157,7 @@ uint32_t Engine::walk_group_size(const impg_gpu_index &ix, uint32_t n, const imp
   if (!per_cu) return 1;
   const uint32_t share = std::max(1u, (uint32_t)cus * std::min(per_cu, 1u) / (uint32_t)std::max(1, ix.max_engines));
   const uint32_t fit = std::max(1u, share / n);
-  return std::min({walk_members ? walk_members : 32u, fit, WALK_MAX_MEMBERS});
+  return std::min({opt.walk_members ? (uint32_t)opt.walk_members : 32u, fit, WALK_MAX_MEMBERS});
 }
 // the walk's slab shape: a BFS processes whole levels (16 waves per query), a DFS step is one popped range (one wave)
 void Engine::walk_caps(bool wide, WalkArgs &a) {
@@ -180,7 +180,7 @@ void Engine::reserve_walk_slabs(const impg_gpu_index &ix, bool dfs_too) {
     walk_caps(wide != 0, a);
     want = std::max(want, walk_slab_bytes(ix.view.n_seq, wide != 0, a.wcap, a.hcap, a.vcap, a.gcap, a.scap) * (size_t)walk_workgroups(ix, wide != 0));
   }
-  if (walk_members != 1) {  // the grid form: queries x members workgroups, at most this launch's share of the CUs (walk_group_size)
+  if (opt.walk_members != 1) {  // the grid form: queries x members workgroups, at most this launch's share of the CUs (walk_group_size)
     WalkArgs a;
     memset(&a, 0, sizeof a);
     walk_caps(true, a);
@@ -356,7 +356,7 @@ static HitArrays hit_arrays(LevelBufs &L, uint32_t n_pairs) {
 // search the same blocks and gather neighbouring entries and CIGAR tiles (L1/L2
 // hits instead of HBM lines).  Returns the permutation, or null when not worth it.
 const uint32_t *Engine::lookup_order(const DeviceIndexView &v, const FrontierRec *fr, uint32_t n_fr, const RecordBlocks *blocks) {
-  if (!locality_min || (n_fr < locality_min && !blocks)) { keys_for = nullptr; return nullptr; }
+  if (!opt.locality_min || (n_fr < opt.locality_min && !blocks)) { keys_for = nullptr; return nullptr; }
   const size_t nb = (size_t)n_fr * 4;
   lo_key.reserve(nb); lo_key2.reserve(nb); lo_idx.reserve(nb); lo_perm.reserve(nb);
   // keys are positions in the entry array: only the bits below n_entries are sorted (plus the block bits above them)
@@ -453,7 +453,7 @@ uint64_t Engine::expand(const DeviceIndexView &v, const FrontierRec *fr, uint32_
                       wide_list.as<uint32_t>(), stream, by_place, by_place ? win_se.as<FrontierRec>() : nullptr,
                       ordered && by_place ? ord_cnt.as<uint32_t>() : nullptr, lk);
   uint64_t P = scan(cnt.as<uint32_t>(), pair_off.as<uint32_t>(), n_fr);
-  if (P > pair_budget || P >= 0xFFFFFFF0ull) {
+  if (P > (uint64_t)opt.pair_budget || P >= 0xFFFFFFF0ull) {
     if (split_ok) throw SplitBatch{};
     if (P >= 0xFFFFFFF0ull) throw Error{IMPG_E_UNSUPPORTED, "more than 2^32 candidate pairs for a single range"};
   }
@@ -530,7 +530,7 @@ uint64_t Engine::expand(const DeviceIndexView &v, const FrontierRec *fr, uint32_
   }
   count_arm(launch_project(v, fr, L.pair_range.as<uint32_t>(), pair_entry.as<uint32_t>(), L.n_pairs, transitive, h,
                            acc_slots.as<unsigned long long>(), (uint32_t *)(counters.as<uint64_t>() + 2), min_identity,
-                           store_cigar ? &sl : nullptr, pl, stream, nullptr, regroup_pairs, by_place ? &wlists : nullptr));
+                           store_cigar ? &sl : nullptr, pl, stream, nullptr, opt.regroup_entries != 0, by_place ? &wlists : nullptr));
   if (!raw && !direct) {
     post_expand(fr, n_fr, L, pair_off.as<uint32_t>(), pair_entry.as<uint32_t>(), v.mrank, sl);
     h = HitArrays{L.qid.as<uint32_t>(), L.coords.as<int4>()};
@@ -644,7 +644,7 @@ uint32_t Engine::update(const DeviceIndexView &v, const FrontierRec *fr, LevelBu
   HitArrays h{L.qid.as<uint32_t>(), L.coords.as<int4>()};
   if (P) {
     const uint32_t P_slots = P;
-    const bool want_flags = filter_covered != 0;
+    const bool want_flags = opt.filter_covered != 0;
     svals.reserve((size_t)P * 8);
     // The hits that carry a key in the stable order by (query, hit sequence).  By segments (kernels.hip, seg_group_kernel:
     // a query's ranges run by run in frontier order, a counting sort by sequence inside the query) when the batch allows
@@ -652,9 +652,9 @@ uint32_t Engine::update(const DeviceIndexView &v, const FrontierRec *fr, LevelBu
     uint32_t seg_active = 0, seg_groups = 0;
     uint32_t *sg_run_start = nullptr, *sg_run_end = nullptr, *sg_q = nullptr, *sg_bins = nullptr;
     // (a query with more than a wave's worth of hits is cut into slices of its frontier ranges: seg_group_parts)
-    uint32_t seg_parts = seg_group && !want_flags && !multi && seg_group_fits(v.n_seq) && L.n_frontier > 0 ? seg_group_parts(P, n_queries, v.n_seq) : 0u;
-    if (seg_parts_force && seg_parts) {  // (forced, for tests: within what the unit index and the counters' buffer take)
-      seg_parts = std::max(1u, std::min(seg_parts_force, 4096u));
+    uint32_t seg_parts = opt.segment_groups && !want_flags && !multi && seg_group_fits(v.n_seq) && L.n_frontier > 0 ? seg_group_parts(P, n_queries, v.n_seq) : 0u;
+    if (opt.segment_parts && seg_parts) {  // (forced, for tests: within what the unit index and the counters' buffer take)
+      seg_parts = std::max(1u, std::min((uint32_t)opt.segment_parts, 4096u));
       while (seg_parts > 1 && ((uint64_t)n_queries * seg_parts >= (1ull << 31) || seg_group_bins_bytes(n_queries, v.n_seq, seg_parts) > (1ull << 30))) seg_parts >>= 1;
     }
     bool by_segments = seg_parts != 0;
@@ -786,7 +786,7 @@ uint32_t Engine::update(const DeviceIndexView &v, const FrontierRec *fr, LevelBu
       // change nothing): worth its three passes when groups are long and lists exist, i.e. from the second update of
       // a walk on -- the deep levels of a saturating closure are almost all such hits.
       const unsigned long long *replay_vals = svals.as<unsigned long long>();
-      const bool filter = filter_covered == 1 || (filter_covered == 2 && tables.size() >= 2 && (uint64_t)n_active >= 8ull * n_groups);
+      const bool filter = opt.filter_covered == 1 || (opt.filter_covered == 2 && tables.size() >= 2 && (uint64_t)n_active >= 8ull * n_groups);
       if (filter && n_active) {
         uint32_t *keep = keys.as<uint32_t>(), *kpos = keep + P;  // (the unsorted key / value buffers are free again)
         launch_covered_flags(svals.as<unsigned long long>(), head.as<uint32_t>(), gid.as<uint32_t>(), vt->keys.as<unsigned long long>(),
@@ -815,9 +815,9 @@ uint32_t Engine::update(const DeviceIndexView &v, const FrontierRec *fr, LevelBu
                             vt->off.as<uint32_t>(), poff.as<uint32_t>(), n_groups, p.min_transitive_len,
                             p.min_distance_between_ranges, vt->ranges.as<int2>(), vt->len.as<uint32_t>(),
                             pieces.as<int2>(), n_pieces.as<uint32_t>(), cap.as<uint32_t>(), pcap.as<uint32_t>(), big_list.as<uint32_t>(),
-                            (uint32_t *)(counters.as<uint64_t>() + 8), update_stats && upd_stats, stream);
+                            (uint32_t *)(counters.as<uint64_t>() + 8), opt.update_stats && upd_stats, stream);
       uint64_t nn = scan(n_pieces.as<uint32_t>(), foff.as<uint32_t>(), n_groups);
-      if (update_stats && upd_stats && n_groups) {  // (the scan has waited for the update: its words are final)
+      if (opt.update_stats && upd_stats && n_groups) {  // (the scan has waited for the update: its words are final)
         IMPG_HIP(hipMemcpyAsync(h_counters, counters.as<uint64_t>() + 8, VU_NBIG_WORDS * 4, hipMemcpyDeviceToHost, stream));
         IMPG_HIP(hipStreamSynchronize(stream));
         const uint32_t *w = reinterpret_cast<const uint32_t *>(h_counters), *reach = w + VU_REACH_BASE;
@@ -834,7 +834,7 @@ uint32_t Engine::update(const DeviceIndexView &v, const FrontierRec *fr, LevelBu
       n_next = (uint32_t)nn;
       next_frontier.reserve(std::max<size_t>((size_t)n_next * sizeof(FrontierRec), 256));
       // (the next level's lookup-order keys with the records, when that level will be looked up in that order on this device)
-      const bool keys_too = !remote && locality_min && n_next >= locality_min;
+      const bool keys_too = !remote && opt.locality_min && n_next >= opt.locality_min;
       if (keys_too) { lo_key.reserve((size_t)n_next * 4); lo_idx.reserve((size_t)n_next * 4); }
       launch_frontier_emit(vt->keys.as<unsigned long long>(), poff.as<uint32_t>(), n_pieces.as<uint32_t>(),
                            foff.as<uint32_t>(), n_groups, pieces.as<int2>(), next_frontier.as<FrontierRec>(), stream,
@@ -957,12 +957,12 @@ void Engine::run(const impg_gpu_index &ix, const RunSpec &spec) {
   min_identity = p.min_identity;
   store_cigar = p.store_cigar != 0 && keep != nullptr;  // slices are only materialised for full results
   // (the approximate mode's CIGAR is two sums, "N= MX" -- impg.rs:1479-1486 --, not an alignment: a caller asks for it by option)
-  if (store_cigar && ix.tp_mode && !ix.opt_approx_cigar)
+  if (store_cigar && ix.tp_mode && !opt.approximate_cigar)
     throw Error{IMPG_E_UNSUPPORTED, "store_cigar on a tracepoint index needs option approximate_cigar = 1 (the approximate mode's "
                                     "CIGAR is a pair of match / mismatch counts, not an alignment)"};
   multi = p.multi_impg != 0;
   // (kept levels too: the device-side row placement, rows_device.hip, only needs a record's slots to be one run)
-  free_slot_order = free_slots_allowed;
+  free_slot_order = opt.free_slot_order != 0;
   const DeviceIndexView &v = ix.view;
   cur_ranges = d_ranges;
   keys_for = nullptr;
@@ -1041,7 +1041,7 @@ void Engine::run(const impg_gpu_index &ix, const RunSpec &spec) {
     if (owners_keep) remote_rows->level = depth;
     // (kept levels too when their reader takes the slots in any order and finds a slot's frontier record through
     // pair_range -- the rows left in HBM, impg_gpu_query_batch_device's attributed layout: keep_any_order)
-    fuse_final = fuse_allowed && last && (!keep || spec.keep_any_order || ordered_rows) && !remote;
+    fuse_final = opt.fuse_final_level && last && (!keep || spec.keep_any_order || ordered_rows) && !remote;
     // (per-range counts / checksums of a fused level cost two atomics per hit -- its slots are in entry order, a range's
     // are no run -- which a deep closure's final level, 10^4+ ranges a query, does not earn back: config 5 with counts
     // 2.8 s per 4 000 windows fused, 1.4 s not)

@@ -115,8 +115,7 @@ struct Engine {
   uint32_t table_queries = 0;  // queries of the batch the tables belong to (their qoff arrays have one entry more)
   void index_table(VisitedStore &t);  // qoff[] of a table whose keys are in place
   uint64_t last_projected = 0;
-  uint64_t pair_budget = 1ull << 28;  // candidate pairs per level kept in HBM at once
-  uint32_t chunk_ranges = 0;          // ranges per chunk (0 = try the whole batch)
+  Options opt;  // the handle's options as they were when the engine was leased (options.hpp; engine_options, capi.cpp)
   bool split_ok = false;
   double min_identity = __builtin_nan("");  // of the batch / stage call in flight
   bool store_cigar = false;
@@ -129,12 +128,9 @@ struct Engine {
   // reads and writes them at its own index.  (Not under store_cigar / MultiImpg, whose slice materialisation and
   // five-key sort walk the reference's slot order.)
   bool free_slot_order = false;
-  bool free_slots_allowed = true;  // option "free_slot_order" (A/B runs)
-  bool regroup_pairs = true;       // option "regroup_entries": a projection block sorts its 256 pairs by entry first
   // A counting run's final level (max_depth reached, or a plain query): no update follows and no row is kept, so nothing
   // reads its slots in order -- the projection kernel enumerates the pairs from the count pass's windows and the emit
   // pass is skipped (WindowLists, kernels.hpp).  Set by run() around that level's hop.
-  bool fuse_allowed = true;        // option "fuse_final_level" (A/B runs)
   bool fuse_final = false, fuse_need_ranges = false, fuse_range_places = false;
   bool last_range_places = false;  // the last expand wrote places of the lookup order into pair_range (a kept fused level)
   // ordered rows placed by slot (RunModes::ordered_rows)
@@ -151,17 +147,14 @@ struct Engine {
   float ms_place = 0;
   DevBuf ent_work, ent_alloc;      // project_entries_kernel: the slice list of its heavy blocks, a place counter per range block
   DevBuf win_se, tile_first;       // the ranges' (start, end) by place; first range of every projection tile
-  int filter_covered = 0;          // option "filter_covered": hits covered by their group's old list dropped before the replay (0 off: it bought nothing on config 5, where hits are covered by the list as it GROWS, not as the level found it; 1 always, 2 long groups)
-  uint64_t covered_dropped = 0;    // ... how many that was, over the engine's life (tuning aid)
-  bool update_stats = false;       // option "update_stats": a level's update copies its list lengths and reach counters home (impg_gpu_index::upd_stats)
+  uint64_t covered_dropped = 0;    // hits option "filter_covered" dropped, over the engine's life (tuning aid)
   DevBuf m_dest, m_qid, m_coords, m_pe, m_sa, m_sn, m_so, m_sr;  // 5-key sort: destination + double buffers
   // projection order (locality): ranges sorted by window position, their slots listed in that order
   DevBuf wide_n, wide_list;  // ranges whose window is wider than the lane-per-range emit pass takes
-  WideEmit wide_emit;        // options "wide_emit_cap" / "wide_emit_bins"; count_reach = option "lookup_stats": a level's lookup copies its list lengths and reach counters home (impg_gpu_index::lk_stats)
+  WideEmit wide_emit;        // from options "wide_emit_cap" / "wide_emit_bins" / "lookup_stats" (count_reach: a level's lookup copies its list lengths and reach counters home)
   std::atomic<uint64_t> *lk_stats = nullptr;  // the handle's lookup_wide_* counters (by LookupStat), or null
   void count_wide_paths(const DeviceIndexView &v, uint32_t n);  // after a level's launch_lookup_emit; nothing without the option
   DevBuf lo_key, lo_key2, lo_idx, lo_perm, lo_cnt, lo_off, lo_offp, slot_of;
-  uint32_t locality_min = 4096;  // frontier ranges below which the reordering is not worth its launches (0 = never reorder)
   const uint32_t *stage_perm = nullptr;  // lookup order of the last stage_count call
   uint32_t stage_n = 0;  // frontier size of the last stage_count call
 
@@ -245,7 +238,7 @@ struct Engine {
     std::vector<uint32_t> h_n_rows;           // row counts, on the host
     std::vector<unsigned long long> h_base;   // where each query's rows start in `rows`
   };
-  bool walk_allowed = true, walk_bfs = false;  // option "walk_kernel": 0 never, 1 DFS (default), 2 also small BFS batches
+  bool walk_allowed = true, walk_bfs = false;  // from option "walk_kernel" and IMPG_NO_WALK
   bool walk_applicable(const impg_gpu_index &ix, uint32_t n, const impg_gpu_params_t &p) const;
   static void walk_caps(bool wide, WalkArgs &a);
   static uint64_t walk_workgroups(const impg_gpu_index &ix, bool wide);
@@ -259,9 +252,6 @@ struct Engine {
   std::atomic<uint64_t> *proj_stats = nullptr;  // ... and its levels per projection kernel (impg_gpu_index::proj_stats, by ProjArm)
   std::atomic<uint64_t> *upd_stats = nullptr;  // ... and its groups per tier / rare path of the visited update (by UpdStat; option update_stats)
   void count_arm(int arm) { if (proj_stats && arm >= 0 && arm < PROJ_ARMS) proj_stats[arm]++; }
-  uint32_t seg_parts_force = 0;  // option "segment_parts": every level that groups by segments cuts its queries into this many slices (0: by size)
-  bool seg_group = true;  // option "segment_groups": the update's hits grouped query by query instead of by the library's radix sort
-  uint32_t walk_members = 0;  // option "walk_members": workgroups per query of the grid form (0: as many as fit, at most 32; 1: no grid form)
   uint32_t walk_group_size(const impg_gpu_index &ix, uint32_t n, const impg_gpu_params_t &p) const;
   char *small_in = nullptr;    // pinned: the ranges on their way in
   char *small_out = nullptr;   // pinned + mapped: header, rows, the rows' ranges (written by the device)

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/impg_gpu.h"
+#include "options.hpp"
 
 namespace impg {
 
@@ -423,28 +424,10 @@ struct impg_gpu_index {
   std::mutex eng_m;
   std::condition_variable eng_cv;
   int max_engines = 4;
-  uint64_t opt_pair_budget = 1ull << 28;  // impg_gpu_set_option values, applied to an engine when it is leased
-  uint32_t opt_chunk_ranges = 0, opt_locality_min = 4096;
-  // failure injection for the tests of the multi-rank failure agreement (0 = off): (rank + 1) << 16 | hop of the batch
-  // (1-based, counted per lane) at which that rank throws on the owner side / on the home side of the hop
-  uint32_t opt_debug_fail_owner = 0, opt_debug_fail_home = 0;
-  uint64_t opt_lane_schedule = 0;  // IMPG_LANE_SCHEDULE / option "lane_schedule": see run_lanes (sharded.cpp); 0 = off
-  uint64_t opt_device_rows_pool = 160ull << 30;  // option "device_rows_pool_bytes"
+  impg::Options opt;  // impg_gpu_set_option values (options.hpp); an engine takes a copy when it is leased
   // a rank of a sharded index: the blocks of the rows impg_gpu_query_batch_device leaves in HBM (sharded.cpp rank_rows).  Not an
   // engine's: a handle gives its blocks back from whichever thread frees it, while the engines serve other calls.
   struct RowsPool : impg::BufPool { RowsPool() { shared = true; } } rows_pool;
-  bool opt_free_slots = true;
-  bool opt_regroup = true;
-  bool opt_fuse_final = true;
-  int opt_filter_covered = 0;
-  bool opt_update_stats = false;  // option "update_stats" (Engine::update_stats)
-  bool opt_lookup_stats = false;  // option "lookup_stats" (Engine::wide_emit.count_reach)
-  bool opt_approx_cigar = false;  // option "approximate_cigar": store_cigar on a tracepoint index returns the approximate CIGAR (Engine::run)
-  uint32_t opt_wide_cap = 4096, opt_wide_bins = 1024;  // options "wide_emit_cap" / "wide_emit_bins" (Engine::wide_emit)
-  int opt_walk = 1;
-  uint32_t opt_walk_members = 0;  // option "walk_members" (Engine::walk_members)
-  bool opt_seg_group = true;      // option "segment_groups" (Engine::seg_group)
-  uint32_t opt_seg_parts = 0;     // option "segment_parts" (Engine::seg_parts_force)
   mutable std::atomic<uint64_t> walk_launches{0}, walk_fallbacks{0}, walk_last_members{1};  // impg_gpu_get_counter
   mutable std::atomic<uint64_t> small_batches{0};  // ... and the batches Engine::run_small answered
   // ... and how the visited updates of its batches grouped their hits: levels cut into slices, levels counted a second time

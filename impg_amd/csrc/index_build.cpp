@@ -180,7 +180,8 @@ void parallel_chunks(size_t n, const std::function<void(size_t, size_t)> &f) {
 void build_index(impg_gpu_index &ix, const impg_gpu_record_t *records, size_t n_records, const uint32_t *cigar_ops,
                  size_t n_ops, const int64_t *seq_len, uint32_t n_seq, bool bidirectional, int order_policy,
                  uint32_t shard, uint32_t n_shards, const uint32_t *owner, const TpInput *tp, const EntryPlan *plan) {
-  const bool timing = getenv("IMPG_BUILD_TIMING") != nullptr;
+  const BuildSwitches sw = build_switches();
+  const bool timing = sw.timing;
   auto tnow = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   double t_prev = tnow();
   auto lap = [&](const char *what) {
@@ -196,7 +197,7 @@ void build_index(impg_gpu_index &ix, const impg_gpu_record_t *records, size_t n_
   // CIGAR indexes in record order are built on the device (index_build_device.hip); this host builder takes the
   // rest (tracepoint indexes, the entry order of a loaded .impg file), is the fallback when the device is short of
   // memory for the build, and the checker of the device build (IMPG_BUILD_HOST=1 forces it).
-  if (!tp && !plan && !getenv("IMPG_BUILD_HOST") &&
+  if (!tp && !plan && !sw.host_build &&
       build_index_device(ix, records, n_records, cigar_ops, n_ops, seq_len, n_seq, bidirectional, order_policy, shard, n_shards, owner))
     return;
   if (n_records >= (1ull << 31)) throw Error{IMPG_E_UNSUPPORTED, "more than 2^31 records in one index"};
@@ -255,11 +256,11 @@ void build_index(impg_gpu_index &ix, const impg_gpu_record_t *records, size_t n_
     n_tiles = (nb * 4 + TILE_WORDS - 1) / TILE_WORDS;  // (the pool is accounted in 128-byte lines like the op pool)
   }
   RawVec<uint32_t> pool(n_tiles * TILE_WORDS);  // (every line is filled by the builder that owns it)
-  const bool with_pfx = !tp && !(getenv("IMPG_PREFIX_LINES") && atoi(getenv("IMPG_PREFIX_LINES")) == 0);
+  const bool with_pfx = !tp && sw.prefix_lines;
   // identity filter: with prefix lines an *identity line* per tile (per-op matched / mismatched sums, impg_internal.hpp),
   // without them the sums before each sub-tile, where the two short walks start counting
   // (with prefix lines they are built on demand, impg_gpu_index::ensure_identity_lines, unless IMPG_IDENTITY_LINES=1 asks for them now)
-  const bool with_idl = with_pfx && getenv("IMPG_IDENTITY_LINES") && atoi(getenv("IMPG_IDENTITY_LINES")) == 1;
+  const bool with_idl = with_pfx && sw.identity_lines;
   RawVec<uint4> idp(tp ? 0 : (with_pfx ? (with_idl ? IDL_WORDS / 4 : 0) : TILE_SUBS) * n_tiles);
   RawVec<uint32_t> pfx(with_pfx ? n_tiles * TILE_WORDS : 0);  // prefix lines (impg_internal.hpp); optional: see index_build_device.hip
   if (tp && n_tiles) {  // the tail of the last 128-byte line behind the last boundary

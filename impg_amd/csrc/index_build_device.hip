@@ -315,7 +315,8 @@ __global__ __launch_bounds__(256) void cigar_tokens_kernel(const char *__restric
 bool build_index_device(impg_gpu_index &ix, const impg_gpu_record_t *records, size_t n_records, const uint32_t *cigar_ops, size_t n_ops,
                         const int64_t *seq_len, uint32_t n_seq, bool bidirectional, int order_policy, uint32_t shard, uint32_t n_shards,
                         const uint32_t *owner, const uint32_t *d_cigar_ops) {
-  const bool timing = getenv("IMPG_BUILD_TIMING") != nullptr;
+  const BuildSwitches sw = build_switches();
+  const bool timing = sw.timing;
   auto tnow = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   double t_prev = tnow();
   auto lap = [&](const char *what) {
@@ -367,9 +368,9 @@ bool build_index_device(impg_gpu_index &ix, const impg_gpu_record_t *records, si
   IMPG_HIP(hipMemGetInfo(&free_b, &total_b));
   // The prefix lines are 40 % of the index and only buy speed (the plain projection reads them instead of replaying
   // ops): an index that does not fit the device with them is built without (IMPG_PREFIX_LINES=0 forces that).
-  bool with_pfx = !(getenv("IMPG_PREFIX_LINES") && atoi(getenv("IMPG_PREFIX_LINES")) == 0);
+  bool with_pfx = sw.prefix_lines;
   // (the identity lines beside them are built when a query first needs them: impg_gpu_index::ensure_identity_lines)
-  const bool with_idl = getenv("IMPG_IDENTITY_LINES") && atoi(getenv("IMPG_IDENTITY_LINES")) == 1;
+  const bool with_idl = sw.identity_lines;
   auto bytes_for = [&](bool pf) { return n_tiles * ((pf ? 2 : 1) * TILE_WORDS * 4 + (pf ? (with_idl ? IDL_WORDS * 4 : 0) : TILE_SUBS * 16)) + n_entries * (sizeof(Entry) + 40) + n_records * 64; };
   if (with_pfx && bytes_for(true) + (1ull << 30) > free_b) with_pfx = false;
   const size_t out_bytes = bytes_for(with_pfx);

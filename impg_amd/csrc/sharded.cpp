@@ -286,7 +286,7 @@ struct ShardedExpander : Expander {
       try {
         // (a hop nobody at home reads hits of -- the final level of a counting run -- takes its pairs from the count
         // pass's windows: no emit pass, Engine::fuse_final)
-        E.fuse_final = E.fuse_allowed && !need_hits;
+        E.fuse_final = E.opt.fuse_final_level && !need_hits;
         E.fuse_need_ranges = rr != nullptr;
         if (rr) E.fuse_range_places = true;  // (a kept level names every slot's record by its place, as on one GPU)
         std::unique_ptr<LevelBufs> kept = rr ? std::make_unique<LevelBufs>(rr->pool) : nullptr;
@@ -555,7 +555,7 @@ struct LaneWork {  // what one lane accumulates
 // 50 000 ranges is the plain engine's chunk: what an owner expands in one hop is, summed over the homes, about one
 // chunk's worth, and every chunk pays its hops' fixed costs (25 000: 74.8 ms per headline step on one rank, 50 000: 69.8).
 size_t shard_chunk(const impg_gpu_index &ix, size_t n) {
-  if (ix.opt_chunk_ranges) return ix.opt_chunk_ranges;
+  if (ix.opt.chunk_ranges) return (size_t)ix.opt.chunk_ranges;
   const size_t lanes = std::max<size_t>(1, ix.shard->comm->lanes.size());
   return std::min<size_t>(50000, std::max<size_t>(1, (n + lanes - 1) / lanes));
 }
@@ -573,15 +573,15 @@ template <class P, class F> void run_lanes(impg_gpu_index &ix, size_t n, P prep,
     S.lanes[l]->agreed = S.lanes[l]->in_transport = false;
     S.lanes[l]->hop_no = 0;
     const uint32_t me1 = (uint32_t)S.comm->rank + 1;
-    S.lanes[l]->fail_owner_hop = (ix.opt_debug_fail_owner >> 16) == me1 ? (ix.opt_debug_fail_owner & 0xFFFFu) : 0;
-    S.lanes[l]->fail_home_hop = (ix.opt_debug_fail_home >> 16) == me1 ? (ix.opt_debug_fail_home & 0xFFFFu) : 0;
+    S.lanes[l]->fail_owner_hop = (ix.opt.debug_fail_owner >> 16) == me1 ? (uint32_t)(ix.opt.debug_fail_owner & 0xFFFF) : 0;
+    S.lanes[l]->fail_home_hop = (ix.opt.debug_fail_home >> 16) == me1 ? (uint32_t)(ix.opt.debug_fail_home & 0xFFFF) : 0;
   }
   // Forced lane schedules (tests; option "lane_schedule" / IMPG_LANE_SCHEDULE = v > 0): bit l(l-1)/2 + l' of v - 1
   // makes lane l take its engine only after lane l' < l has run all its chunks and handed its engine back -- the
   // late lane is then given that very engine (the pool is last-in first-out).  v = 1 .. 2^(L(L-1)/2) enumerates every
   // hand-over pattern of L lanes instead of leaving them to thread timing (the class of the seed-72686 defect above).
   // Not with several RCCL lanes: their issue order (comm.hpp) needs every lane to start.
-  uint64_t sched = ix.opt_lane_schedule;
+  uint64_t sched = (uint64_t)ix.opt.lane_schedule;
   if (!sched) if (const char *e = getenv("IMPG_LANE_SCHEDULE")) sched = strtoull(e, nullptr, 10);
   if (n_lanes > 1 && std::string(S.comm->lanes[0]->kind()) == "rccl") sched = 0;
   std::mutex sched_m;
@@ -713,12 +713,6 @@ void rank_bed(impg_gpu_index &ix, const impg_gpu_range_t *ranges, size_t n, cons
   if (seconds3) for (int k = 0; k < 3; k++) seconds3[k] = t3[k];
 }
 
-// ranges of a multi-GPU handle are dealt to the ranks in contiguous blocks (results concatenate in order)
-void split_blocks(size_t n, size_t W, std::vector<size_t> &cut) {
-  cut.resize(W + 1);
-  for (size_t r = 0; r <= W; r++) cut[r] = n * r / W;
-}
-
 template <class F> void on_every_rank(Cluster &C, F f) {
   const size_t W = C.ranks.size();
   std::vector<std::exception_ptr> errs(W);
@@ -739,11 +733,17 @@ template <class F> void on_every_rank(Cluster &C, F f) {
   if (auto first = first_cause(errs)) std::rethrow_exception(first);
 }
 
-// the options of a multi handle its ranks run a rows batch with
-void forward_options(impg_gpu_index &ix, Cluster &C) {
-  for (auto &r : C.ranks) { r->opt_chunk_ranges = ix.opt_chunk_ranges; r->opt_pair_budget = ix.opt_pair_budget; r->opt_locality_min = ix.opt_locality_min;
-                            r->opt_debug_fail_owner = ix.opt_debug_fail_owner; r->opt_debug_fail_home = ix.opt_debug_fail_home; r->opt_lane_schedule = ix.opt_lane_schedule;
-                            r->opt_fuse_final = ix.opt_fuse_final; r->opt_device_rows_pool = ix.opt_device_rows_pool; }
+// A batch of a multi-GPU handle, of whichever form: its n ranges are dealt to the ranks in contiguous blocks (results
+// concatenate in order), every rank is handed the handle's options (those the option table flags: options_to_ranks),
+// and f(r, rank r's index, first range, ranges) runs on every rank side by side.
+template <class F> void on_rank_blocks(impg_gpu_index &ix, size_t n, F f) {
+  Cluster &C = *ix.cluster;
+  const size_t W = C.ranks.size();
+  for (auto &r : C.ranks) options_to_ranks(ix.opt, r->opt);
+  on_every_rank(C, [&](size_t r) {
+    const size_t b = n * r / W;
+    f(r, *C.ranks[r], b, n * (r + 1) / W - b);
+  });
 }
 // work adds up; the ranks ran side by side, so time is the slowest rank's
 void merge_rank_stats(const std::vector<impg_gpu_stats_t> &sts, impg_gpu_stats_t *stats) {
@@ -771,7 +771,7 @@ void rank_rows(impg_gpu_index &ix, const impg_gpu_range_t *ranges, bool on_devic
   ShardCtx &S = *ix.shard;
   // (the rows of a big batch are tens of GB: their blocks go back to the pool when the handle is freed and are the next
   // call's -- a fresh hipMalloc of them costs more than the batch)
-  ix.rows_pool.raise_max_held((size_t)ix.opt_device_rows_pool);
+  ix.rows_pool.raise_max_held((size_t)ix.opt.device_rows_pool_bytes);
   const size_t n_lanes = S.comm->lanes.size();
   std::vector<impg_gpu_stats_t> per_lane(n_lanes);
   for (auto &x : per_lane) memset(&x, 0, sizeof x);
@@ -876,17 +876,11 @@ int sharded_query_stats(impg_gpu_index &ix, const impg_gpu_range_t *ranges, bool
     rank_stats(ix, ranges, on_device, n, p, per_range_count, per_range_checksum, stats);
     return IMPG_OK;
   }
-  Cluster &C = *ix.cluster;
   check_ranges(ranges, n);
-  const size_t W = C.ranks.size();
-  std::vector<size_t> cut;
-  split_blocks(n, W, cut);
-  std::vector<impg_gpu_stats_t> sts(W);
-  for (auto &r : C.ranks) { r->opt_chunk_ranges = ix.opt_chunk_ranges; r->opt_pair_budget = ix.opt_pair_budget; r->opt_locality_min = ix.opt_locality_min;
-                            r->opt_debug_fail_owner = ix.opt_debug_fail_owner; r->opt_debug_fail_home = ix.opt_debug_fail_home; r->opt_lane_schedule = ix.opt_lane_schedule; }
-  on_every_rank(C, [&](size_t r) {
-    rank_stats(*C.ranks[r], ranges + cut[r], false, cut[r + 1] - cut[r], p, per_range_count ? per_range_count + cut[r] : nullptr,
-               per_range_checksum ? per_range_checksum + cut[r] : nullptr, &sts[r]);
+  std::vector<impg_gpu_stats_t> sts(ix.cluster->ranks.size());
+  on_rank_blocks(ix, n, [&](size_t r, impg_gpu_index &rank, size_t b, size_t k) {
+    rank_stats(rank, ranges + b, false, k, p, per_range_count ? per_range_count + b : nullptr, per_range_checksum ? per_range_checksum + b : nullptr,
+               &sts[r]);
   });
   merge_rank_stats(sts, stats);
   return IMPG_OK;
@@ -901,17 +895,11 @@ void sharded_bed_batch(impg_gpu_index &ix, const impg_gpu_range_t *ranges, size_
     for (auto &c : chunks) if (!c.empty()) sink(c.data(), c.size());
     return;
   }
-  Cluster &C = *ix.cluster;
-  const size_t W = C.ranks.size();
-  std::vector<size_t> cut;
-  split_blocks(n, W, cut);
+  const size_t W = ix.cluster->ranks.size();
   std::vector<std::vector<std::string>> parts(W);
   std::vector<std::array<double, 3>> secs(W);
-  for (auto &r : C.ranks) { r->opt_chunk_ranges = ix.opt_chunk_ranges; r->opt_pair_budget = ix.opt_pair_budget; r->opt_locality_min = ix.opt_locality_min;
-                            r->opt_debug_fail_owner = ix.opt_debug_fail_owner; r->opt_debug_fail_home = ix.opt_debug_fail_home; r->opt_lane_schedule = ix.opt_lane_schedule; }
-  on_every_rank(C, [&](size_t r) {
-    rank_bed(*C.ranks[r], ranges + cut[r], cut[r + 1] - cut[r], p, subset_keep, merge_distance, range_names ? range_names + cut[r] : nullptr, parts[r],
-             secs[r].data());
+  on_rank_blocks(ix, n, [&](size_t r, impg_gpu_index &rank, size_t b, size_t k) {
+    rank_bed(rank, ranges + b, k, p, subset_keep, merge_distance, range_names ? range_names + b : nullptr, parts[r], secs[r].data());
   });
   for (auto &pr : parts)
     for (auto &c : pr) if (!c.empty()) sink(c.data(), c.size());
@@ -936,15 +924,11 @@ void sharded_query_device(impg_gpu_index &ix, const impg_gpu_range_t *ranges, bo
     rank_rows(ix, ranges, on_device, n, offset, total, p, *out[0], stats);
     return;
   }
-  Cluster &C = *ix.cluster;
   check_ranges(ranges, n);
-  const size_t W = C.ranks.size();
-  std::vector<size_t> cut;
-  split_blocks(n, W, cut);
+  const size_t W = ix.cluster->ranks.size();
   std::vector<impg_gpu_stats_t> sts(W);
-  forward_options(ix, C);
   for (size_t r = 0; r < W; r++) out.push_back(std::make_unique<ShardRows>());
-  on_every_rank(C, [&](size_t r) { rank_rows(*C.ranks[r], ranges + cut[r], false, cut[r + 1] - cut[r], cut[r], n, p, *out[r], &sts[r]); });
+  on_rank_blocks(ix, n, [&](size_t r, impg_gpu_index &rank, size_t b, size_t k) { rank_rows(rank, ranges + b, false, k, b, n, p, *out[r], &sts[r]); });
   merge_rank_stats(sts, stats);
 }
 
@@ -978,15 +962,8 @@ int sharded_query_batch(impg_gpu_index &ix, const impg_gpu_range_t *ranges, size
     *out = res.release();
     return IMPG_OK;
   }
-  Cluster &C = *ix.cluster;
-  const size_t W = C.ranks.size();
-  std::vector<size_t> cut;
-  split_blocks(n, W, cut);
-  std::vector<impg_gpu_results> parts(W);
-  for (auto &r : C.ranks) { r->opt_chunk_ranges = ix.opt_chunk_ranges; r->opt_pair_budget = ix.opt_pair_budget; r->opt_locality_min = ix.opt_locality_min;
-                            r->opt_debug_fail_owner = ix.opt_debug_fail_owner; r->opt_debug_fail_home = ix.opt_debug_fail_home; r->opt_lane_schedule = ix.opt_lane_schedule;
-                            r->opt_approx_cigar = ix.opt_approx_cigar; }  // (every shard's engine reads its own rank's handle: Engine::run)
-  on_every_rank(C, [&](size_t r) { rank_query(*C.ranks[r], ranges + cut[r], cut[r + 1] - cut[r], p, mask, subset_keep, parts[r]); });
+  std::vector<impg_gpu_results> parts(ix.cluster->ranks.size());
+  on_rank_blocks(ix, n, [&](size_t r, impg_gpu_index &rank, size_t b, size_t k) { rank_query(rank, ranges + b, k, p, mask, subset_keep, parts[r]); });
   res->offsets.assign(1, 0);
   double run_s = 0, asm_s = 0;
   for (auto &pt : parts) {

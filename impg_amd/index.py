@@ -424,24 +424,12 @@ class GpuImpg:
         return lib().impg_gpu_device_bytes(self._h)
 
     def set_option(self, key, value):
+        """impg_gpu_set_option: one of option_keys(); include/impg_gpu.h describes each."""
         check(lib().impg_gpu_set_option(self._h, key.encode(), int(value)))
 
     def counter(self, key):
-        """impg_gpu_get_counter: "walk_launches", "walk_fallbacks", "walk_members"; "small_batches" (plain batches the
-        small-batch path answered); "segment_sliced_levels",
-        "segment_retries", "segment_library_levels"; and the levels projected per kernel (counted on the host, per
-        launch): "project_lane_levels" (project_kernel), "project_staged_levels", "project_staged_rows_levels"
-        (project_staged_kernel, listed pairs / ordered rows), "project_entries_slots_levels",
-        "project_entries_qs_levels", "project_entries_rows_levels", "project_entries_ident_levels"
-        (project_entries_kernel by output / the identity filter), "project_tp_levels" (tracepoint index).  Under
-        set_option("update_stats", 1), the visited update's groups per tier -- "update_lane_groups",
-        "update_mid_groups", "update_wave_tiny_groups", "update_wave_small_groups", "update_wave_large_groups" -- and
-        per rare path: "update_inplace_groups" (replay on the global slice), "update_tiled_sort_groups" (more pieces
-        than the LDS buffer), "update_lane_spill_groups" (a lane's pieces left its LDS column).  Under
-        set_option("lookup_stats", 1), the lookup's windows of more than 64 entries: "lookup_wide_windows" (listed by
-        the count pass), "lookup_wide_single" (sorted in one LDS pass), "lookup_wide_grouped" (split into rank-bin
-        groups), "lookup_wide_group_passes" (the passes those took), "lookup_wide_overflow" (handed to the
-        wave-per-range kernel: one rank bin alone beyond the buffer)."""
+        """impg_gpu_get_counter: one of counter_keys(); include/impg_gpu.h describes each.  The "update_*" counters
+        move under set_option("update_stats", 1), the "lookup_wide_*" ones under set_option("lookup_stats", 1)."""
         v = C.c_int64(0)
         check(lib().impg_gpu_get_counter(self._h, key.encode(), C.byref(v)))
         return v.value
@@ -957,6 +945,23 @@ class Comm:
         if getattr(self, "_h", None):
             lib().impg_gpu_comm_destroy(self._h)
             self._h = None
+
+
+def _keys(fn):
+    out = []
+    while (k := fn(len(out))) is not None:
+        out.append(k.decode())
+    return out
+
+
+def option_keys():
+    """impg_gpu_option_key: every key GpuImpg.set_option accepts (no GPU needed)."""
+    return _keys(lib().impg_gpu_option_key)
+
+
+def counter_keys():
+    """impg_gpu_counter_key: every key GpuImpg.counter accepts (no GPU needed)."""
+    return _keys(lib().impg_gpu_counter_key)
 
 
 def parse_subsequence(name):

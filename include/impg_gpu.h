@@ -238,12 +238,27 @@ int impg_gpu_index_approximate(const impg_gpu_index_t *);
  * pass and its pair lists are skipped; counts and checksums are identical either way),
  * "approximate_cigar" (0, the default: store_cigar on a tracepoint index is IMPG_E_UNSUPPORTED; 1: its rows carry the
  * approximate mode's CIGAR -- see impg_gpu_index_create_tracepoints.  No effect on an index built from CIGARs.  A
- * run-time setting: impg_gpu_index_save does not write it; a multi-GPU handle hands it to its shards).
+ * run-time setting: impg_gpu_index_save does not write it),
+ * "regroup_entries" (1, the default: a projection block sorts its 256 pairs by entry before reading the index; results
+ * identical), "filter_covered" (visited update: hits covered by their group's old list dropped before the replay -- 0 off,
+ * the default, 1 always, 2 long groups; results identical), "device_rows_pool_bytes" (HBM kept between
+ * impg_gpu_query_batch_device calls: freed slot arrays, reused by the next call; 160 GiB by default),
+ * "update_stats" / "lookup_stats" (0, the default; 1: the "update_*" / "lookup_wide_*" counters below are kept, one small
+ * copy per level).  For tests of the multi-rank paths: "lane_schedule" (forced lane start / hand-over order of a sharded
+ * batch; 0 = off), "debug_fail_owner" / "debug_fail_home" (failure injection: (rank + 1) << 16 | hop of the batch at which
+ * that rank throws on the owner / on the home side of the hop; 0 = off).
+ * A multi-GPU handle hands "chunk_ranges", "pair_budget", "locality_min", "debug_fail_owner", "debug_fail_home",
+ * "lane_schedule", "fuse_final_level", "device_rows_pool_bytes" and "approximate_cigar" to its shards before every batch;
+ * the other settings have no effect on it.  A value outside a key's range, and an unknown key, is IMPG_E_INVALID.
  * Actions rather than settings, so that a process's FIRST call costs what its later ones do: "prewarm_result_bytes" = N
  * pins a host block of N bytes into the result pool now (a 5 GB result pins its block inside the first call
  * otherwise, ~0.3-1 s); "prewarm_walk" = 1 / 2 allocates the per-query walk's slabs (1: the per-call / small-batch BFS
  * shape; 2: also the DFS batch's, ~15 GB) on the index's first engine. */
 int impg_gpu_set_option(impg_gpu_index_t *, const char *key, int64_t value);
+/* The keys impg_gpu_set_option / impg_gpu_get_counter accept, i = 0, 1, ...; NULL past the last one.  No handle and no
+ * device needed: a document or a wrapper can be checked against the library's own tables. */
+const char *impg_gpu_option_key(size_t i);
+const char *impg_gpu_counter_key(size_t i);
 /* Read-only counters of an index handle (no reference counterpart; they tell a test, or an operator, which engine
  * answered): "walk_launches" = per-query walk launches that answered their batch (walk_device.inc: DFS batches, small
  * depth-limited BFS batches incl. masked ones -- the shape of partition.rs:359-391), "walk_fallbacks" = launches whose
@@ -252,7 +267,9 @@ int impg_gpu_set_option(impg_gpu_index_t *, const char *key, int64_t value);
  * small-batch path; how the visited updates grouped their hits: "segment_sliced_levels" =
  * levels whose queries were cut into slices of their frontier ranges, "segment_retries" = levels counted a second time
  * because one query held more hits than a wave should take, "segment_library_levels" = levels that went through the
- * library's radix sort instead.  With option "update_stats" = 1 (0, the default: nothing is copied or counted) every
+ * library's radix sort instead; which kernel projected each level: "project_lane_levels", "project_staged_levels",
+ * "project_staged_rows_levels", "project_entries_slots_levels", "project_entries_qs_levels", "project_entries_rows_levels",
+ * "project_entries_ident_levels", "project_tp_levels".  With option "update_stats" = 1 (0, the default: nothing is copied or counted) every
  * level's visited update also counts its (query, sequence) groups by the kernel that took them -- "update_lane_groups",
  * "update_mid_groups", "update_wave_tiny_groups", "update_wave_small_groups", "update_wave_large_groups" -- and by the
  * rare path they reached: "update_inplace_groups" (the replay ran on the group's global slice), "update_tiled_sort_groups"
