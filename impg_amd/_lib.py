@@ -78,6 +78,23 @@ class PartitionOpts(C.Structure):  # impg_gpu_partition_opts_t
     _fields_ = [("window_size", C.c_int64), ("merge_distance", C.c_int32), ("min_missing_size", C.c_int32),
                 ("min_boundary_distance", C.c_int32), ("selection", C.c_int32), ("separator", C.c_char_p),
                 ("rehome_singletons", C.c_int32), ("state_on_host", C.c_int32)]
+
+
+class SupportOpts(C.Structure):  # impg_gpu_support_opts_t
+    _fields_ = [("span_bp", C.c_int32), ("merge_distance", C.c_int32)]
+
+
+class RefineOpts(C.Structure):  # impg_gpu_refine_opts_t
+    _fields_ = [("span_bp", C.c_int32), ("max_extension", C.c_double), ("extension_step", C.c_int32), ("merge_distance", C.c_int32),
+                ("use_max_entities", C.c_int32), ("support_on_host", C.c_int32)]
+
+
+REFINE_RECORD_DTYPE = np.dtype([("target_id", "<u4"), ("refined_start", "<i4"), ("refined_end", "<i4"), ("original_start", "<i4"),
+                                ("original_end", "<i4"), ("left_extension", "<i4"), ("right_extension", "<i4"), ("support_count", "<u4"),
+                                ("original_support_count", "<u4")])  # impg_gpu_refine_record_t
+ROWS_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p))
+SURVIVOR_DTYPE = np.dtype([("seq_id", "<u4"), ("q_lo", "<i4"), ("q_hi", "<i4")])  # impg_gpu_survivor_t
+NO_ENTITY = 0xFFFFFFFF
 FRONTIER_DTYPE = np.dtype([("target_id", "<u4"), ("start", "<i4"), ("end", "<i4"), ("range_idx", "<u4")])
 
 
@@ -204,6 +221,19 @@ SYMBOLS = [
     ("impg_gpu_partition_regions", _P, [_P]),
     ("impg_gpu_partition_counter", C.c_int, [_P, C.c_char_p, C.POINTER(C.c_int64)]),
     ("impg_gpu_partition_destroy", None, [_P]),
+    ("impg_gpu_support_rows", C.c_int, [_P, _P, _P, C.c_size_t, C.c_uint32, _P, _P, _P, _P, C.POINTER(SupportOpts), C.c_int, C.c_int, _P, _P,
+                                        C.POINTER(_P), C.POINTER(C.c_uint64)]),
+    ("impg_gpu_refine", C.c_int, [_P, _P, C.c_size_t, C.POINTER(Params), C.POINTER(RefineOpts), _P, _P, _P, _P, C.POINTER(_P)]),
+    ("impg_gpu_refine_rows", C.c_int, [ROWS_CB, _P, _P, C.c_uint32, _P, C.c_size_t, C.POINTER(RefineOpts), _P, _P, _P, _P, C.c_int, C.POINTER(_P)]),
+    ("impg_gpu_refine_num_records", C.c_size_t, [_P]),
+    ("impg_gpu_refine_records", _P, [_P]),
+    ("impg_gpu_refine_survivor_offsets", _P, [_P]),
+    ("impg_gpu_refine_survivors", _P, [_P]),
+    ("impg_gpu_refine_stats", None, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("impg_gpu_refine_batch_times", C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("impg_gpu_refine_text", C.c_int, [_P, _P, C.c_uint32, _P, C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(_P), C.POINTER(C.c_size_t)]),
+    ("impg_gpu_refine_free", None, [_P]),
+    ("impg_gpu_entity_ids", C.c_int, [_P, C.c_size_t, C.c_int, C.c_char_p, _P, C.POINTER(C.c_uint32)]),
     ("impg_synth_paf", C.c_int, [C.c_uint64, C.c_size_t, C.c_uint32, C.c_int32, C.c_int32, C.c_uint32, _P, _P, C.c_size_t,
                                  C.POINTER(C.c_size_t)]),
     ("impg_synth_paf_text", C.c_int, [C.c_uint64, C.c_size_t, C.c_uint32, C.c_int32, C.c_int32, C.c_uint32, C.c_char_p]),

@@ -15,6 +15,7 @@
 
 #include "engine.hpp"
 #include "partition.hpp"
+#include "refine.hpp"
 
 namespace impg {
 thread_local std::string g_error;
@@ -658,6 +659,9 @@ static const CounterRow COUNTER_TABLE[] = {
     CTR("update_lane_spill_groups", upd_stats[UPD_LANE_SPILL]),
     CTR("lookup_wide_windows", lk_stats[LK_WIDE]), CTR("lookup_wide_single", lk_stats[LK_SINGLE]), CTR("lookup_wide_grouped", lk_stats[LK_GROUPED]),
     CTR("lookup_wide_group_passes", lk_stats[LK_GROUP_PASSES]), CTR("lookup_wide_overflow", lk_stats[LK_OVERFLOW]),
+    CTR("refine_passes", refine_stats[REFINE_PASSES]), CTR("refine_candidates", refine_stats[REFINE_CANDIDATES]),
+    CTR("refine_parts", refine_stats[REFINE_PARTS]), CTR("refine_rows_to_host", refine_stats[REFINE_ROWS_TO_HOST]),
+    CTR("refine_longest_group", refine_stats[REFINE_LONGEST_GROUP]),
 };
 #undef CTR
 constexpr size_t N_COUNTERS = sizeof(COUNTER_TABLE) / sizeof(COUNTER_TABLE[0]);
@@ -1046,8 +1050,15 @@ struct impg_gpu_device_rows {
 
 int impg_gpu_query_batch_device(impg_gpu_index_t *ix, const impg_gpu_range_t *ranges, size_t n, int ranges_on_device,
                                 const impg_gpu_params_t *params, int layout, impg_gpu_device_rows_t **out) {
+  return impg::query_batch_device_filtered(ix, ranges, n, ranges_on_device, params, layout, nullptr, out);
+}
+}  // extern "C"
+// ... with the subset filter of impg_gpu_query_batch_filtered (one GPU only): what refine's passes call (refine.cpp)
+int impg::query_batch_device_filtered(impg_gpu_index_t *ix, const impg_gpu_range_t *ranges, size_t n, int ranges_on_device,
+                                      const impg_gpu_params_t *params, int layout, const uint8_t *subset_keep, impg_gpu_device_rows_t **out) {
   IMPG_TRY
   if (!ix || !params || !out || (!ranges && n)) throw Error{IMPG_E_INVALID, "null argument"};
+  if (subset_keep && (ix->shard || ix->cluster)) throw Error{IMPG_E_UNSUPPORTED, "rows left on the device take a subset filter on one GPU only"};
   if (layout != IMPG_ROWS_ATTRIBUTED && layout != IMPG_ROWS_ORDERED && layout != IMPG_ROWS_ORDERED_SLOTS) throw Error{IMPG_E_INVALID, "unknown row layout"};
   if (n >= (1ull << 31)) throw Error{IMPG_E_UNSUPPORTED, "more than 2^31 ranges in one batch"};
   if (!ranges_on_device) check_ranges(ranges, n);
@@ -1086,6 +1097,7 @@ int impg_gpu_query_batch_device(impg_gpu_index_t *ix, const impg_gpu_range_t *ra
   h->params = *params;
   h->n = n;
   h->layout = layout;
+  apply_subset(E, *ix, subset_keep);
   const impg_gpu_range_t *d_ranges = ranges_on_device ? ranges : upload_ranges(E.ranges_dev, ranges, n, &E.stream);
   impg_gpu_stats_t tot;
   memset(&tot, 0, sizeof tot);
@@ -1142,6 +1154,7 @@ int impg_gpu_query_batch_device(impg_gpu_index_t *ix, const impg_gpu_range_t *ra
   return IMPG_OK;
   IMPG_CATCH
 }
+extern "C" {
 
 static size_t num_parts(const impg_gpu_device_rows_t *h) { return h->shard_rows.empty() ? h->parts.size() : h->shard_parts.size(); }
 size_t impg_gpu_device_rows_num_parts(const impg_gpu_device_rows_t *h) { return h ? num_parts(h) : 0; }

@@ -102,7 +102,48 @@ void usage() {
           "               [--selection-mode longest|total|sample[,sep]|haplotype[,sep]] [--starting-sequences-file FILE]\n"
           "               [--separate-files] [--no-rehome-singletons] [--output-folder DIR] [-o bed] [--host-state] [-m N]\n"
           "               [--transitive-dfs] [--min-transitive-len N] [--min-distance-between-ranges N] [--min-identity F]\n"
+          "               [--unidirectional] [--order coitrees|sorted] [--device N]\n"
+          "impg-gpu refine (-a <paf>... | -i <file>) (-r seq:start-end | -b <bed>) (-d <bp> | --no-merge) [--span-bp N]\n"
+          "               [--max-extension F] [--extension-step N] [--pansn-mode sample|haplotype] [--support-output FILE]\n"
+          "               [--blacklist-bed FILE] [-x] [-m N] [--transitive-dfs] [--multi-impg] [--min-transitive-len N]\n"
+          "               [--min-distance-between-ranges N] [--min-result-identity F] [--subset-sequence-list FILE]\n"
           "               [--unidirectional] [--order coitrees|sorted] [--device N]\n");
+}
+
+// the index of a command: the saved file if it exists, else built from the alignment files (and saved where -i names a file)
+impg_gpu_index_t *open_index(const std::vector<std::string> &pafs, const std::string &index_file, bool unidirectional, int order, int device) {
+  std::vector<const char *> pp;
+  for (auto &p : pafs) pp.push_back(p.c_str());
+  impg_gpu_index_t *ix = nullptr;
+  FILE *probe = index_file.empty() ? nullptr : fopen(index_file.c_str(), "rb");
+  if (probe) {
+    fclose(probe);
+    if (impg_gpu_index_load(index_file.c_str(), device, &ix) != IMPG_OK) die(impg_gpu_last_error());
+  } else {
+    if (pafs.empty()) die("No such file or directory: " + index_file);
+    if (impg_gpu_index_create_from_paf(pp.data(), (int)pp.size(), unidirectional ? 0 : 1, order, device, &ix) != IMPG_OK) die(impg_gpu_last_error());
+    if (!index_file.empty() && impg_gpu_index_save(ix, index_file.c_str()) != IMPG_OK) die(impg_gpu_last_error());
+  }
+  return ix;
+}
+
+// load_subset_filter (subset_filter.rs:63-82) + one matches() per sequence
+std::vector<uint8_t> load_subset_keep(impg_gpu_index_t *ix, const std::string &subset_list) {
+  FILE *f = fopen(subset_list.c_str(), "rb");
+  if (!f) die("Failed to read subset sequence list '" + subset_list + "'");
+  std::string text;
+  char buf[1 << 16];
+  size_t got;
+  while ((got = fread(buf, 1, sizeof buf, f)) > 0) text.append(buf, got);
+  fclose(f);
+  const uint32_t ns = impg_gpu_num_seqs(ix);
+  std::vector<const char *> nm(ns);
+  for (uint32_t i = 0; i < ns; i++) nm[i] = impg_gpu_seq_name(ix, i);
+  std::vector<uint8_t> keep(ns);
+  size_t entries = 0;
+  if (impg_gpu_subset_keep(text.data(), text.size(), nm.data(), ns, keep.data(), &entries) != IMPG_OK) die(impg_gpu_last_error());
+  if (entries == 0) die("Subset sequence list '" + subset_list + "' did not contain any sequence names");
+  return keep;
 }
 
 // `impg partition` (reference src/main.rs partition arguments; src/commands/partition.rs:158-712) with BED output:
@@ -179,18 +220,7 @@ int partition_main(int argc, char **argv) {
   else if (kind == "sample") selection = IMPG_SELECT_SAMPLE;
   else if (kind == "haplotype") selection = IMPG_SELECT_HAPLOTYPE;
   else die("Invalid selection mode. Must be 'longest', 'total', 'sample[,sep]', or 'haplotype[,sep]'.");
-  std::vector<const char *> pp;
-  for (auto &p : pafs) pp.push_back(p.c_str());
-  impg_gpu_index_t *ix = nullptr;
-  FILE *probe = index_file.empty() ? nullptr : fopen(index_file.c_str(), "rb");
-  if (probe) {
-    fclose(probe);
-    if (impg_gpu_index_load(index_file.c_str(), device, &ix) != IMPG_OK) die(impg_gpu_last_error());
-  } else {
-    if (pafs.empty()) die("No such file or directory: " + index_file);
-    if (impg_gpu_index_create_from_paf(pp.data(), (int)pp.size(), unidirectional ? 0 : 1, order, device, &ix) != IMPG_OK) die(impg_gpu_last_error());
-    if (!index_file.empty() && impg_gpu_index_save(ix, index_file.c_str()) != IMPG_OK) die(impg_gpu_last_error());
-  }
+  impg_gpu_index_t *ix = open_index(pafs, index_file, unidirectional, order, device);
   std::vector<uint32_t> start_ids;
   if (!starting.empty()) {  // partition.rs:186-212: first tab field, trimmed; empty lines, '#' comments and unknown names skipped
     std::ifstream in(starting);
@@ -234,10 +264,191 @@ int partition_main(int argc, char **argv) {
   return 0;
 }
 
+// parse_blacklist_bed (reference src/commands/refine.rs:879-948) into the CSR table of impg_gpu_refine; a sequence the
+// index does not know is never asked for and is left out
+void parse_blacklist_bed(const std::string &path, impg_gpu_index_t *ix, std::vector<uint32_t> &off, std::vector<int32_t> &ranges) {
+  std::ifstream in(path);
+  if (!in) die("No such file or directory: " + path);
+  const uint32_t ns = impg_gpu_num_seqs(ix);
+  std::vector<std::vector<int32_t>> per(ns);
+  std::string line;
+  for (size_t line_num = 1; std::getline(in, line); line_num++) {
+    const size_t a = line.find_first_not_of(" \t\r\n\v\f"), b = line.find_last_not_of(" \t\r\n\v\f");
+    line = a == std::string::npos ? "" : line.substr(a, b - a + 1);
+    if (line.empty() || line[0] == '#') continue;
+    std::vector<std::string> parts;
+    size_t st = 0;
+    for (size_t i = 0; i <= line.size(); i++)
+      if (i == line.size() || line[i] == '\t') { parts.push_back(line.substr(st, i - st)); st = i + 1; }
+    if (parts.size() < 3) die("Line " + std::to_string(line_num) + " has fewer than 3 fields in BED file: " + path);
+    int32_t s = 0, e = 0;
+    if (!parse_i32(parts[1], &s)) die("Invalid start position on line " + std::to_string(line_num));
+    if (!parse_i32(parts[2], &e)) die("Invalid end position on line " + std::to_string(line_num));
+    if (e <= s) die("Invalid range on line " + std::to_string(line_num) + ": end (" + std::to_string(e) + ") <= start (" + std::to_string(s) + ")");
+    const long long id = impg_gpu_seq_id(ix, parts[0].c_str());
+    if (id >= 0) { per[(size_t)id].push_back(s); per[(size_t)id].push_back(e); }
+  }
+  off.assign((size_t)ns + 1, 0);
+  ranges.clear();
+  for (uint32_t q = 0; q < ns; q++) {
+    ranges.insert(ranges.end(), per[q].begin(), per[q].end());
+    off[q + 1] = (uint32_t)(ranges.size() / 2);
+  }
+}
+
+// `impg refine` (reference src/main.rs:7700-7862, src/commands/refine.rs): the table on stdout, --support-output beside it
+int refine_main(int argc, char **argv) {
+  std::vector<std::string> pafs;
+  std::string index_file, range, bed, pansn, support_out, blacklist_bed, subset_list;
+  long long merge_d = 0;
+  bool have_d = false, no_merge = false, transitive = false, dfs = false, multi = false, unidirectional = false;
+  long max_depth = 2, min_tl = -1, mdbr = 10, span_bp = 1000, step = 1000;
+  double min_ident = NAN, max_ext = 0.5;
+  int device = 0, order = IMPG_ORDER_COITREES;
+  auto num = [](const std::string &flag, const char *x, long lo, long hi) -> long {
+    char *end = nullptr;
+    errno = 0;
+    const long r = strtol(x, &end, 10);
+    if (errno || end == x || *end != '\0' || r < lo || r > hi) die("invalid value '" + std::string(x) + "' for '" + flag + "'", 2);
+    return r;
+  };
+  auto real = [](const std::string &flag, const char *v) -> double {
+    char *end = nullptr;
+    errno = 0;
+    const double x = strtod(v, &end);
+    if (errno || end == v || *end != '\0' || !(x == x)) die("invalid value '" + std::string(v) + "' for '" + flag + "'", 2);
+    return x;
+  };
+  for (int i = 2; i < argc; i++) {
+    std::string a = argv[i];
+    auto need = [&](const char *f) -> const char * {
+      if (i + 1 >= argc) die(std::string("a value is required for '") + f + "'", 2);
+      return argv[++i];
+    };
+    if (a == "-a" || a == "--alignment-files") {
+      pafs.push_back(need("-a"));
+      while (i + 1 < argc && argv[i + 1][0] != '-') pafs.push_back(argv[++i]);
+    } else if (a == "-i" || a == "--index") index_file = need("-i");
+    else if (a == "-r" || a == "--target-range") range = need("-r");
+    else if (a == "-b" || a == "--target-bed") bed = need("-b");
+    else if (a == "-d" || a == "--merge-distance") {
+      if (!parse_metric(need("-d"), &merge_d) || merge_d < 0 || merge_d > 2147483647ll) die("invalid value for '-d'", 2);
+      have_d = true;
+    } else if (a == "--no-merge") no_merge = true;
+    else if (a == "--span-bp") span_bp = num(a, need(a.c_str()), -2147483647 - 1, 2147483647);
+    else if (a == "--max-extension") max_ext = real(a, need(a.c_str()));
+    else if (a == "--extension-step") step = num(a, need(a.c_str()), -2147483647 - 1, 2147483647);
+    else if (a == "--pansn-mode") pansn = need(a.c_str());
+    else if (a == "--support-output") support_out = need(a.c_str());
+    else if (a == "--blacklist-bed") blacklist_bed = need(a.c_str());
+    else if (a == "-x" || a == "--transitive") transitive = true;
+    else if (a == "--transitive-dfs") dfs = true;
+    else if (a == "--multi-impg") multi = true;
+    else if (a == "-m" || a == "--max-depth") max_depth = num(a, need("-m"), 0, 65535);
+    else if (a == "--min-transitive-len") min_tl = num(a, need(a.c_str()), 0, 2147483647);
+    else if (a == "--min-distance-between-ranges") mdbr = num(a, need(a.c_str()), 0, 2147483647);
+    else if (a == "--min-result-identity") min_ident = real(a, need(a.c_str()));
+    else if (a == "--subset-sequence-list") subset_list = need(a.c_str());
+    else if (a == "--unidirectional") unidirectional = true;
+    else if (a == "--device") device = (int)num(a, need(a.c_str()), 0, 1023);
+    else if (a == "--order") {
+      std::string o = need("--order");
+      if (o != "sorted" && o != "coitrees") die("invalid value '" + o + "' for '--order'", 2);
+      order = o == "sorted" ? IMPG_ORDER_SORTED : IMPG_ORDER_COITREES;
+    } else if (a == "-t" || a == "--threads" || a == "-v" || a == "--verbose") need(a.c_str());  // accepted, unused
+    else if (a == "-h" || a == "--help") { usage(); return 0; }
+    else die("unexpected argument '" + a + "'", 2);
+  }
+  // RefineOpts::validate (main.rs:4454-4473), validate_merge_distance
+  if (span_bp < 0) die("--span-bp must be >= 0");
+  if (max_ext < 0.0) die("--max-extension must be >= 0");
+  if (step <= 0) die("--extension-step must be > 0");
+  if (!have_d && !no_merge)
+    die("-d/--merge-distance is required. For `impg refine`, pass `-d <bp>`. Use `--no-merge` to explicitly disable merging.");
+  if (!pansn.empty() && pansn != "sample" && pansn != "haplotype" && pansn != "sequence") die("invalid value '" + pansn + "' for '--pansn-mode'", 2);
+  if (pafs.empty() && index_file.empty()) die("the following required arguments were not provided: --alignment-files", 2);
+  if (range.empty() && bed.empty()) die("Either --target-range or --target-bed must be provided");
+  impg_gpu_index_t *ix = open_index(pafs, index_file, unidirectional, order, device);
+  std::vector<uint8_t> keep;
+  if (!subset_list.empty()) keep = load_subset_keep(ix, subset_list);
+  std::vector<Target> targets;
+  if (!range.empty()) {
+    char name[4096];
+    int32_t s, e;
+    if (impg_gpu_parse_target_range(range.c_str(), name, sizeof name, &s, &e) != IMPG_OK) die(impg_gpu_last_error());
+    targets.push_back({name, std::string(name) + ":" + std::to_string(s) + "-" + std::to_string(e), s, e});
+  } else targets = parse_bed_file(bed);
+  const int32_t eff_min_tl = min_tl < 0 ? 101 : (int32_t)min_tl;
+  std::vector<impg_gpu_range_t> loci;
+  std::vector<const char *> labels;
+  for (auto &t : targets) {  // validate_sequence_range, validate_range_min_length (main.rs:7732-7755)
+    const long long id = impg_gpu_seq_id(ix, t.seq.c_str());
+    if (id < 0) die("Sequence '" + t.seq + "' not found in index");
+    const long long len = impg_gpu_seq_len(ix, (uint32_t)id);
+    if (t.start < 0) die("Start position " + std::to_string(t.start) + " cannot be negative");
+    if (t.end < 0) die("End position " + std::to_string(t.end) + " cannot be negative");
+    if (t.start >= t.end) die("Start position must be less than end position");
+    if (t.end > len) die("End position " + std::to_string(t.end) + " exceeds sequence length " + std::to_string(len));
+    if (t.end - t.start < eff_min_tl)
+      die("Range '" + t.name + "' (" + std::to_string(t.end - t.start) + " bp) is below minimum of " + std::to_string(eff_min_tl) +
+          " bp. Lower --min-transitive-len or use a longer range");
+    loci.push_back({(uint32_t)id, t.start, t.end});
+    labels.push_back(t.name.c_str());
+  }
+  std::vector<uint32_t> bl_off;
+  std::vector<int32_t> bl_rng;
+  if (!blacklist_bed.empty()) parse_blacklist_bed(blacklist_bed, ix, bl_off, bl_rng);
+  const uint32_t ns = impg_gpu_num_seqs(ix);
+  std::vector<const char *> nm(ns);
+  for (uint32_t i = 0; i < ns; i++) nm[i] = impg_gpu_seq_name(ix, i);
+  const bool by_entity = pansn == "sample" || pansn == "haplotype";
+  std::vector<uint32_t> ent(ns);
+  if (by_entity && impg_gpu_entity_ids(nm.data(), ns, pansn == "sample" ? IMPG_SELECT_SAMPLE : IMPG_SELECT_HAPLOTYPE, "#", ent.data(), nullptr) != IMPG_OK)
+    die(impg_gpu_last_error());
+  impg_gpu_params_t p;
+  memset(&p, 0, sizeof p);
+  p.transitive = transitive || dfs;
+  p.dfs = dfs;
+  p.multi_impg = multi;
+  p.max_depth = (uint32_t)max_depth;
+  p.min_transitive_len = eff_min_tl;
+  p.min_distance_between_ranges = (int32_t)mdbr;
+  p.min_output_length = -1;
+  p.min_identity = min_ident;
+  impg_gpu_refine_opts_t o;
+  memset(&o, 0, sizeof o);
+  o.span_bp = (int32_t)span_bp;
+  o.max_extension = max_ext;
+  o.extension_step = (int32_t)step;
+  o.merge_distance = no_merge ? -1 : (int32_t)merge_d;
+  o.use_max_entities = by_entity;
+  impg_gpu_refine_t *res = nullptr;
+  if (impg_gpu_refine(ix, loci.data(), loci.size(), &p, &o, by_entity ? ent.data() : nullptr, keep.empty() ? nullptr : keep.data(),
+                      bl_off.empty() ? nullptr : bl_off.data(), bl_rng.data(), &res) != IMPG_OK)
+    die(impg_gpu_last_error());
+  char *text = nullptr, *sup = nullptr;
+  size_t len = 0, sup_len = 0;
+  if (impg_gpu_refine_text(res, nm.data(), ns, labels.data(), &text, &len, &sup, &sup_len) != IMPG_OK) die(impg_gpu_last_error());
+  fwrite(text, 1, len, stdout);
+  fflush(stdout);
+  if (!support_out.empty()) {
+    FILE *f = fopen(support_out.c_str(), "wb");
+    if (!f) die("could not create " + support_out);
+    fwrite(sup, 1, sup_len, f);
+    fclose(f);
+  }
+  free(text);
+  free(sup);
+  impg_gpu_refine_free(res);
+  impg_gpu_index_destroy(ix);
+  return 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
   if (argc >= 2 && strcmp(argv[1], "partition") == 0) return partition_main(argc, argv);
+  if (argc >= 2 && strcmp(argv[1], "refine") == 0) return refine_main(argc, argv);
   if (argc < 2 || (strcmp(argv[1], "query") != 0 && strcmp(argv[1], "index") != 0)) {
     usage();
     return 2;
@@ -409,22 +620,7 @@ int main(int argc, char **argv) {
   p.consider_strandness = consider_strandness;
   impg_gpu_results_t *res = nullptr;
   std::vector<uint8_t> keep;
-  if (!subset_list.empty()) {  // load_subset_filter (subset_filter.rs:63-82) + one matches() per sequence
-    FILE *f = fopen(subset_list.c_str(), "rb");
-    if (!f) die("Failed to read subset sequence list '" + subset_list + "'");
-    std::string text;
-    char buf[1 << 16];
-    size_t got;
-    while ((got = fread(buf, 1, sizeof buf, f)) > 0) text.append(buf, got);
-    fclose(f);
-    const uint32_t ns = impg_gpu_num_seqs(ix);
-    std::vector<const char *> nm(ns);
-    for (uint32_t i = 0; i < ns; i++) nm[i] = impg_gpu_seq_name(ix, i);
-    keep.resize(ns);
-    size_t entries = 0;
-    if (impg_gpu_subset_keep(text.data(), text.size(), nm.data(), ns, keep.data(), &entries) != IMPG_OK) die(impg_gpu_last_error());
-    if (entries == 0) die("Subset sequence list '" + subset_list + "' did not contain any sequence names");
-  }
+  if (!subset_list.empty()) keep = load_subset_keep(ix, subset_list);
   auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   const double t0 = now();
   if (fmt == "bed" && !host_merge) {  // both merges on the device: only merged rows cross PCIe

@@ -442,6 +442,8 @@ struct impg_gpu_index {
   mutable std::atomic<uint64_t> upd_stats[8] = {};
   // ... and, under option lookup_stats, the lookup's wide windows by the path that emitted them (by impg::LookupStat)
   mutable std::atomic<uint64_t> lk_stats[5] = {};
+  // ... and what the refine runs on the handle did (by impg::RefineStat; refine.cpp)
+  mutable std::atomic<uint64_t> refine_stats[5] = {};
   impg::ShardCtx *shard = nullptr;    // set: this index is one rank's shard; queries are collective calls
   impg::Cluster *cluster = nullptr;   // set: this handle fronts n_dev shards in this process (no arrays of its own)
   impg_gpu_index();

@@ -199,20 +199,7 @@ void select_windows(const SelSummary &s, const std::vector<int32_t> &len, int se
   std::map<std::string, std::pair<int64_t, std::vector<uint32_t>>> groups;  // ordered by prefix: the tie rule of :858-864
   for (uint32_t q = 0; q < n_seq; q++) {
     if (s.total[q] <= 0) continue;  // only sequences still in the missing map (:808-810)
-    const std::string &nm = (*names)[q];
-    const size_t a = nm.find(sep);
-    std::string prefix;
-    if (selection == IMPG_SELECT_SAMPLE) prefix = nm.substr(0, a);
-    else {  // p1 + sep + p2, p2 = "" without a second field (:819-823)
-      const std::string p1 = nm.substr(0, a);
-      std::string p2;
-      if (a != std::string::npos) {
-        const size_t b = nm.find(sep, a + sep.size());
-        p2 = nm.substr(a + sep.size(), b == std::string::npos ? std::string::npos : b - a - sep.size());
-      }
-      prefix = p1 + sep + p2;
-    }
-    auto &g = groups[prefix];
+    auto &g = groups[pansn_prefix((*names)[q], sep, selection == IMPG_SELECT_HAPLOTYPE)];
     g.first += s.total[q];
     g.second.push_back(q);
   }
@@ -223,6 +210,19 @@ void select_windows(const SelSummary &s, const std::vector<int32_t> &len, int se
   std::vector<uint32_t> ids = best->second;
   std::stable_sort(ids.begin(), ids.end(), [&](uint32_t a, uint32_t b) { return len[a] > len[b]; });  // ties: ascending id
   for (uint32_t q : ids) window_range(q, 0, len[q], ws, out);
+}
+
+std::string pansn_prefix(const std::string &nm, const std::string &sep, bool haplotype) {
+  const size_t a = nm.find(sep);
+  if (!haplotype) return nm.substr(0, a);
+  // p1 + sep + p2, p2 = "" without a second field (:819-823)
+  const std::string p1 = nm.substr(0, a);
+  std::string p2;
+  if (a != std::string::npos) {
+    const size_t b = nm.find(sep, a + sep.size());
+    p2 = nm.substr(a + sep.size(), b == std::string::npos ? std::string::npos : b - a - sep.size());
+  }
+  return p1 + sep + p2;
 }
 
 void starting_windows(const uint32_t *ids, size_t n, const std::vector<int32_t> &len, int64_t ws, std::vector<impg_gpu_range_t> &out) {

@@ -66,6 +66,8 @@ struct DeviceRegions {
 // select_and_window_sequences from a summary; names may be null for longest / total
 void select_windows(const SelSummary &s, const std::vector<int32_t> &len, int selection, const std::string &sep,
                     const std::vector<std::string> *names, int64_t window_size, std::vector<impg_gpu_range_t> &out);
+// the name prefix sequences are grouped by: the first field, or the first two with the separator between them (:812-823)
+std::string pansn_prefix(const std::string &name, const std::string &sep, bool haplotype);
 // the windows of a starting-sequences list (partition.rs:220-246)
 void starting_windows(const uint32_t *ids, size_t n, const std::vector<int32_t> &len, int64_t window_size, std::vector<impg_gpu_range_t> &out);
 using Partition = std::pair<uint64_t, std::vector<PIv>>;

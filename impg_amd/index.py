@@ -391,6 +391,36 @@ class GpuImpg:
         finally:
             s.close()
 
+    def refine(self, loci, params=None, span_bp=1000, max_extension=0.5, extension_step=1000, merge_distance=0, level="sequence",
+               separator="#", subset_keep=None, blacklist=None, on_host=False, names=None):
+        """`impg refine` (impg_gpu_refine) for loci [(target_id, start, end)]: a RefineResult.  level: 'sequence' | 'sample' |
+        'haplotype' (the PanSN level support is counted at; the latter two also stop a locus at its max_entities);
+        blacklist {seq_id: [(start, end), ...]}; on_host=True: support_on_host; names: the loci's labels."""
+        if level not in ("sequence", "sample", "haplotype"):
+            raise ValueError("level is 'sequence', 'sample' or 'haplotype'")
+        p = params or make_params()
+        n_seq = self.num_seqs()
+        seq_names = [self.seq_name(i) for i in range(n_seq)]
+        if any(nm is None for nm in seq_names):  # an index made without names: records without chrom and text
+            if level != "sequence":
+                raise ValueError("levels 'sample' and 'haplotype' need the sequence names")
+            seq_names = None
+        ent = None if level == "sequence" else entity_ids(seq_names, level, separator)[0]
+        keep = None if subset_keep is None else np.ascontiguousarray(subset_keep, dtype=np.uint8)
+        if keep is not None and keep.size != n_seq:
+            raise ValueError("subset_keep holds one entry per sequence")
+        bo, br = _blacklist_table(blacklist, n_seq)
+        lo = self._ranges(loci)
+        opts = _refine_opts(span_bp, max_extension, extension_step, merge_distance, level != "sequence", on_host)
+        ptr = lambda x: None if x is None else x.ctypes.data
+        h = C.c_void_p()
+        _lib.check(_lib.lib().impg_gpu_refine(self._h, lo.ctypes.data, lo.size, C.byref(p), C.byref(opts), ptr(ent), ptr(keep), ptr(bo), ptr(br),
+                                              C.byref(h)))
+        try:
+            return RefineResult(h, seq_names, list(names) if names is not None else None)
+        finally:
+            _lib.lib().impg_gpu_refine_free(h)
+
     def num_seqs(self):
         return lib().impg_gpu_num_seqs(self._h)
 
@@ -771,6 +801,163 @@ def partitions_bed_text(partitions, names):
         return C.string_at(text, ln.value).decode()
     finally:
         _lib.free(text)
+
+
+def entity_ids(names, level, separator="#"):
+    """PanSN entity ids of sequence names for level 'sample' / 'haplotype' (impg_gpu_entity_ids): a uint32 array,
+    _lib.NO_ENTITY for a name without a key, and the number of entities."""
+    lv = {"sample": _lib.SELECT_SAMPLE, "haplotype": _lib.SELECT_HAPLOTYPE}[level]
+    out = np.zeros(len(names), dtype=np.uint32)
+    n = C.c_uint32(0)
+    _lib.check(_lib.lib().impg_gpu_entity_ids(_names_array(names), len(names), lv, separator.encode(), out.ctypes.data, C.byref(n)))
+    return out, n.value
+
+
+def support_rows(rows, offsets, candidates, n_seq, span_bp=1000, merge_distance=0, entity_of=None, max_entities=None, blacklist=None,
+                 on_host=False, device=0, survivors=True, stats=None):
+    """The boundary support of `impg refine` (impg_gpu_support_rows) for a batch of candidates: rows (INTERVAL_DTYPE) with
+    offsets[n_cand + 1], candidates [(target_id, start, end)], blacklist {seq_id: [(start, end), ...]}.  Returns the
+    counts, and with survivors=True also [[(seq_id, q_lo, q_hi), ...] per candidate].  on_host=True: the host twin.
+    stats: a dict that receives 'longest_group'."""
+    a = np.ascontiguousarray(rows, dtype=_lib.INTERVAL_DTYPE)
+    off = np.ascontiguousarray(offsets, dtype=np.uint64)
+    cand = GpuImpg._ranges(candidates)
+    if off.size != cand.size + 1:
+        raise ValueError("offsets must hold one entry more than there are candidates")
+    ent = None if entity_of is None else np.ascontiguousarray(entity_of, dtype=np.uint32)
+    mx = None if max_entities is None else np.ascontiguousarray(max_entities, dtype=np.uint32)
+    if (ent is not None and ent.size != n_seq) or (mx is not None and mx.size != cand.size):
+        raise ValueError("entity_of holds one entry per sequence, max_entities one per candidate")
+    bo, br = _blacklist_table(blacklist, n_seq)
+    opts = _lib.SupportOpts(span_bp, merge_distance)
+    count = np.zeros(max(cand.size, 1), dtype=np.uint32)
+    soff = np.zeros(cand.size + 1, dtype=np.uint64)
+    sv = C.c_void_p()
+    longest = C.c_uint64(0)
+    ptr = lambda x: None if x is None else x.ctypes.data
+    _lib.check(_lib.lib().impg_gpu_support_rows(a.ctypes.data, off.ctypes.data, cand.ctypes.data, cand.size, n_seq, ptr(ent), ptr(mx), ptr(bo), ptr(br),
+                                                C.byref(opts), int(on_host), device, count.ctypes.data, soff.ctypes.data if survivors else None,
+                                                C.byref(sv) if survivors else None, C.byref(longest)))
+    if stats is not None:
+        stats["longest_group"] = longest.value
+    counts = [int(v) for v in count[:cand.size]]
+    if not survivors:
+        return counts
+    try:
+        n = int(soff[-1])
+        flat = np.frombuffer(C.string_at(sv, n * _lib.SURVIVOR_DTYPE.itemsize), dtype=_lib.SURVIVOR_DTYPE) if n else []
+        flat = [(int(r["seq_id"]), int(r["q_lo"]), int(r["q_hi"])) for r in flat]
+    finally:
+        _lib.free(sv)
+    return counts, [flat[int(soff[c]):int(soff[c + 1])] for c in range(cand.size)]
+
+
+def _blacklist_table(blacklist, n_seq):
+    """{seq_id: [(start, end), ...]} -> (u32 off[n_seq + 1], int32 (start, end) pairs), or (None, None)."""
+    if blacklist is None:
+        return None, None
+    off = np.zeros(n_seq + 1, dtype=np.uint32)
+    flat = []
+    for s in range(n_seq):
+        flat.extend(blacklist.get(s, ()))
+        off[s + 1] = len(flat)
+    return off, (np.array(flat, dtype=np.int32).reshape(-1, 2) if flat else np.zeros((1, 2), dtype=np.int32))
+
+
+class RefineResult:
+    """The records of a refine run (impg_gpu_refine_t): dicts with the reference's RefineRecord fields -- target_id,
+    chrom, refined_start / _end, original_start / _end, label, left_extension / right_extension (applied_*),
+    support_count, original_support_count, survivors [(seq_id, q_lo, q_hi)] (support_entities)."""
+
+    def __init__(self, handle, names, labels):
+        L = _lib.lib()
+        self.names, self.labels = names, labels
+        n = L.impg_gpu_refine_num_records(handle)
+        recs = np.frombuffer(C.string_at(L.impg_gpu_refine_records(handle), n * _lib.REFINE_RECORD_DTYPE.itemsize),
+                             dtype=_lib.REFINE_RECORD_DTYPE) if n else []
+        off = np.frombuffer(C.string_at(L.impg_gpu_refine_survivor_offsets(handle), (n + 1) * 8), dtype=np.uint64)
+        ns = int(off[-1])
+        sv = np.frombuffer(C.string_at(L.impg_gpu_refine_survivors(handle), ns * _lib.SURVIVOR_DTYPE.itemsize),
+                           dtype=_lib.SURVIVOR_DTYPE) if ns else []
+        sv = [(int(r["seq_id"]), int(r["q_lo"]), int(r["q_hi"])) for r in sv]
+        p, c, k = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        L.impg_gpu_refine_stats(handle, C.byref(p), C.byref(c), C.byref(k))
+        self.passes, self.candidates, self.parts = p.value, c.value, k.value
+        nt = C.c_size_t(0)
+        bt = np.zeros(64, dtype=np.float64)
+        _lib.check(L.impg_gpu_refine_batch_times(handle, bt.ctypes.data, bt.size, C.byref(nt)))
+        # per batch: candidates, seconds in the query call, the engine's milliseconds inside it, seconds in the support
+        self.batch_times = [dict(candidates=int(r[0]), query_s=float(r[1]), engine_ms=float(r[2]), support_s=float(r[3]))
+                            for r in bt[:min(nt.value, bt.size)].reshape(-1, 4)]
+        self.records = []
+        for i, r in enumerate(recs):
+            d = {f: int(r[f]) for f in _lib.REFINE_RECORD_DTYPE.names}
+            d["chrom"] = names[d["target_id"]] if names else None
+            d["label"] = labels[i] if labels else ""
+            d["survivors"] = sv[int(off[i]):int(off[i + 1])]
+            self.records.append(d)
+        self.text, self.support_text = None, None
+        if names:
+            t, s = C.c_void_p(), C.c_void_p()
+            tl, sl = C.c_size_t(0), C.c_size_t(0)
+            lab = (C.c_char_p * max(n, 1))(*[(x or "").encode() for x in (labels or [""] * n)])
+            _lib.check(L.impg_gpu_refine_text(handle, _names_array(names), len(names), lab, C.byref(t), C.byref(tl), C.byref(s), C.byref(sl)))
+            try:
+                self.text, self.support_text = C.string_at(t, tl.value).decode(), C.string_at(s, sl.value).decode()
+            finally:
+                _lib.free(t)
+                _lib.free(s)
+
+    def __len__(self):
+        return len(self.records)
+
+    def __getitem__(self, i):
+        return self.records[i]
+
+
+def _refine_opts(span_bp, max_extension, extension_step, merge_distance, use_max, on_host):
+    return _lib.RefineOpts(span_bp, float(max_extension), extension_step, merge_distance, int(use_max), int(on_host))
+
+
+def refine_rows(query, seq_len, loci, span_bp=1000, max_extension=0.5, extension_step=1000, merge_distance=0, entity_of=None,
+                max_entities=None, blacklist=None, on_host=True, device=0, names=None, labels=None):
+    """The refine search over the caller's own row source (impg_gpu_refine_rows): query(regions) -> one array of rows
+    (INTERVAL_DTYPE) per region [(target_id, start, end)], in emission order.  on_host=True needs no GPU."""
+    sl = np.ascontiguousarray(seq_len, dtype=np.int64)
+    lo = GpuImpg._ranges(loci)
+    ent = None if entity_of is None else np.ascontiguousarray(entity_of, dtype=np.uint32)
+    mx = None if max_entities is None else np.ascontiguousarray(max_entities, dtype=np.uint32)
+    bo, br = _blacklist_table(blacklist, sl.size)
+    keep = {}
+    err = []
+
+    def cb(ctx, regions, n, rows_out, off_out):
+        try:
+            reg = np.frombuffer(C.string_at(regions, n * RANGE_DTYPE.itemsize), dtype=RANGE_DTYPE)
+            per = [np.ascontiguousarray(r, dtype=_lib.INTERVAL_DTYPE) for r in query([(int(r["target_id"]), int(r["start"]), int(r["end"])) for r in reg])]
+            keep["off"] = np.concatenate([[0], np.cumsum([p.size for p in per])]).astype(np.uint64)
+            keep["rows"] = np.concatenate(per) if per else np.zeros(0, dtype=_lib.INTERVAL_DTYPE)
+            if keep["rows"].size == 0:
+                keep["rows"] = np.zeros(1, dtype=_lib.INTERVAL_DTYPE)
+            rows_out[0] = keep["rows"].ctypes.data
+            off_out[0] = keep["off"].ctypes.data
+            return 0
+        except Exception as e:  # nothing unwinds through the library
+            err.append(e)
+            return 1
+
+    ptr = lambda x: None if x is None else x.ctypes.data
+    opts = _refine_opts(span_bp, max_extension, extension_step, merge_distance, False, on_host)
+    h = C.c_void_p()
+    rc = _lib.lib().impg_gpu_refine_rows(_lib.ROWS_CB(cb), None, sl.ctypes.data, sl.size, lo.ctypes.data, lo.size, C.byref(opts), ptr(ent), ptr(mx),
+                                         ptr(bo), ptr(br), device, C.byref(h))
+    if err:
+        raise err[0]
+    _lib.check(rc)
+    try:
+        return RefineResult(h, names, labels)
+    finally:
+        _lib.lib().impg_gpu_refine_free(h)
 
 
 class PartitionSession:

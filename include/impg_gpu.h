@@ -719,6 +719,128 @@ impg_gpu_regions_t *impg_gpu_partition_regions(impg_gpu_partition_t *); /* borro
 int impg_gpu_partition_counter(const impg_gpu_partition_t *, const char *key, int64_t *value);
 void impg_gpu_partition_destroy(impg_gpu_partition_t *);
 
+/* ---- refine: the boundary support of `impg refine` (src/commands/refine.rs:665-850) --------------------------------------
+ * The reference evaluates a grid of flank extensions per locus, each a query followed by a per-sequence fold over the
+ * query's rows.  What is built here is that fold as a batch primitive: the rows of n_cand candidate regions in one call,
+ * rows[offsets[c] .. offsets[c + 1]) those of candidate c in the reference's emission order (what impg_gpu_query_batch
+ * returns, self interval included; a row with query_id 0xFFFFFFFF is a hole of IMPG_ROWS_ORDERED_SLOTS and is skipped),
+ * cand[c] = its target and the clamped region (start, end).  Per candidate (compute_support_sets, :665-783):
+ *   a candidate of at most one row supports nothing (:680-682); rows whose query is the candidate's target are dropped;
+ *   the others are grouped by query sequence -- the row's target_id is NOT looked at, as in the reference --, a group is
+ *   sorted stably by (q_start, q_end) and folded by merge_intervals / should_merge (:799-850; merge_distance < 0: no
+ *   merge); a merged interval covers when t_start <= start, t_end >= end, t_end >= start + effective_span and t_start <=
+ *   end - effective_span, effective_span = min(max(end - start, 0), max(span_bp, 0)); a group's hull is the min / max
+ *   query coordinate of its covering intervals; a group is dropped when a blacklisted range of its sequence shares a
+ *   position with [q_lo, q_hi], both ends inclusive on both sides (coitrees' query(first, last), :736-748); every other
+ *   group with a hull is a SURVIVOR (seq_id, q_lo, q_hi), and count[c] = the number of distinct entities among the
+ *   survivors, min'ed with max_entities[c] where given.
+ * entity_of[n_seq] maps a sequence to its entity (PanSN keys are strings and stay with the caller; impg_gpu_entity_ids
+ * makes the ids); 0xFFFFFFFF = the sequence has no key: it is a survivor and counts nothing (:750-757).  NULL = every
+ * sequence its own entity (level `sequence`).  The blacklist is a CSR table over the sequence ids, blacklist_off[n_seq + 1]
+ * and (start, end) pairs in any order (end < start: IMPG_E_INVALID); NULL = none.
+ * The one place the output is a SUPERSET of the reference's: the reference stops walking its hash map when the count
+ * reaches max_entities (:758-763), so the survivors it prints then depend on hash order; here every survivor is returned
+ * and only the count is clamped.
+ * on_host = 1: the host twin, plain C++, no GPU.  on_host = 0: the rows are uploaded to `device` and the kernels of
+ * refine_device.hip run; each (candidate, sequence) group is folded by one lane -- the fold is order-dependent, not a
+ * scan -- so one very long group makes one lane run long (*longest_group_out = the rows of the longest group folded).
+ * A row whose query_id is neither a hole nor < n_seq: IMPG_E_INVALID (on the device after the kernels have run; the row
+ * is dropped before anything indexes with it).  count_out[n_cand]; survivor_offsets_out[n_cand + 1] and *survivors_out
+ * (malloc'ed; free() it), ascending seq_id inside a candidate, both NULL when not wanted. */
+typedef struct {
+  int32_t span_bp;        /* reference default 1000 */
+  int32_t merge_distance; /* < 0 = --no-merge */
+} impg_gpu_support_opts_t;
+typedef struct {
+  uint32_t seq_id;
+  int32_t q_lo, q_hi;
+} impg_gpu_survivor_t;
+int impg_gpu_support_rows(const impg_gpu_interval_t *rows, const uint64_t *offsets, const impg_gpu_range_t *cand, size_t n_cand,
+                          uint32_t n_seq, const uint32_t *entity_of, const uint32_t *max_entities, const uint32_t *blacklist_off,
+                          const int32_t *blacklist_ranges, const impg_gpu_support_opts_t *opts, int on_host, int device,
+                          uint32_t *count_out, uint64_t *survivor_offsets_out, impg_gpu_survivor_t **survivors_out,
+                          uint64_t *longest_group_out);
+/* Entity ids of PanSN names "sample<sep>haplotype<sep>contig" for level = IMPG_SELECT_SAMPLE (the first field) or
+ * IMPG_SELECT_HAPLOTYPE (the first two fields, separator included), numbered as the keys are first seen; separator NULL =
+ * "#".  UNPINNED: what sweepga's extract_pansn_key returns for a name with too few fields could not be checked; here a
+ * name that does not contain the separator has no key (0xFFFFFFFF) at either level, and "a<sep>b" has both.
+ * Host-only: needs no device. */
+int impg_gpu_entity_ids(const char *const *names, size_t n, int level, const char *separator, uint32_t *entity_out,
+                        uint32_t *n_entities_out);
+
+/* The search: run_refine (refine.rs:81-409) for n loci (target_id, start, end), end > start.  A candidate (left, right)
+ * of a locus is the region start = max(s - left, 0), end = min(e + right, len(target)) -- none if end <= start -- with
+ * left_extension = s - start and right_extension = end - e, the clamped values (:426-467).  flanks = build_flanks(
+ * max_extension_bp, extension_step) (:852-876), max_extension_bp = ceil(locus length x max_extension) for max_extension
+ * <= 1, else ceil(max_extension) (:177-185).  Pass 0 evaluates (0, 0): original_support_count.  Unless the best has reached
+ * the locus's max_entities, pass 1 evaluates (l, 0) for l > 0, pass 2 (left_best, r) for every r, pass 3 (l, right_best) for
+ * every l, each stopping the locus when the maximum is reached; inside a pass the candidates are reduced in flank order and
+ * one replaces the best only when compare_candidates is strictly Greater (:548-582: more support, then smaller left + right,
+ * then smaller max(left, right), then shorter), and so does the pass's winner against the running best.
+ * The reference runs a query per candidate; here the live candidates of ALL loci of a pass are ONE batch, so a run is at most
+ * four batches plus one small batch that reads the winners' survivors, whatever n is (counter "refine_passes").
+ * impg_gpu_refine: the rows are the index's.  Plain and BFS queries on a CIGAR or tracepoint index leave their rows in HBM
+ * (IMPG_ROWS_ORDERED_SLOTS; a batch may come back as several parts -- "chunk_ranges", "pair_budget" -- and the support runs
+ * part by part: counter "refine_parts") and only count[] comes home.  DFS and MultiImpg params, which
+ * impg_gpu_query_batch_device does not offer, and support_on_host = 1 go through impg_gpu_query_batch_filtered: the rows
+ * cross PCIe ("refine_rows_to_host" counts them) and the support runs on them with the kernels, or with the host twin under
+ * support_on_host.  "refine_candidates" = candidates evaluated, "refine_longest_group" = the longest (candidate, sequence)
+ * group a lane folded.  use_max_entities = 1 (levels sample and haplotype): compute_max_entities (:589-632) per distinct
+ * target from the index's entries -- distinct entity_of[] over the target's entries, without entries of the target itself,
+ * of sequences subset_keep drops, of sequences without a key, and without the target's own key; the blacklist is not applied.
+ * subset_keep as in impg_gpu_query_batch_filtered; entity_of / blacklist as in impg_gpu_support_rows.
+ * impg_gpu_refine_rows: the same search over the caller's own row source -- `query` is handed every pass's candidate regions
+ * and returns their rows, grouped by region in emission order with offsets[n + 1], valid until its next call; non-zero =
+ * IMPG_E_CANCELLED -- with seq_len[n_seq] for the clamp and max_entities[n] per locus (NULL: none).  With support_on_host = 1
+ * it needs no GPU; else the rows are uploaded to `device`.
+ * Refused: a sharded index (IMPG_E_UNSUPPORTED); store_cigar or min_output_length >= 0 (IMPG_E_INVALID: refine passes
+ * neither, :497-502); span_bp < 0, max_extension < 0 or NaN, extension_step <= 0 (RefineOpts::validate, main.rs:4454-4473);
+ * a locus with end <= start, an unknown target, or no candidate at all (:153-168, :374-382): IMPG_E_INVALID. */
+typedef struct {
+  int32_t span_bp;        /* reference default 1000 */
+  double max_extension;   /* 0.5 */
+  int32_t extension_step; /* 1000 */
+  int32_t merge_distance;
+  int32_t use_max_entities;
+  int32_t support_on_host;
+} impg_gpu_refine_opts_t;
+typedef struct { /* RefineRecord (refine.rs:41-53) without its strings */
+  uint32_t target_id;
+  int32_t refined_start, refined_end;
+  int32_t original_start, original_end;
+  int32_t left_extension, right_extension;
+  uint32_t support_count, original_support_count;
+} impg_gpu_refine_record_t;
+typedef struct impg_gpu_refine_run impg_gpu_refine_t;
+typedef int (*impg_gpu_rows_cb)(void *ctx, const impg_gpu_range_t *regions, size_t n, const impg_gpu_interval_t **rows,
+                                const uint64_t **offsets);
+int impg_gpu_refine(impg_gpu_index_t *, const impg_gpu_range_t *loci, size_t n, const impg_gpu_params_t *params,
+                    const impg_gpu_refine_opts_t *opts, const uint32_t *entity_of, const uint8_t *subset_keep,
+                    const uint32_t *blacklist_off, const int32_t *blacklist_ranges, impg_gpu_refine_t **out);
+int impg_gpu_refine_rows(impg_gpu_rows_cb query, void *ctx, const int64_t *seq_len, uint32_t n_seq, const impg_gpu_range_t *loci,
+                         size_t n, const impg_gpu_refine_opts_t *opts, const uint32_t *entity_of, const uint32_t *max_entities,
+                         const uint32_t *blacklist_off, const int32_t *blacklist_ranges, int device, impg_gpu_refine_t **out);
+size_t impg_gpu_refine_num_records(const impg_gpu_refine_t *);
+const impg_gpu_refine_record_t *impg_gpu_refine_records(const impg_gpu_refine_t *);
+/* The survivors of the winners (support_entities), read at the end by evaluating the n winning candidates once more:
+ * offsets[n + 1] into survivors[], ascending seq_id inside a record; owned by the object. */
+const uint64_t *impg_gpu_refine_survivor_offsets(const impg_gpu_refine_t *);
+const impg_gpu_survivor_t *impg_gpu_refine_survivors(const impg_gpu_refine_t *);
+/* passes (batches) of the run, candidates evaluated and parts the batches came back as: any may be NULL */
+void impg_gpu_refine_stats(const impg_gpu_refine_t *, uint64_t *passes, uint64_t *candidates, uint64_t *parts);
+/* impg_gpu_refine only: four doubles per batch of the run, the passes in order and then the read of the winners' survivors --
+ * candidates in the batch, wall seconds of the query call, HIP-event milliseconds of the engine inside it (stage clocks +
+ * row placement; on the routes through the host: the engine's wall milliseconds), wall seconds of the support (upload or
+ * kernels, its copies home).  *n_out = doubles there are; at most cap are written. */
+int impg_gpu_refine_batch_times(const impg_gpu_refine_t *, double *out, size_t cap, size_t *n_out);
+/* The two texts of main.rs:7817-7861: the table -- a header line, then chrom, refined start, refined end, name, original
+ * support, new support, left, right -- and the --support-output file: sequence, start, end, name per survivor, sorted by
+ * sequence name.  names[n_seq] are the sequence names; labels[i] (labels or an entry may be NULL = "") is the locus's label:
+ * blank or "." becomes chrom:start-end of the original locus.  Both malloc'ed (free() them); support_text may be NULL. */
+int impg_gpu_refine_text(const impg_gpu_refine_t *, const char *const *names, uint32_t n_seq, const char *const *labels, char **text,
+                         size_t *len, char **support_text, size_t *support_len);
+void impg_gpu_refine_free(impg_gpu_refine_t *);
+
 /* ---- synthetic workload generators (SplitMix64) ----- */
 /* Fills records / ops for `n_records` synthetic alignments (200-op CIGARs by
  * default).  Call with ops == NULL to size: *n_ops_out receives the op count. */
