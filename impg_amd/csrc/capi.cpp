@@ -647,7 +647,8 @@ const char *impg_gpu_option_key(size_t i) { return i < N_OPTIONS ? OPTION_TABLE[
 struct CounterRow { const char *key; const std::atomic<uint64_t> &(*at)(const impg_gpu_index &); };
 #define CTR(key, member) {key, [](const impg_gpu_index &ix) -> const std::atomic<uint64_t> & { return ix.member; }}
 static const CounterRow COUNTER_TABLE[] = {
-    CTR("walk_launches", walk_launches), CTR("walk_fallbacks", walk_fallbacks), CTR("walk_members", walk_last_members), CTR("small_batches", small_batches),
+    CTR("walk_launches", walk_launches), CTR("walk_fallbacks", walk_fallbacks), CTR("walk_members", walk_last_members), CTR("walk_overflow", walk_last_overflow),
+    CTR("small_batches", small_batches),
     CTR("segment_sliced_levels", seg_stats[0]), CTR("segment_retries", seg_stats[1]), CTR("segment_library_levels", seg_stats[2]),
     CTR("project_lane_levels", proj_stats[PROJ_ARM_LANE]), CTR("project_staged_levels", proj_stats[PROJ_ARM_STAGED]),
     CTR("project_staged_rows_levels", proj_stats[PROJ_ARM_STAGED_ROWS]), CTR("project_entries_slots_levels", proj_stats[PROJ_ARM_ENTRIES_SLOTS]),

@@ -277,6 +277,7 @@ bool Engine::run_walk(const impg_gpu_index &ix, const impg_gpu_range_t *d_ranges
     fprintf(stderr, "[walk] n=%u %s wg=%u members=%u slab=%.2f MB dfs=%d depth=%u overflow=0x%x (1 unknown target, 2 pairs per step, 4 visited pool, 8 piece scratch, 16 pieces, 32 stack / frontier, 128 hand-off timed out) %.3f ms\n",
             n, wide ? "wide" : "wave", n_wg, members, slab / 1048576.0, a.dfs, a.max_depth, flags[1], st ? st->ms_total : -1.0f);
   ix.walk_last_members = members;
+  ix.walk_last_overflow = flags[1];  // the cause word of this launch (0: taken), bits as in impg_gpu.h
   if (flags[1]) { ix.walk_fallbacks++; return false; }  // a query outgrew its slab: the batch engine runs the batch
   ix.walk_launches++;
   if (st) st->levels = p.max_depth;

@@ -428,7 +428,7 @@ struct impg_gpu_index {
   // a rank of a sharded index: the blocks of the rows impg_gpu_query_batch_device leaves in HBM (sharded.cpp rank_rows).  Not an
   // engine's: a handle gives its blocks back from whichever thread frees it, while the engines serve other calls.
   struct RowsPool : impg::BufPool { RowsPool() { shared = true; } } rows_pool;
-  mutable std::atomic<uint64_t> walk_launches{0}, walk_fallbacks{0}, walk_last_members{1};  // impg_gpu_get_counter
+  mutable std::atomic<uint64_t> walk_launches{0}, walk_fallbacks{0}, walk_last_members{1}, walk_last_overflow{0};  // impg_gpu_get_counter
   mutable std::atomic<uint64_t> small_batches{0};  // ... and the batches Engine::run_small answered
   // ... and how the visited updates of its batches grouped their hits: levels cut into slices, levels counted a second time
   // for one huge query, levels that went to the library sort ([0], [1], [2]; Engine::update)

@@ -559,6 +559,7 @@ __device__ __forceinline__ void walk_body(const WalkArgs &A) {
     __syncthreads();
     uint32_t level = 0;
     bool failed = S.flag != 0;
+    bool named = false;  // the failure's cause bit is in A.overflow already
     if (A.dbg && tid == 0) tmark = clock64();
     // ---- the walk -----------------------------------------------------------------------------------------------------
     while (!failed) {
@@ -632,7 +633,7 @@ __device__ __forceinline__ void walk_body(const WalkArgs &A) {
           uint32_t rows_l = 0;
           const bool fine = walk_final_level<NW, MODE>(A, q, 0u, A.members, ctl, B.wa, nw, S.rows_run, B, S.wsum, FL, cnt_l, ck_l, rows_l);
           lap(10);
-          if (!fine) { failed = true; break; }
+          if (!fine) { failed = true; named = true; break; }  // (walk_final_level has raised the cause: 2 or 128)
           if (tid == 0) { S.acc_count += cnt_l; S.acc_cksum += ck_l; S.rows_run = rows_l; S.nw = 0; }
           __syncthreads();
           break;
@@ -1018,7 +1019,7 @@ __device__ __forceinline__ void walk_body(const WalkArgs &A) {
     __syncthreads();
     if (GRID && !published) wk_publish(&ctl->state, 2u, false);  // no last level to share: the helpers leave
     if (tid == 0) {
-      if (failed) atomicOr(A.overflow, S.flag ? S.flag : 64u);  // which capacity (the host's debug line names it)
+      if (failed && !named) atomicOr(A.overflow, S.flag ? S.flag : 64u);  // which capacity (the host's debug line names it)
       if (failed && A.dbg) { A.dbg[24] = q; A.dbg[25] = S.flag; A.dbg[26] = rq.target_id; A.dbg[27] = v.n_seq; A.dbg[28] = S.nw; A.dbg[29] = S.npc; A.dbg[30] = S.vused; }
       if (A.count) A.count[q] = S.acc_count;
       if (A.cksum) A.cksum[q] = S.acc_cksum;

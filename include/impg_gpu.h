@@ -263,7 +263,11 @@ const char *impg_gpu_counter_key(size_t i);
  * answered): "walk_launches" = per-query walk launches that answered their batch (walk_device.inc: DFS batches, small
  * depth-limited BFS batches incl. masked ones -- the shape of partition.rs:359-391), "walk_fallbacks" = launches whose
  * batch the batch engine had to run again (a query outgrew its slab), "walk_members" = workgroups per query of the
- * last grid-form launch (1: not the grid form), "small_batches" = plain batches of <= 64 ranges answered by the one-chain
+ * last grid-form launch (1: not the grid form), "walk_overflow" = the cause word of the most recent walk launch (0: the
+ * launch answered its batch; otherwise the limits its queries outgrew, ORed: 1 unknown target, 2 pairs of one step / of one
+ * member's share of the last level, 4 visited pool or a mask list, 8 piece scratch, 16 pieces of one level / pop, 32 DFS
+ * stack (a BFS frontier is bounded by 16 first), 64 unnamed, 128 a grid hand-off timed out),
+ * "small_batches" = plain batches of <= 64 ranges answered by the one-chain
  * small-batch path; how the visited updates grouped their hits: "segment_sliced_levels" =
  * levels whose queries were cut into slices of their frontier ranges, "segment_retries" = levels counted a second time
  * because one query held more hits than a wave should take, "segment_library_levels" = levels that went through the
