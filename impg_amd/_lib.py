@@ -71,6 +71,7 @@ class DevicePart(C.Structure):  # impg_gpu_device_part_t
 ROWS_ATTRIBUTED, ROWS_ORDERED, ROWS_ORDERED_SLOTS = 0, 1, 2
 REGIONS_MASKED, REGIONS_MISSING = 0, 1
 SELECT_LONGEST, SELECT_TOTAL, SELECT_SAMPLE, SELECT_HAPLOTYPE = 0, 1, 2, 3
+BED_ROW_DTYPE = np.dtype([("range", "<u4"), ("query_id", "<u4"), ("start", "<i4"), ("end", "<i4"), ("strand", "<u4")])  # impg_gpu_bed_row_t
 PARTITION_ROW_DTYPE = np.dtype([("seq_id", "<u4"), ("start", "<i4"), ("end", "<i4")])  # impg_gpu_partition_row_t
 
 
@@ -239,6 +240,9 @@ SYMBOLS = [
     ("impg_synth_paf_text", C.c_int, [C.c_uint64, C.c_size_t, C.c_uint32, C.c_int32, C.c_int32, C.c_uint32, C.c_char_p]),
     ("impg_synth_skewed_paf_text", C.c_int, [C.c_uint64, C.c_size_t, C.c_uint32, C.c_int32, C.c_char_p, C.POINTER(C.c_uint64)]),
     ("impg_gpu_selftest_order_sort", C.c_int, [C.c_int, C.c_uint32, C.c_uint, C.c_uint64]),
+    ("impg_gpu_selftest_bed_rows", C.c_int, [_P, _P, _P, C.c_size_t, C.c_uint32, C.c_uint64, C.c_int32, C.c_int, C.c_int, _P, C.POINTER(_P),
+                                             C.POINTER(C.c_size_t), C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(_P), C.POINTER(_P),
+                                             C.POINTER(C.c_size_t)]),
     ("impg_synth_seq_name", C.c_int, [C.c_uint32, C.c_char_p, C.c_size_t]),
     ("impg_synth_bed", C.c_int, [C.c_uint64, C.c_size_t, C.c_uint32, C.c_int32, C.c_int32, _P]),
 ]

@@ -114,7 +114,7 @@ void merge_query_axis(std::vector<impg_gpu_interval_t> &r, int32_t merge_distanc
     const int32_t cs = std::min(cur.q_first, cur.q_last), ce = std::max(cur.q_first, cur.q_last);
     const int32_t ns = std::min(nx.q_first, nx.q_last), ne = std::max(nx.q_first, nx.q_last);
     const bool keep_apart = merge_distance < 0 || cur.query_id != nx.query_id || (!merge_strands && cf != nf) ||
-                            ns > ce + merge_distance;
+                            ns > (int32_t)((uint32_t)ce + (uint32_t)merge_distance);  // (main.rs:12523: an i32 sum, wrapping in a release build)
     if (keep_apart) {
       w++;
       if (w != k) std::swap(r[w], r[k]);

@@ -152,9 +152,10 @@ __global__ __launch_bounds__(256) void axis_run_heads_kernel(Rows R, const uint3
   bool head = seg_head[k] != 0 || merge_distance < 0;  // main.rs:12515: a negative distance keeps everything apart
   if (!head) {
     const int4 c = R.c[perm[k]];
-    const long long ns = min(c.x, c.y);
-    const long long ce = (long long)(int32_t)((uint32_t)(pmax[k - 1] & 0xFFFFFFFFull) ^ 0x80000000u);
-    head = ns > ce + merge_distance;
+    const int32_t ns = min(c.x, c.y);
+    const uint32_t ce = (uint32_t)(pmax[k - 1] & 0xFFFFFFFFull) ^ 0x80000000u;
+    // main.rs:12523 adds in i32 and the reference's release build wraps: the sum is taken unsigned and read back signed
+    head = ns > (int32_t)(ce + (uint32_t)merge_distance);
   }
   run_head[k] = head ? 1u : 0u;
 }
@@ -276,30 +277,16 @@ __global__ __launch_bounds__(256) void text_write_kernel(const BedRow *__restric
   *p++ = '\n';
 }
 
-// Rows of one chunk -> merged BED rows, left on the device in `out` (grouped by range, in output order); returns
-// their number.  levels / self_dev: what Engine::run kept for the chunk.
-uint32_t device_bed_rows(Engine &E, const impg_gpu_index &ix, uint32_t n_ranges, const impg_gpu_params_t &p, int32_t merge_distance,
-                         std::vector<std::unique_ptr<LevelBufs>> &levels, DevBuf &self_dev, DevBuf &out) {
+// Scattered rows -> merged BED rows, left on the device in `out` (grouped by range, in output order); returns their
+// number.  R: n rows numbered in emission order (within a range: the reference's; rows of different ranges may
+// interleave), ids < n_seq, range indices < n_ranges.  Counts into the handle's bed_* counters.  gap (diagnostics):
+// the rows between the two merges, copied to the host in their order -- a chain stands where its first row stood.
+static uint32_t merge_rows(Engine &E, const impg_gpu_index &ix, Rows R, uint32_t n, uint64_t n_seq, uint32_t n_ranges, int32_t merge_distance,
+                           bool merge_strands, DevBuf &out, BedGapRows *gap = nullptr) {
   hipStream_t s = E.stream;
-  const bool merge_strands = p.consider_strandness == 0;
-  // ---- rows: range-major, the reference's emission order within a range (rows_device.hip) ---------------------------
-  uint32_t n = 0;
-  DevBuf rq, rqid, rtid, rc;
-  Rows R{nullptr, nullptr, nullptr, nullptr};
-  {
-    RowPlan pl;  // (its tables go back to the pool at the end of this block, before the sorts take their memory)
-    plan_rows(E, n_ranges, p, levels, self_dev, /*plain_retain=*/true, pl);
-    n = pl.n_rows;
-    if (!n) return 0;
-    rq.reserve((size_t)n * 4); rqid.reserve((size_t)n * 4); rtid.reserve((size_t)n * 4); rc.reserve((size_t)n * 16);
-    R = Rows{rq.as<uint32_t>(), rqid.as<uint32_t>(), rtid.as<uint32_t>(), rc.as<int4>()};
-    scatter_rows(E, levels, pl, RowSinks{nullptr, R.q, R.qid, R.tid, R.c, nullptr});
-    IMPG_HIP(hipStreamSynchronize(s));
-  }
-  // the levels' slots are not needed any more: give their memory back before the sorts take theirs
-  levels.clear();
-  const unsigned seq_bits = bits_for(ix.view.n_seq), q_bits = bits_for(n_ranges);
-  if (q_bits + 2 * seq_bits + 1 > 64) throw Error{IMPG_E_UNSUPPORTED, "too many sequences for the device-side BED merge (use impg_gpu_results_bed)"};
+  const unsigned seq_bits = bits_for(n_seq), q_bits = bits_for(n_ranges);
+  // (with no merge at all the rows are only grouped by range: no key holds a sequence id)
+  if ((merge_distance >= 0 || merge_strands) && q_bits + 2 * seq_bits + 1 > 64) throw Error{IMPG_E_UNSUPPORTED, "too many sequences for the device-side BED merge (use impg_gpu_results_bed)"};
   DevBuf k32a, k32b, k64a, k64b, ia, ib, tmp;
   const size_t nb4 = (size_t)n * 4, nb8 = (size_t)n * 8;
   k32a.reserve(nb4); k32b.reserve(nb4); k64a.reserve(nb8); k64b.reserve(nb8); ia.reserve(nb4); ib.reserve(nb4);
@@ -319,13 +306,25 @@ uint32_t device_bed_rows(Engine &E, const impg_gpu_index &ix, uint32_t n_ranges,
     parent.reserve(nb4); box.reserve((size_t)n * 16); root_flag.reserve(nb4); root_pos.reserve(nb4);
     prims::iota_kernel<<<cdiv(n, 256), 256, 0, s>>>(parent.as<uint32_t>(), n);
     gap_link_kernel<<<cdiv(n, 256), 256, 0, s>>>(R, ia.as<uint32_t>(), k64a.as<unsigned long long>(), n, merge_distance, parent.as<uint32_t>());
-    IMPG_HIP(hipMemcpyAsync(box.p, rc.p, (size_t)n * 16, hipMemcpyDeviceToDevice, s));
+    IMPG_HIP(hipMemcpyAsync(box.p, R.c, (size_t)n * 16, hipMemcpyDeviceToDevice, s));
     gap_box_kernel<<<cdiv(n, 256), 256, 0, s>>>(R, n, parent.as<uint32_t>(), box.as<int4>(), root_flag.as<uint32_t>());
     m = (uint32_t)E.scan(root_flag.as<uint32_t>(), root_pos.as<uint32_t>(), n);
     rq2.reserve((size_t)m * 4 + 256); rqid2.reserve((size_t)m * 4 + 256); rtid2.reserve((size_t)m * 4 + 256); rc2.reserve((size_t)m * 16 + 256);
     Rows R2{rq2.as<uint32_t>(), rqid2.as<uint32_t>(), rtid2.as<uint32_t>(), rc2.as<int4>()};
     compact_rows_kernel<<<cdiv(n, 256), 256, 0, s>>>(R, box.as<int4>(), n, root_flag.as<uint32_t>(), root_pos.as<uint32_t>(), R2);
     cur = R2;
+  }
+  if (gap) {
+    std::vector<uint32_t> hq(m), hqid(m), htid(m);
+    std::vector<int4> hc(m);
+    IMPG_HIP(hipMemcpyAsync(hq.data(), cur.q, (size_t)m * 4, hipMemcpyDeviceToHost, s));
+    IMPG_HIP(hipMemcpyAsync(hqid.data(), cur.qid, (size_t)m * 4, hipMemcpyDeviceToHost, s));
+    IMPG_HIP(hipMemcpyAsync(htid.data(), cur.tid, (size_t)m * 4, hipMemcpyDeviceToHost, s));
+    IMPG_HIP(hipMemcpyAsync(hc.data(), cur.c, (size_t)m * 16, hipMemcpyDeviceToHost, s));
+    IMPG_HIP(hipStreamSynchronize(s));
+    gap->range = hq;
+    gap->rows.resize(m);
+    for (uint32_t i = 0; i < m; i++) gap->rows[i] = impg_gpu_interval_t{hqid[i], hc[i].x, hc[i].y, htid[i], hc[i].z, hc[i].w};
   }
   // ---- query axis ----------------------------------------------------------------------------------------------------
   DevBuf strand_key, seg_head, seg_id, val, pmax, run_head, run_pos;
@@ -392,11 +391,68 @@ uint32_t device_bed_rows(Engine &E, const impg_gpu_index &ix, uint32_t n_ranges,
     axis_strand_kernel<<<cdiv(n_runs, 256), 256, 0, s>>>(out.as<BedRow>(), strand_key.as<uint32_t>(), n_runs);
   }
   IMPG_HIP(hipStreamSynchronize(s));  // (the scratch buffers of this function die here)
+  ix.bed_stats[BED_ROWS] += n;
+  ix.bed_stats[BED_GAP_ROOTS] += m;
+  ix.bed_stats[BED_RUNS] += n_runs;
   return n_runs;
 }
 
-// The merged rows of a chunk as text, streamed to `sink(ptr, bytes)` in pieces of at most PIECE bytes through two
-// pinned buffers: while the host consumes one piece the device formats and copies the next.
+// Rows of one chunk -> merged BED rows (merge_rows).  levels / self_dev: what Engine::run kept for the chunk.
+uint32_t device_bed_rows(Engine &E, const impg_gpu_index &ix, uint32_t n_ranges, const impg_gpu_params_t &p, int32_t merge_distance,
+                         std::vector<std::unique_ptr<LevelBufs>> &levels, DevBuf &self_dev, DevBuf &out) {
+  hipStream_t s = E.stream;
+  // ---- rows: range-major, the reference's emission order within a range (rows_device.hip) ---------------------------
+  uint32_t n = 0;
+  DevBuf rq, rqid, rtid, rc;
+  Rows R{nullptr, nullptr, nullptr, nullptr};
+  {
+    RowPlan pl;  // (its tables go back to the pool at the end of this block, before the sorts take their memory)
+    plan_rows(E, n_ranges, p, levels, self_dev, /*plain_retain=*/true, pl);
+    n = pl.n_rows;
+    if (!n) return 0;
+    rq.reserve((size_t)n * 4); rqid.reserve((size_t)n * 4); rtid.reserve((size_t)n * 4); rc.reserve((size_t)n * 16);
+    R = Rows{rq.as<uint32_t>(), rqid.as<uint32_t>(), rtid.as<uint32_t>(), rc.as<int4>()};
+    scatter_rows(E, levels, pl, RowSinks{nullptr, R.q, R.qid, R.tid, R.c, nullptr});
+    IMPG_HIP(hipStreamSynchronize(s));
+  }
+  // the levels' slots are not needed any more: give their memory back before the sorts take theirs
+  levels.clear();
+  return merge_rows(E, ix, R, n, ix.view.n_seq, n_ranges, merge_distance, p.consider_strandness == 0, out);
+}
+
+// The merge and the text on rows the caller brings (impg_gpu_selftest_bed_rows): uploaded as they are, then merge_rows
+// and device_bed_text as a chunk of a query runs them.  merged: the rows as the device left them; text: appended to.
+void device_bed_selftest(Engine &E, const impg_gpu_index &ix, const impg_gpu_interval_t *rows, const uint32_t *row_range, uint32_t n,
+                         uint32_t n_ranges, uint64_t n_seq, int32_t merge_distance, bool merge_strands, bool original_coords,
+                         const std::vector<std::string> &rnames, std::vector<impg_gpu_bed_row_t> &merged, std::string &text, BedGapRows *gap) {
+  merged.clear();
+  if (!n) return;
+  hipStream_t s = E.stream;
+  std::vector<uint32_t> qid(n), tid(n);
+  std::vector<int4> c(n);
+  for (uint32_t i = 0; i < n; i++) {
+    qid[i] = rows[i].query_id; tid[i] = rows[i].target_id;
+    c[i] = int4{rows[i].q_first, rows[i].q_last, rows[i].t_first, rows[i].t_last};
+  }
+  DevBuf rq, rqid, rtid, rc, out;
+  rq.reserve((size_t)n * 4); rqid.reserve((size_t)n * 4); rtid.reserve((size_t)n * 4); rc.reserve((size_t)n * 16);
+  IMPG_HIP(hipMemsetAsync(E.counters.p, 0, 64, s));  // (as a run starts: Engine::scan reads its bad-range flag)
+  IMPG_HIP(hipMemcpyAsync(rq.p, row_range, (size_t)n * 4, hipMemcpyHostToDevice, s));
+  IMPG_HIP(hipMemcpyAsync(rqid.p, qid.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+  IMPG_HIP(hipMemcpyAsync(rtid.p, tid.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+  IMPG_HIP(hipMemcpyAsync(rc.p, c.data(), (size_t)n * 16, hipMemcpyHostToDevice, s));
+  IMPG_HIP(hipStreamSynchronize(s));
+  const uint32_t n_runs = merge_rows(E, ix, Rows{rq.as<uint32_t>(), rqid.as<uint32_t>(), rtid.as<uint32_t>(), rc.as<int4>()}, n, n_seq, n_ranges,
+                                     merge_distance, merge_strands, out, gap);
+  std::vector<BedRow> h(n_runs);
+  if (n_runs) IMPG_HIP(hipMemcpy(h.data(), out.p, (size_t)n_runs * sizeof(BedRow), hipMemcpyDeviceToHost));
+  merged.resize(n_runs);
+  for (uint32_t r = 0; r < n_runs; r++) merged[r] = impg_gpu_bed_row_t{h[r].q_strand & 0x7FFFFFFFu, h[r].query_id, h[r].start, h[r].end, h[r].q_strand >> 31};
+  device_bed_text(E, ix, out, n_runs, n_ranges, rnames, original_coords, [&](const char *p, size_t k) { text.append(p, k); });
+}
+
+// The merged rows of a chunk as text, streamed to `sink(ptr, bytes)` in pieces of at most PIECE bytes (option
+// bed_text_piece_bytes) through two pinned buffers: while the host consumes one piece the device formats and copies the next.
 void device_bed_text(Engine &E, const impg_gpu_index &ix, const DevBuf &rows, uint32_t n_rows, uint32_t n_ranges,
                      const std::vector<std::string> &rnames, bool original_coords,
                      const std::function<void(const char *, size_t)> &sink) {
@@ -426,17 +482,21 @@ void device_bed_text(Engine &E, const impg_gpu_index &ix, const DevBuf &rows, ui
   text_len_kernel<<<cdiv(n_rows, 256), 256, 0, s>>>(rows.as<BedRow>(), n_rows, t, len.as<uint32_t>());
   prims::exclusive_sum(stmp, len.as<uint32_t>(), off.as<unsigned long long>(), n_rows, s);
   // piece boundaries: whole rows, at most PIECE bytes each; found on the host from a sampled copy of the offsets
-  constexpr size_t PIECE = 256ull << 20;
+  const unsigned long long PIECE = (unsigned long long)E.opt.bed_text_piece_bytes;
   std::vector<unsigned long long> h_off(n_rows);
   IMPG_HIP(hipMemcpyAsync(h_off.data(), off.p, (size_t)n_rows * 8, hipMemcpyDeviceToHost, s));
   uint32_t last_len = 0;
   IMPG_HIP(hipMemcpyAsync(&last_len, len.as<uint32_t>() + (n_rows - 1), 4, hipMemcpyDeviceToHost, s));
   IMPG_HIP(hipStreamSynchronize(s));
   const unsigned long long total = h_off[n_rows - 1] + last_len;
+  const size_t cap = (size_t)std::min<unsigned long long>(total, PIECE) + 4096;
+  // a piece holds whole rows; only a piece of one row can outgrow PIECE, and it must still fit the buffer.  Refused
+  // here, with nothing queued and no pinned buffer in flight.
+  for (uint32_t r = 0; r < n_rows; r++)
+    if ((r + 1 < n_rows ? h_off[r + 1] : total) - h_off[r] > cap) throw Error{IMPG_E_UNSUPPORTED, "a single BED row longer than the text buffer"};
   DevBuf piece[2];
   char *pin[2] = {nullptr, nullptr};
   struct Unpin { char **p; ~Unpin() { for (int k = 0; k < 2; k++) if (p[k]) (void)hipHostFree(p[k]); } } unpin{pin};
-  const size_t cap = (size_t)std::min<unsigned long long>(total, PIECE) + 4096;
   for (int k = 0; k < 2; k++) { piece[k].reserve(cap); IMPG_HIP(hipHostMalloc((void **)&pin[k], cap, hipHostMallocDefault)); }
   hipEvent_t done[2];
   for (int k = 0; k < 2; k++) IMPG_HIP(hipEventCreateWithFlags(&done[k], hipEventDisableTiming));
@@ -452,11 +512,12 @@ void device_bed_text(Engine &E, const impg_gpu_index &ix, const DevBuf &rows, ui
       if (r1 == n_rows) { if (total - base > PIECE && n_rows - 1 > r0) r1 = n_rows - 1; }
       else r1 = std::max(r1 - 1, r0 + 1);
       const unsigned long long end = r1 < n_rows ? h_off[r1] : total;
-      if (end - base > cap) throw Error{IMPG_E_UNSUPPORTED, "a single BED row longer than the text buffer"};
       text_write_kernel<<<cdiv(r1 - r0, 256), 256, 0, s>>>(rows.as<BedRow>() + r0, r1 - r0, t, off.as<unsigned long long>() + r0, base, piece[slot].as<char>());
       IMPG_HIP(hipMemcpyAsync(pin[slot], piece[slot].p, (size_t)(end - base), hipMemcpyDeviceToHost, s));
       IMPG_HIP(hipEventRecord(done[slot], s));
       pend[slot] = {(size_t)(end - base), true};
+      ix.bed_stats[BED_TEXT_PIECES]++;
+      ix.bed_stats[BED_TEXT_BYTES] += end - base;
       r0 = r1;
     }
     // consume the OTHER slot's piece while this one is in flight (or drain at the end)

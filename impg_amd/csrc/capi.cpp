@@ -663,6 +663,8 @@ static const CounterRow COUNTER_TABLE[] = {
     CTR("refine_passes", refine_stats[REFINE_PASSES]), CTR("refine_candidates", refine_stats[REFINE_CANDIDATES]),
     CTR("refine_parts", refine_stats[REFINE_PARTS]), CTR("refine_rows_to_host", refine_stats[REFINE_ROWS_TO_HOST]),
     CTR("refine_longest_group", refine_stats[REFINE_LONGEST_GROUP]),
+    CTR("bed_rows", bed_stats[BED_ROWS]), CTR("bed_gap_roots", bed_stats[BED_GAP_ROOTS]), CTR("bed_runs", bed_stats[BED_RUNS]),
+    CTR("bed_text_pieces", bed_stats[BED_TEXT_PIECES]), CTR("bed_text_bytes", bed_stats[BED_TEXT_BYTES]),
 };
 #undef CTR
 constexpr size_t N_COUNTERS = sizeof(COUNTER_TABLE) / sizeof(COUNTER_TABLE[0]);
@@ -1288,6 +1290,7 @@ void bed_batch(impg_gpu_index_t *ix, const impg_gpu_range_t *ranges, size_t n, c
   IMPG_HIP(hipSetDevice(ix->device));
   EngineLease lease(*ix);
   Engine &E = *lease;
+  ix->bed_stats_reset();
   apply_subset(E, *ix, subset_keep);
   const impg_gpu_range_t *d_ranges = upload_ranges(E.ranges_dev, ranges, n, &E.stream);
   double t3[3] = {0, 0, 0};  // engine, merge, text
@@ -1354,6 +1357,50 @@ int impg_gpu_results_paf(const impg_gpu_results_t *res, const impg_gpu_index_t *
   std::vector<std::string> parts;
   render_paf(*res, *ix, range_names, *params, merge_distance, format == IMPG_OUT_BEDPE, parts);
   *text = join_parts(parts, len);
+  return IMPG_OK;
+  IMPG_CATCH
+}
+
+// The device BED merge and text on rows the caller brings (diagnostics; tests/test_gpu_bed_device.py): what a chunk of
+// impg_gpu_query_batch_bed runs once its rows are placed (bed_device.hip), without a query in front of it.
+int impg_gpu_selftest_bed_rows(impg_gpu_index_t *ix, const impg_gpu_interval_t *rows, const uint32_t *row_range, size_t n_rows,
+                               uint32_t n_ranges, uint64_t n_seq, int32_t merge_distance, int merge_strands, int original_sequence_coordinates,
+                               const char *const *range_names, impg_gpu_bed_row_t **merged_out, size_t *n_merged, char **text, size_t *len,
+                               impg_gpu_interval_t **gap_rows_out, uint32_t **gap_range_out, size_t *n_gap) {
+  IMPG_TRY
+  if (!ix || !merged_out || !n_merged || !text || !len || (n_rows && (!rows || !row_range))) throw Error{IMPG_E_INVALID, "null argument"};
+  const bool want_gap = gap_rows_out || gap_range_out || n_gap;
+  if (want_gap && !(gap_rows_out && gap_range_out && n_gap)) throw Error{IMPG_E_INVALID, "the gap outputs come together"};
+  if (ix->shard || ix->cluster) throw Error{IMPG_E_INVALID, "impg_gpu_selftest_bed_rows takes a single-GPU handle"};
+  if (n_rows >= 0xFFFFFFF0ull) throw Error{IMPG_E_INVALID, "too many rows"};
+  n_seq = std::min<uint64_t>(n_seq, 1ull << 32);  // (ids are 32 bits wide)
+  for (size_t i = 0; i < n_rows; i++) {
+    if (rows[i].query_id >= n_seq || rows[i].target_id >= n_seq) throw Error{IMPG_E_INVALID, "a row's sequence id is not below n_seq"};
+    if (row_range[i] >= n_ranges) throw Error{IMPG_E_INVALID, "a row's range index is not below n_ranges"};
+  }
+  std::vector<std::string> rnames(n_ranges);
+  for (uint32_t q = 0; q < n_ranges; q++) rnames[q] = range_names && range_names[q] ? std::string(range_names[q]) : std::to_string(q);
+  IMPG_HIP(hipSetDevice(ix->device));
+  EngineLease lease(*ix);
+  ix->bed_stats_reset();
+  std::vector<impg_gpu_bed_row_t> merged;
+  std::string out;
+  BedGapRows gap;
+  device_bed_selftest(*lease, *ix, rows, row_range, (uint32_t)n_rows, n_ranges, n_seq, merge_distance, merge_strands != 0,
+                      original_sequence_coordinates != 0, rnames, merged, out, want_gap ? &gap : nullptr);
+  impg_gpu_bed_row_t *m = (impg_gpu_bed_row_t *)malloc(std::max<size_t>(merged.size(), 1) * sizeof(impg_gpu_bed_row_t));
+  char *t = (char *)malloc(out.size() + 1);
+  impg_gpu_interval_t *gr = want_gap ? (impg_gpu_interval_t *)malloc(std::max<size_t>(gap.rows.size(), 1) * sizeof(impg_gpu_interval_t)) : nullptr;
+  uint32_t *gq = want_gap ? (uint32_t *)malloc(std::max<size_t>(gap.range.size(), 1) * 4) : nullptr;
+  if (!m || !t || (want_gap && (!gr || !gq))) { free(m); free(t); free(gr); free(gq); throw Error{IMPG_E_OOM, "host out of memory"}; }
+  if (want_gap) {
+    if (!gap.rows.empty()) { memcpy(gr, gap.rows.data(), gap.rows.size() * sizeof(impg_gpu_interval_t)); memcpy(gq, gap.range.data(), gap.range.size() * 4); }
+    *gap_rows_out = gr; *gap_range_out = gq; *n_gap = gap.rows.size();
+  }
+  if (!merged.empty()) memcpy(m, merged.data(), merged.size() * sizeof(impg_gpu_bed_row_t));
+  memcpy(t, out.data(), out.size());
+  t[out.size()] = 0;
+  *merged_out = m; *n_merged = merged.size(); *text = t; *len = out.size();
   return IMPG_OK;
   IMPG_CATCH
 }

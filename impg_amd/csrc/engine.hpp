@@ -377,6 +377,11 @@ uint32_t device_bed_rows(Engine &E, const impg_gpu_index &ix, uint32_t n_ranges,
 void device_bed_text(Engine &E, const impg_gpu_index &ix, const DevBuf &rows, uint32_t n_rows, uint32_t n_ranges,
                      const std::vector<std::string> &rnames, bool original_coords,
                      const std::function<void(const char *, size_t)> &sink);
+// the diagnostic entry's device part: the caller's rows through the same merge and text (impg_gpu_selftest_bed_rows)
+struct BedGapRows { std::vector<uint32_t> range; std::vector<impg_gpu_interval_t> rows; };  // the rows between the two merges, in their order
+void device_bed_selftest(Engine &E, const impg_gpu_index &ix, const impg_gpu_interval_t *rows, const uint32_t *row_range, uint32_t n,
+                         uint32_t n_ranges, uint64_t n_seq, int32_t merge_distance, bool merge_strands, bool original_coords,
+                         const std::vector<std::string> &rnames, std::vector<impg_gpu_bed_row_t> &merged, std::string &text, BedGapRows *gap);
 // the names BED rows print for ranges [b, e): the caller's, else "{chrom}:{start}-{end}" (partition.rs:1741, :1762)
 std::vector<std::string> bed_range_names(const impg_gpu_index &ix, const impg_gpu_range_t *ranges, const char *const *range_names,
                                          size_t b, size_t e);

@@ -381,6 +381,7 @@ inline uint32_t put_original_name(std::string &s, const std::string &name, bool 
 }
 
 // ---- BED (bed.cpp) -----------------------------------------------------------
+enum BedStat { BED_ROWS, BED_GAP_ROOTS, BED_RUNS, BED_TEXT_PIECES, BED_TEXT_BYTES };  // impg_gpu_index::bed_stats
 size_t bed_merge(impg_gpu_interval_t *iv, size_t n, int32_t merge_distance, bool merge_strands);
 
 struct Engine;    // engine.hpp
@@ -444,6 +445,10 @@ struct impg_gpu_index {
   mutable std::atomic<uint64_t> lk_stats[5] = {};
   // ... and what the refine runs on the handle did (by impg::RefineStat; refine.cpp)
   mutable std::atomic<uint64_t> refine_stats[5] = {};
+  // ... and the last device BED call on the handle (by impg::BedStat; bed_device.hip): set to zero when a call starts, added
+  // to by each of its chunks.  On a multi-GPU handle the ranks' handles count, not the front.
+  mutable std::atomic<uint64_t> bed_stats[5] = {};
+  void bed_stats_reset() const { for (auto &b : bed_stats) b = 0; }
   impg::ShardCtx *shard = nullptr;    // set: this index is one rank's shard; queries are collective calls
   impg::Cluster *cluster = nullptr;   // set: this handle fronts n_dev shards in this process (no arrays of its own)
   impg_gpu_index();

@@ -700,6 +700,7 @@ void rank_bed(impg_gpu_index &ix, const impg_gpu_range_t *ranges, size_t n, cons
   const impg_gpu_range_t *dr = upload_ranges(d_ranges, ranges, n, nullptr);
   const size_t chunk = shard_chunk(ix, n);
   chunks_out.assign((n + chunk - 1) / chunk + 1, std::string());
+  ix.bed_stats_reset();
   std::mutex tm;
   double t3[3] = {0, 0, 0};
   run_lanes(ix, n, [&](Engine &E) { apply_subset(E, ix, subset_keep); }, [&](size_t, Engine &E, size_t b, size_t e) {

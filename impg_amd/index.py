@@ -572,6 +572,41 @@ class GpuImpg:
         out = out if raw else out.decode()
         return (out, list(sec)) if timing else out
 
+    def bed_rows(self, rows, row_range, n_ranges, n_seq, merge_distance=0, merge_strands=True, original_sequence_coordinates=False,
+                 range_names=None, gap=False):
+        """impg_gpu_selftest_bed_rows (diagnostics): the device BED merges and text of query_batch_bed on the caller's
+        rows (INTERVAL_DTYPE; row_range[i] = the range of rows[i]).  Returns (merged rows as BED_ROW_DTYPE, text bytes);
+        gap=True: also (the rows between the two merges as INTERVAL_DTYPE, their ranges), in their order."""
+        a = np.ascontiguousarray(rows, dtype=INTERVAL_DTYPE)
+        rr = np.ascontiguousarray(row_range, dtype=np.uint32)
+        if a.size != rr.size:
+            raise _lib.ImpgGpuError(_lib.IMPG_E_INVALID, "one range index per row")
+        arr = None
+        if range_names is not None:
+            if len(range_names) != n_ranges:
+                raise _lib.ImpgGpuError(_lib.IMPG_E_INVALID, "one name per range")
+            arr = (C.c_char_p * len(range_names))(*[None if s is None else (s if isinstance(s, bytes) else s.encode()) for s in range_names])
+        merged, text = C.c_void_p(None), C.c_void_p(None)
+        nm, ln = C.c_size_t(0), C.c_size_t(0)
+        grows, grange, ng = C.c_void_p(None), C.c_void_p(None), C.c_size_t(0)
+        check(lib().impg_gpu_selftest_bed_rows(self._h, a.ctypes.data, rr.ctypes.data, a.size, n_ranges, n_seq, merge_distance,
+                                               int(bool(merge_strands)), int(bool(original_sequence_coordinates)), arr,
+                                               C.byref(merged), C.byref(nm), C.byref(text), C.byref(ln),
+                                               C.byref(grows) if gap else None, C.byref(grange) if gap else None, C.byref(ng) if gap else None))
+        try:
+            out = np.frombuffer(C.string_at(merged, nm.value * _lib.BED_ROW_DTYPE.itemsize), dtype=_lib.BED_ROW_DTYPE).copy()
+            txt = C.string_at(text, ln.value)
+            if gap:
+                gr = np.frombuffer(C.string_at(grows, ng.value * INTERVAL_DTYPE.itemsize), dtype=INTERVAL_DTYPE).copy()
+                gq = np.frombuffer(C.string_at(grange, ng.value * 4), dtype=np.uint32).copy()
+        finally:
+            _lib.free(merged)
+            _lib.free(text)
+            if gap:
+                _lib.free(grows)
+                _lib.free(grange)
+        return (out, txt, gr, gq) if gap else (out, txt)
+
     def approximate(self):
         """True for an index built from tracepoints (every answer is the reference's approximate mode)."""
         return bool(lib().impg_gpu_index_approximate(self._h))

@@ -244,7 +244,9 @@ int impg_gpu_index_approximate(const impg_gpu_index_t *);
  * the default, 1 always, 2 long groups; results identical), "device_rows_pool_bytes" (HBM kept between
  * impg_gpu_query_batch_device calls: freed slot arrays, reused by the next call; 160 GiB by default),
  * "update_stats" / "lookup_stats" (0, the default; 1: the "update_*" / "lookup_wide_*" counters below are kept, one small
- * copy per level).  For tests of the multi-rank paths: "lane_schedule" (forced lane start / hand-over order of a sharded
+ * copy per level), "bed_text_piece_bytes" (64 .. 2^40; 256 MiB by default: the text of impg_gpu_query_batch_bed crosses
+ * PCIe in pieces of whole rows of at most this many bytes, a piece of one row may be up to 4096 bytes longer; a row
+ * beyond that is IMPG_E_UNSUPPORTED; the text is identical for every value).  For tests of the multi-rank paths: "lane_schedule" (forced lane start / hand-over order of a sharded
  * batch; 0 = off), "debug_fail_owner" / "debug_fail_home" (failure injection: (rank + 1) << 16 | hop of the batch at which
  * that rank throws on the owner / on the home side of the hop; 0 = off).
  * A multi-GPU handle hands "chunk_ranges", "pair_budget", "locality_min", "debug_fail_owner", "debug_fail_home",
@@ -281,7 +283,11 @@ const char *impg_gpu_counter_key(size_t i);
  * "lookup_stats" = 1 (0, the default: nothing is copied or counted) every level's lookup counts its windows of more than 64
  * entries: "lookup_wide_windows" (all of them), "lookup_wide_single" (hits sorted in one pass), "lookup_wide_grouped" (hits
  * split into groups of rank bins), "lookup_wide_group_passes" (the passes those took), "lookup_wide_overflow" (one rank bin
- * alone beyond the buffer: handed to the wave-per-range kernel). */
+ * alone beyond the buffer: handed to the wave-per-range kernel).  Of the last device BED call on the handle
+ * (impg_gpu_query_batch_bed, impg_gpu_query_batch_bed_fd, impg_gpu_selftest_bed_rows; zero when it starts, every chunk adds;
+ * on a multi-GPU handle its ranks count, not the handle): "bed_rows" = rows entering the merges, "bed_gap_roots" = rows
+ * after merge_adjusted_intervals_gap_2d, "bed_runs" = merged rows out, "bed_text_pieces" = text pieces sent to the host,
+ * "bed_text_bytes" = bytes printed. */
 int impg_gpu_get_counter(const impg_gpu_index_t *, const char *key, int64_t *value_out);
 /* Large result arrays live in pinned host blocks that are recycled through a process-wide pool (at most
  * IMPG_PINNED_POOL_BYTES, default 6 GiB, are kept when results are freed).  Gives pooled blocks back to the system
@@ -867,6 +873,28 @@ int impg_synth_bed(uint64_t seed, size_t n, uint32_t n_seq, int32_t seq_len, int
  * pseudo-random keys of `end_bit` bits on `device` and checked on the host: a permutation, keys non-decreasing, equal keys
  * in index order.  IMPG_OK or IMPG_E_INVALID with the first offending place in impg_gpu_last_error(). */
 int impg_gpu_selftest_order_sort(int device, uint32_t n, unsigned end_bit, uint64_t seed);
+/* Diagnostics: the device BED merges and text of impg_gpu_query_batch_bed (impg_amd/csrc/bed_device.hip) on rows the
+ * caller brings instead of a query's.  rows[i] belongs to range row_range[i] < n_ranges; array order within a range is
+ * the emission order the reference's tie rules refer to, rows of different ranges may interleave.  n_seq: the id
+ * universe of rows[].query_id / target_id -- it may exceed the handle's; an id the handle has no name for prints as a
+ * decimal.  The handle (single-GPU) gives the device, an engine and the sequence names.  range_names: n_ranges strings,
+ * or NULL / a NULL entry = the range's index in decimal.  merged_out: the merged rows in output order (grouped by
+ * range), text: what they print, NUL-terminated; both malloc'ed, free() them.  gap_rows_out / gap_range_out / n_gap
+ * (all three or all NULL): the rows between the two merges with their ranges, in the order the second merge meets them
+ * -- a chain of merge_adjusted_intervals_gap_2d stands where its first row stood; malloc'ed.  IMPG_E_INVALID: an id >= n_seq, a range
+ * index >= n_ranges, a sharded or multi-GPU handle; IMPG_E_UNSUPPORTED as impg_gpu_query_batch_bed (a row longer than
+ * the text buffer; bits(n_ranges) + 2 * bits(n_seq) + 1 > 64, the merges' sort key -- not with merge_distance < 0 and
+ * merge_strands = 0, where nothing merges and no key holds a sequence id: n_seq may then be 2^32). */
+typedef struct {
+  uint32_t range, query_id;
+  int32_t start, end; /* printed as u32 */
+  uint32_t strand;    /* 0 '+', 1 '-' */
+} impg_gpu_bed_row_t;
+int impg_gpu_selftest_bed_rows(impg_gpu_index_t *ix, const impg_gpu_interval_t *rows, const uint32_t *row_range, size_t n_rows,
+                               uint32_t n_ranges, uint64_t n_seq, int32_t merge_distance, int merge_strands,
+                               int original_sequence_coordinates, const char *const *range_names,
+                               impg_gpu_bed_row_t **merged_out, size_t *n_merged, char **text, size_t *len,
+                               impg_gpu_interval_t **gap_rows_out, uint32_t **gap_range_out, size_t *n_gap);
 
 #ifdef __cplusplus
 }

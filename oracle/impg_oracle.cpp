@@ -1225,7 +1225,9 @@ void merge_query_adjusted_intervals(std::vector<oracle_interval_t> &results, int
     int32_t curr_start = curr_is_forward ? curr.q_first : curr.q_last, curr_end = curr_is_forward ? curr.q_last : curr.q_first;
     int32_t next_start = next_is_forward ? next.q_first : next.q_last, next_end = next_is_forward ? next.q_last : next.q_first;
     if (merge_distance < 0 || curr.query_id != next.query_id ||
-        (!merge_strands && curr_is_forward != next_is_forward) || next_start > curr_end + merge_distance) {
+        (!merge_strands && curr_is_forward != next_is_forward) ||
+        /* main.rs:12523: an i32 sum; the reference's release build wraps, so the sum is taken unsigned and read back signed */
+        next_start > (int32_t)((uint32_t)curr_end + (uint32_t)merge_distance)) {
       write_idx += 1;
       if (write_idx != read_idx) std::swap(results[write_idx], results[read_idx]);
     } else {
@@ -2132,6 +2134,14 @@ long oracle_bed_merge(oracle_interval_t *iv, size_t n, int32_t merge_distance, i
    * because store_cigar=false (main.rs:7447) */
   merge_adjusted_intervals_gap_2d(v, merge_distance);
   merge_query_adjusted_intervals(v, merge_distance, merge_strands != 0);
+  std::copy(v.begin(), v.end(), iv);
+  return (long)v.size();
+}
+
+/* merge_adjusted_intervals_gap_2d alone (main.rs:12858-13011): the first of the two BED merges */
+long oracle_merge_gap_2d(oracle_interval_t *iv, size_t n, int32_t merge_distance) {
+  std::vector<oracle_interval_t> v(iv, iv + n);
+  merge_adjusted_intervals_gap_2d(v, merge_distance);
   std::copy(v.begin(), v.end(), iv);
   return (long)v.size();
 }

@@ -186,6 +186,8 @@ uint64_t oracle_last_projection_count(void);
  * Returns the new count. */
 long oracle_bed_merge(oracle_interval_t *iv, size_t n, int32_t merge_distance,
                       int merge_strands);
+/* merge_adjusted_intervals_gap_2d alone (main.rs:12858-13011) */
+long oracle_merge_gap_2d(oracle_interval_t *iv, size_t n, int32_t merge_distance);
 /* merge_query_adjusted_intervals alone (main.rs:12474-12560) */
 long oracle_merge_query(oracle_interval_t *iv, size_t n, int32_t merge_distance,
                         int merge_strands);

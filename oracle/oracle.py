@@ -441,6 +441,15 @@ def merge_query(intervals, merge_distance, merge_strands=True):
     return a[:n].copy()
 
 
+def merge_gap_2d(intervals, merge_distance):
+    a = np.ascontiguousarray(intervals, dtype=INTERVAL_DTYPE).copy()
+    f = lib().oracle_merge_gap_2d
+    f.restype = C.c_long
+    f.argtypes = [C.c_void_p, C.c_size_t, C.c_int32]
+    n = f(a.ctypes.data, a.size, merge_distance)
+    return a[:n].copy()
+
+
 def bed_merge(intervals, merge_distance, merge_strands=True):
     a = np.ascontiguousarray(intervals, dtype=INTERVAL_DTYPE).copy()
     n = lib().oracle_bed_merge(a.ctypes.data, a.size, merge_distance, int(merge_strands))

@@ -18,7 +18,7 @@ RANGED = [("pair_budget", 1024, 0xFFFFFFF0 - 1), ("chunk_ranges", 0, 2 ** 31 - 1
           ("device_rows_pool_bytes", 0, None), ("walk_kernel", 0, 2), ("segment_parts", 0, 4096), ("walk_members", 0, 64),
           ("filter_covered", 0, 2), ("wide_emit_cap", 64, 4096), ("wide_emit_bins", 2, 1024), ("approximate_cigar", 0, 1),
           ("debug_fail_owner", 0, 0xFFFFFFFF), ("debug_fail_home", 0, 0xFFFFFFFF), ("lane_schedule", 0, None),
-          ("prewarm_result_bytes", 0, None), ("prewarm_walk", 0, 2)]
+          ("bed_text_piece_bytes", 64, 2 ** 40), ("prewarm_result_bytes", 0, None), ("prewarm_walk", 0, 2)]
 # accepting their upper end allocates gigabytes (pinned host memory, walk slabs, the rows pool's cap): 0 and 1 only
 NO_HIGH_END = ("prewarm_result_bytes", "prewarm_walk", "device_rows_pool_bytes")
 FLAGS = ["fuse_final_level", "regroup_entries", "segment_groups", "update_stats", "lookup_stats", "free_slot_order"]
@@ -27,7 +27,7 @@ STORED = {"pair_budget": (1 << 28, 4096), "chunk_ranges": (0, 3), "locality_min"
           "fuse_final_level": (1, 0), "regroup_entries": (1, 0), "walk_kernel": (1, 0), "segment_groups": (1, 0), "segment_parts": (0, 2),
           "walk_members": (0, 1), "filter_covered": (0, 1), "update_stats": (0, 1), "lookup_stats": (0, 1), "wide_emit_cap": (4096, 64),
           "wide_emit_bins": (1024, 2), "approximate_cigar": (0, 1), "free_slot_order": (1, 0), "debug_fail_owner": (0, (1 << 16) | 1),
-          "debug_fail_home": (0, (1 << 16) | 1), "lane_schedule": (0, 1)}
+          "debug_fail_home": (0, (1 << 16) | 1), "lane_schedule": (0, 1), "bed_text_piece_bytes": (256 << 20, 64)}
 BFS = dict(transitive=True, max_depth=3, min_transitive_len=20)
 
 
