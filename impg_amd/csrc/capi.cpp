@@ -523,6 +523,7 @@ int impg_gpu_index_create_from_paf(const char *const *paths, int n_paths, int bi
     if (pp.file_first.size() < 2 || pp.file_first.front() != 0 || pp.file_first.back() != pp.records.size())
       throw Error{IMPG_E_INVALID, "internal: bad file boundaries"};
     ix->file_first = pp.file_first;
+    ix->build_stats[BUILD_TOKENIZED_DEVICE] = 1;
     if (order_policy != IMPG_ORDER_COITREES && order_policy != IMPG_ORDER_SORTED) throw Error{IMPG_E_INVALID, "bad order policy"};
     if (build_index_device(*ix, pp.records.data(), pp.records.size(), nullptr, n_ops, lens.data(), (uint32_t)lens.size(), bidirectional != 0,
                            order_policy, 0, 1, nullptr, d_ops.as<uint32_t>())) {
@@ -536,6 +537,7 @@ int impg_gpu_index_create_from_paf(const char *const *paths, int n_paths, int bi
   }
   *out = make_index(pp.records.data(), pp.records.size(), pp.ops.data(), pp.ops.size(), lens.data(), (uint32_t)lens.size(),
                     bidirectional, order_policy, device, 0, 1, &pp.seq, &pp.file_first, nullptr).release();
+  if (raw) (*out)->build_stats[BUILD_TOKENIZED_DEVICE] = 1;  // (the device tokenised; the host builder took over)
   return IMPG_OK;
   IMPG_CATCH
 }
@@ -644,8 +646,10 @@ int impg_gpu_set_option(impg_gpu_index_t *ix, const char *key, int64_t value) {
 const char *impg_gpu_option_key(size_t i) { return i < N_OPTIONS ? OPTION_TABLE[i].key : nullptr; }
 
 // impg_gpu_get_counter: every key and the atomic of the handle it reads
-struct CounterRow { const char *key; const std::atomic<uint64_t> &(*at)(const impg_gpu_index &); };
-#define CTR(key, member) {key, [](const impg_gpu_index &ix) -> const std::atomic<uint64_t> & { return ix.member; }}
+// (over_ranks: a multi-GPU handle answers with the sum over its ranks' handles)
+struct CounterRow { const char *key; const std::atomic<uint64_t> &(*at)(const impg_gpu_index &); bool over_ranks; };
+#define CTR(key, member) {key, [](const impg_gpu_index &ix) -> const std::atomic<uint64_t> & { return ix.member; }, false}
+#define CTR_RANKS(key, member) {key, [](const impg_gpu_index &ix) -> const std::atomic<uint64_t> & { return ix.member; }, true}
 static const CounterRow COUNTER_TABLE[] = {
     CTR("walk_launches", walk_launches), CTR("walk_fallbacks", walk_fallbacks), CTR("walk_members", walk_last_members), CTR("walk_overflow", walk_last_overflow),
     CTR("small_batches", small_batches),
@@ -665,8 +669,11 @@ static const CounterRow COUNTER_TABLE[] = {
     CTR("refine_longest_group", refine_stats[REFINE_LONGEST_GROUP]),
     CTR("bed_rows", bed_stats[BED_ROWS]), CTR("bed_gap_roots", bed_stats[BED_GAP_ROOTS]), CTR("bed_runs", bed_stats[BED_RUNS]),
     CTR("bed_text_pieces", bed_stats[BED_TEXT_PIECES]), CTR("bed_text_bytes", bed_stats[BED_TEXT_BYTES]),
+    CTR_RANKS("build_device", build_stats[BUILD_DEVICE]), CTR_RANKS("tokenized_device", build_stats[BUILD_TOKENIZED_DEVICE]),
+    CTR_RANKS("build_batches", build_stats[BUILD_BATCHES]),
 };
 #undef CTR
+#undef CTR_RANKS
 constexpr size_t N_COUNTERS = sizeof(COUNTER_TABLE) / sizeof(COUNTER_TABLE[0]);
 
 int impg_gpu_get_counter(const impg_gpu_index_t *ix, const char *key, int64_t *value_out) {
@@ -674,7 +681,10 @@ int impg_gpu_get_counter(const impg_gpu_index_t *ix, const char *key, int64_t *v
   if (!ix || !key || !value_out) throw Error{IMPG_E_INVALID, "null argument"};
   for (const CounterRow &c : COUNTER_TABLE)
     if (!strcmp(c.key, key)) {
-      *value_out = (int64_t)c.at(*ix).load();
+      uint64_t v = 0;
+      if (c.over_ranks) for_each_rank(*ix, [&](const impg_gpu_index &r) { v += c.at(r).load(); });
+      else v = c.at(*ix).load();
+      *value_out = (int64_t)v;
       return IMPG_OK;
     }
   throw Error{IMPG_E_INVALID, std::string("unknown counter ") + key};

@@ -49,7 +49,7 @@ long parse_cigar(const char *s, size_t n, uint32_t *out, size_t cap) {
       case 'M': code = 4; break;
       default: return -1;
     }
-    if (k < cap) out[k] = (code << 29) | (len & OP_LEN_MASK);
+    if (k < cap) out[k] = (code << 29) | len;  // no mask: CigarOp::new (impg.rs:90-92); a length >= 2^29 changes the code
     k++;
     len = 0;
   }

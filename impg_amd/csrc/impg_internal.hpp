@@ -4,6 +4,7 @@
 #include <atomic>
 #include <chrono>
 #include <exception>
+#include <functional>
 #include <vector>
 #include <hip/hip_runtime.h>
 
@@ -381,6 +382,9 @@ inline uint32_t put_original_name(std::string &s, const std::string &name, bool 
 }
 
 // ---- BED (bed.cpp) -----------------------------------------------------------
+enum BuildStat { BUILD_DEVICE, BUILD_TOKENIZED_DEVICE, BUILD_BATCHES };  // impg_gpu_index::build_stats
+// sharded.cpp: f(rank's handle) for every rank of a multi-GPU handle, f(ix) itself for any other handle
+void for_each_rank(const impg_gpu_index &ix, const std::function<void(const impg_gpu_index &)> &f);
 enum BedStat { BED_ROWS, BED_GAP_ROOTS, BED_RUNS, BED_TEXT_PIECES, BED_TEXT_BYTES };  // impg_gpu_index::bed_stats
 size_t bed_merge(impg_gpu_interval_t *iv, size_t n, int32_t merge_distance, bool merge_strands);
 
@@ -431,6 +435,9 @@ struct impg_gpu_index {
   struct RowsPool : impg::BufPool { RowsPool() { shared = true; } } rows_pool;
   mutable std::atomic<uint64_t> walk_launches{0}, walk_fallbacks{0}, walk_last_members{1}, walk_last_overflow{0};  // impg_gpu_get_counter
   mutable std::atomic<uint64_t> small_batches{0};  // ... and the batches Engine::run_small answered
+  // ... and who built this index (by impg::BuildStat): 1 if build_index_device produced it (0: the host builder), 1 if the
+  // device tokenised its CIGAR text, the tiles_kernel launches of its build.  A multi-GPU handle reports its ranks' sum.
+  mutable std::atomic<uint64_t> build_stats[3] = {};
   // ... and how the visited updates of its batches grouped their hits: levels cut into slices, levels counted a second time
   // for one huge query, levels that went to the library sort ([0], [1], [2]; Engine::update)
   // host <-> device traffic of the masked queries, counted where the copies are issued: mask tables uploaded (apply_mask,

@@ -14,7 +14,8 @@
 //   columns   starts / ends / running max (a segmented max-scan) / levels, checkpoints from the tiles' own headers
 //
 // The host builder stays for what this one does not take (tracepoint indexes, a loaded .impg file's entry order) and
-// as the checker: tests/test_gpu_parity.py::test_device_build_matches_host_build compares the saved bytes.
+// as the checker: tests/test_gpu_index_build.py compares the saved bytes of both with each other and with a model of the
+// layout written from impg_internal.hpp alone (tests/index_ref.py), fixture by fixture at the edges of this file.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -303,7 +304,7 @@ __global__ __launch_bounds__(256) void cigar_tokens_kernel(const char *__restric
       uint32_t len = 0;  // ... then forward, len * 10 + d in 32-bit arithmetic like the host's tokenizer
       for (uint32_t k = st; k < i; k++) len = len * 10u + ((unsigned char)s[k] - (unsigned)'0');
       const uint32_t code = ch == '=' ? 0u : ch == 'X' ? 1u : ch == 'I' ? 2u : ch == 'D' ? 3u : 4u;
-      out[done + (uint32_t)__popcll(m & ((1ull << lane()) - 1ull))] = (code << 29) | (len & OP_LEN_MASK);
+      out[done + (uint32_t)__popcll(m & ((1ull << lane()) - 1ull))] = (code << 29) | len;  // no mask: CigarOp::new (impg.rs:90-92)
     }
     done += (uint32_t)__popcll(m);
   }
@@ -408,7 +409,8 @@ bool build_index_device(impg_gpu_index &ix, const impg_gpu_record_t *records, si
   size_blob(ix, 12, n_tiles * (with_pfx ? (with_idl ? IDL_WORDS * 4 : 0) : TILE_SUBS * 16), acc);
   uint4 *const d_idp = (with_pfx && !with_idl) ? nullptr : ix.blob(12)->as<uint4>();
   {
-    const size_t BATCH_OPS = 64ull << 20;  // 256 MB of ops per upload
+    const uint64_t BATCH_OPS = sw.batch_ops;  // ops per upload (options.hpp: 256 MB unless a test asks for less)
+    uint64_t launches = 0;
     DevBuf d_ops;
     size_t b0 = 0;
     if (d_cigar_ops) {  // the pool is already here (tokenize_on_device): one launch over all records
@@ -416,6 +418,7 @@ bool build_index_device(impg_gpu_index &ix, const impg_gpu_record_t *records, si
         tiles_kernel<<<cdiv(n_records, 4), 256, 0, s>>>(d_rec.as<impg_gpu_record_t>(), d_need.as<uint8_t>(), d_tb.as<uint32_t>(), 0u, (uint32_t)n_records,
                                                           d_cigar_ops, 0ull, ix.blob(10)->as<uint32_t>(), d_pfx,
                                                           d_idp, d_totT.as<uint32_t>(), d_totQ.as<uint32_t>(), d_flag.as<uint32_t>());
+      if (n_records) launches++;
       IMPG_HIP(hipStreamSynchronize(s));
       b0 = n_records;
     } else if (!monotone && n_ops) {
@@ -441,9 +444,11 @@ bool build_index_device(impg_gpu_index &ix, const impg_gpu_record_t *records, si
       tiles_kernel<<<cdiv(nr, 4), 256, 0, s>>>(d_rec.as<impg_gpu_record_t>(), d_need.as<uint8_t>(), d_tb.as<uint32_t>(), (uint32_t)b0, nr,
                                                 d_ops.as<uint32_t>(), lo, ix.blob(10)->as<uint32_t>(), d_pfx,
                                                 d_idp, d_totT.as<uint32_t>(), d_totQ.as<uint32_t>(), d_flag.as<uint32_t>());
+      launches++;
       IMPG_HIP(hipStreamSynchronize(s));  // (the next batch overwrites d_ops)
       b0 = b1;
     }
+    ix.build_stats[BUILD_BATCHES] = launches;
     uint32_t bad = 0;
     IMPG_HIP(hipMemcpy(&bad, d_flag.p, 4, hipMemcpyDeviceToHost));
     if (bad) throw Error{IMPG_E_INVALID, "Invalid CIGAR operation"};
@@ -599,6 +604,7 @@ bool build_index_device(impg_gpu_index &ix, const impg_gpu_record_t *records, si
   ix.multi_file = multi_file;
   ix.tp_mode = false;
   ix.bind_view(n_seq, order_policy == IMPG_ORDER_SORTED);
+  ix.build_stats[BUILD_DEVICE] = 1;
   return true;
 }
 

@@ -106,10 +106,14 @@ struct BuildSwitches {
   bool identity_lines;  // IMPG_IDENTITY_LINES=1 builds the identity lines with the index, not on first use
   bool host_build;      // IMPG_BUILD_HOST: host threads build (and tokenise) instead of the device
   bool timing;          // IMPG_BUILD_TIMING: the builders' phases on stderr
+  uint64_t batch_ops;   // IMPG_BUILD_BATCH_OPS: ops per upload of the device builder's batches (tests; the host builder has no batches)
 };
+constexpr uint64_t BUILD_BATCH_OPS = 64ull << 20;  // 256 MB of ops per upload
 inline BuildSwitches build_switches() {
-  const char *pfx = getenv("IMPG_PREFIX_LINES"), *idl = getenv("IMPG_IDENTITY_LINES");
-  return BuildSwitches{!(pfx && atoi(pfx) == 0), idl && atoi(idl) == 1, getenv("IMPG_BUILD_HOST") != nullptr, getenv("IMPG_BUILD_TIMING") != nullptr};
+  const char *pfx = getenv("IMPG_PREFIX_LINES"), *idl = getenv("IMPG_IDENTITY_LINES"), *bat = getenv("IMPG_BUILD_BATCH_OPS");
+  const unsigned long long b = bat ? strtoull(bat, nullptr, 10) : 0ull;
+  return BuildSwitches{!(pfx && atoi(pfx) == 0), idl && atoi(idl) == 1, getenv("IMPG_BUILD_HOST") != nullptr, getenv("IMPG_BUILD_TIMING") != nullptr,
+                       b ? (uint64_t)b : BUILD_BATCH_OPS};
 }
 
 }  // namespace impg

@@ -511,6 +511,10 @@ struct Cluster {
 
 }  // namespace impg
 
+void impg::for_each_rank(const impg_gpu_index &ix, const std::function<void(const impg_gpu_index &)> &f) {
+  if (!ix.cluster) return f(ix);
+  for (const auto &r : ix.cluster->ranks) if (r) f(*r);
+}
 impg_gpu_index::impg_gpu_index() {}
 impg_gpu_index::~impg_gpu_index() {
   delete cluster;

@@ -287,7 +287,12 @@ const char *impg_gpu_counter_key(size_t i);
  * (impg_gpu_query_batch_bed, impg_gpu_query_batch_bed_fd, impg_gpu_selftest_bed_rows; zero when it starts, every chunk adds;
  * on a multi-GPU handle its ranks count, not the handle): "bed_rows" = rows entering the merges, "bed_gap_roots" = rows
  * after merge_adjusted_intervals_gap_2d, "bed_runs" = merged rows out, "bed_text_pieces" = text pieces sent to the host,
- * "bed_text_bytes" = bytes printed. */
+ * "bed_text_bytes" = bytes printed.  Of the build of the index itself (a multi-GPU handle answers with the sum over its
+ * ranks): "build_device" = 1 if the device builder produced it, 0 if the host builder did (IMPG_BUILD_HOST, tracepoints, a
+ * loaded .impg file's entry order, a card short of memory for the build, an index loaded from a saved file);
+ * "tokenized_device" = 1 if the device tokenised its CIGAR text (impg_gpu_index_create_from_paf on one GPU);
+ * "build_batches" = the op-pool uploads of the device build, one tiles launch each (1 unless the pool exceeds the batch
+ * size, 64 M ops or IMPG_BUILD_BATCH_OPS). */
 int impg_gpu_get_counter(const impg_gpu_index_t *, const char *key, int64_t *value_out);
 /* Large result arrays live in pinned host blocks that are recycled through a process-wide pool (at most
  * IMPG_PINNED_POOL_BYTES, default 6 GiB, are kept when results are freed).  Gives pooled blocks back to the system

@@ -81,9 +81,12 @@ def test_option_ranges(world):
 def test_every_counter_reads(world):
     g = impg_amd.GpuImpg.from_paf(world[0])
     keys = impg_amd.counter_keys()
-    assert len(keys) >= 28
+    assert len(keys) >= 31 and {"build_device", "tokenized_device", "build_batches"} <= set(keys)
     for key in keys:
         assert g.counter(key) >= 0, key
+    assert [g.counter(k) for k in ("build_device", "tokenized_device", "build_batches")] == [1, 1, 1]  # from_paf, one tiles launch
+    m = impg_amd.GpuImpg.from_paf(world[0], devices=[0, 0], lanes=1)  # a multi handle: the sum over its ranks
+    assert [m.counter(k) for k in ("build_device", "tokenized_device", "build_batches")] == [2, 0, 2]
 
 
 def test_same_answers_after_an_options_round_trip(world):

@@ -1514,6 +1514,8 @@ def test_device_build_matches_host_build(tmp_path, seed, max_ops, bidirectional,
             g = impg_amd.GpuImpg.from_paf(paths, bidirectional=bidirectional, order=order)
         finally:
             os.environ.pop("IMPG_BUILD_HOST", None)
+        # (a device build that fell back to the host builder -- a card short of memory -- would compare the host builder with itself)
+        assert (g.counter("build_device"), g.counter("tokenized_device")) == ((1, 1) if mode == "device" else (0, 0)), mode
         f = str(tmp_path / (mode + ".idx"))
         g.save(f)
         files[mode] = open(f, "rb").read()
@@ -1540,6 +1542,7 @@ def test_index_without_prefix_lines(tmp_path):
     finally:
         os.environ.pop("IMPG_PREFIX_LINES", None)
         os.environ.pop("IMPG_BUILD_HOST", None)
+    assert [x.counter("build_device") for x in (g_full, g, g_host)] == [1, 1, 0]  # (no silent fallback to the host builder)
     assert g.device_bytes() < 0.85 * g_full.device_bytes()  # (op lines + sub-tile rows against op + prefix lines; the identity lines come on demand)
     ranges = random_ranges(5, 150, 6, 60_000, max_len=6000, min_len=1)
     assert_same(g, c, ranges)
@@ -1584,6 +1587,7 @@ def test_identity_lines_on_demand(tmp_path):
     finally:
         os.environ.pop("IMPG_IDENTITY_LINES", None)
         os.environ.pop("IMPG_BUILD_HOST", None)
+    assert [x.counter("build_device") for x in (g, eager, eager_host)] == [1, 1, 0]  # (no silent fallback to the host builder)
     assert eager.device_bytes() == full == eager_host.device_bytes()
     eager.save(str(tmp_path / "eager.idx"))
     eager_host.save(str(tmp_path / "eager_host.idx"))
