@@ -25,6 +25,7 @@
 
 #include "device_prims.hpp"
 #include "engine.hpp"
+#include "text_device.hpp"
 
 namespace impg {
 
@@ -220,23 +221,6 @@ inline unsigned bits_for(uint64_t n) {
 // ---- text ---------------------------------------------------------------------------------------------------------------
 // "{name}\t{start}\t{end}\t{range name}\t.\t{strand}\n" per merged row (output_results_bed, main.rs:11868-11890), written
 // by the device: a transitive batch prints gigabytes, which the host's cores format slower than PCIe moves them.
-struct TextTables {
-  const char *names;            // printed sequence names back to back ("base" under --original-sequence-coordinates)
-  const uint32_t *name_off;     // [n_seq + 1]
-  const uint32_t *shift;        // [n_seq] offset added to the coordinates (main.rs:11876-11883)
-  uint32_t n_names;             // 0: sequences print as their ids
-  const char *rnames;           // the chunk's range names back to back
-  const uint32_t *rname_off;    // [n_ranges + 1]
-};
-__device__ __forceinline__ uint32_t dec_digits(uint32_t v) {
-  uint32_t d = 1;
-  while (v >= 10u) { v /= 10u; d++; }
-  return d;
-}
-__device__ __forceinline__ char *put_dec(char *p, uint32_t v, uint32_t digits) {
-  for (uint32_t k = digits; k > 0; k--) { p[k - 1] = (char)('0' + v % 10u); v /= 10u; }
-  return p + digits;
-}
 __global__ __launch_bounds__(256) void text_len_kernel(const BedRow *__restrict__ rows, uint32_t n, TextTables t, uint32_t *__restrict__ len) {
   const uint32_t r = blockIdx.x * 256u + threadIdx.x;
   if (r >= n) return;
@@ -451,49 +435,65 @@ void device_bed_selftest(Engine &E, const impg_gpu_index &ix, const impg_gpu_int
   device_bed_text(E, ix, out, n_runs, n_ranges, rnames, original_coords, [&](const char *p, size_t k) { text.append(p, k); });
 }
 
-// The merged rows of a chunk as text, streamed to `sink(ptr, bytes)` in pieces of at most PIECE bytes (option
-// bed_text_piece_bytes) through two pinned buffers: while the host consumes one piece the device formats and copies the next.
-void device_bed_text(Engine &E, const impg_gpu_index &ix, const DevBuf &rows, uint32_t n_rows, uint32_t n_ranges,
-                     const std::vector<std::string> &rnames, bool original_coords,
-                     const std::function<void(const char *, size_t)> &sink) {
-  if (!n_rows) return;
+// The name / shift / range-name tables of a chunk (text_device.hpp)
+TextTableBufs::TextTableBufs(Engine &E, const impg_gpu_index &ix, uint32_t n_ranges, const std::vector<std::string> &rnames, bool original_coords) {
   hipStream_t s = E.stream;
-  // ---- tables -------------------------------------------------------------------------------------------------------
-  std::string nb;
-  std::vector<uint32_t> noff(1, 0), nshift;
+  noff.assign(1, 0);
   for (const std::string &nm : ix.seq.names) {
     nshift.push_back(put_original_name(nb, nm, original_coords));
     noff.push_back((uint32_t)nb.size());
   }
-  std::string rb;
-  std::vector<uint32_t> roff(1, 0);
+  roff.assign(1, 0);
   for (uint32_t q = 0; q < n_ranges; q++) { rb += rnames[q]; roff.push_back((uint32_t)rb.size()); }
-  DevBuf d_nb, d_noff, d_shift, d_rb, d_roff, len, off, stmp;
   auto up = [&](DevBuf &d, const void *src, size_t bytes) {
     d.reserve(std::max<size_t>(bytes, 256));
     if (bytes) IMPG_HIP(hipMemcpyAsync(d.p, src, bytes, hipMemcpyHostToDevice, s));
   };
   up(d_nb, nb.data(), nb.size()); up(d_noff, noff.data(), noff.size() * 4); up(d_shift, nshift.data(), nshift.size() * 4);
   up(d_rb, rb.data(), rb.size()); up(d_roff, roff.data(), roff.size() * 4);
-  TextTables t{d_nb.as<char>(), d_noff.as<uint32_t>(), d_shift.as<uint32_t>(), (uint32_t)ix.seq.names.size(), d_rb.as<char>(), d_roff.as<uint32_t>()};
-  // ---- lengths -> 64-bit offsets (a transitive batch prints more than 4 GB) ----------------------------------------------
+  t = TextTables{d_nb.as<char>(), d_noff.as<uint32_t>(), d_shift.as<uint32_t>(), (uint32_t)ix.seq.names.size(), d_rb.as<char>(), d_roff.as<uint32_t>()};
+}
+
+// The merged rows of a chunk as text (device_text_pieces streams it)
+void device_bed_text(Engine &E, const impg_gpu_index &ix, const DevBuf &rows, uint32_t n_rows, uint32_t n_ranges,
+                     const std::vector<std::string> &rnames, bool original_coords,
+                     const std::function<void(const char *, size_t)> &sink) {
+  if (!n_rows) return;
+  hipStream_t s = E.stream;
+  TextTableBufs tb(E, ix, n_ranges, rnames, original_coords);
+  const TextTables t = tb.t;
+  DevBuf len;
   len.reserve((size_t)n_rows * 4);
-  off.reserve((size_t)(n_rows + 1) * 8);
   text_len_kernel<<<cdiv(n_rows, 256), 256, 0, s>>>(rows.as<BedRow>(), n_rows, t, len.as<uint32_t>());
-  prims::exclusive_sum(stmp, len.as<uint32_t>(), off.as<unsigned long long>(), n_rows, s);
+  device_text_pieces(E, len.as<uint32_t>(), n_rows, "BED",
+                     [&](uint32_t r0, uint32_t r1, const unsigned long long *off, unsigned long long base, char *out) {
+                       text_write_kernel<<<cdiv(r1 - r0, 256), 256, 0, s>>>(rows.as<BedRow>() + r0, r1 - r0, t, off, base, out);
+                     },
+                     sink, ix.bed_stats[BED_TEXT_PIECES], ix.bed_stats[BED_TEXT_BYTES]);
+}
+
+void device_text_pieces(Engine &E, const uint32_t *d_len, uint32_t n_rows, const char *what,
+                        const std::function<void(uint32_t, uint32_t, const unsigned long long *, unsigned long long, char *)> &write,
+                        const std::function<void(const char *, size_t)> &sink, std::atomic<uint64_t> &pieces, std::atomic<uint64_t> &bytes) {
+  if (!n_rows) return;
+  hipStream_t s = E.stream;
+  DevBuf off, stmp;
+  // ---- lengths -> 64-bit offsets (a transitive batch prints more than 4 GB) ----------------------------------------------
+  off.reserve((size_t)(n_rows + 1) * 8);
+  prims::exclusive_sum(stmp, d_len, off.as<unsigned long long>(), n_rows, s);
   // piece boundaries: whole rows, at most PIECE bytes each; found on the host from a sampled copy of the offsets
   const unsigned long long PIECE = (unsigned long long)E.opt.bed_text_piece_bytes;
   std::vector<unsigned long long> h_off(n_rows);
   IMPG_HIP(hipMemcpyAsync(h_off.data(), off.p, (size_t)n_rows * 8, hipMemcpyDeviceToHost, s));
   uint32_t last_len = 0;
-  IMPG_HIP(hipMemcpyAsync(&last_len, len.as<uint32_t>() + (n_rows - 1), 4, hipMemcpyDeviceToHost, s));
+  IMPG_HIP(hipMemcpyAsync(&last_len, d_len + (n_rows - 1), 4, hipMemcpyDeviceToHost, s));
   IMPG_HIP(hipStreamSynchronize(s));
   const unsigned long long total = h_off[n_rows - 1] + last_len;
   const size_t cap = (size_t)std::min<unsigned long long>(total, PIECE) + 4096;
   // a piece holds whole rows; only a piece of one row can outgrow PIECE, and it must still fit the buffer.  Refused
   // here, with nothing queued and no pinned buffer in flight.
   for (uint32_t r = 0; r < n_rows; r++)
-    if ((r + 1 < n_rows ? h_off[r + 1] : total) - h_off[r] > cap) throw Error{IMPG_E_UNSUPPORTED, "a single BED row longer than the text buffer"};
+    if ((r + 1 < n_rows ? h_off[r + 1] : total) - h_off[r] > cap) throw Error{IMPG_E_UNSUPPORTED, std::string("a single ") + what + " row longer than the text buffer"};
   DevBuf piece[2];
   char *pin[2] = {nullptr, nullptr};
   struct Unpin { char **p; ~Unpin() { for (int k = 0; k < 2; k++) if (p[k]) (void)hipHostFree(p[k]); } } unpin{pin};
@@ -512,12 +512,12 @@ void device_bed_text(Engine &E, const impg_gpu_index &ix, const DevBuf &rows, ui
       if (r1 == n_rows) { if (total - base > PIECE && n_rows - 1 > r0) r1 = n_rows - 1; }
       else r1 = std::max(r1 - 1, r0 + 1);
       const unsigned long long end = r1 < n_rows ? h_off[r1] : total;
-      text_write_kernel<<<cdiv(r1 - r0, 256), 256, 0, s>>>(rows.as<BedRow>() + r0, r1 - r0, t, off.as<unsigned long long>() + r0, base, piece[slot].as<char>());
+      write(r0, r1, off.as<unsigned long long>() + r0, base, piece[slot].as<char>());
       IMPG_HIP(hipMemcpyAsync(pin[slot], piece[slot].p, (size_t)(end - base), hipMemcpyDeviceToHost, s));
       IMPG_HIP(hipEventRecord(done[slot], s));
       pend[slot] = {(size_t)(end - base), true};
-      ix.bed_stats[BED_TEXT_PIECES]++;
-      ix.bed_stats[BED_TEXT_BYTES] += end - base;
+      pieces++;
+      bytes += end - base;
       r0 = r1;
     }
     // consume the OTHER slot's piece while this one is in flight (or drain at the end)

@@ -204,7 +204,7 @@ bool run_chunk_rows(const impg_gpu_index &ix, Engine &E, const impg_gpu_range_t 
 
 bool run_chunk_bed(const impg_gpu_index &ix, Engine &E, const impg_gpu_range_t *d_ranges, const impg_gpu_range_t *h_ranges,
                    const char *const *range_names, size_t b, size_t e, const impg_gpu_params_t &p, int32_t merge_distance,
-                   const std::function<void(const char *, size_t)> &sink, double *seconds3, std::mutex *gpu_turn) {
+                   const std::function<void(const char *, size_t)> &sink, double *seconds3, std::mutex *gpu_turn, bool bedpe) {
   std::vector<std::unique_ptr<LevelBufs>> levels;
   DevBuf self_dev, rows;
   self_dev.pool = &E.level_pool;
@@ -216,10 +216,10 @@ bool run_chunk_bed(const impg_gpu_index &ix, Engine &E, const impg_gpu_range_t *
   E.run(ix, rs);
   const auto c1 = std::chrono::steady_clock::now();
   if (e == b) return false;
-  const uint32_t n_rows = device_bed_rows(E, ix, (uint32_t)(e - b), p, merge_distance, levels, self_dev, rows);
+  const uint32_t n_rows = (bedpe ? device_bedpe_rows : device_bed_rows)(E, ix, (uint32_t)(e - b), p, merge_distance, levels, self_dev, rows);
   const auto c2 = std::chrono::steady_clock::now();
-  device_bed_text(E, ix, rows, n_rows, (uint32_t)(e - b), bed_range_names(ix, h_ranges, range_names, b, e),
-                  p.original_sequence_coordinates != 0, sink);
+  (bedpe ? device_bedpe_text : device_bed_text)(E, ix, rows, n_rows, (uint32_t)(e - b), bed_range_names(ix, h_ranges, range_names, b, e),
+                                                p.original_sequence_coordinates != 0, sink);
   const auto c3 = std::chrono::steady_clock::now();
   seconds3[0] += std::chrono::duration<double>(c1 - c0).count();
   seconds3[1] += std::chrono::duration<double>(c2 - c1).count();
@@ -669,6 +669,10 @@ static const CounterRow COUNTER_TABLE[] = {
     CTR("refine_longest_group", refine_stats[REFINE_LONGEST_GROUP]),
     CTR("bed_rows", bed_stats[BED_ROWS]), CTR("bed_gap_roots", bed_stats[BED_GAP_ROOTS]), CTR("bed_runs", bed_stats[BED_RUNS]),
     CTR("bed_text_pieces", bed_stats[BED_TEXT_PIECES]), CTR("bed_text_bytes", bed_stats[BED_TEXT_BYTES]),
+    CTR("bedpe_rows", bedpe_stats[BEDPE_ROWS]), CTR("bedpe_runs", bedpe_stats[BEDPE_RUNS]),
+    CTR("bedpe_joins_contiguous", bedpe_stats[BEDPE_JOINS_CONTIGUOUS]), CTR("bedpe_joins_gap", bedpe_stats[BEDPE_JOINS_GAP]),
+    CTR("bedpe_fused_ops", bedpe_stats[BEDPE_FUSED_OPS]), CTR("bedpe_summary_ops", bedpe_stats[BEDPE_SUMMARY_OPS]),
+    CTR("bedpe_text_pieces", bedpe_stats[BEDPE_TEXT_PIECES]), CTR("bedpe_text_bytes", bedpe_stats[BEDPE_TEXT_BYTES]),
     CTR_RANKS("build_device", build_stats[BUILD_DEVICE]), CTR_RANKS("tokenized_device", build_stats[BUILD_TOKENIZED_DEVICE]),
     CTR_RANKS("build_batches", build_stats[BUILD_BATCHES]),
 };
@@ -1286,39 +1290,50 @@ int impg_gpu_results_bed(const impg_gpu_results_t *res, const impg_gpu_index_t *
   IMPG_CATCH
 }
 
-// query + both BED merges + the text on the device: only text crosses PCIe, in pinned pieces
+// query + merge + the text on the device: only text crosses PCIe, in pinned pieces.  BED: both BED merges
+// (bed_device.hip); BEDPE: the CIGAR summaries and merge_adjusted_intervals (bedpe_device.hip).
 namespace {
-void bed_batch(impg_gpu_index_t *ix, const impg_gpu_range_t *ranges, size_t n, const impg_gpu_params_t *params, const uint8_t *subset_keep,
-               int32_t merge_distance, const char *const *range_names, const std::function<void(const char *, size_t)> &sink,
-               double *seconds3) {
+// what the device BEDPE route does not serve (the host route, impg_gpu_results_paf, does): raised before anything runs
+void bedpe_refusals(const impg_gpu_index &ix) {
+  if (ix.shard || ix.cluster) throw Error{IMPG_E_UNSUPPORTED, "device-side BEDPE on a sharded index (use impg_gpu_query_batch + impg_gpu_results_paf)"};
+  // an op is no longer than the sequence it lies on; a fused op of 2^29 bases or more would wrap into its code bits on the
+  // host route (CigarOp::new, impg.rs:90-92), which the sums here do not restate
+  for (const int64_t len : ix.seq.lens)
+    if (len >= (int64_t)OP_LEN_MASK + 1) throw Error{IMPG_E_UNSUPPORTED, "device-side BEDPE on an index with a sequence of 2^29 bases or more (use impg_gpu_results_paf)"};
+  if (ix.tp_mode && !ix.opt.approximate_cigar)
+    throw Error{IMPG_E_UNSUPPORTED, "store_cigar on a tracepoint index needs option approximate_cigar = 1 (the approximate mode's "
+                                    "CIGAR is a pair of match / mismatch counts, not an alignment)"};
+}
+void text_batch(impg_gpu_index_t *ix, const impg_gpu_range_t *ranges, size_t n, const impg_gpu_params_t *params, const uint8_t *subset_keep,
+                int32_t merge_distance, const char *const *range_names, const std::function<void(const char *, size_t)> &sink,
+                double *seconds3, bool bedpe) {
   if (!ix || !params || (!ranges && n)) throw Error{IMPG_E_INVALID, "null argument"};
   check_ranges(ranges, n);
   Engine::check_params(*params);
   impg_gpu_params_t p = *params;
-  p.store_cigar = 0;  // BED never needs CIGARs (main.rs:7447)
-  if (ix->shard || ix->cluster) { sharded_bed_batch(*ix, ranges, n, p, subset_keep, merge_distance, range_names, sink, seconds3); return; }
+  p.store_cigar = bedpe ? 1 : 0;  // BED never needs CIGARs, BEDPE rates them (main.rs:7447)
+  if (bedpe) bedpe_refusals(*ix);
+  else if (ix->shard || ix->cluster) { sharded_bed_batch(*ix, ranges, n, p, subset_keep, merge_distance, range_names, sink, seconds3); return; }
   IMPG_HIP(hipSetDevice(ix->device));
   EngineLease lease(*ix);
   Engine &E = *lease;
-  ix->bed_stats_reset();
+  if (bedpe) ix->bedpe_stats_reset();
+  else ix->bed_stats_reset();
   apply_subset(E, *ix, subset_keep);
   const impg_gpu_range_t *d_ranges = upload_ranges(E.ranges_dev, ranges, n, &E.stream);
   double t3[3] = {0, 0, 0};  // engine, merge, text
-  for_chunks(E, n, [&](size_t b, size_t e) { run_chunk_bed(*ix, E, d_ranges, ranges, range_names, b, e, p, merge_distance, sink, t3); });
+  for_chunks(E, n, [&](size_t b, size_t e) { run_chunk_bed(*ix, E, d_ranges, ranges, range_names, b, e, p, merge_distance, sink, t3, nullptr, bedpe); });
   if (seconds3) for (int k = 0; k < 3; k++) seconds3[k] = t3[k];
 }
-}  // namespace
-
-int impg_gpu_query_batch_bed(impg_gpu_index_t *ix, const impg_gpu_range_t *ranges, size_t n, const impg_gpu_params_t *params,
-                             const uint8_t *subset_keep, int32_t merge_distance, const char *const *range_names, char **text,
-                             size_t *len, double *seconds3) {
+// the text arrives in pieces; it is collected into one malloc'ed buffer that grows geometrically
+int text_batch_buffer(impg_gpu_index_t *ix, const impg_gpu_range_t *ranges, size_t n, const impg_gpu_params_t *params, const uint8_t *subset_keep,
+                      int32_t merge_distance, const char *const *range_names, char **text, size_t *len, double *seconds3, bool bedpe) {
   IMPG_TRY
   if (!text || !len) throw Error{IMPG_E_INVALID, "null argument"};
-  // the text arrives in pieces; it is collected into one malloc'ed buffer that grows geometrically
   char *buf = nullptr;
   size_t used = 0, cap = 0;
   struct Guard { char *&b; bool keep = false; ~Guard() { if (!keep) free(b); } } guard{buf};
-  bed_batch(ix, ranges, n, params, subset_keep, merge_distance, range_names, [&](const char *p, size_t k) {
+  text_batch(ix, ranges, n, params, subset_keep, merge_distance, range_names, [&](const char *p, size_t k) {
     if (used + k + 1 > cap) {
       const size_t nc = std::max(cap * 2, used + k + 1 + (1u << 20));
       char *nb = (char *)realloc(buf, nc);
@@ -1327,7 +1342,7 @@ int impg_gpu_query_batch_bed(impg_gpu_index_t *ix, const impg_gpu_range_t *range
     }
     memcpy(buf + used, p, k);
     used += k;
-  }, seconds3);
+  }, seconds3, bedpe);
   if (!buf) { buf = (char *)malloc(1); if (!buf) throw Error{IMPG_E_OOM, "host out of memory"}; }
   buf[used] = 0;
   guard.keep = true;
@@ -1336,13 +1351,11 @@ int impg_gpu_query_batch_bed(impg_gpu_index_t *ix, const impg_gpu_range_t *range
   return IMPG_OK;
   IMPG_CATCH
 }
-
-int impg_gpu_query_batch_bed_fd(impg_gpu_index_t *ix, const impg_gpu_range_t *ranges, size_t n, const impg_gpu_params_t *params,
-                                const uint8_t *subset_keep, int32_t merge_distance, const char *const *range_names, int fd,
-                                uint64_t *bytes_written, double *seconds3) {
+int text_batch_fd(impg_gpu_index_t *ix, const impg_gpu_range_t *ranges, size_t n, const impg_gpu_params_t *params, const uint8_t *subset_keep,
+                  int32_t merge_distance, const char *const *range_names, int fd, uint64_t *bytes_written, double *seconds3, bool bedpe) {
   IMPG_TRY
   uint64_t total = 0;
-  bed_batch(ix, ranges, n, params, subset_keep, merge_distance, range_names, [&](const char *p, size_t k) {
+  text_batch(ix, ranges, n, params, subset_keep, merge_distance, range_names, [&](const char *p, size_t k) {
     size_t done = 0;
     while (done < k) {
       const ssize_t w = write(fd, p + done, k - done);
@@ -1353,10 +1366,32 @@ int impg_gpu_query_batch_bed_fd(impg_gpu_index_t *ix, const impg_gpu_range_t *ra
       done += (size_t)w;
     }
     total += k;
-  }, seconds3);
+  }, seconds3, bedpe);
   if (bytes_written) *bytes_written = total;
   return IMPG_OK;
   IMPG_CATCH
+}
+}  // namespace
+
+int impg_gpu_query_batch_bed(impg_gpu_index_t *ix, const impg_gpu_range_t *ranges, size_t n, const impg_gpu_params_t *params,
+                             const uint8_t *subset_keep, int32_t merge_distance, const char *const *range_names, char **text,
+                             size_t *len, double *seconds3) {
+  return text_batch_buffer(ix, ranges, n, params, subset_keep, merge_distance, range_names, text, len, seconds3, false);
+}
+int impg_gpu_query_batch_bed_fd(impg_gpu_index_t *ix, const impg_gpu_range_t *ranges, size_t n, const impg_gpu_params_t *params,
+                                const uint8_t *subset_keep, int32_t merge_distance, const char *const *range_names, int fd,
+                                uint64_t *bytes_written, double *seconds3) {
+  return text_batch_fd(ix, ranges, n, params, subset_keep, merge_distance, range_names, fd, bytes_written, seconds3, false);
+}
+int impg_gpu_query_batch_bedpe(impg_gpu_index_t *ix, const impg_gpu_range_t *ranges, size_t n, const impg_gpu_params_t *params,
+                               const uint8_t *subset_keep, int32_t merge_distance, const char *const *range_names, char **text,
+                               size_t *len, double *seconds3) {
+  return text_batch_buffer(ix, ranges, n, params, subset_keep, merge_distance, range_names, text, len, seconds3, true);
+}
+int impg_gpu_query_batch_bedpe_fd(impg_gpu_index_t *ix, const impg_gpu_range_t *ranges, size_t n, const impg_gpu_params_t *params,
+                                  const uint8_t *subset_keep, int32_t merge_distance, const char *const *range_names, int fd,
+                                  uint64_t *bytes_written, double *seconds3) {
+  return text_batch_fd(ix, ranges, n, params, subset_keep, merge_distance, range_names, fd, bytes_written, seconds3, true);
 }
 
 int impg_gpu_results_paf(const impg_gpu_results_t *res, const impg_gpu_index_t *ix, const char *const *range_names,
@@ -1411,6 +1446,38 @@ int impg_gpu_selftest_bed_rows(impg_gpu_index_t *ix, const impg_gpu_interval_t *
   memcpy(t, out.data(), out.size());
   t[out.size()] = 0;
   *merged_out = m; *n_merged = merged.size(); *text = t; *len = out.size();
+  return IMPG_OK;
+  IMPG_CATCH
+}
+
+// The device BEDPE merge and text on rows and CIGARs the caller brings (diagnostics; tests/test_gpu_bedpe_device.py): what a
+// chunk of impg_gpu_query_batch_bedpe runs once its rows and their ops are placed (bedpe_device.hip), without a query in front.
+int impg_gpu_selftest_bedpe_rows(impg_gpu_index_t *ix, const impg_gpu_interval_t *rows, const uint32_t *row_range, size_t n_rows,
+                                 uint32_t n_ranges, const uint64_t *cigar_off, const uint32_t *cigar_ops, int32_t merge_distance,
+                                 int original_sequence_coordinates, const char *const *range_names, char **text, size_t *len) {
+  IMPG_TRY
+  if (!ix || !text || !len || !cigar_off || (n_rows && (!rows || !row_range))) throw Error{IMPG_E_INVALID, "null argument"};
+  bedpe_refusals(*ix);
+  if (n_rows >= 0xFFFFFFF0ull) throw Error{IMPG_E_INVALID, "too many rows"};
+  if (cigar_off[0] != 0 || (cigar_off[n_rows] && !cigar_ops)) throw Error{IMPG_E_INVALID, "CIGAR offsets start at 0 and come with their ops"};
+  for (size_t i = 0; i < n_rows; i++) {
+    if (rows[i].query_id >= ix->view.n_seq || rows[i].target_id >= ix->view.n_seq) throw Error{IMPG_E_INVALID, "a row's sequence id is not one of the index's"};
+    if (row_range[i] >= n_ranges || (i && row_range[i] < row_range[i - 1])) throw Error{IMPG_E_INVALID, "the rows come grouped by range, range indices below n_ranges"};
+    if (cigar_off[i + 1] < cigar_off[i]) throw Error{IMPG_E_INVALID, "CIGAR offsets must not decrease"};
+  }
+  std::vector<std::string> rnames(n_ranges);
+  for (uint32_t q = 0; q < n_ranges; q++) rnames[q] = range_names && range_names[q] ? std::string(range_names[q]) : std::to_string(q);
+  IMPG_HIP(hipSetDevice(ix->device));
+  EngineLease lease(*ix);
+  ix->bedpe_stats_reset();
+  std::string out;
+  if (n_ranges) device_bedpe_selftest(*lease, *ix, rows, row_range, (uint32_t)n_rows, n_ranges, cigar_off, cigar_ops, merge_distance,
+                                      original_sequence_coordinates != 0, rnames, out);
+  char *t = (char *)malloc(out.size() + 1);
+  if (!t) throw Error{IMPG_E_OOM, "host out of memory"};
+  memcpy(t, out.data(), out.size());
+  t[out.size()] = 0;
+  *text = t; *len = out.size();
   return IMPG_OK;
   IMPG_CATCH
 }

@@ -347,7 +347,8 @@ bool run_chunk_rows(const impg_gpu_index &ix, Engine &E, const impg_gpu_range_t 
 // added to seconds3.  gpu_turn is held through the text.  false: an empty chunk, as above (no time is added).
 bool run_chunk_bed(const impg_gpu_index &ix, Engine &E, const impg_gpu_range_t *d_ranges, const impg_gpu_range_t *h_ranges,
                    const char *const *range_names, size_t b, size_t e, const impg_gpu_params_t &p, int32_t merge_distance,
-                   const std::function<void(const char *, size_t)> &sink, double *seconds3, std::mutex *gpu_turn = nullptr);
+                   const std::function<void(const char *, size_t)> &sink, double *seconds3, std::mutex *gpu_turn = nullptr,
+                   bool bedpe = false);  // bedpe: p.store_cigar set; the BEDPE merge and lines instead (bedpe_device.hip)
 // ---- result rows on the device (rows_device.hip) ---------------------------------------------------------------
 // Where every emitted slot of a chunk goes among the chunk's result rows (grouped by range, emission order within).
 struct RowPlan {
@@ -377,6 +378,15 @@ uint32_t device_bed_rows(Engine &E, const impg_gpu_index &ix, uint32_t n_ranges,
 void device_bed_text(Engine &E, const impg_gpu_index &ix, const DevBuf &rows, uint32_t n_rows, uint32_t n_ranges,
                      const std::vector<std::string> &rnames, bool original_coords,
                      const std::function<void(const char *, size_t)> &sink);
+// ---- BEDPE on the device (bedpe_device.hip): the same two steps for a chunk run with store_cigar ---------------------------
+uint32_t device_bedpe_rows(Engine &E, const impg_gpu_index &ix, uint32_t n_ranges, const impg_gpu_params_t &p, int32_t merge_distance,
+                           std::vector<std::unique_ptr<LevelBufs>> &levels, DevBuf &self_dev, DevBuf &out);
+void device_bedpe_text(Engine &E, const impg_gpu_index &ix, const DevBuf &runs, uint32_t n_runs, uint32_t n_ranges,
+                       const std::vector<std::string> &rnames, bool original_coords,
+                       const std::function<void(const char *, size_t)> &sink);
+void device_bedpe_selftest(Engine &E, const impg_gpu_index &ix, const impg_gpu_interval_t *rows, const uint32_t *row_range, uint32_t n,
+                           uint32_t n_ranges, const uint64_t *cigar_off, const uint32_t *cigar_ops, int32_t merge_distance, bool original_coords,
+                           const std::vector<std::string> &rnames, std::string &text);
 // the diagnostic entry's device part: the caller's rows through the same merge and text (impg_gpu_selftest_bed_rows)
 struct BedGapRows { std::vector<uint32_t> range; std::vector<impg_gpu_interval_t> rows; };  // the rows between the two merges, in their order
 void device_bed_selftest(Engine &E, const impg_gpu_index &ix, const impg_gpu_interval_t *rows, const uint32_t *row_range, uint32_t n,

@@ -1,0 +1,71 @@
+// What the device text writers share (bed_device.hip: BED rows; bedpe_device.hip: BEDPE lines): the name / shift /
+// range-name tables, the decimal printers, and the piece loop that moves finished text across PCIe
+// (device_text_pieces, defined in bed_device.hip).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <atomic>
+#include <functional>
+#include <string>
+#include <vector>
+
+#include "engine.hpp"
+
+namespace impg {
+
+struct TextTables {
+  const char *names;            // printed sequence names back to back ("base" under --original-sequence-coordinates)
+  const uint32_t *name_off;     // [n_seq + 1]
+  const uint32_t *shift;        // [n_seq] offset added to the coordinates (main.rs:11876-11883)
+  uint32_t n_names;             // 0: sequences print as their ids
+  const char *rnames;           // the chunk's range names back to back
+  const uint32_t *rname_off;    // [n_ranges + 1]
+};
+__device__ __forceinline__ uint32_t dec_digits(uint32_t v) {
+  uint32_t d = 1;
+  while (v >= 10u) { v /= 10u; d++; }
+  return d;
+}
+__device__ __forceinline__ char *put_dec(char *p, uint32_t v, uint32_t digits) {
+  for (uint32_t k = digits; k > 0; k--) { p[k - 1] = (char)('0' + v % 10u); v /= 10u; }
+  return p + digits;
+}
+// a sequence as it prints: its name, or its id where the index has no names
+__device__ __forceinline__ uint32_t seq_text_len(const TextTables &t, uint32_t id) {
+  return id < t.n_names ? t.name_off[id + 1] - t.name_off[id] : dec_digits(id);
+}
+__device__ __forceinline__ char *put_seq(char *p, const TextTables &t, uint32_t id) {
+  if (id >= t.n_names) return put_dec(p, id, dec_digits(id));
+  const char *nm = t.names + t.name_off[id];
+  const uint32_t nl = t.name_off[id + 1] - t.name_off[id];
+  for (uint32_t k = 0; k < nl; k++) p[k] = nm[k];
+  return p + nl;
+}
+__device__ __forceinline__ uint32_t seq_shift(const TextTables &t, uint32_t id) { return id < t.n_names ? t.shift[id] : 0u; }
+__device__ __forceinline__ char *put_range_name(char *p, const TextTables &t, uint32_t q) {
+  const char *rn = t.rnames + t.rname_off[q];
+  const uint32_t rl = t.rname_off[q + 1] - t.rname_off[q];
+  for (uint32_t k = 0; k < rl; k++) p[k] = rn[k];
+  return p + rl;
+}
+
+// The tables of one chunk on the device (uploaded on E.stream; they live as long as this object)
+struct TextTableBufs {
+  DevBuf d_nb, d_noff, d_shift, d_rb, d_roff;
+  TextTables t{};
+  TextTableBufs(Engine &E, const impg_gpu_index &ix, uint32_t n_ranges, const std::vector<std::string> &rnames, bool original_coords);
+
+ private:
+  std::string nb, rb;  // (the sources of the asynchronous uploads)
+  std::vector<uint32_t> noff, nshift, roff;
+};
+
+// n_rows rows of d_len[r] bytes each as text, streamed to `sink(ptr, bytes)` in pieces of whole rows of at most PIECE
+// bytes (option bed_text_piece_bytes) through two pinned buffers: while the host consumes one piece the device formats
+// and copies the next.  write(r0, r1, d_off + r0, base, out) enqueues the kernel that writes rows [r0, r1), row r at
+// out + (d_off[r] - base).  what: the row's kind, for the refusal of a single row longer than the buffer.
+void device_text_pieces(Engine &E, const uint32_t *d_len, uint32_t n_rows, const char *what,
+                        const std::function<void(uint32_t, uint32_t, const unsigned long long *, unsigned long long, char *)> &write,
+                        const std::function<void(const char *, size_t)> &sink, std::atomic<uint64_t> &pieces, std::atomic<uint64_t> &bytes);
+
+}  // namespace impg

@@ -554,6 +554,29 @@ class GpuImpg:
 
     def query_batch_bed(self, ranges, params=None, merge_distance=0, range_names=None, subset_keep=None, timing=False, raw=False, **kw):
         """impg_gpu_query_batch_bed: query + both BED merges on the device + text (what `impg query -o bed` prints)."""
+        return self._query_batch_text(lib().impg_gpu_query_batch_bed, ranges, params, merge_distance, range_names, subset_keep, timing, raw, kw)
+
+    def query_batch_bedpe(self, ranges, params=None, merge_distance=0, range_names=None, subset_keep=None, timing=False, raw=False, fd=None,
+                          **kw):
+        """impg_gpu_query_batch_bedpe: query + CIGAR summaries + merge_adjusted_intervals on the device + text (what
+        `impg query -b` prints by default); store_cigar is implied.  fd: impg_gpu_query_batch_bedpe_fd -- the text is
+        written there and the number of bytes returned in its place."""
+        if fd is None:
+            return self._query_batch_text(lib().impg_gpu_query_batch_bedpe, ranges, params, merge_distance, range_names, subset_keep, timing,
+                                          raw, kw)
+        p = params or make_params(**kw)
+        r = self._ranges(ranges)
+        arr = None
+        if range_names is not None:
+            arr = (C.c_char_p * len(range_names))(*[None if s is None else s.encode() for s in range_names])
+        keep = None if subset_keep is None else np.ascontiguousarray(subset_keep, dtype=np.uint8)
+        done = C.c_uint64(0)
+        sec = (C.c_double * 3)()
+        check(lib().impg_gpu_query_batch_bedpe_fd(self._h, r.ctypes.data, r.size, C.byref(p), None if keep is None else keep.ctypes.data,
+                                                  merge_distance, arr, fd, C.byref(done), sec))
+        return (done.value, list(sec)) if timing else done.value
+
+    def _query_batch_text(self, entry, ranges, params, merge_distance, range_names, subset_keep, timing, raw, kw):
         p = params or make_params(**kw)
         r = self._ranges(ranges)
         arr = None
@@ -563,8 +586,8 @@ class GpuImpg:
         text = C.c_void_p(None)
         ln = C.c_size_t(0)
         sec = (C.c_double * 3)()
-        check(lib().impg_gpu_query_batch_bed(self._h, r.ctypes.data, r.size, C.byref(p), None if keep is None else keep.ctypes.data,
-                                             merge_distance, arr, C.byref(text), C.byref(ln), sec))
+        check(entry(self._h, r.ctypes.data, r.size, C.byref(p), None if keep is None else keep.ctypes.data, merge_distance, arr, C.byref(text),
+                    C.byref(ln), sec))
         try:
             out = C.string_at(text, ln.value)
         finally:
@@ -606,6 +629,28 @@ class GpuImpg:
                 _lib.free(grows)
                 _lib.free(grange)
         return (out, txt, gr, gq) if gap else (out, txt)
+
+    def bedpe_rows(self, rows, row_range, n_ranges, cigars, merge_distance=0, original_sequence_coordinates=False, range_names=None):
+        """impg_gpu_selftest_bedpe_rows (diagnostics): the device BEDPE merge and text of query_batch_bedpe on the caller's
+        rows (INTERVAL_DTYPE, grouped by range: row_range[i] = the range of rows[i], its first row the one that is dropped)
+        and their packed CIGAR ops (cigars[i]: uint32 array of rows[i]).  Returns the text as bytes."""
+        a = np.ascontiguousarray(rows, dtype=INTERVAL_DTYPE)
+        rr = np.ascontiguousarray(row_range, dtype=np.uint32)
+        if a.size != rr.size or a.size != len(cigars):
+            raise _lib.ImpgGpuError(_lib.IMPG_E_INVALID, "one range index and one CIGAR per row")
+        off = np.zeros(a.size + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(cg) for cg in cigars], dtype=np.uint64)
+        ops = np.ascontiguousarray(np.concatenate([np.asarray(cg, dtype=np.uint32) for cg in cigars] + [np.zeros(0, dtype=np.uint32)]))
+        arr = None
+        if range_names is not None:
+            arr = (C.c_char_p * len(range_names))(*[None if s is None else (s if isinstance(s, bytes) else s.encode()) for s in range_names])
+        text, ln = C.c_void_p(None), C.c_size_t(0)
+        check(lib().impg_gpu_selftest_bedpe_rows(self._h, a.ctypes.data, rr.ctypes.data, a.size, n_ranges, off.ctypes.data, ops.ctypes.data,
+                                                 merge_distance, int(bool(original_sequence_coordinates)), arr, C.byref(text), C.byref(ln)))
+        try:
+            return C.string_at(text, ln.value)
+        finally:
+            _lib.free(text)
 
     def approximate(self):
         """True for an index built from tracepoints (every answer is the reference's approximate mode)."""

@@ -246,7 +246,9 @@ int impg_gpu_index_approximate(const impg_gpu_index_t *);
  * "update_stats" / "lookup_stats" (0, the default; 1: the "update_*" / "lookup_wide_*" counters below are kept, one small
  * copy per level), "bed_text_piece_bytes" (64 .. 2^40; 256 MiB by default: the text of impg_gpu_query_batch_bed crosses
  * PCIe in pieces of whole rows of at most this many bytes, a piece of one row may be up to 4096 bytes longer; a row
- * beyond that is IMPG_E_UNSUPPORTED; the text is identical for every value).  For tests of the multi-rank paths: "lane_schedule" (forced lane start / hand-over order of a sharded
+ * beyond that is IMPG_E_UNSUPPORTED; the text is identical for every value; impg_gpu_query_batch_bedpe's text crosses the
+ * same way), "bedpe_group_log2" (2 .. 6; 2 by default: impg_gpu_query_batch_bedpe sums a row's CIGAR ops with 2^value
+ * lanes; results identical).  For tests of the multi-rank paths: "lane_schedule" (forced lane start / hand-over order of a sharded
  * batch; 0 = off), "debug_fail_owner" / "debug_fail_home" (failure injection: (rank + 1) << 16 | hop of the batch at which
  * that rank throws on the owner / on the home side of the hop; 0 = off).
  * A multi-GPU handle hands "chunk_ranges", "pair_budget", "locality_min", "debug_fail_owner", "debug_fail_home",
@@ -287,7 +289,12 @@ const char *impg_gpu_counter_key(size_t i);
  * (impg_gpu_query_batch_bed, impg_gpu_query_batch_bed_fd, impg_gpu_selftest_bed_rows; zero when it starts, every chunk adds;
  * on a multi-GPU handle its ranks count, not the handle): "bed_rows" = rows entering the merges, "bed_gap_roots" = rows
  * after merge_adjusted_intervals_gap_2d, "bed_runs" = merged rows out, "bed_text_pieces" = text pieces sent to the host,
- * "bed_text_bytes" = bytes printed.  Of the build of the index itself (a multi-GPU handle answers with the sum over its
+ * "bed_text_bytes" = bytes printed.  Of the last device BEDPE call on the handle (impg_gpu_query_batch_bedpe,
+ * impg_gpu_query_batch_bedpe_fd; kept the same way): "bedpe_rows" = rows after each range's first is dropped,
+ * "bedpe_runs" = lines printed, "bedpe_joins_contiguous" / "bedpe_joins_gap" = rows joined to the row before them by either
+ * arm of merge_adjusted_intervals, "bedpe_fused_ops" = I / D ops removed by fusing neighbours, at joins and inside joined
+ * rows, "bedpe_summary_ops" = CIGAR ops the summary kernel read, "bedpe_text_pieces" = text pieces sent to the host,
+ * "bedpe_text_bytes" = bytes printed.  Of the build of the index itself (a multi-GPU handle answers with the sum over its
  * ranks): "build_device" = 1 if the device builder produced it, 0 if the host builder did (IMPG_BUILD_HOST, tracepoints, a
  * loaded .impg file's entry order, a card short of memory for the build, an index loaded from a saved file);
  * "tokenized_device" = 1 if the device tokenised its CIGAR text (impg_gpu_index_create_from_paf on one GPU);
@@ -540,6 +547,26 @@ int impg_gpu_query_batch_bed_fd(impg_gpu_index_t *, const impg_gpu_range_t *rang
 int impg_gpu_results_paf(const impg_gpu_results_t *, const impg_gpu_index_t *,
                          const char *const *range_names, const impg_gpu_params_t *params,
                          int32_t merge_distance, int format, char **text, size_t *len);
+
+/* ---- BEDPE on the device (bedpe_device.hip): perform_query + results.remove(0) + merge_adjusted_intervals +
+ *      output_results_bedpe for a whole batch in one call, byte-identical to impg_gpu_query_batch_filtered with
+ *      store_cigar = 1 + impg_gpu_results_paf(IMPG_OUT_BEDPE) (what `impg query -b` prints by default).  BEDPE prints no
+ *      CIGAR, only gi:f / bi:f: every row's ops are summed where the engine left them, rows are sorted, joined with the
+ *      row before them and printed on the device; no row and no op crosses PCIe, only text, in pinned pieces (option
+ *      "bed_text_piece_bytes").  Arguments, range_names, subset_keep and seconds3 {engine, rows + CIGARs + summaries +
+ *      merge, text} as impg_gpu_query_batch_bed; params->store_cigar is taken as 1.  Errors, each raised before any text
+ *      of the chunk (option "chunk_ranges") that holds it is delivered: IMPG_E_INVALID for a range without a row to drop
+ *      and for a target interval that runs backwards where the reference looks (a range with two rows or more, merge_distance
+ *      >= 0); IMPG_E_UNSUPPORTED for a row without ops, and -- where impg_gpu_results_paf still serves -- for a sharded or
+ *      multi-GPU handle, for an index with a sequence of 2^29 bases or more (a fused op that long would wrap into its code
+ *      bits there) and for a tracepoint index without option "approximate_cigar". ---- */
+int impg_gpu_query_batch_bedpe(impg_gpu_index_t *, const impg_gpu_range_t *ranges, size_t n, const impg_gpu_params_t *params,
+                               const uint8_t *subset_keep, int32_t merge_distance, const char *const *range_names, char **text,
+                               size_t *len, double *seconds3);
+/* The same, the text written to a file descriptor piece by piece (what the CLI does). */
+int impg_gpu_query_batch_bedpe_fd(impg_gpu_index_t *, const impg_gpu_range_t *ranges, size_t n, const impg_gpu_params_t *params,
+                                  const uint8_t *subset_keep, int32_t merge_distance, const char *const *range_names, int fd,
+                                  uint64_t *bytes_written, double *seconds3);
 
 /* ---- host-side ingest helpers (paf.rs, partition.rs parsers) -------------- */
 /* parse_cigar_to_delta (impg.rs:2935-2950): returns #ops or <0 */
@@ -895,6 +922,15 @@ typedef struct {
   int32_t start, end; /* printed as u32 */
   uint32_t strand;    /* 0 '+', 1 '-' */
 } impg_gpu_bed_row_t;
+/* Diagnostics: the device BEDPE merge and text of impg_gpu_query_batch_bedpe (impg_amd/csrc/bedpe_device.hip) on rows and
+ * CIGARs the caller brings instead of a query's.  rows[i] belongs to range row_range[i] < n_ranges; the rows come grouped
+ * by range (row_range does not decrease), a range's first row being the one that is dropped; cigar_ops[cigar_off[i] ..
+ * cigar_off[i + 1]) are row i's packed ops (cigar_off[n_rows + 1], starting at 0); sequence ids are the index's.
+ * range_names: NULL, or NULL entries, print the range's index.  Errors as impg_gpu_query_batch_bedpe; IMPG_E_INVALID also
+ * for arrays that break the rules above.  *text is malloc'ed; free() it.  Sets the "bedpe_*" counters. */
+int impg_gpu_selftest_bedpe_rows(impg_gpu_index_t *ix, const impg_gpu_interval_t *rows, const uint32_t *row_range, size_t n_rows,
+                                 uint32_t n_ranges, const uint64_t *cigar_off, const uint32_t *cigar_ops, int32_t merge_distance,
+                                 int original_sequence_coordinates, const char *const *range_names, char **text, size_t *len);
 int impg_gpu_selftest_bed_rows(impg_gpu_index_t *ix, const impg_gpu_interval_t *rows, const uint32_t *row_range, size_t n_rows,
                                uint32_t n_ranges, uint64_t n_seq, int32_t merge_distance, int merge_strands,
                                int original_sequence_coordinates, const char *const *range_names,
