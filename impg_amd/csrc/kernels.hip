@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstring>
+#include <type_traits>
 
 #include "device_prims.hpp"
 #include "impg_internal.hpp"
@@ -2357,7 +2358,7 @@ void project_entries_kernel(DeviceIndexView v, const uint32_t *__restrict__ pair
   constexpr bool ordered = OUT == OUT_ROWS;
   constexpr bool qs = OUT == OUT_QS;  // slots as {query id, the range's place} pairs in h.qid (a kept fused level)
   constexpr bool WIDE_LISTED = ordered;  // windows wider than the hit mask: listed (pair_entry, in visit order) or by the window test
-  __shared__ uint32_t st_nwide, st_alloc, st_next;
+  __shared__ uint32_t st_nwide, st_alloc, st_next, st_anywide;
   __shared__ uint32_t wred[2u * ENT_WAVES];
   __shared__ uint32_t wcnt[ENT_WAVES];
   const uint32_t r0 = sblock * ENT_RANGES;
@@ -2371,9 +2372,11 @@ void project_entries_kernel(DeviceIndexView v, const uint32_t *__restrict__ pair
 #define STG_MARK(i) do { } while (0)
 #endif
   STG_MARK(0);
-  if (threadIdx.x == 0) { st_nwide = 0u; st_alloc = 0u; st_next = 0u; }
+  if (threadIdx.x == 0) { st_nwide = 0u; st_alloc = 0u; st_next = 0u; st_anywide = 0u; }
   __syncthreads();
-  // the block's ranges: place offsets, windows, ends; the span of entries their masks name; the ranges listed instead
+  // the block's ranges: place offsets, windows, ends; the span of entries their masks name; the ranges listed instead.
+  // Beyond the level's last range the windows are padded with empty ones ({0, 0, no mask bit}: nothing hits them), so
+  // the entry loop's scan tests whole groups of 64 ranges without asking how many the block has.
   uint32_t emin = 0xFFFFFFFFu, emax = 0u;
 #pragma unroll
   for (uint32_t t = threadIdx.x; t < ENT_RANGES; t += ENT_THREADS) {
@@ -2388,6 +2391,7 @@ void project_entries_kernel(DeviceIndexView v, const uint32_t *__restrict__ pair
       { const FrontierRec sf = wl.se[r0 + t]; st_se[t] = make_int2(sf.start, sf.end); }
       if (ordered) st_dest[t] = wl.ord.dest[r0 + t];
       if (w.y - (w.x & ~3u) > 64u) {
+        st_anywide = 1u;  // (block-uniform once the block has met: its entry loop takes the general scan)
         // a window wider than the hit mask (a dense target, a repeat hot spot).  Where slots may be filled entry by entry its hits
         // join the entry-major loop below, named by the window test itself instead of a mask bit; ordered rows need the hit's
         // visit position, which only the listed form has: those ranges are listed and taken a lane per place at the end
@@ -2399,7 +2403,7 @@ void project_entries_kernel(DeviceIndexView v, const uint32_t *__restrict__ pair
         emin = min(emin, glo);
         emax = max(emax, ghi);
       }
-    }
+    } else st_win[t] = make_uint4(0u, 0u, 0u, 0u);
   }
   {
 #pragma unroll
@@ -2446,110 +2450,138 @@ void project_entries_kernel(DeviceIndexView v, const uint32_t *__restrict__ pair
     // bytes (one address for the whole wave, then scalar registers), then its record's <= 8 prefix lines, a 16-byte
     // piece per lane, into the wave's own LDS record -- two entries ahead / one record ahead of the one being worked
     // on, so that the index's latency hides behind the projections.  No barrier: the block shares only the ranges' data.
-    const uint4 *ents = reinterpret_cast<const uint4 *>(v.entries);
+    //
+    // The loop exists twice, chosen once per block (a scalar branch): NARROW where no window of the block is wider than
+    // the hit mask -- every block of the headline -- tests nothing but the mask bit; the general form also carries the
+    // wide windows' test on the entry's own end.  In one loop body the compiler keeps both arms, their branches and
+    // their registers for every group of 64 ranges.
+    // Both prefetches are addressed as a wave-uniform 64-bit base (scalar registers) plus the lane's 16-byte piece as a
+    // 32-bit offset: as 64-bit vector addresses the two base pointers were spilled and reloaded, behind a full drain of
+    // the loads in flight, once an entry.
     const uint4 zero4 = make_uint4(0u, 0u, 0u, 0u);
     const uint32_t n_span = emax - emin + 1u;
-    auto take = [&]() -> uint32_t {  // the next entry of the span (>= n_span: none left); a slice takes every n_slices-th
-      uint32_t i = 0;
-      if (l == 0) i = atomicAdd(&st_next, 1u);
-      i = (uint32_t)__builtin_amdgcn_readfirstlane((int)i);
-      return n_slices > 1u ? min(n_span, slice + i * n_slices) : i;
-    };
-    uint32_t ic = take(), in = take();
-    // (an entry's 64 bytes are held as one 16-byte piece in each of lanes 0 .. 3 -- four registers for an entry in flight
-    // instead of sixteen with every lane reading all four pieces: with two entries in flight that is 24 registers of
-    // the kernel's 126; its words are picked off the lanes into scalar registers when its turn comes)
-    uint4 cq = zero4, nq = zero4, lc = zero4;
-    auto fetch_entry = [&](uint32_t i) -> uint4 {
-      uint4 q = zero4;
-      if (i < n_span && l < 4u) q = ents[(size_t)(emin + i) * 4u + l];
-      return q;
-    };
+    const bool any_wide = (uint32_t)__builtin_amdgcn_readfirstlane((int)st_anywide) != 0u;
+    auto entry_loop = [&](auto narrow_c) __attribute__((always_inline)) {
+      constexpr bool NARROW = decltype(narrow_c)::value;
+      // (the base is pinned to a scalar register pair and the lane's offset stays 32 bits wide: `global_load v, s[base:base+1]`)
+      auto load_piece = [&](const void *base, size_t off, uint32_t lane) -> uint4 {
+        typedef uint32_t words4 __attribute__((ext_vector_type(4)));
+        unsigned long long b = (unsigned long long)base + off;
+        asm volatile("" : "+s"(b));
+        const words4 x = *reinterpret_cast<const __attribute__((address_space(1))) words4 *>(b + (unsigned long long)(lane << 4));
+        return make_uint4(x.x, x.y, x.z, x.w);
+      };
+      // (the lane number as the loop sees it: taken afresh every entry, so that what is derived from it -- the lanes' LDS
+      // addresses, the masks of lanes 0 and 0 .. 3 -- is formed where it is used and not kept, or spilled, across the chunks)
+      uint32_t ll = l;
+      auto take = [&]() -> uint32_t {  // the next entry of the span (>= n_span: none left); a slice takes every n_slices-th
+        uint32_t i = 0;
+        if (ll == 0) i = atomicAdd(&st_next, 1u);
+        i = (uint32_t)__builtin_amdgcn_readfirstlane((int)i);
+        return min(n_span, slice + i * n_slices);  // (a block taken whole: slice 0 of 1)
+      };
+      uint32_t ic = take(), in = take();
+      // (an entry's 64 bytes are held as one 16-byte piece in each of lanes 0 .. 3 -- four registers for an entry in flight
+      // instead of sixteen with every lane reading all four pieces: with two entries in flight that is 24 registers of
+      // the kernel's 126; its words are picked off the lanes into scalar registers when its turn comes)
+      uint4 cq = zero4, nq = zero4, lc = zero4;
+      auto fetch_entry = [&](uint32_t i) -> uint4 {
+        uint4 q = zero4;
+        if (i < n_span && ll < 4u) q = load_piece(v.entries, (size_t)(emin + i) * 64u, ll);
+        return q;
+      };
 #define IMPG_RDL(x, j) (uint32_t)__builtin_amdgcn_readlane((int)(x), j)
-    auto fetch_record = [&](const uint4 &q) -> uint4 {  // the record's <= 8 prefix lines, a 16-byte piece per lane
-      uint4 r = zero4;
-      const uint32_t nz = IMPG_RDL(q.z, 1), ny = IMPG_RDL(q.y, 1);  // the entry's words 6 and 5: op count | flags, first tile
-      const uint32_t m = ((nz & OP_LEN_MASK) + TILE_OPS - 1u) / TILE_OPS;
-      if (m <= INLINE_TILES && (l >> 3) < m) r = reinterpret_cast<const uint4 *>(v.pfx + (size_t)ny * TILE_WORDS)[l];
-      return r;
-    };
-    cq = fetch_entry(ic);
-    nq = fetch_entry(in);
-    if (ic < n_span) lc = fetch_record(cq);
+      auto fetch_record = [&](const uint4 &q) -> uint4 {  // the record's <= 8 prefix lines, a 16-byte piece per lane
+        uint4 r = zero4;
+        const uint32_t nz = IMPG_RDL(q.z, 1), ny = IMPG_RDL(q.y, 1);  // the entry's words 6 and 5: op count | flags, first tile
+        const uint32_t m = ((nz & OP_LEN_MASK) + TILE_OPS - 1u) / TILE_OPS;
+        if (m <= INLINE_TILES && (ll >> 3) < m) r = load_piece(v.pfx, (size_t)ny * (TILE_WORDS * 4u), ll);
+        return r;
+      };
+      cq = fetch_entry(ic);
+      nq = fetch_entry(in);
+      if (ic < n_span) lc = fetch_record(cq);
 #pragma unroll 1
-    while (ic < n_span) {
-      const uint32_t eidx = emin + ic;
-      // this entry's record into the wave's LDS record (the previous entry's reads are done: their results were used)
-      __builtin_amdgcn_wave_barrier();
-      st_rec[wv][(l >> 3) * (STG_LINE_STRIDE / 4u) + (l & 7u)] = lc;
-      if (l < 4u) st_rec[wv][ENT_CP_OFF / 4u + ((l + 3u) & 3u)] = cq;  // (words 4 .. 15, then 0 .. 3)
-      uint4 e0, e1, e2, e3;
-      e0.x = IMPG_RDL(cq.x, 0); e0.y = IMPG_RDL(cq.y, 0); e0.z = IMPG_RDL(cq.z, 0); e0.w = IMPG_RDL(cq.w, 0);
-      e1.x = IMPG_RDL(cq.x, 1); e1.y = IMPG_RDL(cq.y, 1); e1.z = IMPG_RDL(cq.z, 1); e1.w = IMPG_RDL(cq.w, 1);
-      e2.x = IMPG_RDL(cq.x, 2); e2.y = IMPG_RDL(cq.y, 2); e2.z = IMPG_RDL(cq.z, 2); e2.w = IMPG_RDL(cq.w, 2);
-      e3.x = IMPG_RDL(cq.x, 3); e3.y = IMPG_RDL(cq.y, 3); e3.z = IMPG_RDL(cq.z, 3); e3.w = IMPG_RDL(cq.w, 3);
-      // the next entry of the wave moves up; its record and the entry after it are requested
-      ic = in;
-      cq = nq;
-      lc = zero4;
-      if (ic < n_span) {
-        lc = fetch_record(cq);
-        in = take();
-        nq = fetch_entry(in);
-      }
-      // the block's ranges that hit the entry, 64 at a time: bit (entry - window start) of the range's mask
-      uint32_t cnt = 0;
-      // (what the count pass tested a wide window's entries with -- ends[] / ends_t[] -- from the entry's own words: no load)
-      const int32_t e_end = TRANSITIVE ? ((int32_t)e0.x < (int32_t)e0.y ? (int32_t)e0.y : (-2147483647 - 1)) : (int32_t)e0.y;
+      while (ic < n_span) {
+        const uint32_t eidx = emin + ic;
+        asm volatile("" : "+v"(ll));
+        // this entry's record into the wave's LDS record (the previous entry's reads are done: their results were used)
+        __builtin_amdgcn_wave_barrier();
+        st_rec[wv][(ll >> 3) * (STG_LINE_STRIDE / 4u) + (ll & 7u)] = lc;
+        if (ll < 4u) st_rec[wv][ENT_CP_OFF / 4u + ((ll + 3u) & 3u)] = cq;  // (words 4 .. 15, then 0 .. 3)
+        uint4 e0, e1, e2, e3;
+        e0.x = IMPG_RDL(cq.x, 0); e0.y = IMPG_RDL(cq.y, 0); e0.z = IMPG_RDL(cq.z, 0); e0.w = IMPG_RDL(cq.w, 0);
+        e1.x = IMPG_RDL(cq.x, 1); e1.y = IMPG_RDL(cq.y, 1); e1.z = IMPG_RDL(cq.z, 1); e1.w = IMPG_RDL(cq.w, 1);
+        e2.x = IMPG_RDL(cq.x, 2); e2.y = IMPG_RDL(cq.y, 2); e2.z = IMPG_RDL(cq.z, 2); e2.w = IMPG_RDL(cq.w, 2);
+        e3.x = IMPG_RDL(cq.x, 3); e3.y = IMPG_RDL(cq.y, 3); e3.z = IMPG_RDL(cq.z, 3); e3.w = IMPG_RDL(cq.w, 3);
+        // the next entry of the wave moves up; its record and the entry after it are requested
+        ic = in;
+        cq = nq;
+        lc = zero4;
+        if (ic < n_span) {
+          lc = fetch_record(cq);
+          in = take();
+          nq = fetch_entry(in);
+        }
+        // the block's ranges that hit the entry, 64 at a time: bit (entry - window start) of the range's mask
+        uint32_t cnt = 0;
+        // (what the count pass tested a wide window's entries with -- ends[] / ends_t[] -- from the entry's own words: no load)
+        const int32_t e_end = TRANSITIVE ? ((int32_t)e0.x < (int32_t)e0.y ? (int32_t)e0.y : (-2147483647 - 1)) : (int32_t)e0.y;
 #pragma unroll
-      for (uint32_t q = 0; q < ENT_RANGES / 64u; q++) {
-        const uint32_t r = q * 64u + l;
-        bool hit = false;
-        if (r < nr) {
-          const uint4 w = st_win[r];
+        for (uint32_t q = 0; q < ENT_RANGES / 64u; q++) {
+          const uint32_t r = q * 64u + ll;
+          bool hit = false;
+          const uint4 w = st_win[r];  // (a padded window beyond the block's ranges is empty and has no mask bit)
           const uint32_t d = eidx - w.x;
-          if (w.y - (w.x & ~3u) <= 64u) hit = d < 64u && (((d < 32u ? w.z >> d : w.w >> (d - 32u)) & 1u) != 0u);
+          if (NARROW) {
+            // bit d of the mask, shifted up into the sign: by 63 - d, of which the shift reads the low six bits -- those of
+            // ~d = window start + ~entry, one addition.  No short cut between the two tests: one read, no branch
+            const uint32_t nd = w.x + ~eidx;
+            hit = (nd >= ~63u) & ((int32_t)(((((unsigned long long)w.w << 32) | w.z) << (nd & 63u)) >> 32) < 0);
+          } else if (w.y - (w.x & ~3u) <= 64u) hit = d < 64u && (((d < 32u ? w.z >> d : w.w >> (d - 32u)) & 1u) != 0u);
           else if (!WIDE_LISTED) hit = eidx >= w.x && eidx < w.y && window_hit<TRANSITIVE>(e_end, st_se[r].x);  // the count pass's own test
+          const unsigned long long b = __builtin_amdgcn_ballot_w64(hit);
+          if (hit) (&st_list[wv][cnt])[__builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u))] = (uint16_t)r;  // (+ the hits in lower lanes)
+          cnt += (uint32_t)__popcll(b);
         }
-        const unsigned long long b = __ballot(hit);
-        if (hit) st_list[wv][cnt + (uint32_t)__popcll(b & lanemask_lt())] = (uint16_t)r;
-        cnt += (uint32_t)__popcll(b);
-      }
-      uint32_t run = 0;  // compact: the entry's first place
-      if (compact) {
-        if (l == 0) run = n_slices > 1u ? atomicAdd(&sl.alloc[sblock], cnt) : atomicAdd(&st_alloc, cnt);  // (slices share the block's places)
-        run = P0 + (uint32_t)__builtin_amdgcn_readfirstlane((int)run);
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_wave_barrier();
-      const uint32_t *rec = reinterpret_cast<const uint32_t *>(&st_rec[wv][0]);
-      const int orient = (e1.z & OP_LEN_MASK) > INLINE_TILES * TILE_OPS ? -1 : !(e1.z & EF_REVERSED) ? 0 : (e1.z & EF_STRAND) ? 2 : 1;
-      // ordered rows: the target of every row of this entry is the sequence its ranges look up -- the first one's says it
-      uint32_t tid = 0;
-      if (ordered && cnt) tid = wl.se[r0 + (uint32_t)__builtin_amdgcn_readfirstlane((int)st_list[wv][0])].target_id;
+        uint32_t run = 0;  // compact: the entry's first place
+        if (compact) {
+          if (ll == 0) run = n_slices > 1u ? atomicAdd(&sl.alloc[sblock], cnt) : atomicAdd(&st_alloc, cnt);  // (slices share the block's places)
+          run = P0 + (uint32_t)__builtin_amdgcn_readfirstlane((int)run);
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_wave_barrier();
+        const uint32_t *rec = reinterpret_cast<const uint32_t *>(&st_rec[wv][0]);
+        const int orient = (e1.z & OP_LEN_MASK) > INLINE_TILES * TILE_OPS ? -1 : !(e1.z & EF_REVERSED) ? 0 : (e1.z & EF_STRAND) ? 2 : 1;
+        // ordered rows: the target of every row of this entry is the sequence its ranges look up -- the first one's says it
+        uint32_t tid = 0;
+        if (ordered && cnt) tid = wl.se[r0 + (uint32_t)__builtin_amdgcn_readfirstlane((int)st_list[wv][0])].target_id;
 #pragma unroll 1
-      for (uint32_t k0 = 0; k0 < cnt; k0 += 64u) {
-        const bool live = k0 + l < cnt;
-        const uint32_t r = live ? (uint32_t)st_list[wv][k0 + l] : 0u;
-        const int2 se = st_se[r];
-        uint32_t p = run + k0 + l;
-        if (!compact) {  // slot = the range's first place + the mask bits below the entry's (ordered rows / the by-range experiment: narrow windows only)
-          const uint4 w = st_win[r];
-          const uint32_t d = eidx - w.x;
-          const uint32_t below = d < 32u ? (uint32_t)__popc(w.z & ((1u << d) - 1u))
-                                         : (uint32_t)__popc(w.z) + (uint32_t)__popc(w.w & ((1u << (d - 32u)) - 1u));
-          p = st_off[r] + below;
+        for (uint32_t k0 = 0; k0 < cnt; k0 += 64u) {
+          const bool live = k0 + l < cnt;
+          const uint32_t r = live ? (uint32_t)st_list[wv][k0 + l] : 0u;
+          const int2 se = st_se[r];
+          uint32_t p = run + k0 + l;
+          if (!compact) {  // slot = the range's first place + the mask bits below the entry's (ordered rows / the by-range experiment: narrow windows only)
+            const uint4 w = st_win[r];
+            const uint32_t d = eidx - w.x;
+            const uint32_t below = d < 32u ? (uint32_t)__popc(w.z & ((1u << d) - 1u))
+                                           : (uint32_t)__popc(w.z) + (uint32_t)__popc(w.w & ((1u << (d - 32u)) - 1u));
+            p = st_off[r] + below;
+          }
+          if (ordered) {  // the row's final place: the range's first row + the hit's visit position (the byte the lookup left at its place)
+            if (live) p = st_dest[r] + (uint32_t)wl.ord.vpos[p];
+          } else if (qs) tid = r0 + r;
+          else if (live && wl.range_out) wl.range_out[p] = wl.range_places ? r0 + r : wl.perm[r0 + r];
+          if (orient == 0) project_entry_chunk<TRANSITIVE, 0, MODE, OUT>(v, e0, e1, e2, e3, eidx, live, se.x, se.y, p, rec, h, accepted, err_flag, n_ok PHASE_PASS, min_identity, wl.ord, tid);
+          else if (orient == 1) project_entry_chunk<TRANSITIVE, 1, MODE, OUT>(v, e0, e1, e2, e3, eidx, live, se.x, se.y, p, rec, h, accepted, err_flag, n_ok PHASE_PASS, min_identity, wl.ord, tid);
+          else if (orient == 2) project_entry_chunk<TRANSITIVE, 2, MODE, OUT>(v, e0, e1, e2, e3, eidx, live, se.x, se.y, p, rec, h, accepted, err_flag, n_ok PHASE_PASS, min_identity, wl.ord, tid);
+          else project_entry_chunk<TRANSITIVE, -1, MODE, OUT>(v, e0, e1, e2, e3, eidx, live, se.x, se.y, p, rec, h, accepted, err_flag, n_ok PHASE_PASS, min_identity, wl.ord, tid);
         }
-        if (ordered) {  // the row's final place: the range's first row + the hit's visit position (the byte the lookup left at its place)
-          if (live) p = st_dest[r] + (uint32_t)wl.ord.vpos[p];
-        } else if (qs) tid = r0 + r;
-        else if (live && wl.range_out) wl.range_out[p] = wl.range_places ? r0 + r : wl.perm[r0 + r];
-        if (orient == 0) project_entry_chunk<TRANSITIVE, 0, MODE, OUT>(v, e0, e1, e2, e3, eidx, live, se.x, se.y, p, rec, h, accepted, err_flag, n_ok PHASE_PASS, min_identity, wl.ord, tid);
-        else if (orient == 1) project_entry_chunk<TRANSITIVE, 1, MODE, OUT>(v, e0, e1, e2, e3, eidx, live, se.x, se.y, p, rec, h, accepted, err_flag, n_ok PHASE_PASS, min_identity, wl.ord, tid);
-        else if (orient == 2) project_entry_chunk<TRANSITIVE, 2, MODE, OUT>(v, e0, e1, e2, e3, eidx, live, se.x, se.y, p, rec, h, accepted, err_flag, n_ok PHASE_PASS, min_identity, wl.ord, tid);
-        else project_entry_chunk<TRANSITIVE, -1, MODE, OUT>(v, e0, e1, e2, e3, eidx, live, se.x, se.y, p, rec, h, accepted, err_flag, n_ok PHASE_PASS, min_identity, wl.ord, tid);
       }
-    }
+    };
+    if (any_wide) entry_loop(std::false_type{});
+    else entry_loop(std::true_type{});
 #undef IMPG_RDL
 #ifdef IMPG_PHASE_CLOCKS
     STG_MARK(2);
