@@ -31,15 +31,12 @@ namespace impg {
 
 namespace {
 
-__device__ __forceinline__ uint32_t ord_u32(int32_t v) { return (uint32_t)v ^ 0x80000000u; }  // order-preserving
-
-struct Rows {  // SoA rows of a chunk
-  uint32_t *q, *qid, *tid;
-  int4 *c;  // {q_first, q_last, t_first, t_last}
-};
+using prims::bits_for;
+using prims::cdiv;
+using prims::ord_u32;
 
 // ---- gap_2d --------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void gap_keys_kernel(Rows R, uint32_t n, unsigned seq_bits, uint32_t *__restrict__ k32,
+__global__ __launch_bounds__(256) void gap_keys_kernel(ConstRows R, uint32_t n, unsigned seq_bits, uint32_t *__restrict__ k32,
                                                        unsigned long long *__restrict__ k64, uint32_t *__restrict__ idx) {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   if (i >= n) return;
@@ -69,7 +66,7 @@ __device__ __forceinline__ void uf_unite(uint32_t *parent, uint32_t a, uint32_t 
   }
 }
 // one thread per sorted position a: the reference's loop over b > a inside a's group (main.rs:12925-12960)
-__global__ __launch_bounds__(256) void gap_link_kernel(Rows R, const uint32_t *__restrict__ perm, const unsigned long long *__restrict__ skey,
+__global__ __launch_bounds__(256) void gap_link_kernel(ConstRows R, const uint32_t *__restrict__ perm, const unsigned long long *__restrict__ skey,
                                                        uint32_t n, int32_t merge_distance, uint32_t *__restrict__ parent) {
   const uint32_t a = blockIdx.x * 256u + threadIdx.x;
   if (a >= n) return;
@@ -91,7 +88,7 @@ __global__ __launch_bounds__(256) void gap_link_kernel(Rows R, const uint32_t *_
   }
 }
 // the chain's bounding box, gathered at its root (the box itself is order-independent)
-__global__ __launch_bounds__(256) void gap_box_kernel(Rows R, uint32_t n, uint32_t *__restrict__ parent, int4 *__restrict__ box,
+__global__ __launch_bounds__(256) void gap_box_kernel(ConstRows R, uint32_t n, uint32_t *__restrict__ parent, int4 *__restrict__ box,
                                                       uint32_t *__restrict__ is_root) {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   if (i >= n) return;
@@ -105,7 +102,7 @@ __global__ __launch_bounds__(256) void gap_box_kernel(Rows R, uint32_t n, uint32
   atomicMin(b + 2, c.z);
   atomicMax(b + 3, c.w);
 }
-__global__ __launch_bounds__(256) void compact_rows_kernel(Rows in, const int4 *__restrict__ box, uint32_t n, const uint32_t *__restrict__ flag,
+__global__ __launch_bounds__(256) void compact_rows_kernel(ConstRows in, const int4 *__restrict__ box, uint32_t n, const uint32_t *__restrict__ flag,
                                                            const uint32_t *__restrict__ pos, Rows out) {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   if (i >= n || !flag[i]) return;
@@ -115,7 +112,7 @@ __global__ __launch_bounds__(256) void compact_rows_kernel(Rows in, const int4 *
 }
 
 // ---- query axis ------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void axis_keys_kernel(Rows R, uint32_t n, unsigned seq_bits, unsigned long long *__restrict__ k_lo,
+__global__ __launch_bounds__(256) void axis_keys_kernel(ConstRows R, uint32_t n, unsigned seq_bits, unsigned long long *__restrict__ k_lo,
                                                         unsigned long long *__restrict__ k_hi, uint32_t *__restrict__ idx) {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   if (i >= n) return;
@@ -127,7 +124,7 @@ __global__ __launch_bounds__(256) void axis_keys_kernel(Rows R, uint32_t n, unsi
 }
 // per sorted row: (segment id << 32 | end) for the prefix maximum; a segment = one (range, query sequence) [+ strand
 // run when the strands stay apart]
-__global__ __launch_bounds__(256) void axis_seg_kernel(Rows R, const uint32_t *__restrict__ perm, const unsigned long long *__restrict__ skey,
+__global__ __launch_bounds__(256) void axis_seg_kernel(ConstRows R, const uint32_t *__restrict__ perm, const unsigned long long *__restrict__ skey,
                                                        uint32_t n, int merge_strands, uint32_t *__restrict__ seg_head) {
   const uint32_t k = blockIdx.x * 256u + threadIdx.x;
   if (k >= n) return;
@@ -138,14 +135,14 @@ __global__ __launch_bounds__(256) void axis_seg_kernel(Rows R, const uint32_t *_
   }
   seg_head[k] = head ? 1u : 0u;
 }
-__global__ __launch_bounds__(256) void axis_val_kernel(Rows R, const uint32_t *__restrict__ perm, const uint32_t *__restrict__ seg_head,
+__global__ __launch_bounds__(256) void axis_val_kernel(ConstRows R, const uint32_t *__restrict__ perm, const uint32_t *__restrict__ seg_head,
                                                        const uint32_t *__restrict__ seg_id, uint32_t n, unsigned long long *__restrict__ val) {
   const uint32_t k = blockIdx.x * 256u + threadIdx.x;
   if (k >= n) return;
   const int4 c = R.c[perm[k]];
   val[k] = ((unsigned long long)(seg_id[k] + seg_head[k]) << 32) | ord_u32(max(c.x, c.y));  // (exclusive scan + own flag = 1-based id)
 }
-__global__ __launch_bounds__(256) void axis_run_heads_kernel(Rows R, const uint32_t *__restrict__ perm, const uint32_t *__restrict__ seg_head,
+__global__ __launch_bounds__(256) void axis_run_heads_kernel(ConstRows R, const uint32_t *__restrict__ perm, const uint32_t *__restrict__ seg_head,
                                                              const unsigned long long *__restrict__ pmax, uint32_t n, int32_t merge_distance,
                                                              uint32_t *__restrict__ run_head) {
   const uint32_t k = blockIdx.x * 256u + threadIdx.x;
@@ -166,7 +163,7 @@ struct BedRow {  // a merged row, 16 bytes
   int32_t start, end;  // (printed as u32, like the reference: an inconsistent CIGAR can project below zero)
 };
 // one thread per sorted row; run r = run_id[k] (exclusive scan of the heads + own flag - 1)
-__global__ __launch_bounds__(256) void axis_emit_kernel(Rows R, const uint32_t *__restrict__ perm, const uint32_t *__restrict__ run_head,
+__global__ __launch_bounds__(256) void axis_emit_kernel(ConstRows R, const uint32_t *__restrict__ perm, const uint32_t *__restrict__ run_head,
                                                         const uint32_t *__restrict__ run_pos, const unsigned long long *__restrict__ pmax,
                                                         const uint32_t *__restrict__ head_of, uint32_t n, int merge_strands,
                                                         BedRow *__restrict__ out, uint32_t *__restrict__ strand_key) {
@@ -209,13 +206,6 @@ __global__ __launch_bounds__(256) void axis_strand_kernel(BedRow *__restrict__ o
   if (r < n_runs) out[r].q_strand |= (strand_key[r] & 1u) << 31;
 }
 
-inline uint32_t cdiv(uint64_t a, uint32_t b) { return (uint32_t)((a + b - 1) / b); }
-inline unsigned bits_for(uint64_t n) {
-  unsigned b = 0;
-  while ((1ull << b) < n) b++;
-  return std::max(1u, b);
-}
-
 }  // namespace
 
 // ---- text ---------------------------------------------------------------------------------------------------------------
@@ -225,11 +215,9 @@ __global__ __launch_bounds__(256) void text_len_kernel(const BedRow *__restrict_
   const uint32_t r = blockIdx.x * 256u + threadIdx.x;
   if (r >= n) return;
   const BedRow x = rows[r];
-  const bool named = x.query_id < t.n_names;
-  const uint32_t sh = named ? t.shift[x.query_id] : 0u;
-  const uint32_t nl = named ? t.name_off[x.query_id + 1] - t.name_off[x.query_id] : dec_digits(x.query_id);
+  const uint32_t sh = seq_shift(t, x.query_id);
   const uint32_t q = x.q_strand & 0x7FFFFFFFu;
-  len[r] = nl + dec_digits((uint32_t)x.start + sh) + dec_digits((uint32_t)x.end + sh) + (t.rname_off[q + 1] - t.rname_off[q]) + 8u;
+  len[r] = seq_text_len(t, x.query_id) + dec_digits((uint32_t)x.start + sh) + dec_digits((uint32_t)x.end + sh) + (t.rname_off[q + 1] - t.rname_off[q]) + 8u;
 }
 __global__ __launch_bounds__(256) void text_write_kernel(const BedRow *__restrict__ rows, uint32_t n, TextTables t,
                                                          const unsigned long long *__restrict__ off, unsigned long long base, char *__restrict__ out) {
@@ -237,28 +225,83 @@ __global__ __launch_bounds__(256) void text_write_kernel(const BedRow *__restric
   if (r >= n) return;
   const BedRow x = rows[r];
   char *p = out + (off[r] - base);
-  const bool named = x.query_id < t.n_names;
-  const uint32_t sh = named ? t.shift[x.query_id] : 0u;
-  if (named) {
-    const char *nm = t.names + t.name_off[x.query_id];
-    const uint32_t nl = t.name_off[x.query_id + 1] - t.name_off[x.query_id];
-    for (uint32_t k = 0; k < nl; k++) p[k] = nm[k];
-    p += nl;
-  } else p = put_dec(p, x.query_id, dec_digits(x.query_id));
-  *p++ = '\t';
+  const uint32_t sh = seq_shift(t, x.query_id);
   const uint32_t a = (uint32_t)x.start + sh, b = (uint32_t)x.end + sh;
-  const uint32_t q = x.q_strand & 0x7FFFFFFFu;
-  p = put_dec(p, a, dec_digits(a));
-  *p++ = '\t';
-  p = put_dec(p, b, dec_digits(b));
-  *p++ = '\t';
-  const char *rn = t.rnames + t.rname_off[q];
-  const uint32_t rl = t.rname_off[q + 1] - t.rname_off[q];
-  for (uint32_t k = 0; k < rl; k++) p[k] = rn[k];
-  p += rl;
+  p = put_seq(p, t, x.query_id); *p++ = '\t';
+  p = put_dec(p, a, dec_digits(a)); *p++ = '\t';
+  p = put_dec(p, b, dec_digits(b)); *p++ = '\t';
+  p = put_range_name(p, t, x.q_strand & 0x7FFFFFFFu);
   *p++ = '\t'; *p++ = '.'; *p++ = '\t';
   *p++ = (x.q_strand >> 31) ? '-' : '+';
   *p++ = '\n';
+}
+
+typedef unsigned long long u64;
+
+// The rows' chains (gap_2d): n > 1 rows -> one row per chain in `to`, the chain's box where its first row stood; returns
+// their number.  ks.perm, k32, k64: n words each.
+static uint32_t gap_2d(Engine &E, ConstRows R, uint32_t n, unsigned seq_bits, unsigned q_bits, int32_t merge_distance, prims::KeySort &ks,
+                       DevBuf &k32, DevBuf &k64, DevRows &to) {
+  hipStream_t s = E.stream;
+  gap_keys_kernel<<<cdiv(n, 256), 256, 0, s>>>(R, n, seq_bits, k32.as<uint32_t>(), k64.as<u64>(), ks.perm.as<uint32_t>());
+  ks.run({{k32.p, false, 32}, {k64.p, true, q_bits + 2 * seq_bits + 1}}, /*first_in_order=*/true, n, s);
+  DevBuf parent, box, root_flag, root_pos;
+  parent.reserve((size_t)n * 4); box.reserve((size_t)n * 16); root_flag.reserve((size_t)n * 4); root_pos.reserve((size_t)n * 4);
+  prims::iota_kernel<<<cdiv(n, 256), 256, 0, s>>>(parent.as<uint32_t>(), n);
+  gap_link_kernel<<<cdiv(n, 256), 256, 0, s>>>(R, ks.order, (const u64 *)ks.sorted_keys, n, merge_distance, parent.as<uint32_t>());
+  IMPG_HIP(hipMemcpyAsync(box.p, R.c, (size_t)n * 16, hipMemcpyDeviceToDevice, s));
+  gap_box_kernel<<<cdiv(n, 256), 256, 0, s>>>(R, n, parent.as<uint32_t>(), box.as<int4>(), root_flag.as<uint32_t>());
+  const uint32_t m = (uint32_t)E.scan(root_flag.as<uint32_t>(), root_pos.as<uint32_t>(), n);
+  to.reserve(m, 256);
+  compact_rows_kernel<<<cdiv(n, 256), 256, 0, s>>>(R, box.as<int4>(), n, root_flag.as<uint32_t>(), root_pos.as<uint32_t>(), to.view());
+  return m;
+}
+
+// The sweep along the query axis: m rows -> their runs as BedRows in `out`, grouped by range; returns their number.
+// ks.perm, k_lo, k_hi: m words each.  The stream is synchronised when this returns.
+static uint32_t query_axis(Engine &E, ConstRows R, uint32_t m, unsigned seq_bits, unsigned q_bits, int32_t merge_distance, bool merge_strands,
+                           prims::KeySort &ks, DevBuf &k_lo, DevBuf &k_hi, DevBuf &out) {
+  hipStream_t s = E.stream;
+  DevBuf kq, seg_head, seg_id, val, pmax, run_head, run_pos, head_of, strand_key, stmp;  // (stmp: the two prefix maxima's temp storage)
+  const size_t mb4 = (size_t)m * 4, mb8 = (size_t)m * 8;
+  seg_head.reserve(mb4); seg_id.reserve(mb4); pmax.reserve(mb8); run_head.reserve(mb4); run_pos.reserve(mb4);
+  out.reserve((size_t)m * sizeof(BedRow) + 256);
+  // (besides the sweep's keys this lists the rows in ks.perm, which is all the branch without a sweep takes from it)
+  axis_keys_kernel<<<cdiv(m, 256), 256, 0, s>>>(R, m, seq_bits, k_lo.as<u64>(), k_hi.as<u64>(), ks.perm.as<uint32_t>());
+  // (main.rs:12479: the sweep runs when a range has more than one row and (d >= 0 or strands merge); a range with one
+  // row is its own run either way, so running it for every range changes nothing)
+  if (merge_distance >= 0 || merge_strands) {
+    ks.run({{k_lo.p, true, 33}, {k_hi.p, true, q_bits + seq_bits}}, /*first_in_order=*/true, m, s);
+    val.reserve(mb8);
+    axis_seg_kernel<<<cdiv(m, 256), 256, 0, s>>>(R, ks.order, (const u64 *)ks.sorted_keys, m, merge_strands ? 1 : 0, seg_head.as<uint32_t>());
+    (void)E.scan(seg_head.as<uint32_t>(), seg_id.as<uint32_t>(), m);
+    axis_val_kernel<<<cdiv(m, 256), 256, 0, s>>>(R, ks.order, seg_head.as<uint32_t>(), seg_id.as<uint32_t>(), m, val.as<u64>());
+    prims::inclusive_max(stmp, val.as<u64>(), pmax.as<u64>(), m, s);
+    axis_run_heads_kernel<<<cdiv(m, 256), 256, 0, s>>>(R, ks.order, seg_head.as<uint32_t>(), pmax.as<u64>(), m, merge_distance, run_head.as<uint32_t>());
+  } else {
+    // no merging at all: the rows as they are, sorted by range only (stable: emission order within a range), each its own
+    // run -- one segment, and a negative distance keeps everything apart
+    kq.reserve(mb4);
+    IMPG_HIP(hipMemcpyAsync(kq.p, R.q, mb4, hipMemcpyDeviceToDevice, s));
+    ks.run({{kq.p, false, q_bits}}, /*first_in_order=*/true, m, s);
+    IMPG_HIP(hipMemsetAsync(seg_head.p, 0, mb4, s));
+    IMPG_HIP(hipMemsetAsync(seg_id.p, 0, mb4, s));
+    axis_val_kernel<<<cdiv(m, 256), 256, 0, s>>>(R, ks.order, seg_head.as<uint32_t>(), seg_id.as<uint32_t>(), m, pmax.as<u64>());
+    axis_run_heads_kernel<<<cdiv(m, 256), 256, 0, s>>>(R, ks.order, seg_head.as<uint32_t>(), pmax.as<u64>(), m, -1, run_head.as<uint32_t>());
+  }
+  const uint32_t n_runs = (uint32_t)E.scan(run_head.as<uint32_t>(), run_pos.as<uint32_t>(), m);
+  strand_key.reserve((size_t)n_runs * 4 + 256);
+  IMPG_HIP(hipMemsetAsync(strand_key.p, 0, (size_t)n_runs * 4, s));
+  if (merge_strands) {
+    head_of.reserve(mb4);
+    head_pos_kernel<<<cdiv(m, 256), 256, 0, s>>>(run_head.as<uint32_t>(), m, seg_id.as<uint32_t>());
+    prims::inclusive_max(stmp, seg_id.as<uint32_t>(), head_of.as<uint32_t>(), m, s);
+  }
+  axis_emit_kernel<<<cdiv(m, 256), 256, 0, s>>>(R, ks.order, run_head.as<uint32_t>(), run_pos.as<uint32_t>(), pmax.as<u64>(), head_of.as<uint32_t>(), m,
+                                                 merge_strands ? 1 : 0, out.as<BedRow>(), strand_key.as<uint32_t>());
+  axis_strand_kernel<<<cdiv(n_runs, 256), 256, 0, s>>>(out.as<BedRow>(), strand_key.as<uint32_t>(), n_runs);
+  IMPG_HIP(hipStreamSynchronize(s));  // (the scratch buffers of this function die here)
+  return n_runs;
 }
 
 // Scattered rows -> merged BED rows, left on the device in `out` (grouped by range, in output order); returns their
@@ -271,32 +314,15 @@ static uint32_t merge_rows(Engine &E, const impg_gpu_index &ix, Rows R, uint32_t
   const unsigned seq_bits = bits_for(n_seq), q_bits = bits_for(n_ranges);
   // (with no merge at all the rows are only grouped by range: no key holds a sequence id)
   if ((merge_distance >= 0 || merge_strands) && q_bits + 2 * seq_bits + 1 > 64) throw Error{IMPG_E_UNSUPPORTED, "too many sequences for the device-side BED merge (use impg_gpu_results_bed)"};
-  DevBuf k32a, k32b, k64a, k64b, ia, ib, tmp;
-  const size_t nb4 = (size_t)n * 4, nb8 = (size_t)n * 8;
-  k32a.reserve(nb4); k32b.reserve(nb4); k64a.reserve(nb8); k64b.reserve(nb8); ia.reserve(nb4); ib.reserve(nb4);
-  tmp.reserve(std::max(sort_u32_scratch_bytes(n), sort_pairs_scratch_bytes(n)));
-  DevBuf rq2, rqid2, rtid2, rc2;
+  prims::KeySort ks;
+  DevBuf k32, k64a, k64b;  // the sorts' keys, at the rows' own indices
+  ks.perm.reserve((size_t)n * 4); k32.reserve((size_t)n * 4); k64a.reserve((size_t)n * 8); k64b.reserve((size_t)n * 8);
+  DevRows chains;
   Rows cur = R;
   uint32_t m = n;
-  // ---- gap_2d ------------------------------------------------------------------------------------------------------
   if (merge_distance >= 0 && n > 1) {
-    gap_keys_kernel<<<cdiv(n, 256), 256, 0, s>>>(R, n, seq_bits, k32a.as<uint32_t>(), k64a.as<unsigned long long>(), ia.as<uint32_t>());
-    launch_sort_u32(tmp.p, tmp.cap, k32a.as<uint32_t>(), k32b.as<uint32_t>(), ia.as<uint32_t>(), ib.as<uint32_t>(), n, s, 0, 32);
-    prims::gather_kernel<<<cdiv(n, 256), 256, 0, s>>>(k64a.as<unsigned long long>(), ib.as<uint32_t>(), n, k64b.as<unsigned long long>());
-    launch_sort_pairs(tmp.p, tmp.cap, k64b.as<unsigned long long>(), k64a.as<unsigned long long>(), ib.as<uint32_t>(), ia.as<uint32_t>(), n,
-                      q_bits + 2 * seq_bits + 1, s);
-    // sorted: keys in k64a, perm in ia
-    DevBuf parent, box, root_flag, root_pos;
-    parent.reserve(nb4); box.reserve((size_t)n * 16); root_flag.reserve(nb4); root_pos.reserve(nb4);
-    prims::iota_kernel<<<cdiv(n, 256), 256, 0, s>>>(parent.as<uint32_t>(), n);
-    gap_link_kernel<<<cdiv(n, 256), 256, 0, s>>>(R, ia.as<uint32_t>(), k64a.as<unsigned long long>(), n, merge_distance, parent.as<uint32_t>());
-    IMPG_HIP(hipMemcpyAsync(box.p, R.c, (size_t)n * 16, hipMemcpyDeviceToDevice, s));
-    gap_box_kernel<<<cdiv(n, 256), 256, 0, s>>>(R, n, parent.as<uint32_t>(), box.as<int4>(), root_flag.as<uint32_t>());
-    m = (uint32_t)E.scan(root_flag.as<uint32_t>(), root_pos.as<uint32_t>(), n);
-    rq2.reserve((size_t)m * 4 + 256); rqid2.reserve((size_t)m * 4 + 256); rtid2.reserve((size_t)m * 4 + 256); rc2.reserve((size_t)m * 16 + 256);
-    Rows R2{rq2.as<uint32_t>(), rqid2.as<uint32_t>(), rtid2.as<uint32_t>(), rc2.as<int4>()};
-    compact_rows_kernel<<<cdiv(n, 256), 256, 0, s>>>(R, box.as<int4>(), n, root_flag.as<uint32_t>(), root_pos.as<uint32_t>(), R2);
-    cur = R2;
+    m = gap_2d(E, R, n, seq_bits, q_bits, merge_distance, ks, k32, k64a, chains);
+    cur = chains.view();
   }
   if (gap) {
     std::vector<uint32_t> hq(m), hqid(m), htid(m);
@@ -310,71 +336,7 @@ static uint32_t merge_rows(Engine &E, const impg_gpu_index &ix, Rows R, uint32_t
     gap->rows.resize(m);
     for (uint32_t i = 0; i < m; i++) gap->rows[i] = impg_gpu_interval_t{hqid[i], hc[i].x, hc[i].y, htid[i], hc[i].z, hc[i].w};
   }
-  // ---- query axis ----------------------------------------------------------------------------------------------------
-  DevBuf strand_key, seg_head, seg_id, val, pmax, run_head, run_pos;
-  uint32_t n_runs = m;
-  out.reserve((size_t)m * sizeof(BedRow) + 256);
-  // (main.rs:12479: the sweep runs when a range has more than one row and (d >= 0 or strands merge); a range with one
-  // row is its own run either way, so running it for every range changes nothing)
-  if (merge_distance >= 0 || merge_strands) {
-    axis_keys_kernel<<<cdiv(m, 256), 256, 0, s>>>(cur, m, seq_bits, k64a.as<unsigned long long>(), k64b.as<unsigned long long>(), ia.as<uint32_t>());
-    DevBuf k64c;
-    k64c.reserve(nb8);
-    launch_sort_pairs(tmp.p, tmp.cap, k64a.as<unsigned long long>(), k64c.as<unsigned long long>(), ia.as<uint32_t>(), ib.as<uint32_t>(), m, 33, s);
-    prims::gather_kernel<<<cdiv(m, 256), 256, 0, s>>>(k64b.as<unsigned long long>(), ib.as<uint32_t>(), m, k64a.as<unsigned long long>());
-    launch_sort_pairs(tmp.p, tmp.cap, k64a.as<unsigned long long>(), k64c.as<unsigned long long>(), ib.as<uint32_t>(), ia.as<uint32_t>(), m,
-                      q_bits + seq_bits, s);
-    // sorted: keys in k64c, perm in ia
-    seg_head.reserve((size_t)m * 4); seg_id.reserve((size_t)m * 4); val.reserve((size_t)m * 8); pmax.reserve((size_t)m * 8);
-    run_head.reserve((size_t)m * 4); run_pos.reserve((size_t)m * 4);
-    axis_seg_kernel<<<cdiv(m, 256), 256, 0, s>>>(cur, ia.as<uint32_t>(), k64c.as<unsigned long long>(), m, merge_strands ? 1 : 0, seg_head.as<uint32_t>());
-    (void)E.scan(seg_head.as<uint32_t>(), seg_id.as<uint32_t>(), m);
-    axis_val_kernel<<<cdiv(m, 256), 256, 0, s>>>(cur, ia.as<uint32_t>(), seg_head.as<uint32_t>(), seg_id.as<uint32_t>(), m, val.as<unsigned long long>());
-    {
-      DevBuf stmp;
-      prims::inclusive_max(stmp, val.as<unsigned long long>(), pmax.as<unsigned long long>(), m, s);
-      IMPG_HIP(hipStreamSynchronize(s));  // (stmp dies here)
-    }
-    axis_run_heads_kernel<<<cdiv(m, 256), 256, 0, s>>>(cur, ia.as<uint32_t>(), seg_head.as<uint32_t>(), pmax.as<unsigned long long>(), m, merge_distance,
-                                                        run_head.as<uint32_t>());
-    n_runs = (uint32_t)E.scan(run_head.as<uint32_t>(), run_pos.as<uint32_t>(), m);
-    strand_key.reserve((size_t)n_runs * 4 + 256);
-    IMPG_HIP(hipMemsetAsync(strand_key.p, 0, (size_t)n_runs * 4, s));
-    DevBuf head_of;
-    head_of.reserve((size_t)m * 4);
-    if (merge_strands) {
-      head_pos_kernel<<<cdiv(m, 256), 256, 0, s>>>(run_head.as<uint32_t>(), m, seg_id.as<uint32_t>());
-      DevBuf stmp;
-      prims::inclusive_max(stmp, seg_id.as<uint32_t>(), head_of.as<uint32_t>(), m, s);
-      IMPG_HIP(hipStreamSynchronize(s));
-    }
-    axis_emit_kernel<<<cdiv(m, 256), 256, 0, s>>>(cur, ia.as<uint32_t>(), run_head.as<uint32_t>(), run_pos.as<uint32_t>(), pmax.as<unsigned long long>(),
-                                                   head_of.as<uint32_t>(), m, merge_strands ? 1 : 0, out.as<BedRow>(), strand_key.as<uint32_t>());
-    axis_strand_kernel<<<cdiv(n_runs, 256), 256, 0, s>>>(out.as<BedRow>(), strand_key.as<uint32_t>(), n_runs);
-  } else {
-    // no merging at all: rows as they are, in emission order (already grouped by range? no: by level) -- sort by range only
-    axis_keys_kernel<<<cdiv(m, 256), 256, 0, s>>>(cur, m, seq_bits, k64a.as<unsigned long long>(), k64b.as<unsigned long long>(), ia.as<uint32_t>());
-    // key = range index alone (stable: emission order within a range)
-    DevBuf kq;
-    kq.reserve(nb4);
-    IMPG_HIP(hipMemcpyAsync(kq.p, cur.q, (size_t)m * 4, hipMemcpyDeviceToDevice, s));
-    launch_sort_u32(tmp.p, tmp.cap, kq.as<uint32_t>(), k32b.as<uint32_t>(), ia.as<uint32_t>(), ib.as<uint32_t>(), m, s, 0, q_bits);
-    // every row its own run
-    run_head.reserve((size_t)m * 4); run_pos.reserve((size_t)m * 4); pmax.reserve((size_t)m * 8); val.reserve((size_t)m * 8);
-    seg_head.reserve((size_t)m * 4); seg_id.reserve((size_t)m * 4);
-    IMPG_HIP(hipMemsetAsync(seg_head.p, 0, (size_t)m * 4, s));
-    IMPG_HIP(hipMemsetAsync(seg_id.p, 0, (size_t)m * 4, s));
-    axis_val_kernel<<<cdiv(m, 256), 256, 0, s>>>(cur, ib.as<uint32_t>(), seg_head.as<uint32_t>(), seg_id.as<uint32_t>(), m, pmax.as<unsigned long long>());
-    axis_run_heads_kernel<<<cdiv(m, 256), 256, 0, s>>>(cur, ib.as<uint32_t>(), seg_head.as<uint32_t>(), pmax.as<unsigned long long>(), m, -1,
-                                                        run_head.as<uint32_t>());
-    n_runs = (uint32_t)E.scan(run_head.as<uint32_t>(), run_pos.as<uint32_t>(), m);
-    strand_key.reserve((size_t)n_runs * 4 + 256);
-    IMPG_HIP(hipMemsetAsync(strand_key.p, 0, (size_t)n_runs * 4, s));
-    axis_emit_kernel<<<cdiv(m, 256), 256, 0, s>>>(cur, ib.as<uint32_t>(), run_head.as<uint32_t>(), run_pos.as<uint32_t>(), pmax.as<unsigned long long>(),
-                                                   nullptr, m, 0, out.as<BedRow>(), strand_key.as<uint32_t>());
-    axis_strand_kernel<<<cdiv(n_runs, 256), 256, 0, s>>>(out.as<BedRow>(), strand_key.as<uint32_t>(), n_runs);
-  }
-  IMPG_HIP(hipStreamSynchronize(s));  // (the scratch buffers of this function die here)
+  const uint32_t n_runs = query_axis(E, cur, m, seq_bits, q_bits, merge_distance, merge_strands, ks, k64a, k64b, out);
   ix.bed_stats[BED_ROWS] += n;
   ix.bed_stats[BED_GAP_ROOTS] += m;
   ix.bed_stats[BED_RUNS] += n_runs;
@@ -384,24 +346,21 @@ static uint32_t merge_rows(Engine &E, const impg_gpu_index &ix, Rows R, uint32_t
 // Rows of one chunk -> merged BED rows (merge_rows).  levels / self_dev: what Engine::run kept for the chunk.
 uint32_t device_bed_rows(Engine &E, const impg_gpu_index &ix, uint32_t n_ranges, const impg_gpu_params_t &p, int32_t merge_distance,
                          std::vector<std::unique_ptr<LevelBufs>> &levels, DevBuf &self_dev, DevBuf &out) {
-  hipStream_t s = E.stream;
   // ---- rows: range-major, the reference's emission order within a range (rows_device.hip) ---------------------------
   uint32_t n = 0;
-  DevBuf rq, rqid, rtid, rc;
-  Rows R{nullptr, nullptr, nullptr, nullptr};
+  DevRows rows;
   {
     RowPlan pl;  // (its tables go back to the pool at the end of this block, before the sorts take their memory)
     plan_rows(E, n_ranges, p, levels, self_dev, /*plain_retain=*/true, pl);
     n = pl.n_rows;
     if (!n) return 0;
-    rq.reserve((size_t)n * 4); rqid.reserve((size_t)n * 4); rtid.reserve((size_t)n * 4); rc.reserve((size_t)n * 16);
-    R = Rows{rq.as<uint32_t>(), rqid.as<uint32_t>(), rtid.as<uint32_t>(), rc.as<int4>()};
-    scatter_rows(E, levels, pl, RowSinks{nullptr, R.q, R.qid, R.tid, R.c, nullptr});
-    IMPG_HIP(hipStreamSynchronize(s));
+    rows.reserve(n);
+    scatter_rows(E, levels, pl, rows.sinks());
+    IMPG_HIP(hipStreamSynchronize(E.stream));
   }
   // the levels' slots are not needed any more: give their memory back before the sorts take theirs
   levels.clear();
-  return merge_rows(E, ix, R, n, ix.view.n_seq, n_ranges, merge_distance, p.consider_strandness == 0, out);
+  return merge_rows(E, ix, rows.view(), n, ix.view.n_seq, n_ranges, merge_distance, p.consider_strandness == 0, out);
 }
 
 // The merge and the text on rows the caller brings (impg_gpu_selftest_bed_rows): uploaded as they are, then merge_rows
@@ -411,23 +370,10 @@ void device_bed_selftest(Engine &E, const impg_gpu_index &ix, const impg_gpu_int
                          const std::vector<std::string> &rnames, std::vector<impg_gpu_bed_row_t> &merged, std::string &text, BedGapRows *gap) {
   merged.clear();
   if (!n) return;
-  hipStream_t s = E.stream;
-  std::vector<uint32_t> qid(n), tid(n);
-  std::vector<int4> c(n);
-  for (uint32_t i = 0; i < n; i++) {
-    qid[i] = rows[i].query_id; tid[i] = rows[i].target_id;
-    c[i] = int4{rows[i].q_first, rows[i].q_last, rows[i].t_first, rows[i].t_last};
-  }
-  DevBuf rq, rqid, rtid, rc, out;
-  rq.reserve((size_t)n * 4); rqid.reserve((size_t)n * 4); rtid.reserve((size_t)n * 4); rc.reserve((size_t)n * 16);
-  IMPG_HIP(hipMemsetAsync(E.counters.p, 0, 64, s));  // (as a run starts: Engine::scan reads its bad-range flag)
-  IMPG_HIP(hipMemcpyAsync(rq.p, row_range, (size_t)n * 4, hipMemcpyHostToDevice, s));
-  IMPG_HIP(hipMemcpyAsync(rqid.p, qid.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
-  IMPG_HIP(hipMemcpyAsync(rtid.p, tid.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
-  IMPG_HIP(hipMemcpyAsync(rc.p, c.data(), (size_t)n * 16, hipMemcpyHostToDevice, s));
-  IMPG_HIP(hipStreamSynchronize(s));
-  const uint32_t n_runs = merge_rows(E, ix, Rows{rq.as<uint32_t>(), rqid.as<uint32_t>(), rtid.as<uint32_t>(), rc.as<int4>()}, n, n_seq, n_ranges,
-                                     merge_distance, merge_strands, out, gap);
+  DevRows dev;
+  DevBuf out;
+  dev.upload(E, rows, row_range, n);
+  const uint32_t n_runs = merge_rows(E, ix, dev.view(), n, n_seq, n_ranges, merge_distance, merge_strands, out, gap);
   std::vector<BedRow> h(n_runs);
   if (n_runs) IMPG_HIP(hipMemcpy(h.data(), out.p, (size_t)n_runs * sizeof(BedRow), hipMemcpyDeviceToHost));
   merged.resize(n_runs);
@@ -435,104 +381,12 @@ void device_bed_selftest(Engine &E, const impg_gpu_index &ix, const impg_gpu_int
   device_bed_text(E, ix, out, n_runs, n_ranges, rnames, original_coords, [&](const char *p, size_t k) { text.append(p, k); });
 }
 
-// The name / shift / range-name tables of a chunk (text_device.hpp)
-TextTableBufs::TextTableBufs(Engine &E, const impg_gpu_index &ix, uint32_t n_ranges, const std::vector<std::string> &rnames, bool original_coords) {
-  hipStream_t s = E.stream;
-  noff.assign(1, 0);
-  for (const std::string &nm : ix.seq.names) {
-    nshift.push_back(put_original_name(nb, nm, original_coords));
-    noff.push_back((uint32_t)nb.size());
-  }
-  roff.assign(1, 0);
-  for (uint32_t q = 0; q < n_ranges; q++) { rb += rnames[q]; roff.push_back((uint32_t)rb.size()); }
-  auto up = [&](DevBuf &d, const void *src, size_t bytes) {
-    d.reserve(std::max<size_t>(bytes, 256));
-    if (bytes) IMPG_HIP(hipMemcpyAsync(d.p, src, bytes, hipMemcpyHostToDevice, s));
-  };
-  up(d_nb, nb.data(), nb.size()); up(d_noff, noff.data(), noff.size() * 4); up(d_shift, nshift.data(), nshift.size() * 4);
-  up(d_rb, rb.data(), rb.size()); up(d_roff, roff.data(), roff.size() * 4);
-  t = TextTables{d_nb.as<char>(), d_noff.as<uint32_t>(), d_shift.as<uint32_t>(), (uint32_t)ix.seq.names.size(), d_rb.as<char>(), d_roff.as<uint32_t>()};
-}
-
-// The merged rows of a chunk as text (device_text_pieces streams it)
+// The merged rows of a chunk as text (text_device.hpp)
 void device_bed_text(Engine &E, const impg_gpu_index &ix, const DevBuf &rows, uint32_t n_rows, uint32_t n_ranges,
                      const std::vector<std::string> &rnames, bool original_coords,
                      const std::function<void(const char *, size_t)> &sink) {
-  if (!n_rows) return;
-  hipStream_t s = E.stream;
-  TextTableBufs tb(E, ix, n_ranges, rnames, original_coords);
-  const TextTables t = tb.t;
-  DevBuf len;
-  len.reserve((size_t)n_rows * 4);
-  text_len_kernel<<<cdiv(n_rows, 256), 256, 0, s>>>(rows.as<BedRow>(), n_rows, t, len.as<uint32_t>());
-  device_text_pieces(E, len.as<uint32_t>(), n_rows, "BED",
-                     [&](uint32_t r0, uint32_t r1, const unsigned long long *off, unsigned long long base, char *out) {
-                       text_write_kernel<<<cdiv(r1 - r0, 256), 256, 0, s>>>(rows.as<BedRow>() + r0, r1 - r0, t, off, base, out);
-                     },
-                     sink, ix.bed_stats[BED_TEXT_PIECES], ix.bed_stats[BED_TEXT_BYTES]);
-}
-
-void device_text_pieces(Engine &E, const uint32_t *d_len, uint32_t n_rows, const char *what,
-                        const std::function<void(uint32_t, uint32_t, const unsigned long long *, unsigned long long, char *)> &write,
-                        const std::function<void(const char *, size_t)> &sink, std::atomic<uint64_t> &pieces, std::atomic<uint64_t> &bytes) {
-  if (!n_rows) return;
-  hipStream_t s = E.stream;
-  DevBuf off, stmp;
-  // ---- lengths -> 64-bit offsets (a transitive batch prints more than 4 GB) ----------------------------------------------
-  off.reserve((size_t)(n_rows + 1) * 8);
-  prims::exclusive_sum(stmp, d_len, off.as<unsigned long long>(), n_rows, s);
-  // piece boundaries: whole rows, at most PIECE bytes each; found on the host from a sampled copy of the offsets
-  const unsigned long long PIECE = (unsigned long long)E.opt.bed_text_piece_bytes;
-  std::vector<unsigned long long> h_off(n_rows);
-  IMPG_HIP(hipMemcpyAsync(h_off.data(), off.p, (size_t)n_rows * 8, hipMemcpyDeviceToHost, s));
-  uint32_t last_len = 0;
-  IMPG_HIP(hipMemcpyAsync(&last_len, d_len + (n_rows - 1), 4, hipMemcpyDeviceToHost, s));
-  IMPG_HIP(hipStreamSynchronize(s));
-  const unsigned long long total = h_off[n_rows - 1] + last_len;
-  const size_t cap = (size_t)std::min<unsigned long long>(total, PIECE) + 4096;
-  // a piece holds whole rows; only a piece of one row can outgrow PIECE, and it must still fit the buffer.  Refused
-  // here, with nothing queued and no pinned buffer in flight.
-  for (uint32_t r = 0; r < n_rows; r++)
-    if ((r + 1 < n_rows ? h_off[r + 1] : total) - h_off[r] > cap) throw Error{IMPG_E_UNSUPPORTED, std::string("a single ") + what + " row longer than the text buffer"};
-  DevBuf piece[2];
-  char *pin[2] = {nullptr, nullptr};
-  struct Unpin { char **p; ~Unpin() { for (int k = 0; k < 2; k++) if (p[k]) (void)hipHostFree(p[k]); } } unpin{pin};
-  for (int k = 0; k < 2; k++) { piece[k].reserve(cap); IMPG_HIP(hipHostMalloc((void **)&pin[k], cap, hipHostMallocDefault)); }
-  hipEvent_t done[2];
-  for (int k = 0; k < 2; k++) IMPG_HIP(hipEventCreateWithFlags(&done[k], hipEventDisableTiming));
-  struct EvFree { hipEvent_t *e; ~EvFree() { (void)hipEventDestroy(e[0]); (void)hipEventDestroy(e[1]); } } evfree{done};
-  struct Pending { size_t bytes; bool live; } pend[2] = {{0, false}, {0, false}};
-  uint32_t r0 = 0;
-  int slot = 0;
-  while (r0 < n_rows || pend[0].live || pend[1].live) {
-    if (r0 < n_rows) {
-      // rows [r0, r1): as many whole rows as fit one piece
-      const unsigned long long base = h_off[r0];
-      uint32_t r1 = (uint32_t)(std::upper_bound(h_off.begin() + r0 + 1, h_off.end(), base + PIECE) - h_off.begin());
-      if (r1 == n_rows) { if (total - base > PIECE && n_rows - 1 > r0) r1 = n_rows - 1; }
-      else r1 = std::max(r1 - 1, r0 + 1);
-      const unsigned long long end = r1 < n_rows ? h_off[r1] : total;
-      write(r0, r1, off.as<unsigned long long>() + r0, base, piece[slot].as<char>());
-      IMPG_HIP(hipMemcpyAsync(pin[slot], piece[slot].p, (size_t)(end - base), hipMemcpyDeviceToHost, s));
-      IMPG_HIP(hipEventRecord(done[slot], s));
-      pend[slot] = {(size_t)(end - base), true};
-      pieces++;
-      bytes += end - base;
-      r0 = r1;
-    }
-    // consume the OTHER slot's piece while this one is in flight (or drain at the end)
-    const int other = slot ^ 1;
-    if (pend[other].live) {
-      IMPG_HIP(hipEventSynchronize(done[other]));
-      sink(pin[other], pend[other].bytes);
-      pend[other].live = false;
-    } else if (r0 >= n_rows && pend[slot].live) {
-      IMPG_HIP(hipEventSynchronize(done[slot]));
-      sink(pin[slot], pend[slot].bytes);
-      pend[slot].live = false;
-    }
-    slot ^= 1;
-  }
+  device_rows_text<BedRow, text_len_kernel, text_write_kernel>(E, ix, rows, n_rows, n_ranges, rnames, original_coords, sink, "BED",
+                                                               ix.bed_stats[BED_TEXT_PIECES], ix.bed_stats[BED_TEXT_BYTES]);
 }
 
 }  // namespace impg

@@ -30,18 +30,9 @@ namespace impg {
 
 namespace {
 
-__device__ __forceinline__ uint32_t ord_u32(int32_t v) { return (uint32_t)v ^ 0x80000000u; }  // order-preserving
-inline uint32_t cdiv(uint64_t a, uint32_t b) { return (uint32_t)((a + b - 1) / b); }
-inline unsigned bits_for(uint64_t n) {
-  unsigned b = 0;
-  while ((1ull << b) < n) b++;
-  return std::max(1u, b);
-}
-
-struct Rows {  // SoA rows of a chunk, in emission order, grouped by range
-  const uint32_t *q, *qid, *tid;
-  const int4 *c;  // {q_first, q_last, t_first, t_last}
-};
+using prims::bits_for;
+using prims::cdiv;
+using prims::ord_u32;
 struct RowSum {         // 32 bytes: two 16-byte stores
   uint32_t m, x, ibp, dbp;
   uint32_t ni_first;    // I ops | first op code << 29 (a row has fewer than 2^29 ops)
@@ -123,7 +114,7 @@ __global__ __launch_bounds__(256) void summary_kernel(const uint32_t *__restrict
 // ---- order -----------------------------------------------------------------------------------------------------------
 // one thread per row: the three sort keys at the row's own index, and the row listed among the kept ones (every range
 // before it dropped one row, and so did its own: kept row r of range q is number r - (q + 1))
-__global__ __launch_bounds__(256) void keys_kernel(Rows R, const uint32_t *__restrict__ offsets, uint32_t n, unsigned seq_bits, int sorted,
+__global__ __launch_bounds__(256) void keys_kernel(ConstRows R, const uint32_t *__restrict__ offsets, uint32_t n, unsigned seq_bits, int sorted,
                                                    uint32_t *__restrict__ k_t, unsigned long long *__restrict__ k_mid,
                                                    unsigned long long *__restrict__ k_hi, uint32_t *__restrict__ kept, Control *__restrict__ ctl) {
   const uint32_t r = blockIdx.x * 256u + threadIdx.x;
@@ -147,7 +138,7 @@ __global__ __launch_bounds__(256) void keys_kernel(Rows R, const uint32_t *__res
 // Does row b continue the run of row a, the row before it in sorted order?  0: no, 1: contiguous, 2: gap.  qd / td: the
 // gap on either axis.  (paf_out.cpp merge_rows with its overlap arm, which cannot fire, left out; the differences wrap
 // like the reference's release build.)
-__device__ __forceinline__ int join_kind(const Rows &R, uint32_t a, uint32_t b, int32_t d, bool &f, int32_t &qd, int32_t &td) {
+__device__ __forceinline__ int join_kind(const ConstRows &R, uint32_t a, uint32_t b, int32_t d, bool &f, int32_t &qd, int32_t &td) {
   const int4 A = R.c[a], B = R.c[b];
   f = A.x <= A.y;
   if (R.q[a] != R.q[b] || R.qid[a] != R.qid[b] || R.tid[a] != R.tid[b] || f != (B.x <= B.y)) return 0;
@@ -159,7 +150,7 @@ __device__ __forceinline__ int join_kind(const Rows &R, uint32_t a, uint32_t b, 
   if (!q_over && td >= 0 && qd >= 0 && (qd > 0 || td > 0) && qd <= d && td <= d) return 2;
   return 0;
 }
-__global__ __launch_bounds__(256) void heads_kernel(Rows R, const uint32_t *__restrict__ perm, uint32_t m, int32_t d, uint32_t *__restrict__ head) {
+__global__ __launch_bounds__(256) void heads_kernel(ConstRows R, const uint32_t *__restrict__ perm, uint32_t m, int32_t d, uint32_t *__restrict__ head) {
   const uint32_t k = blockIdx.x * 256u + threadIdx.x;
   if (k >= m) return;
   bool is_head = k == 0 || d < 0;
@@ -171,7 +162,7 @@ __global__ __launch_bounds__(256) void heads_kernel(Rows R, const uint32_t *__re
   head[k] = is_head ? 1u : 0u;
 }
 // one thread per sorted row; run = run_pos[k] + head[k] - 1 (exclusive scan of the heads + own flag).  runs: zeroed.
-__global__ __launch_bounds__(256) void reduce_kernel(Rows R, const RowSum *__restrict__ sum, const uint32_t *__restrict__ perm,
+__global__ __launch_bounds__(256) void reduce_kernel(ConstRows R, const RowSum *__restrict__ sum, const uint32_t *__restrict__ perm,
                                                      const uint32_t *__restrict__ head, const uint32_t *__restrict__ run_pos, uint32_t m, int32_t d,
                                                      Run *__restrict__ runs, Control *__restrict__ ctl) {
   __shared__ uint32_t block_ctr[3];  // contiguous joins, gap joins, fused ops
@@ -335,47 +326,9 @@ void require_rows(const std::vector<uint32_t> &h_off) {
   for (size_t q = 0; q + 1 < h_off.size(); q++)
     if (h_off[q + 1] == h_off[q]) throw Error{IMPG_E_INVALID, "no result row to drop (the reference panics in Vec::remove(0))"};
 }
-uint32_t merge_rows(Engine &E, const impg_gpu_index &ix, Rows R, uint32_t n, uint32_t n_ranges, const uint32_t *d_offsets,
-                    const unsigned long long *d_coff, const uint32_t *d_pool, int32_t merge_distance, DevBuf &out);
-
-}  // namespace
-
-// Rows of one chunk -> the runs BEDPE prints, left on the device in `out` (grouped by range, in output order); returns
-// their number.  levels / self_dev: what Engine::run kept for the chunk, with store_cigar.  Every refusal is raised here,
-// before any of the chunk's text exists.  Counts into the handle's bedpe_* counters.
-uint32_t device_bedpe_rows(Engine &E, const impg_gpu_index &ix, uint32_t n_ranges, const impg_gpu_params_t &p, int32_t merge_distance,
-                           std::vector<std::unique_ptr<LevelBufs>> &levels, DevBuf &self_dev, DevBuf &out) {
-  hipStream_t s = E.stream;
-  DevBuf rq, rqid, rtid, rc, clen, coff, pool, offsets;
-  for (DevBuf *b : {&rq, &rqid, &rtid, &rc, &clen, &coff, &pool, &offsets}) b->pool = &E.level_pool;
-  uint32_t n = 0;
-  {
-    // ---- rows and their CIGARs: range-major, the reference's emission order within a range (rows_device.hip) ---------
-    RowPlan pl;  // (its tables go back to the pool at the end of this block, before the sorts take their memory)
-    plan_rows(E, n_ranges, p, levels, self_dev, /*plain_retain=*/true, pl);
-    n = pl.n_rows;
-    std::vector<uint32_t> h_off((size_t)n_ranges + 1);
-    IMPG_HIP(hipMemcpyAsync(h_off.data(), pl.offsets.p, ((size_t)n_ranges + 1) * 4, hipMemcpyDeviceToHost, s));
-    IMPG_HIP(hipStreamSynchronize(s));
-    require_rows(h_off);
-    rq.reserve((size_t)n * 4); rqid.reserve((size_t)n * 4); rtid.reserve((size_t)n * 4); rc.reserve((size_t)n * 16); clen.reserve((size_t)n * 4);
-    scatter_rows(E, levels, pl, RowSinks{nullptr, rq.as<uint32_t>(), rqid.as<uint32_t>(), rtid.as<uint32_t>(), rc.as<int4>(), clen.as<uint32_t>()});
-    (void)build_row_cigars(E, levels, pl, clen, coff, pool);
-    offsets.reserve(((size_t)n_ranges + 1) * 4);
-    IMPG_HIP(hipMemcpyAsync(offsets.p, pl.offsets.p, ((size_t)n_ranges + 1) * 4, hipMemcpyDeviceToDevice, s));
-    IMPG_HIP(hipStreamSynchronize(s));
-  }
-  // the levels' slots and slices are not needed any more: give their memory back before the sorts take theirs
-  levels.clear();
-  clen.release();
-  return merge_rows(E, ix, Rows{rq.as<uint32_t>(), rqid.as<uint32_t>(), rtid.as<uint32_t>(), rc.as<int4>()}, n, n_ranges, offsets.as<uint32_t>(),
-                    coff.as<unsigned long long>(), pool.as<uint32_t>(), merge_distance, out);
-}
-
-namespace {
 // R: n rows grouped by range in emission order, range q's at [d_offsets[q], d_offsets[q + 1]), none of the ranges empty;
 // row r's ops at d_pool[d_coff[r] .. d_coff[r + 1])
-uint32_t merge_rows(Engine &E, const impg_gpu_index &ix, Rows R, uint32_t n, uint32_t n_ranges, const uint32_t *d_offsets,
+uint32_t merge_rows(Engine &E, const impg_gpu_index &ix, ConstRows R, uint32_t n, uint32_t n_ranges, const uint32_t *d_offsets,
                     const unsigned long long *d_coff, const uint32_t *d_pool, int32_t merge_distance, DevBuf &out) {
   hipStream_t s = E.stream;
   const bool sorted = merge_distance >= 0;  // (a negative distance: neither a sort nor a merge, emission order)
@@ -392,39 +345,29 @@ uint32_t merge_rows(Engine &E, const impg_gpu_index &ix, Rows R, uint32_t n, uin
   Control *d_ctl = ctl.as<Control>();
   // ---- summaries -----------------------------------------------------------------------------------------------------
   sum.reserve((size_t)n * sizeof(RowSum));
-  {
-    const uint32_t *d_off = d_offsets;
-    RowSum *d_sum = sum.as<RowSum>();
-    switch (E.opt.bedpe_group_log2) {
-      case 3: launch_summary<8>(R.q, d_off, d_coff, d_pool, n, d_sum, d_ctl, s); break;
-      case 4: launch_summary<16>(R.q, d_off, d_coff, d_pool, n, d_sum, d_ctl, s); break;
-      case 5: launch_summary<32>(R.q, d_off, d_coff, d_pool, n, d_sum, d_ctl, s); break;
-      case 6: launch_summary<64>(R.q, d_off, d_coff, d_pool, n, d_sum, d_ctl, s); break;
-      default: launch_summary<4>(R.q, d_off, d_coff, d_pool, n, d_sum, d_ctl, s); break;
-    }
+  RowSum *d_sum = sum.as<RowSum>();
+  switch (E.opt.bedpe_group_log2) {
+    case 3: launch_summary<8>(R.q, d_offsets, d_coff, d_pool, n, d_sum, d_ctl, s); break;
+    case 4: launch_summary<16>(R.q, d_offsets, d_coff, d_pool, n, d_sum, d_ctl, s); break;
+    case 5: launch_summary<32>(R.q, d_offsets, d_coff, d_pool, n, d_sum, d_ctl, s); break;
+    case 6: launch_summary<64>(R.q, d_offsets, d_coff, d_pool, n, d_sum, d_ctl, s); break;
+    default: launch_summary<4>(R.q, d_offsets, d_coff, d_pool, n, d_sum, d_ctl, s); break;
   }
   // ---- order -----------------------------------------------------------------------------------------------------------
-  DevBuf k_t, k_mid, k_hi, ia, ib, s32a, s32b, s64a, s64b, tmp, head, run_pos;
-  for (DevBuf *b : {&k_t, &k_mid, &k_hi, &ia, &ib, &s32a, &s32b, &s64a, &s64b, &tmp, &head, &run_pos}) b->pool = &E.level_pool;
-  const size_t mb4 = (size_t)m * 4, mb8 = (size_t)m * 8;
-  ia.reserve(mb4);
+  prims::KeySort ks(&E.level_pool);
+  DevBuf k_t, k_mid, k_hi, head, run_pos;
+  for (DevBuf *b : {&k_t, &k_mid, &k_hi, &head, &run_pos}) b->pool = &E.level_pool;
+  const size_t mb4 = (size_t)m * 4;
+  ks.perm.reserve(mb4);
   if (sorted) { k_t.reserve((size_t)n * 4); k_mid.reserve((size_t)n * 8); k_hi.reserve((size_t)n * 8); }
   keys_kernel<<<cdiv(n, 256), 256, 0, s>>>(R, d_offsets, n, seq_bits, sorted ? 1 : 0, k_t.as<uint32_t>(), k_mid.as<unsigned long long>(),
-                                           k_hi.as<unsigned long long>(), ia.as<uint32_t>(), d_ctl);
-  const uint32_t *perm = ia.as<uint32_t>();
+                                           k_hi.as<unsigned long long>(), ks.perm.as<uint32_t>(), d_ctl);
+  const uint32_t *perm = ks.perm.as<uint32_t>();
   if (sorted && m > 1) {
-    ib.reserve(mb4); s32a.reserve(mb4); s32b.reserve(mb4); s64a.reserve(mb8); s64b.reserve(mb8);
-    tmp.reserve(std::max(sort_u32_scratch_bytes(m), sort_pairs_scratch_bytes(m)));
-    // least significant key first: t_first | (forward?, q start, target seq) | (range, query seq)
-    prims::gather_kernel<<<cdiv(m, 256), 256, 0, s>>>(k_t.as<uint32_t>(), ia.as<uint32_t>(), m, s32a.as<uint32_t>());
-    launch_sort_u32(tmp.p, tmp.cap, s32a.as<uint32_t>(), s32b.as<uint32_t>(), ia.as<uint32_t>(), ib.as<uint32_t>(), m, s, 0, 32);
-    prims::gather_kernel<<<cdiv(m, 256), 256, 0, s>>>(k_mid.as<unsigned long long>(), ib.as<uint32_t>(), m, s64a.as<unsigned long long>());
-    launch_sort_pairs(tmp.p, tmp.cap, s64a.as<unsigned long long>(), s64b.as<unsigned long long>(), ib.as<uint32_t>(), ia.as<uint32_t>(), m,
-                      33 + seq_bits, s);
-    prims::gather_kernel<<<cdiv(m, 256), 256, 0, s>>>(k_hi.as<unsigned long long>(), ia.as<uint32_t>(), m, s64a.as<unsigned long long>());
-    launch_sort_pairs(tmp.p, tmp.cap, s64a.as<unsigned long long>(), s64b.as<unsigned long long>(), ia.as<uint32_t>(), ib.as<uint32_t>(), m,
-                      q_bits + seq_bits, s);
-    perm = ib.as<uint32_t>();
+    // least significant key first: t_first | (forward?, q start, target seq) | (range, query seq); the keys stand at the
+    // rows' indices and ks.perm lists the kept rows, so every pass gathers
+    ks.run({{k_t.p, false, 32}, {k_mid.p, true, 33 + seq_bits}, {k_hi.p, true, q_bits + seq_bits}}, /*first_in_order=*/false, m, s);
+    perm = ks.order;
   }
   // ---- link and reduce -------------------------------------------------------------------------------------------------
   head.reserve(mb4); run_pos.reserve(mb4);
@@ -451,54 +394,66 @@ uint32_t merge_rows(Engine &E, const impg_gpu_index &ix, Rows R, uint32_t n, uin
 }
 }  // namespace
 
+// Rows of one chunk -> the runs BEDPE prints, left on the device in `out` (grouped by range, in output order); returns
+// their number.  levels / self_dev: what Engine::run kept for the chunk, with store_cigar.  Every refusal is raised here,
+// before any of the chunk's text exists.  Counts into the handle's bedpe_* counters.
+uint32_t device_bedpe_rows(Engine &E, const impg_gpu_index &ix, uint32_t n_ranges, const impg_gpu_params_t &p, int32_t merge_distance,
+                           std::vector<std::unique_ptr<LevelBufs>> &levels, DevBuf &self_dev, DevBuf &out) {
+  hipStream_t s = E.stream;
+  DevRows rows(&E.level_pool);
+  DevBuf clen, coff, pool, offsets;
+  for (DevBuf *b : {&clen, &coff, &pool, &offsets}) b->pool = &E.level_pool;
+  uint32_t n = 0;
+  {
+    // ---- rows and their CIGARs: range-major, the reference's emission order within a range (rows_device.hip) ---------
+    RowPlan pl;  // (its tables go back to the pool at the end of this block, before the sorts take their memory)
+    plan_rows(E, n_ranges, p, levels, self_dev, /*plain_retain=*/true, pl);
+    n = pl.n_rows;
+    std::vector<uint32_t> h_off((size_t)n_ranges + 1);
+    IMPG_HIP(hipMemcpyAsync(h_off.data(), pl.offsets.p, ((size_t)n_ranges + 1) * 4, hipMemcpyDeviceToHost, s));
+    IMPG_HIP(hipStreamSynchronize(s));
+    require_rows(h_off);
+    rows.reserve(n); clen.reserve((size_t)n * 4);
+    scatter_rows(E, levels, pl, rows.sinks(clen.as<uint32_t>()));
+    (void)build_row_cigars(E, levels, pl, clen, coff, pool);
+    offsets.reserve(((size_t)n_ranges + 1) * 4);
+    IMPG_HIP(hipMemcpyAsync(offsets.p, pl.offsets.p, ((size_t)n_ranges + 1) * 4, hipMemcpyDeviceToDevice, s));
+    IMPG_HIP(hipStreamSynchronize(s));
+  }
+  // the levels' slots and slices are not needed any more: give their memory back before the sorts take theirs
+  levels.clear();
+  clen.release();
+  return merge_rows(E, ix, rows.view(), n, n_ranges, offsets.as<uint32_t>(), coff.as<unsigned long long>(), pool.as<uint32_t>(), merge_distance, out);
+}
+
 // The merge and the text on rows and CIGARs the caller brings (impg_gpu_selftest_bedpe_rows): uploaded as they are, then
 // merge_rows and device_bedpe_text as a chunk of a query runs them.  row_range does not decrease; text: appended to.
 void device_bedpe_selftest(Engine &E, const impg_gpu_index &ix, const impg_gpu_interval_t *rows, const uint32_t *row_range, uint32_t n,
                            uint32_t n_ranges, const uint64_t *cigar_off, const uint32_t *cigar_ops, int32_t merge_distance, bool original_coords,
                            const std::vector<std::string> &rnames, std::string &text) {
   hipStream_t s = E.stream;
-  std::vector<uint32_t> h_off((size_t)n_ranges + 1, 0), qid(n), tid(n);
-  std::vector<int4> c(n);
-  for (uint32_t i = 0; i < n; i++) {
-    h_off[row_range[i] + 1]++;
-    qid[i] = rows[i].query_id; tid[i] = rows[i].target_id;
-    c[i] = int4{rows[i].q_first, rows[i].q_last, rows[i].t_first, rows[i].t_last};
-  }
+  std::vector<uint32_t> h_off((size_t)n_ranges + 1, 0);
+  for (uint32_t i = 0; i < n; i++) h_off[row_range[i] + 1]++;
   for (uint32_t q = 0; q < n_ranges; q++) h_off[q + 1] += h_off[q];
   require_rows(h_off);
   const uint64_t n_ops = cigar_off[n];
-  DevBuf rq, rqid, rtid, rc, coff, pool, offsets, out;
-  rq.reserve((size_t)n * 4); rqid.reserve((size_t)n * 4); rtid.reserve((size_t)n * 4); rc.reserve((size_t)n * 16);
+  DevRows dev;
+  DevBuf coff, pool, offsets, out;
   coff.reserve(((size_t)n + 1) * 8); pool.reserve(std::max<size_t>(n_ops * 4, 256)); offsets.reserve(((size_t)n_ranges + 1) * 4);
-  IMPG_HIP(hipMemsetAsync(E.counters.p, 0, 64, s));  // (as a run starts: Engine::scan reads its bad-range flag)
-  IMPG_HIP(hipMemcpyAsync(rq.p, row_range, (size_t)n * 4, hipMemcpyHostToDevice, s));
-  IMPG_HIP(hipMemcpyAsync(rqid.p, qid.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
-  IMPG_HIP(hipMemcpyAsync(rtid.p, tid.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
-  IMPG_HIP(hipMemcpyAsync(rc.p, c.data(), (size_t)n * 16, hipMemcpyHostToDevice, s));
   IMPG_HIP(hipMemcpyAsync(coff.p, cigar_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, s));
   if (n_ops) IMPG_HIP(hipMemcpyAsync(pool.p, cigar_ops, n_ops * 4, hipMemcpyHostToDevice, s));
   IMPG_HIP(hipMemcpyAsync(offsets.p, h_off.data(), ((size_t)n_ranges + 1) * 4, hipMemcpyHostToDevice, s));
-  IMPG_HIP(hipStreamSynchronize(s));
-  const uint32_t n_runs = merge_rows(E, ix, Rows{rq.as<uint32_t>(), rqid.as<uint32_t>(), rtid.as<uint32_t>(), rc.as<int4>()}, n, n_ranges,
-                                     offsets.as<uint32_t>(), coff.as<unsigned long long>(), pool.as<uint32_t>(), merge_distance, out);
+  dev.upload(E, rows, row_range, n);  // (waits for the three copies above too)
+  const uint32_t n_runs = merge_rows(E, ix, dev.view(), n, n_ranges, offsets.as<uint32_t>(), coff.as<unsigned long long>(), pool.as<uint32_t>(),
+                                     merge_distance, out);
   device_bedpe_text(E, ix, out, n_runs, n_ranges, rnames, original_coords, [&](const char *p, size_t k) { text.append(p, k); });
 }
 
-// The runs of a chunk as text (device_text_pieces streams it)
+// The runs of a chunk as text (text_device.hpp)
 void device_bedpe_text(Engine &E, const impg_gpu_index &ix, const DevBuf &runs, uint32_t n_runs, uint32_t n_ranges,
                        const std::vector<std::string> &rnames, bool original_coords, const std::function<void(const char *, size_t)> &sink) {
-  if (!n_runs) return;
-  hipStream_t s = E.stream;
-  TextTableBufs tb(E, ix, n_ranges, rnames, original_coords);
-  const TextTables t = tb.t;
-  DevBuf len;
-  len.reserve((size_t)n_runs * 4);
-  text_len_kernel<<<cdiv(n_runs, 256), 256, 0, s>>>(runs.as<Run>(), n_runs, t, len.as<uint32_t>());
-  device_text_pieces(E, len.as<uint32_t>(), n_runs, "BEDPE",
-                     [&](uint32_t r0, uint32_t r1, const unsigned long long *off, unsigned long long base, char *out) {
-                       text_write_kernel<<<cdiv(r1 - r0, 256), 256, 0, s>>>(runs.as<Run>() + r0, r1 - r0, t, off, base, out);
-                     },
-                     sink, ix.bedpe_stats[BEDPE_TEXT_PIECES], ix.bedpe_stats[BEDPE_TEXT_BYTES]);
+  device_rows_text<Run, text_len_kernel, text_write_kernel>(E, ix, runs, n_runs, n_ranges, rnames, original_coords, sink, "BEDPE",
+                                                            ix.bedpe_stats[BEDPE_TEXT_PIECES], ix.bedpe_stats[BEDPE_TEXT_BYTES]);
 }
 
 }  // namespace impg

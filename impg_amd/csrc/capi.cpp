@@ -249,6 +249,15 @@ template <class F> void for_chunks(Engine &E, size_t n, F fn) {
   }
 }
 
+// what the two self-tests (impg_gpu_selftest_bed_rows, _bedpe_rows) share: the rows' number fits the device's 32-bit row
+// indices; the names their ranges print under are the caller's, else the range's index
+void check_row_count(size_t n_rows) { if (n_rows >= 0xFFFFFFF0ull) throw Error{IMPG_E_INVALID, "too many rows"}; }
+std::vector<std::string> default_range_names(uint32_t n_ranges, const char *const *range_names) {
+  std::vector<std::string> rnames(n_ranges);
+  for (uint32_t q = 0; q < n_ranges; q++) rnames[q] = range_names && range_names[q] ? std::string(range_names[q]) : std::to_string(q);
+  return rnames;
+}
+
 }  // namespace
 
 namespace {
@@ -1325,6 +1334,14 @@ void text_batch(impg_gpu_index_t *ix, const impg_gpu_range_t *ranges, size_t n, 
   for_chunks(E, n, [&](size_t b, size_t e) { run_chunk_bed(*ix, E, d_ranges, ranges, range_names, b, e, p, merge_distance, sink, t3, nullptr, bedpe); });
   if (seconds3) for (int k = 0; k < 3; k++) seconds3[k] = t3[k];
 }
+// a text as the caller gets it: malloc'ed and NUL-terminated behind its bytes
+char *malloc_text(const std::string &s) {
+  char *t = (char *)malloc(s.size() + 1);
+  if (!t) throw Error{IMPG_E_OOM, "host out of memory"};
+  memcpy(t, s.data(), s.size());
+  t[s.size()] = 0;
+  return t;
+}
 // the text arrives in pieces; it is collected into one malloc'ed buffer that grows geometrically
 int text_batch_buffer(impg_gpu_index_t *ix, const impg_gpu_range_t *ranges, size_t n, const impg_gpu_params_t *params, const uint8_t *subset_keep,
                       int32_t merge_distance, const char *const *range_names, char **text, size_t *len, double *seconds3, bool bedpe) {
@@ -1343,7 +1360,7 @@ int text_batch_buffer(impg_gpu_index_t *ix, const impg_gpu_range_t *ranges, size
     memcpy(buf + used, p, k);
     used += k;
   }, seconds3, bedpe);
-  if (!buf) { buf = (char *)malloc(1); if (!buf) throw Error{IMPG_E_OOM, "host out of memory"}; }
+  if (!buf) buf = malloc_text(std::string());
   buf[used] = 0;
   guard.keep = true;
   *text = buf;
@@ -1417,14 +1434,13 @@ int impg_gpu_selftest_bed_rows(impg_gpu_index_t *ix, const impg_gpu_interval_t *
   const bool want_gap = gap_rows_out || gap_range_out || n_gap;
   if (want_gap && !(gap_rows_out && gap_range_out && n_gap)) throw Error{IMPG_E_INVALID, "the gap outputs come together"};
   if (ix->shard || ix->cluster) throw Error{IMPG_E_INVALID, "impg_gpu_selftest_bed_rows takes a single-GPU handle"};
-  if (n_rows >= 0xFFFFFFF0ull) throw Error{IMPG_E_INVALID, "too many rows"};
+  check_row_count(n_rows);
   n_seq = std::min<uint64_t>(n_seq, 1ull << 32);  // (ids are 32 bits wide)
   for (size_t i = 0; i < n_rows; i++) {
     if (rows[i].query_id >= n_seq || rows[i].target_id >= n_seq) throw Error{IMPG_E_INVALID, "a row's sequence id is not below n_seq"};
     if (row_range[i] >= n_ranges) throw Error{IMPG_E_INVALID, "a row's range index is not below n_ranges"};
   }
-  std::vector<std::string> rnames(n_ranges);
-  for (uint32_t q = 0; q < n_ranges; q++) rnames[q] = range_names && range_names[q] ? std::string(range_names[q]) : std::to_string(q);
+  const std::vector<std::string> rnames = default_range_names(n_ranges, range_names);
   IMPG_HIP(hipSetDevice(ix->device));
   EngineLease lease(*ix);
   ix->bed_stats_reset();
@@ -1433,18 +1449,16 @@ int impg_gpu_selftest_bed_rows(impg_gpu_index_t *ix, const impg_gpu_interval_t *
   BedGapRows gap;
   device_bed_selftest(*lease, *ix, rows, row_range, (uint32_t)n_rows, n_ranges, n_seq, merge_distance, merge_strands != 0,
                       original_sequence_coordinates != 0, rnames, merged, out, want_gap ? &gap : nullptr);
+  char *t = malloc_text(out);
   impg_gpu_bed_row_t *m = (impg_gpu_bed_row_t *)malloc(std::max<size_t>(merged.size(), 1) * sizeof(impg_gpu_bed_row_t));
-  char *t = (char *)malloc(out.size() + 1);
   impg_gpu_interval_t *gr = want_gap ? (impg_gpu_interval_t *)malloc(std::max<size_t>(gap.rows.size(), 1) * sizeof(impg_gpu_interval_t)) : nullptr;
   uint32_t *gq = want_gap ? (uint32_t *)malloc(std::max<size_t>(gap.range.size(), 1) * 4) : nullptr;
-  if (!m || !t || (want_gap && (!gr || !gq))) { free(m); free(t); free(gr); free(gq); throw Error{IMPG_E_OOM, "host out of memory"}; }
+  if (!m || (want_gap && (!gr || !gq))) { free(m); free(t); free(gr); free(gq); throw Error{IMPG_E_OOM, "host out of memory"}; }
   if (want_gap) {
     if (!gap.rows.empty()) { memcpy(gr, gap.rows.data(), gap.rows.size() * sizeof(impg_gpu_interval_t)); memcpy(gq, gap.range.data(), gap.range.size() * 4); }
     *gap_rows_out = gr; *gap_range_out = gq; *n_gap = gap.rows.size();
   }
   if (!merged.empty()) memcpy(m, merged.data(), merged.size() * sizeof(impg_gpu_bed_row_t));
-  memcpy(t, out.data(), out.size());
-  t[out.size()] = 0;
   *merged_out = m; *n_merged = merged.size(); *text = t; *len = out.size();
   return IMPG_OK;
   IMPG_CATCH
@@ -1458,26 +1472,21 @@ int impg_gpu_selftest_bedpe_rows(impg_gpu_index_t *ix, const impg_gpu_interval_t
   IMPG_TRY
   if (!ix || !text || !len || !cigar_off || (n_rows && (!rows || !row_range))) throw Error{IMPG_E_INVALID, "null argument"};
   bedpe_refusals(*ix);
-  if (n_rows >= 0xFFFFFFF0ull) throw Error{IMPG_E_INVALID, "too many rows"};
+  check_row_count(n_rows);
   if (cigar_off[0] != 0 || (cigar_off[n_rows] && !cigar_ops)) throw Error{IMPG_E_INVALID, "CIGAR offsets start at 0 and come with their ops"};
   for (size_t i = 0; i < n_rows; i++) {
     if (rows[i].query_id >= ix->view.n_seq || rows[i].target_id >= ix->view.n_seq) throw Error{IMPG_E_INVALID, "a row's sequence id is not one of the index's"};
     if (row_range[i] >= n_ranges || (i && row_range[i] < row_range[i - 1])) throw Error{IMPG_E_INVALID, "the rows come grouped by range, range indices below n_ranges"};
     if (cigar_off[i + 1] < cigar_off[i]) throw Error{IMPG_E_INVALID, "CIGAR offsets must not decrease"};
   }
-  std::vector<std::string> rnames(n_ranges);
-  for (uint32_t q = 0; q < n_ranges; q++) rnames[q] = range_names && range_names[q] ? std::string(range_names[q]) : std::to_string(q);
+  const std::vector<std::string> rnames = default_range_names(n_ranges, range_names);
   IMPG_HIP(hipSetDevice(ix->device));
   EngineLease lease(*ix);
   ix->bedpe_stats_reset();
   std::string out;
   if (n_ranges) device_bedpe_selftest(*lease, *ix, rows, row_range, (uint32_t)n_rows, n_ranges, cigar_off, cigar_ops, merge_distance,
                                       original_sequence_coordinates != 0, rnames, out);
-  char *t = (char *)malloc(out.size() + 1);
-  if (!t) throw Error{IMPG_E_OOM, "host out of memory"};
-  memcpy(t, out.data(), out.size());
-  t[out.size()] = 0;
-  *text = t; *len = out.size();
+  *text = malloc_text(out); *len = out.size();
   return IMPG_OK;
   IMPG_CATCH
 }

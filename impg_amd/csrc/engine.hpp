@@ -365,6 +365,20 @@ struct RowSinks {  // any of the two forms (null = not wanted)
   int4 *c;                        // ... {q_first, q_last, t_first, t_last} (the BED merges work on these)
   uint32_t *clen;                 // store_cigar: number of ops of the row's CIGAR
 };
+// The SoA rows of a chunk as the BED / BEDPE kernels take them, numbered in emission order: range, query sequence, target
+// sequence, {q_first, q_last, t_first, t_last}.  ConstRows: for a kernel that only reads them.  DevRows: their buffers.
+struct Rows { uint32_t *q, *qid, *tid; int4 *c; };
+struct ConstRows { const uint32_t *q, *qid, *tid; const int4 *c; ConstRows(const Rows &r) : q(r.q), qid(r.qid), tid(r.tid), c(r.c) {} };
+struct DevRows {
+  DevBuf q, qid, tid, c;
+  explicit DevRows(BufPool *pool = nullptr) { for (DevBuf *b : {&q, &qid, &tid, &c}) b->pool = pool; }
+  void reserve(size_t n, size_t slack = 0) { q.reserve(n * 4 + slack); qid.reserve(n * 4 + slack); tid.reserve(n * 4 + slack); c.reserve(n * 16 + slack); }
+  Rows view() const { return Rows{q.as<uint32_t>(), qid.as<uint32_t>(), tid.as<uint32_t>(), c.as<int4>()}; }
+  RowSinks sinks(uint32_t *clen = nullptr) const { return RowSinks{nullptr, q.as<uint32_t>(), qid.as<uint32_t>(), tid.as<uint32_t>(), c.as<int4>(), clen}; }
+  // n rows a caller brings (the self-tests) as a run would have left them: E.counters cleared as a run's start clears
+  // them (Engine::scan reads its bad-range flag); E.stream is synchronised, with whatever the caller queued before
+  void upload(Engine &E, const impg_gpu_interval_t *rows, const uint32_t *row_range, uint32_t n);
+};
 // plain_retain: a plain query's rows also pass perform_query's min_output_length retain (main.rs:11682-11688: the text writers)
 void plan_rows(Engine &E, uint32_t n_ranges, const impg_gpu_params_t &p, std::vector<std::unique_ptr<LevelBufs>> &levels,
                DevBuf &self_dev, bool plain_retain, RowPlan &pl);

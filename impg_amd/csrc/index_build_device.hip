@@ -33,12 +33,8 @@ namespace impg {
 
 namespace {
 
-inline uint32_t cdiv(uint64_t a, uint32_t b) { return (uint32_t)((a + b - 1) / b); }
-inline unsigned bits_for(uint64_t n) {
-  unsigned b = 0;
-  while ((1ull << b) < n) b++;
-  return std::max(1u, b);
-}
+using prims::bits_for;
+using prims::cdiv;
 __device__ __forceinline__ unsigned lane() { return threadIdx.x & 63u; }
 __device__ __forceinline__ uint32_t wscan(uint32_t x) {  // inclusive scan over the wave's 64 lanes
 #pragma unroll
@@ -478,13 +474,7 @@ bool build_index_device(impg_gpu_index &ix, const impg_gpu_record_t *records, si
   uint64_t n_ext = 0;
   if (n_entries) {
     ext_counts_kernel<<<cdiv(n_entries, 256), 256, 0, s>>>(d_rec.as<impg_gpu_record_t>(), val2.as<uint32_t>(), (uint32_t)n_entries, ext_cnt.as<uint32_t>());
-    prims::exclusive_sum(tmp, ext_cnt.as<uint32_t>(), ext_off.as<unsigned long long>(), n_entries, s);
-    unsigned long long last_off = 0;
-    uint32_t last_cnt = 0;
-    IMPG_HIP(hipMemcpyAsync(&last_off, ext_off.as<unsigned long long>() + (n_entries - 1), 8, hipMemcpyDeviceToHost, s));
-    IMPG_HIP(hipMemcpyAsync(&last_cnt, ext_cnt.as<uint32_t>() + (n_entries - 1), 4, hipMemcpyDeviceToHost, s));
-    IMPG_HIP(hipStreamSynchronize(s));
-    n_ext = last_off + last_cnt;
+    n_ext = prims::offsets_and_total(tmp, ext_cnt.as<uint32_t>(), ext_off.as<unsigned long long>(), (uint32_t)n_entries, s);
     if (n_ext >= (1ull << 32)) throw Error{IMPG_E_UNSUPPORTED, "external checkpoint array exceeds 2^32"};
   }
   size_blob(ix, 1, n_entries * 4, acc); size_blob(ix, 2, n_entries * 4, acc); size_blob(ix, 3, n_entries * 4, acc); size_blob(ix, 4, n_entries * 4, acc);

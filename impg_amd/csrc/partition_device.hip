@@ -355,12 +355,8 @@ __global__ void finish_kernel(const u64 *__restrict__ key, const int32_t *__rest
   if (i < n_out) out[i] = PIv{key_seq(o_key[i]), key_lo(o_key[i]), o_hi[i]};
 }
 
-inline uint32_t cdiv(size_t a, uint32_t b) { return (uint32_t)std::max<size_t>((a + b - 1) / b, 1); }
-inline unsigned bits_for(uint32_t v) {  // bits that hold 0..v
-  unsigned b = 1;
-  while (b < 32 && (v >> b)) b++;
-  return b;
-}
+using prims::bits_upto;
+using prims::cdiv1;
 
 struct Ops {
   DeviceRegions &R;
@@ -376,11 +372,11 @@ struct Ops {
   void merge(const u64 *key, const int32_t *hi, uint32_t n_ub, const uint32_t *d_n, int32_t d, u64 *out_key, int32_t *out_hi, uint32_t *d_n_out) {
     prims::grow(R.mk, (size_t)n_ub * 8); prims::grow(R.pm, (size_t)n_ub * 8);
     prims::grow(R.head, ((size_t)n_ub + 1) * 4); prims::grow(R.pos, ((size_t)n_ub + 1) * 4);
-    maxkey_kernel<<<cdiv(n_ub, 256), 256, 0, s>>>(key, hi, n_ub, d_n, R.mk.as<u64>());
+    maxkey_kernel<<<cdiv1(n_ub, 256), 256, 0, s>>>(key, hi, n_ub, d_n, R.mk.as<u64>());
     max_scan(R.mk.as<u64>(), R.pm.as<u64>(), n_ub);
-    head_kernel<<<cdiv((size_t)n_ub + 1, 256), 256, 0, s>>>(key, R.pm.as<u64>(), n_ub, d_n, d, R.head.as<uint32_t>());
+    head_kernel<<<cdiv1((size_t)n_ub + 1, 256), 256, 0, s>>>(key, R.pm.as<u64>(), n_ub, d_n, d, R.head.as<uint32_t>());
     excl_scan(R.head.as<uint32_t>(), R.pos.as<uint32_t>(), (size_t)n_ub + 1);
-    run_write_kernel<<<cdiv(n_ub, 256), 256, 0, s>>>(key, R.pm.as<u64>(), R.head.as<uint32_t>(), R.pos.as<uint32_t>(), n_ub, d_n, out_key, out_hi, d_n_out);
+    run_write_kernel<<<cdiv1(n_ub, 256), 256, 0, s>>>(key, R.pm.as<u64>(), R.head.as<uint32_t>(), R.pos.as<uint32_t>(), n_ub, d_n, out_key, out_hi, d_n_out);
     R.launches += 3;
   }
 };
@@ -440,30 +436,30 @@ void DeviceRegions::apply(const impg_gpu_interval_t *d_rows, uint32_t n, int32_t
   if (n_seq == 0) throw Error{IMPG_E_INVALID, "rows for a state without sequences"};
   hipStream_t s = stream;
   Ops op{*this, s};
-  const unsigned end_bit = 32 + bits_for(n_seq);
+  const unsigned end_bit = 32 + bits_upto(n_seq);
   uint32_t *c = ctr.as<uint32_t>();
   const uint32_t n_old = n_mask, n_x = n_missing;
   const int mo = m_cur, xo = x_cur, mn = m_cur ^ 1, xn = x_cur ^ 1, tn = t_cur ^ 1;
   // 1
   prims::grow(key_a, (size_t)2 * n * 8); prims::grow(key_b, (size_t)2 * n * 8); prims::grow(val_a, (size_t)2 * n * 4); prims::grow(val_b, (size_t)2 * n * 4);
   IMPG_HIP(hipMemsetAsync(c + C_HDR, 0, H_WORDS * 4, s));
-  norm_kernel<<<cdiv(n, 256), 256, 0, s>>>(d_rows, n, n_seq, key_a.as<u64>(), val_a.as<int32_t>(), c);
+  norm_kernel<<<cdiv1(n, 256), 256, 0, s>>>(d_rows, n, n_seq, key_a.as<u64>(), val_a.as<int32_t>(), c);
   op.sort(key_a.as<u64>(), key_b.as<u64>(), val_a.as<int32_t>(), val_b.as<int32_t>(), n, end_bit);
   // 2
   prims::grow(a_key, (size_t)n * 8); prims::grow(a_hi, (size_t)n * 4);
   op.merge(key_b.as<u64>(), val_b.as<int32_t>(), n, c + C_N, d, a_key.as<u64>(), a_hi.as<int32_t>(), c + C_M);
   // 3 + 4
   prims::grow(b_lo, (size_t)n * 4); prims::grow(b_hi, (size_t)n * 4);
-  extend_cand_kernel<<<cdiv(n, 256), 256, 0, s>>>(a_key.as<u64>(), a_hi.as<int32_t>(), n, c + C_M, len.as<int32_t>(), x_off[xo].as<uint32_t>(),
+  extend_cand_kernel<<<cdiv1(n, 256), 256, 0, s>>>(a_key.as<u64>(), a_hi.as<int32_t>(), n, c + C_M, len.as<int32_t>(), x_off[xo].as<uint32_t>(),
                                                   x_rng[xo].as<int2>(), min_boundary, min_missing, n_seq, b_lo.as<int32_t>(), b_hi.as<int32_t>(),
                                                   key_a.as<u64>(), val_a.as<int32_t>(), c);
   op.sort(key_a.as<u64>(), key_b.as<u64>(), val_a.as<int32_t>(), val_b.as<int32_t>(), (size_t)2 * n, end_bit);
-  count_valid_kernel<<<cdiv((size_t)2 * n, 256), 256, 0, s>>>(key_b.as<u64>(), 2 * n, n_seq, c + C_CAND);
+  count_valid_kernel<<<cdiv1((size_t)2 * n, 256), 256, 0, s>>>(key_b.as<u64>(), 2 * n, n_seq, c + C_CAND);
   prims::grow(e_key, (size_t)2 * n * 8); prims::grow(e_hi, (size_t)2 * n * 4);
   op.merge(key_b.as<u64>(), val_b.as<int32_t>(), 2 * n, c + C_CAND, 0, e_key.as<u64>(), e_hi.as<int32_t>(), c + C_EXT);
   // 5
   prims::grow(s_a, ((size_t)n + 1) * 4); prims::grow(s_first, ((size_t)n + 1) * 4); prims::grow(s_cnt, ((size_t)n + 1) * 4); prims::grow(s_off, ((size_t)n + 1) * 4);
-  apply_count_kernel<<<cdiv((size_t)n + 1, 256), 256, 0, s>>>(a_key.as<u64>(), n, c + C_M, b_lo.as<int32_t>(), b_hi.as<int32_t>(), e_key.as<u64>(),
+  apply_count_kernel<<<cdiv1((size_t)n + 1, 256), 256, 0, s>>>(a_key.as<u64>(), n, c + C_M, b_lo.as<int32_t>(), b_hi.as<int32_t>(), e_key.as<u64>(),
                                                                e_hi.as<int32_t>(), c + C_EXT, m_off[mo].as<uint32_t>(), m_rng[mo].as<int2>(),
                                                                s_a.as<uint32_t>(), s_first.as<uint32_t>(), s_cnt.as<uint32_t>());
   op.excl_scan(s_cnt.as<uint32_t>(), s_off.as<uint32_t>(), (size_t)n + 1);
@@ -476,7 +472,7 @@ void DeviceRegions::apply(const impg_gpu_interval_t *d_rows, uint32_t n, int32_t
   const uint32_t sg = std::max(n_seg, 1u);
   prims::grow(t_key, (size_t)sg * 8); prims::grow(t_hi, (size_t)sg * 4); prims::grow(n_key, (size_t)sg * 8); prims::grow(n_hi, (size_t)sg * 4);
   prims::grow(o_key, (size_t)sg * 8); prims::grow(o_hi, (size_t)sg * 4);
-  piece_write_kernel<<<cdiv(sg, 256), 256, 0, s>>>(a_key.as<u64>(), b_lo.as<int32_t>(), b_hi.as<int32_t>(), n, s_a.as<uint32_t>(),
+  piece_write_kernel<<<cdiv1(sg, 256), 256, 0, s>>>(a_key.as<u64>(), b_lo.as<int32_t>(), b_hi.as<int32_t>(), n, s_a.as<uint32_t>(),
                                                     s_first.as<uint32_t>(), s_off.as<uint32_t>(), m_rng[mo].as<int2>(), sg, t_key.as<u64>(),
                                                     t_hi.as<int32_t>(), c + C_SEG);
   launches++;
@@ -488,11 +484,11 @@ void DeviceRegions::apply(const impg_gpu_interval_t *d_rows, uint32_t n, int32_t
   const uint32_t comb = n_old + n;
   prims::grow(c_key, (size_t)comb * 8); prims::grow(c_hi, (size_t)comb * 4);
   prims::grow(key_a, (size_t)comb * 8); prims::grow(val_a, (size_t)comb * 4);
-  mask_merge_kernel<<<cdiv(comb, 256), 256, 0, s>>>(m_off[mo].as<uint32_t>(), m_rng[mo].as<int2>(), n_old, n_seq, a_key.as<u64>(), b_lo.as<int32_t>(),
+  mask_merge_kernel<<<cdiv1(comb, 256), 256, 0, s>>>(m_off[mo].as<uint32_t>(), m_rng[mo].as<int2>(), n_old, n_seq, a_key.as<u64>(), b_lo.as<int32_t>(),
                                                     b_hi.as<int32_t>(), n, c + C_M, c_key.as<u64>(), c_hi.as<int32_t>(), c + C_COMB);
   op.merge(c_key.as<u64>(), c_hi.as<int32_t>(), comb, c + C_COMB, 0, key_a.as<u64>(), val_a.as<int32_t>(), c + C_NMASK);
   prims::grow(m_rng[mn], (size_t)comb * 8);
-  table_kernel<<<cdiv(std::max<size_t>(comb, (size_t)n_seq + 1), 256), 256, 0, s>>>(key_a.as<u64>(), val_a.as<int32_t>(), comb, c + C_NMASK, n_seq,
+  table_kernel<<<cdiv1(std::max<size_t>(comb, (size_t)n_seq + 1), 256), 256, 0, s>>>(key_a.as<u64>(), val_a.as<int32_t>(), comb, c + C_NMASK, n_seq,
                                                                                    m_off[mn].as<uint32_t>(), m_rng[mn].as<int2>(), c + C_HDR, H_NMASK, H_EMPTY);
   launches += 2;
   // 8
@@ -500,26 +496,26 @@ void DeviceRegions::apply(const impg_gpu_interval_t *d_rows, uint32_t n, int32_t
   const uint32_t nx1 = std::max(n_x, 1u);
   prims::grow(key_b, (size_t)nx1 * 8); prims::grow(b_lo, (size_t)nx1 * 4); prims::grow(b_hi, (size_t)nx1 * 4);
   prims::grow(s_a, ((size_t)n_x + 1) * 4); prims::grow(s_first, ((size_t)n_x + 1) * 4); prims::grow(s_cnt, ((size_t)n_x + 1) * 4); prims::grow(s_off, ((size_t)n_x + 1) * 4);
-  missing_count_kernel<<<cdiv((size_t)n_x + 1, 256), 256, 0, s>>>(x_off[xo].as<uint32_t>(), x_rng[xo].as<int2>(), n_x, n_seq, m_off[mn].as<uint32_t>(),
+  missing_count_kernel<<<cdiv1((size_t)n_x + 1, 256), 256, 0, s>>>(x_off[xo].as<uint32_t>(), x_rng[xo].as<int2>(), n_x, n_seq, m_off[mn].as<uint32_t>(),
                                                                   m_rng[mn].as<int2>(), key_b.as<u64>(), b_lo.as<int32_t>(), b_hi.as<int32_t>(),
                                                                   s_a.as<uint32_t>(), s_first.as<uint32_t>(), s_cnt.as<uint32_t>());
   op.excl_scan(s_cnt.as<uint32_t>(), s_off.as<uint32_t>(), (size_t)n_x + 1);
   prims::grow(c_key, (size_t)xs_ub * 8); prims::grow(c_hi, (size_t)xs_ub * 4);
   prims::grow(key_a, (size_t)xs_ub * 8); prims::grow(val_a, (size_t)xs_ub * 4);
-  piece_write_kernel<<<cdiv(xs_ub, 256), 256, 0, s>>>(key_b.as<u64>(), b_lo.as<int32_t>(), b_hi.as<int32_t>(), n_x, s_a.as<uint32_t>(),
+  piece_write_kernel<<<cdiv1(xs_ub, 256), 256, 0, s>>>(key_b.as<u64>(), b_lo.as<int32_t>(), b_hi.as<int32_t>(), n_x, s_a.as<uint32_t>(),
                                                        s_first.as<uint32_t>(), s_off.as<uint32_t>(), m_rng[mn].as<int2>(), xs_ub, c_key.as<u64>(),
                                                        c_hi.as<int32_t>(), c + C_XSEG);
   op.merge(c_key.as<u64>(), c_hi.as<int32_t>(), xs_ub, c + C_XSEG, 0, key_a.as<u64>(), val_a.as<int32_t>(), c + C_NMISS);
   prims::grow(x_rng[xn], (size_t)xs_ub * 8);
-  table_kernel<<<cdiv(std::max<size_t>(xs_ub, (size_t)n_seq + 1), 256), 256, 0, s>>>(key_a.as<u64>(), val_a.as<int32_t>(), xs_ub, c + C_NMISS, n_seq,
+  table_kernel<<<cdiv1(std::max<size_t>(xs_ub, (size_t)n_seq + 1), 256), 256, 0, s>>>(key_a.as<u64>(), val_a.as<int32_t>(), xs_ub, c + C_NMISS, n_seq,
                                                                                     x_off[xn].as<uint32_t>(), x_rng[xn].as<int2>(), c + C_HDR, H_NMISS, -1);
   launches += 3;
   // 9
   IMPG_HIP(hipMemsetAsync(totals[tn].p, 0, std::max<size_t>((size_t)n_seq * 8, 8), s));
   IMPG_HIP(hipMemsetAsync(c + C_BEST, 0, 8, s));
-  select_kernel<<<cdiv(xs_ub, 256), 256, 0, s>>>(key_a.as<u64>(), val_a.as<int32_t>(), xs_ub, c + C_NMISS, (u64 *)(c + C_BEST), totals[tn].as<u64>());
+  select_kernel<<<cdiv1(xs_ub, 256), 256, 0, s>>>(key_a.as<u64>(), val_a.as<int32_t>(), xs_ub, c + C_NMISS, (u64 *)(c + C_BEST), totals[tn].as<u64>());
   prims::grow(out_rows, (size_t)sg * sizeof(PIv));
-  finish_kernel<<<cdiv(sg, 256), 256, 0, s>>>(key_a.as<u64>(), val_a.as<int32_t>(), (const u64 *)(c + C_BEST), c, o_key.as<u64>(), o_hi.as<int32_t>(),
+  finish_kernel<<<cdiv1(sg, 256), 256, 0, s>>>(key_a.as<u64>(), val_a.as<int32_t>(), (const u64 *)(c + C_BEST), c, o_key.as<u64>(), o_hi.as<int32_t>(),
                                               sg, out_rows.as<PIv>());
   launches += 4;
   IMPG_HIP(hipMemcpyAsync(h_hdr, c + C_HDR, H_WORDS * 4, hipMemcpyDeviceToHost, s));

@@ -177,12 +177,8 @@ __global__ __launch_bounds__(256) void count_finish_kernel(const uint32_t *__res
   count[c] = v;
 }
 
-inline uint32_t cdiv(size_t a, uint32_t b) { return (uint32_t)std::max<size_t>((a + b - 1) / b, 1); }
-inline unsigned bits_for(uint32_t v) {  // bits that hold 0..v
-  unsigned b = 1;
-  while (b < 32 && (v >> b)) b++;
-  return b;
-}
+using prims::bits_upto;
+using prims::cdiv1;
 
 }  // namespace
 
@@ -237,36 +233,36 @@ void SupportDevice::run(const impg_gpu_interval_t *d_rows, uint32_t n, const uin
   grow(key_a, (size_t)n * 8); grow(key_b, (size_t)n * 8); grow(s_rng, (size_t)n * 8);
   grow(val_a, (size_t)n * 4); grow(val_b, (size_t)n * 4);
   u64 *k2 = s_rng.as<u64>();  // (the survivors' ranges are written after the second sort has read this)
-  key_kernel<<<cdiv(n, 256), 256, 0, s>>>(d_rows, n, d_offsets, n_cand, d_cand.as<impg_gpu_range_t>(), in.n_seq, key_a.as<u64>(), k2,
+  key_kernel<<<cdiv1(n, 256), 256, 0, s>>>(d_rows, n, d_offsets, n_cand, d_cand.as<impg_gpu_range_t>(), in.n_seq, key_a.as<u64>(), k2,
                                           val_a.as<uint32_t>(), d_nrow.as<uint32_t>(), ctr.as<uint32_t>());
   // 2
   prims::radix_sort_pairs(tmp, key_a.as<u64>(), key_b.as<u64>(), val_a.as<uint32_t>(), val_b.as<uint32_t>(), n, 0u, 64u, s);
-  prims::gather_kernel<u64><<<cdiv(n, 256), 256, 0, s>>>(k2, val_b.as<uint32_t>(), n, key_a.as<u64>());
-  prims::radix_sort_pairs(tmp, key_a.as<u64>(), key_b.as<u64>(), val_b.as<uint32_t>(), val_a.as<uint32_t>(), n, 0u, 32u + bits_for(n_cand), s);
+  prims::gather_kernel<u64><<<cdiv1(n, 256), 256, 0, s>>>(k2, val_b.as<uint32_t>(), n, key_a.as<u64>());
+  prims::radix_sort_pairs(tmp, key_a.as<u64>(), key_b.as<u64>(), val_b.as<uint32_t>(), val_a.as<uint32_t>(), n, 0u, 32u + bits_upto(n_cand), s);
   const u64 *skey = key_b.as<u64>();
   const uint32_t *sidx = val_a.as<uint32_t>();
   // 3
   grow(flag, ((size_t)n + 1) * 4); grow(pos, ((size_t)n + 1) * 4); grow(hull, (size_t)n * 8);
-  fold_kernel<<<cdiv((size_t)n + 1, 256), 256, 0, s>>>(d_rows, skey, sidx, n, n_cand, d_cand.as<impg_gpu_range_t>(), d_nrow.as<uint32_t>(),
+  fold_kernel<<<cdiv1((size_t)n + 1, 256), 256, 0, s>>>(d_rows, skey, sidx, n, n_cand, d_cand.as<impg_gpu_range_t>(), d_nrow.as<uint32_t>(),
                                                        bl ? d_bloff.as<uint32_t>() : nullptr, d_blrng.as<int2>(), in.span_bp, in.merge_distance,
                                                        flag.as<uint32_t>(), hull.as<int2>(), ctr.as<uint32_t>());
   // 4
   prims::exclusive_sum(tmp, flag.as<uint32_t>(), pos.as<uint32_t>(), (size_t)n + 1, s);
   grow(s_cand, (size_t)n * 4); grow(s_seq, (size_t)n * 4); grow(s_off, ((size_t)n_cand + 1) * 4);
-  compact_kernel<<<cdiv(n, 256), 256, 0, s>>>(skey, flag.as<uint32_t>(), pos.as<uint32_t>(), hull.as<int2>(), n, n_cand,
+  compact_kernel<<<cdiv1(n, 256), 256, 0, s>>>(skey, flag.as<uint32_t>(), pos.as<uint32_t>(), hull.as<int2>(), n, n_cand,
                                               identity ? nullptr : d_ent.as<uint32_t>(), s_cand.as<uint32_t>(), s_seq.as<uint32_t>(),
                                               s_rng.as<int2>(), key_a.as<u64>(), ctr.as<uint32_t>());
   IMPG_HIP(hipMemcpyAsync(h_hdr, ctr.p, C_WORDS * 4, hipMemcpyDeviceToHost, s));
   IMPG_HIP(hipStreamSynchronize(s));
   const uint32_t n_surv = h_hdr[C_NSURV];
   if (n_surv > n) throw Error{IMPG_E_HIP, "internal: more survivors than rows"};
-  offsets_kernel<<<cdiv((size_t)n_cand + 1, 256), 256, 0, s>>>(s_cand.as<uint32_t>(), n_surv, n_cand, s_off.as<uint32_t>());
+  offsets_kernel<<<cdiv1((size_t)n_cand + 1, 256), 256, 0, s>>>(s_cand.as<uint32_t>(), n_surv, n_cand, s_off.as<uint32_t>());
   // 5
   if (!identity && n_surv) {
-    prims::radix_sort_pairs(tmp, key_a.as<u64>(), key_b.as<u64>(), val_a.as<uint32_t>(), val_b.as<uint32_t>(), n_surv, 0u, 32u + bits_for(n_cand), s);
-    entity_heads_kernel<<<cdiv(n_surv, 256), 256, 0, s>>>(key_b.as<u64>(), n_surv, n_cand, d_count.as<uint32_t>());
+    prims::radix_sort_pairs(tmp, key_a.as<u64>(), key_b.as<u64>(), val_a.as<uint32_t>(), val_b.as<uint32_t>(), n_surv, 0u, 32u + bits_upto(n_cand), s);
+    entity_heads_kernel<<<cdiv1(n_surv, 256), 256, 0, s>>>(key_b.as<u64>(), n_surv, n_cand, d_count.as<uint32_t>());
   }
-  count_finish_kernel<<<cdiv(n_cand, 256), 256, 0, s>>>(s_off.as<uint32_t>(), in.max_entities ? d_max.as<uint32_t>() : nullptr, n_cand, identity ? 1 : 0,
+  count_finish_kernel<<<cdiv1(n_cand, 256), 256, 0, s>>>(s_off.as<uint32_t>(), in.max_entities ? d_max.as<uint32_t>() : nullptr, n_cand, identity ? 1 : 0,
                                                         d_count.as<uint32_t>());
   IMPG_HIP(hipMemcpyAsync(out.count.data(), d_count.p, (size_t)n_cand * 4, hipMemcpyDeviceToHost, s));
   std::vector<uint32_t> off32, seqs;

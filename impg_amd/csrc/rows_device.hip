@@ -31,12 +31,8 @@ namespace impg {
 
 namespace {
 
-inline uint32_t cdiv(uint64_t a, uint32_t b) { return (uint32_t)((a + b - 1) / b); }
-inline unsigned bits_for(uint64_t n) {
-  unsigned b = 0;
-  while ((1ull << b) < n) b++;
-  return std::max(1u, b);
-}
+using prims::bits_for;
+using prims::cdiv;
 
 __global__ __launch_bounds__(256) void self_flags_kernel(const FrontierRec *__restrict__ self, uint32_t n_self, int transitive,
                                                          int32_t min_len_plain, uint32_t *__restrict__ flag) {
@@ -258,6 +254,23 @@ void scatter_rows(Engine &E, std::vector<std::unique_ptr<LevelBufs>> &levels, co
   }
 }
 
+void DevRows::upload(Engine &E, const impg_gpu_interval_t *rows, const uint32_t *row_range, uint32_t n) {
+  hipStream_t s = E.stream;
+  std::vector<uint32_t> h_qid(n), h_tid(n);
+  std::vector<int4> h_c(n);
+  for (uint32_t i = 0; i < n; i++) {
+    h_qid[i] = rows[i].query_id; h_tid[i] = rows[i].target_id;
+    h_c[i] = int4{rows[i].q_first, rows[i].q_last, rows[i].t_first, rows[i].t_last};
+  }
+  reserve(n);
+  IMPG_HIP(hipMemsetAsync(E.counters.p, 0, 64, s));
+  IMPG_HIP(hipMemcpyAsync(q.p, row_range, (size_t)n * 4, hipMemcpyHostToDevice, s));
+  IMPG_HIP(hipMemcpyAsync(qid.p, h_qid.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+  IMPG_HIP(hipMemcpyAsync(tid.p, h_tid.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+  IMPG_HIP(hipMemcpyAsync(c.p, h_c.data(), (size_t)n * 16, hipMemcpyHostToDevice, s));
+  IMPG_HIP(hipStreamSynchronize(s));
+}
+
 // store_cigar: clen[row] (written by scatter_rows) -> coff[n_rows + 1] and the pool.  Returns the number of ops.
 uint64_t build_row_cigars(Engine &E, std::vector<std::unique_ptr<LevelBufs>> &levels, const RowPlan &pl, const DevBuf &clen, DevBuf &coff,
                           DevBuf &pool) {
@@ -269,13 +282,7 @@ uint64_t build_row_cigars(Engine &E, std::vector<std::unique_ptr<LevelBufs>> &le
   }
   DevBuf stmp;
   stmp.pool = &E.level_pool;
-  prims::exclusive_sum(stmp, clen.as<uint32_t>(), coff.as<unsigned long long>(), pl.n_rows, s);
-  unsigned long long last_off = 0;
-  uint32_t last_len = 0;
-  IMPG_HIP(hipMemcpyAsync(&last_off, coff.as<unsigned long long>() + (pl.n_rows - 1), 8, hipMemcpyDeviceToHost, s));
-  IMPG_HIP(hipMemcpyAsync(&last_len, clen.as<uint32_t>() + (pl.n_rows - 1), 4, hipMemcpyDeviceToHost, s));
-  IMPG_HIP(hipStreamSynchronize(s));
-  const uint64_t total = last_off + last_len;
+  const uint64_t total = prims::offsets_and_total(stmp, clen.as<uint32_t>(), coff.as<unsigned long long>(), pl.n_rows, s);
   IMPG_HIP(hipMemcpyAsync(coff.as<unsigned long long>() + pl.n_rows, &total, 8, hipMemcpyHostToDevice, s));
   pool.reserve(std::max<size_t>(total * 4, 256));
   const uint32_t *fl = pl.flag.as<uint32_t>(), *pos = pl.pos.as<uint32_t>(), *rs = pl.rec_start.as<uint32_t>(), *rd = pl.rec_dest.as<uint32_t>();

@@ -1,6 +1,7 @@
-// What the device text writers share (bed_device.hip: BED rows; bedpe_device.hip: BEDPE lines): the name / shift /
-// range-name tables, the decimal printers, and the piece loop that moves finished text across PCIe
-// (device_text_pieces, defined in bed_device.hip).
+// What the device text writers share (bed_device.hip: BED rows; bedpe_device.hip: BEDPE lines; each keeps only its line's
+// field layout, a length kernel and a write kernel): the name / shift / range-name tables and the printers of a sequence,
+// a range name and a decimal (here); the tables' upload and the piece loop that moves finished text across PCIe
+// (TextTableBufs, device_text_pieces: text_device.hip); and device_rows_text, which runs a format's two kernels around them.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -9,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "device_prims.hpp"
 #include "engine.hpp"
 
 namespace impg {
@@ -67,5 +69,26 @@ struct TextTableBufs {
 void device_text_pieces(Engine &E, const uint32_t *d_len, uint32_t n_rows, const char *what,
                         const std::function<void(uint32_t, uint32_t, const unsigned long long *, unsigned long long, char *)> &write,
                         const std::function<void(const char *, size_t)> &sink, std::atomic<uint64_t> &pieces, std::atomic<uint64_t> &bytes);
+
+// n_rows records of type Row (in `rows`, on the device) as text: the chunk's tables, len_kernel for every line's length,
+// then write_kernel piece by piece.  pieces / bytes: the format's two text counters.
+template <class Row, void (*len_kernel)(const Row *, uint32_t, TextTables, uint32_t *),
+          void (*write_kernel)(const Row *, uint32_t, TextTables, const unsigned long long *, unsigned long long, char *)>
+void device_rows_text(Engine &E, const impg_gpu_index &ix, const DevBuf &rows, uint32_t n_rows, uint32_t n_ranges,
+                      const std::vector<std::string> &rnames, bool original_coords, const std::function<void(const char *, size_t)> &sink,
+                      const char *what, std::atomic<uint64_t> &pieces, std::atomic<uint64_t> &bytes) {
+  if (!n_rows) return;
+  hipStream_t s = E.stream;
+  TextTableBufs tb(E, ix, n_ranges, rnames, original_coords);
+  const TextTables t = tb.t;
+  DevBuf len;
+  len.reserve((size_t)n_rows * 4);
+  len_kernel<<<prims::cdiv(n_rows, 256), 256, 0, s>>>(rows.as<Row>(), n_rows, t, len.as<uint32_t>());
+  device_text_pieces(E, len.as<uint32_t>(), n_rows, what,
+                     [&](uint32_t r0, uint32_t r1, const unsigned long long *off, unsigned long long base, char *out) {
+                       write_kernel<<<prims::cdiv(r1 - r0, 256), 256, 0, s>>>(rows.as<Row>() + r0, r1 - r0, t, off, base, out);
+                     },
+                     sink, pieces, bytes);
+}
 
 }  // namespace impg

@@ -194,6 +194,45 @@ def test_no_merge_branch(g, dense):
             assert got[k] == [bed_gen.merged_tuple(x) for x in o.bed_merge(s.astype(o.INTERVAL_DTYPE), -1, True)], (k, interleave)
 
 
+# ---- where the sorts' guards stand ------------------------------------------------------------------------------------
+def tied_rows(n=257):
+    """n forward rows of one range that are equal on every sort key of both merges (sequences, strand, q_first = start)
+    and differ in their ends and targets: only emission order tells them apart.  One more than a block of threads."""
+    rng = np.random.default_rng(257)
+    a = np.zeros(n, dtype=impg_amd.INTERVAL_DTYPE)
+    a["q_first"], a["q_last"] = 100, 100 + rng.integers(0, 50, n)
+    t = rng.integers(0, 300, n)
+    a["t_first"], a["t_last"] = t, t + rng.integers(1, 20, n)
+    assert (np.diff(a["q_last"]) < 0).any() and (np.diff(a["t_first"]) < 0).any()  # (no key would have put them in this order)
+    return a
+
+
+GUARD_SETS = {"one row": [bed_gen.intervals([(1, 30, 20, 0, 5, 9)])],
+              "two rows in two ranges": [bed_gen.intervals([(0, 10, 20, 1, 5, 9)]), bed_gen.intervals([(0, 12, 18, 1, 7, 9)])],
+              "257 tied rows": [tied_rows()]}
+
+
+@pytest.mark.parametrize("d", [-1, 0, 5])
+@pytest.mark.parametrize("ms", [True, False])
+@pytest.mark.parametrize("case", sorted(GUARD_SETS))
+def test_sort_guard_edges(g, case, d, ms):
+    """a call of one row (no gap_2d sort), one of two rows that share no range, and 257 rows that tie on every key of
+    every pass: merged rows, the rows between the merges, counters and text as the oracle and bed_gen state them"""
+    sets = GUARD_SETS[case]
+    rows, rr = bed_gen.batch(sets)
+    merged, text, grows, grange = g.bed_rows(rows, rr, len(sets), 2, d, ms, gap=True)
+    got, ggot = by_range(merged, len(sets)), gap_by_range(grows, grange, len(sets))
+    for k, s in enumerate(sets):
+        so = s.astype(o.INTERVAL_DTYPE)
+        assert ggot[k] == [tuple(x) for x in o.merge_gap_2d(so, d).tolist()], (case, d, k)
+        assert got[k] == [bed_gen.merged_tuple(x) for x in o.bed_merge(so, d, ms)], (case, d, ms, k)
+    if d < 0 and not ms:
+        assert [x for r in got for x in r] == [bed_gen.merged_tuple(x) for x in rows]  # untouched, in emission order
+    c = counters(g)
+    assert c["bed_rows"] == len(rows) and c["bed_gap_roots"] == len(grows) and c["bed_runs"] == len(merged)
+    assert text == text_of(merged, [str(k) for k in range(len(sets))], names_of(g)) and c["bed_text_bytes"] == len(text)
+
+
 # ---- overflow -----------------------------------------------------------------------------------------------------
 def test_overflow_pair_on_the_device(g):
     iv = bed_gen.intervals(bed_gen.OVERFLOW_PAIR)

@@ -344,6 +344,40 @@ def test_refused_rows(world):
     assert run([], [], 0, [], 0) == ""
 
 
+@pytest.mark.parametrize("d", [-1, 0])
+def test_sort_guard_edges(world, d):
+    """where the order's guards stand, on rows of our own: no row left after the drop (no text), exactly one left (no
+    sort), and 257 left -- one more than a block of threads -- that tie on every key of all three passes, so that only
+    emission order tells them apart: the text and the counters are the model's"""
+    g = world[0]
+    rng = np.random.default_rng(258)
+    self_row = iv(0, 100, 200, 0, 100, 200)
+
+    def row(ln):  # same sequences, strand, q start and t_first; the ends and the ops differ: "a= bX c="
+        a, b = (int(x) for x in rng.integers(0, ln + 1, 2))
+        a, b = min(a, b), max(a, b) - min(a, b)
+        ops = [n | code << 29 for n, code in ((a, 0), (b, 1), (ln - a - b, 0)) if n]
+        return iv(1, 10, 10 + ln, 0, 110, 110 + ln), np.array(ops, dtype=np.uint32)
+
+    tied = [row(int(ln)) for ln in rng.integers(1, 60, 257)]
+    assert any(x[0][2] > y[0][2] for x, y in zip(tied, tied[1:]))  # (no key would have put them in this order)
+    eq = np.array([100], dtype=np.uint32)
+    cases = [([[self_row]] * 3, [[eq]] * 3, 0),
+             ([[self_row, tied[0][0]]], [[eq, tied[0][1]]], 1),
+             ([[self_row] + [r for r, _ in tied]], [[eq] + [c for _, c in tied]], 257)]
+    for rows, cigars, left in cases:
+        names = ["x%d" % q for q in range(len(rows))]
+        tally = ref.new_counters()
+        want = "".join(ref.bedpe_range(r, c, d, nm, g.seq_name, transitive=True, counters=tally) for r, c, nm in zip(rows, cigars, names))
+        flat = np.array([x for r in rows for x in r], dtype=impg_amd.INTERVAL_DTYPE)
+        rr = [q for q, r in enumerate(rows) for _ in r]
+        got = g.bedpe_rows(flat, rr, len(rows), [x for c in cigars for x in c], merge_distance=d, range_names=names).decode()
+        assert got == want and got.count("\n") == left, (d, left)
+        have = counters(g)
+        assert {k: have[k] for k in ref.COUNTERS} == {k: tally[k] for k in ref.COUNTERS}, (d, left)
+        assert have["bedpe_rows"] == left == have["bedpe_runs"] and have["bedpe_text_pieces"] == (1 if left else 0)
+
+
 def test_refused_handles(tmp_path):
     """handles the device route leaves to the host route: sharded and multi-GPU ones, a sequence of 2^29 bases or more"""
     text, names = random_paf(96, 200, n_seq=4, seq_len=20000, max_ops=40, self_aln=True)
