@@ -188,6 +188,9 @@ SYMBOLS = [
     ("impg_gpu_query_batch_bedpe", C.c_int, [_P, _P, C.c_size_t, C.POINTER(Params), _P, C.c_int32, _P, C.POINTER(_P), C.POINTER(C.c_size_t),
                                              _P]),
     ("impg_gpu_query_batch_bedpe_fd", C.c_int, [_P, _P, C.c_size_t, C.POINTER(Params), _P, C.c_int32, _P, C.c_int, C.POINTER(C.c_uint64), _P]),
+    ("impg_gpu_query_batch_paf", C.c_int, [_P, _P, C.c_size_t, C.POINTER(Params), _P, C.c_int32, _P, C.POINTER(_P), C.POINTER(C.c_size_t),
+                                           _P]),
+    ("impg_gpu_query_batch_paf_fd", C.c_int, [_P, _P, C.c_size_t, C.POINTER(Params), _P, C.c_int32, _P, C.c_int, C.POINTER(C.c_uint64), _P]),
     ("impg_gpu_results_paf", C.c_int, [_P, _P, _P, C.POINTER(Params), C.c_int32, C.c_int, C.POINTER(_P), C.POINTER(C.c_size_t)]),
     ("impg_gpu_parse_cigar", C.c_long, [C.c_char_p, C.c_size_t, _P, C.c_size_t]),
     ("impg_gpu_parse_target_range", C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
@@ -248,6 +251,8 @@ SYMBOLS = [
                                              C.POINTER(C.c_size_t)]),
     ("impg_gpu_selftest_bedpe_rows", C.c_int, [_P, _P, _P, C.c_size_t, C.c_uint32, _P, _P, C.c_int32, C.c_int, _P, C.POINTER(_P),
                                                C.POINTER(C.c_size_t)]),
+    ("impg_gpu_selftest_paf_rows", C.c_int, [_P, _P, _P, C.c_size_t, C.c_uint32, _P, _P, C.c_int32, C.c_int, _P, C.POINTER(_P),
+                                             C.POINTER(C.c_size_t)]),
     ("impg_synth_seq_name", C.c_int, [C.c_uint32, C.c_char_p, C.c_size_t]),
     ("impg_synth_bed", C.c_int, [C.c_uint64, C.c_size_t, C.c_uint32, C.c_int32, C.c_int32, _P]),
 ]

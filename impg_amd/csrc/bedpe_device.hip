@@ -16,6 +16,7 @@
 //             and one I / D op each, and merge_consecutive_cigar_ops (main.rs:13014-13035) removes one op for every
 //             adjacent I-I / D-D pair: those inside the joined rows, and those of `A.last [I] [D] B.first` at the join.
 //   text      one line per run, written by the device; gi / bi divided in f32 and printed as format!("{:.6}") does
+// PAF (paf_device.inc, included at the end) runs the same summary, order and link stages and prints the merged CIGARs too.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -326,20 +327,28 @@ void require_rows(const std::vector<uint32_t> &h_off) {
   for (size_t q = 0; q + 1 < h_off.size(); q++)
     if (h_off[q + 1] == h_off[q]) throw Error{IMPG_E_INVALID, "no result row to drop (the reference panics in Vec::remove(0))"};
 }
+// What the summary, order and link stages leave on the device.  BEDPE needs only the run records and drops the rest when
+// merge_rows returns; PAF reads the summaries, the order and the heads again for its CIGARs (PafChunk, below).
+struct Merged {
+  DevBuf sum, ctl, head, run_pos;
+  prims::KeySort ks;
+  const uint32_t *perm = nullptr;  // the kept rows in sorted order (emission order when nothing is sorted)
+  uint32_t m = 0, n_runs = 0;      // rows after the drop, lines
+  Control counts{};                // the stages' counters, home
+  explicit Merged(BufPool *pool) : ks(pool) { for (DevBuf *b : {&sum, &ctl, &head, &run_pos}) b->pool = pool; }
+};
 // R: n rows grouped by range in emission order, range q's at [d_offsets[q], d_offsets[q + 1]), none of the ranges empty;
-// row r's ops at d_pool[d_coff[r] .. d_coff[r + 1])
-uint32_t merge_rows(Engine &E, const impg_gpu_index &ix, ConstRows R, uint32_t n, uint32_t n_ranges, const uint32_t *d_offsets,
-                    const unsigned long long *d_coff, const uint32_t *d_pool, int32_t merge_distance, DevBuf &out) {
+// row r's ops at d_pool[d_coff[r] .. d_coff[r + 1]).  The run records go to `out`; M.m, M.n_runs and M.counts say what ran.
+void merge_rows(Engine &E, const impg_gpu_index &ix, ConstRows R, uint32_t n, uint32_t n_ranges, const uint32_t *d_offsets,
+                const unsigned long long *d_coff, const uint32_t *d_pool, int32_t merge_distance, DevBuf &out, Merged &M) {
   hipStream_t s = E.stream;
   const bool sorted = merge_distance >= 0;  // (a negative distance: neither a sort nor a merge, emission order)
   const unsigned seq_bits = bits_for(ix.view.n_seq), q_bits = bits_for(n_ranges);
   if (sorted && (33 + seq_bits > 64 || q_bits + seq_bits > 64))
     throw Error{IMPG_E_UNSUPPORTED, "too many sequences for the device-side BEDPE merge (use impg_gpu_results_paf)"};
-  DevBuf sum, ctl;
-  sum.pool = ctl.pool = &E.level_pool;
-  const uint32_t m = n - n_ranges;  // rows after the drop
-  ix.bedpe_stats[BEDPE_ROWS] += m;
-  if (!m) return 0;
+  DevBuf &sum = M.sum, &ctl = M.ctl;
+  const uint32_t m = M.m = n - n_ranges;  // rows after the drop
+  if (!m) return;
   ctl.reserve(256);
   IMPG_HIP(hipMemsetAsync(ctl.p, 0, sizeof(Control), s));
   Control *d_ctl = ctl.as<Control>();
@@ -354,9 +363,10 @@ uint32_t merge_rows(Engine &E, const impg_gpu_index &ix, ConstRows R, uint32_t n
     default: launch_summary<4>(R.q, d_offsets, d_coff, d_pool, n, d_sum, d_ctl, s); break;
   }
   // ---- order -----------------------------------------------------------------------------------------------------------
-  prims::KeySort ks(&E.level_pool);
-  DevBuf k_t, k_mid, k_hi, head, run_pos;
-  for (DevBuf *b : {&k_t, &k_mid, &k_hi, &head, &run_pos}) b->pool = &E.level_pool;
+  prims::KeySort &ks = M.ks;
+  DevBuf k_t, k_mid, k_hi;
+  DevBuf &head = M.head, &run_pos = M.run_pos;
+  for (DevBuf *b : {&k_t, &k_mid, &k_hi}) b->pool = &E.level_pool;
   const size_t mb4 = (size_t)m * 4;
   ks.perm.reserve(mb4);
   if (sorted) { k_t.reserve((size_t)n * 4); k_mid.reserve((size_t)n * 8); k_hi.reserve((size_t)n * 8); }
@@ -369,12 +379,13 @@ uint32_t merge_rows(Engine &E, const impg_gpu_index &ix, ConstRows R, uint32_t n
     ks.run({{k_t.p, false, 32}, {k_mid.p, true, 33 + seq_bits}, {k_hi.p, true, q_bits + seq_bits}}, /*first_in_order=*/false, m, s);
     perm = ks.order;
   }
+  M.perm = perm;
   // ---- link and reduce -------------------------------------------------------------------------------------------------
   head.reserve(mb4); run_pos.reserve(mb4);
   heads_kernel<<<cdiv(m, 256), 256, 0, s>>>(R, perm, m, merge_distance, head.as<uint32_t>());
   const uint32_t n_runs = (uint32_t)E.scan(head.as<uint32_t>(), run_pos.as<uint32_t>(), m);
   // the flags are home with the scan's synchronisation behind them: refuse before a run record exists
-  Control h_ctl;
+  Control &h_ctl = M.counts;
   IMPG_HIP(hipMemcpyAsync(&h_ctl, ctl.p, sizeof(Control), hipMemcpyDeviceToHost, s));
   IMPG_HIP(hipStreamSynchronize(s));
   if (h_ctl.flags[FLAG_NO_CIGAR]) throw Error{IMPG_E_UNSUPPORTED, "a result row without CIGAR"};
@@ -384,28 +395,32 @@ uint32_t merge_rows(Engine &E, const impg_gpu_index &ix, ConstRows R, uint32_t n
   reduce_kernel<<<cdiv(m, 256), 256, 0, s>>>(R, sum.as<RowSum>(), perm, head.as<uint32_t>(), run_pos.as<uint32_t>(), m, merge_distance,
                                              out.as<Run>(), d_ctl);
   IMPG_HIP(hipMemcpyAsync(&h_ctl, ctl.p, sizeof(Control), hipMemcpyDeviceToHost, s));
-  IMPG_HIP(hipStreamSynchronize(s));  // (the scratch buffers of this function go back to the pool here)
-  ix.bedpe_stats[BEDPE_RUNS] += n_runs;
-  ix.bedpe_stats[BEDPE_SUMMARY_OPS] += h_ctl.ctr[CTR_SUMMARY_OPS];
-  ix.bedpe_stats[BEDPE_JOINS_CONTIGUOUS] += h_ctl.ctr[CTR_JOINS_CONTIGUOUS];
-  ix.bedpe_stats[BEDPE_JOINS_GAP] += h_ctl.ctr[CTR_JOINS_GAP];
-  ix.bedpe_stats[BEDPE_FUSED_OPS] += h_ctl.ctr[CTR_FUSED_OPS];
-  return n_runs;
+  IMPG_HIP(hipStreamSynchronize(s));  // (the key buffers of this function go back to the pool here)
+  M.n_runs = n_runs;
 }
-}  // namespace
+// BEDPE's use of it: the stages' buffers go back to the pool on return, the counters into the handle's bedpe_* ones
+uint32_t merge_rows_bedpe(Engine &E, const impg_gpu_index &ix, ConstRows R, uint32_t n, uint32_t n_ranges, const uint32_t *d_offsets,
+                          const unsigned long long *d_coff, const uint32_t *d_pool, int32_t merge_distance, DevBuf &out) {
+  Merged M(&E.level_pool);
+  ix.bedpe_stats[BEDPE_ROWS] += n - n_ranges;
+  merge_rows(E, ix, R, n, n_ranges, d_offsets, d_coff, d_pool, merge_distance, out, M);
+  ix.bedpe_stats[BEDPE_RUNS] += M.n_runs;
+  ix.bedpe_stats[BEDPE_SUMMARY_OPS] += M.counts.ctr[CTR_SUMMARY_OPS];
+  ix.bedpe_stats[BEDPE_JOINS_CONTIGUOUS] += M.counts.ctr[CTR_JOINS_CONTIGUOUS];
+  ix.bedpe_stats[BEDPE_JOINS_GAP] += M.counts.ctr[CTR_JOINS_GAP];
+  ix.bedpe_stats[BEDPE_FUSED_OPS] += M.counts.ctr[CTR_FUSED_OPS];
+  return M.n_runs;
+}
 
-// Rows of one chunk -> the runs BEDPE prints, left on the device in `out` (grouped by range, in output order); returns
-// their number.  levels / self_dev: what Engine::run kept for the chunk, with store_cigar.  Every refusal is raised here,
-// before any of the chunk's text exists.  Counts into the handle's bedpe_* counters.
-uint32_t device_bedpe_rows(Engine &E, const impg_gpu_index &ix, uint32_t n_ranges, const impg_gpu_params_t &p, int32_t merge_distance,
-                           std::vector<std::unique_ptr<LevelBufs>> &levels, DevBuf &self_dev, DevBuf &out) {
+// The rows of a chunk and their CIGARs where the stages above take them: range-major, the reference's emission order
+// within a range (rows_device.hip).  Returns the number of rows; the levels' memory goes back to the pool.
+uint32_t place_rows(Engine &E, uint32_t n_ranges, const impg_gpu_params_t &p, std::vector<std::unique_ptr<LevelBufs>> &levels, DevBuf &self_dev,
+                    DevRows &rows, DevBuf &coff, DevBuf &pool, DevBuf &offsets) {
   hipStream_t s = E.stream;
-  DevRows rows(&E.level_pool);
-  DevBuf clen, coff, pool, offsets;
-  for (DevBuf *b : {&clen, &coff, &pool, &offsets}) b->pool = &E.level_pool;
+  DevBuf clen;
+  clen.pool = &E.level_pool;
   uint32_t n = 0;
   {
-    // ---- rows and their CIGARs: range-major, the reference's emission order within a range (rows_device.hip) ---------
     RowPlan pl;  // (its tables go back to the pool at the end of this block, before the sorts take their memory)
     plan_rows(E, n_ranges, p, levels, self_dev, /*plain_retain=*/true, pl);
     n = pl.n_rows;
@@ -422,8 +437,36 @@ uint32_t device_bedpe_rows(Engine &E, const impg_gpu_index &ix, uint32_t n_range
   }
   // the levels' slots and slices are not needed any more: give their memory back before the sorts take theirs
   levels.clear();
-  clen.release();
-  return merge_rows(E, ix, rows.view(), n, n_ranges, offsets.as<uint32_t>(), coff.as<unsigned long long>(), pool.as<uint32_t>(), merge_distance, out);
+  return n;
+}
+// rows and CIGARs the caller brings (the self-tests), uploaded as they are; row_range does not decrease
+uint32_t upload_rows(Engine &E, const impg_gpu_interval_t *rows, const uint32_t *row_range, uint32_t n, uint32_t n_ranges, const uint64_t *cigar_off,
+                     const uint32_t *cigar_ops, DevRows &dev, DevBuf &coff, DevBuf &pool, DevBuf &offsets) {
+  hipStream_t s = E.stream;
+  std::vector<uint32_t> h_off((size_t)n_ranges + 1, 0);
+  for (uint32_t i = 0; i < n; i++) h_off[row_range[i] + 1]++;
+  for (uint32_t q = 0; q < n_ranges; q++) h_off[q + 1] += h_off[q];
+  require_rows(h_off);
+  const uint64_t n_ops = cigar_off[n];
+  coff.reserve(((size_t)n + 1) * 8); pool.reserve(std::max<size_t>(n_ops * 4, 256)); offsets.reserve(((size_t)n_ranges + 1) * 4);
+  IMPG_HIP(hipMemcpyAsync(coff.p, cigar_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, s));
+  if (n_ops) IMPG_HIP(hipMemcpyAsync(pool.p, cigar_ops, n_ops * 4, hipMemcpyHostToDevice, s));
+  IMPG_HIP(hipMemcpyAsync(offsets.p, h_off.data(), ((size_t)n_ranges + 1) * 4, hipMemcpyHostToDevice, s));
+  dev.upload(E, rows, row_range, n);  // (waits for the three copies above too)
+  return n;
+}
+}  // namespace
+
+// Rows of one chunk -> the runs BEDPE prints, left on the device in `out` (grouped by range, in output order); returns
+// their number.  levels / self_dev: what Engine::run kept for the chunk, with store_cigar.  Every refusal is raised here,
+// before any of the chunk's text exists.  Counts into the handle's bedpe_* counters.
+uint32_t device_bedpe_rows(Engine &E, const impg_gpu_index &ix, uint32_t n_ranges, const impg_gpu_params_t &p, int32_t merge_distance,
+                           std::vector<std::unique_ptr<LevelBufs>> &levels, DevBuf &self_dev, DevBuf &out) {
+  DevRows rows(&E.level_pool);
+  DevBuf coff, pool, offsets;
+  for (DevBuf *b : {&coff, &pool, &offsets}) b->pool = &E.level_pool;
+  const uint32_t n = place_rows(E, n_ranges, p, levels, self_dev, rows, coff, pool, offsets);
+  return merge_rows_bedpe(E, ix, rows.view(), n, n_ranges, offsets.as<uint32_t>(), coff.as<unsigned long long>(), pool.as<uint32_t>(), merge_distance, out);
 }
 
 // The merge and the text on rows and CIGARs the caller brings (impg_gpu_selftest_bedpe_rows): uploaded as they are, then
@@ -431,21 +474,11 @@ uint32_t device_bedpe_rows(Engine &E, const impg_gpu_index &ix, uint32_t n_range
 void device_bedpe_selftest(Engine &E, const impg_gpu_index &ix, const impg_gpu_interval_t *rows, const uint32_t *row_range, uint32_t n,
                            uint32_t n_ranges, const uint64_t *cigar_off, const uint32_t *cigar_ops, int32_t merge_distance, bool original_coords,
                            const std::vector<std::string> &rnames, std::string &text) {
-  hipStream_t s = E.stream;
-  std::vector<uint32_t> h_off((size_t)n_ranges + 1, 0);
-  for (uint32_t i = 0; i < n; i++) h_off[row_range[i] + 1]++;
-  for (uint32_t q = 0; q < n_ranges; q++) h_off[q + 1] += h_off[q];
-  require_rows(h_off);
-  const uint64_t n_ops = cigar_off[n];
   DevRows dev;
   DevBuf coff, pool, offsets, out;
-  coff.reserve(((size_t)n + 1) * 8); pool.reserve(std::max<size_t>(n_ops * 4, 256)); offsets.reserve(((size_t)n_ranges + 1) * 4);
-  IMPG_HIP(hipMemcpyAsync(coff.p, cigar_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, s));
-  if (n_ops) IMPG_HIP(hipMemcpyAsync(pool.p, cigar_ops, n_ops * 4, hipMemcpyHostToDevice, s));
-  IMPG_HIP(hipMemcpyAsync(offsets.p, h_off.data(), ((size_t)n_ranges + 1) * 4, hipMemcpyHostToDevice, s));
-  dev.upload(E, rows, row_range, n);  // (waits for the three copies above too)
-  const uint32_t n_runs = merge_rows(E, ix, dev.view(), n, n_ranges, offsets.as<uint32_t>(), coff.as<unsigned long long>(), pool.as<uint32_t>(),
-                                     merge_distance, out);
+  upload_rows(E, rows, row_range, n, n_ranges, cigar_off, cigar_ops, dev, coff, pool, offsets);
+  const uint32_t n_runs = merge_rows_bedpe(E, ix, dev.view(), n, n_ranges, offsets.as<uint32_t>(), coff.as<unsigned long long>(), pool.as<uint32_t>(),
+                                           merge_distance, out);
   device_bedpe_text(E, ix, out, n_runs, n_ranges, rnames, original_coords, [&](const char *p, size_t k) { text.append(p, k); });
 }
 
@@ -455,5 +488,8 @@ void device_bedpe_text(Engine &E, const impg_gpu_index &ix, const DevBuf &runs, 
   device_rows_text<Run, text_len_kernel, text_write_kernel>(E, ix, runs, n_runs, n_ranges, rnames, original_coords, sink, "BEDPE",
                                                             ix.bedpe_stats[BEDPE_TEXT_PIECES], ix.bedpe_stats[BEDPE_TEXT_BYTES]);
 }
+
+// PAF: the same rows, summaries, order, link and run records, then the merged CIGARs themselves as cg:Z
+#include "paf_device.inc"
 
 }  // namespace impg

@@ -204,9 +204,10 @@ bool run_chunk_rows(const impg_gpu_index &ix, Engine &E, const impg_gpu_range_t 
 
 bool run_chunk_bed(const impg_gpu_index &ix, Engine &E, const impg_gpu_range_t *d_ranges, const impg_gpu_range_t *h_ranges,
                    const char *const *range_names, size_t b, size_t e, const impg_gpu_params_t &p, int32_t merge_distance,
-                   const std::function<void(const char *, size_t)> &sink, double *seconds3, std::mutex *gpu_turn, bool bedpe) {
+                   const std::function<void(const char *, size_t)> &sink, double *seconds3, std::mutex *gpu_turn, TextFormat format) {
   std::vector<std::unique_ptr<LevelBufs>> levels;
   DevBuf self_dev, rows;
+  PafChunkPtr paf;  // (PAF: the chunk's rows, ops and order live until its text is out)
   self_dev.pool = &E.level_pool;
   const auto turn = take_turn(gpu_turn);
   const auto c0 = std::chrono::steady_clock::now();
@@ -216,10 +217,14 @@ bool run_chunk_bed(const impg_gpu_index &ix, Engine &E, const impg_gpu_range_t *
   E.run(ix, rs);
   const auto c1 = std::chrono::steady_clock::now();
   if (e == b) return false;
-  const uint32_t n_rows = (bedpe ? device_bedpe_rows : device_bed_rows)(E, ix, (uint32_t)(e - b), p, merge_distance, levels, self_dev, rows);
+  uint32_t n_rows = 0;
+  if (format == TEXT_PAF) paf = device_paf_rows(E, ix, (uint32_t)(e - b), p, merge_distance, levels, self_dev);
+  else n_rows = (format == TEXT_BEDPE ? device_bedpe_rows : device_bed_rows)(E, ix, (uint32_t)(e - b), p, merge_distance, levels, self_dev, rows);
   const auto c2 = std::chrono::steady_clock::now();
-  (bedpe ? device_bedpe_text : device_bed_text)(E, ix, rows, n_rows, (uint32_t)(e - b), bed_range_names(ix, h_ranges, range_names, b, e),
-                                                p.original_sequence_coordinates != 0, sink);
+  const std::vector<std::string> rnames = bed_range_names(ix, h_ranges, range_names, b, e);
+  const bool orig = p.original_sequence_coordinates != 0;
+  if (format == TEXT_PAF) device_paf_text(E, ix, *paf, (uint32_t)(e - b), rnames, orig, sink);
+  else (format == TEXT_BEDPE ? device_bedpe_text : device_bed_text)(E, ix, rows, n_rows, (uint32_t)(e - b), rnames, orig, sink);
   const auto c3 = std::chrono::steady_clock::now();
   seconds3[0] += std::chrono::duration<double>(c1 - c0).count();
   seconds3[1] += std::chrono::duration<double>(c2 - c1).count();
@@ -682,6 +687,11 @@ static const CounterRow COUNTER_TABLE[] = {
     CTR("bedpe_joins_contiguous", bedpe_stats[BEDPE_JOINS_CONTIGUOUS]), CTR("bedpe_joins_gap", bedpe_stats[BEDPE_JOINS_GAP]),
     CTR("bedpe_fused_ops", bedpe_stats[BEDPE_FUSED_OPS]), CTR("bedpe_summary_ops", bedpe_stats[BEDPE_SUMMARY_OPS]),
     CTR("bedpe_text_pieces", bedpe_stats[BEDPE_TEXT_PIECES]), CTR("bedpe_text_bytes", bedpe_stats[BEDPE_TEXT_BYTES]),
+    CTR("paf_rows", paf_stats[PAF_ROWS]), CTR("paf_runs", paf_stats[PAF_RUNS]),
+    CTR("paf_joins_contiguous", paf_stats[PAF_JOINS_CONTIGUOUS]), CTR("paf_joins_gap", paf_stats[PAF_JOINS_GAP]),
+    CTR("paf_ops_read", paf_stats[PAF_OPS_READ]), CTR("paf_ops_printed", paf_stats[PAF_OPS_PRINTED]),
+    CTR("paf_through_rows", paf_stats[PAF_THROUGH_ROWS]), CTR("paf_text_pieces", paf_stats[PAF_TEXT_PIECES]),
+    CTR("paf_text_bytes", paf_stats[PAF_TEXT_BYTES]),
     CTR_RANKS("build_device", build_stats[BUILD_DEVICE]), CTR_RANKS("tokenized_device", build_stats[BUILD_TOKENIZED_DEVICE]),
     CTR_RANKS("build_batches", build_stats[BUILD_BATCHES]),
 };
@@ -1302,36 +1312,45 @@ int impg_gpu_results_bed(const impg_gpu_results_t *res, const impg_gpu_index_t *
 // query + merge + the text on the device: only text crosses PCIe, in pinned pieces.  BED: both BED merges
 // (bed_device.hip); BEDPE: the CIGAR summaries and merge_adjusted_intervals (bedpe_device.hip).
 namespace {
-// what the device BEDPE route does not serve (the host route, impg_gpu_results_paf, does): raised before anything runs
-void bedpe_refusals(const impg_gpu_index &ix) {
-  if (ix.shard || ix.cluster) throw Error{IMPG_E_UNSUPPORTED, "device-side BEDPE on a sharded index (use impg_gpu_query_batch + impg_gpu_results_paf)"};
+// what the device BEDPE and PAF routes do not serve (the host route, impg_gpu_results_paf, does): raised before anything runs
+void bedpe_refusals(const impg_gpu_index &ix, const std::string &what = "BEDPE") {
+  if (ix.shard || ix.cluster) throw Error{IMPG_E_UNSUPPORTED, "device-side " + what + " on a sharded index (use impg_gpu_query_batch + impg_gpu_results_paf)"};
   // an op is no longer than the sequence it lies on; a fused op of 2^29 bases or more would wrap into its code bits on the
   // host route (CigarOp::new, impg.rs:90-92), which the sums here do not restate
   for (const int64_t len : ix.seq.lens)
-    if (len >= (int64_t)OP_LEN_MASK + 1) throw Error{IMPG_E_UNSUPPORTED, "device-side BEDPE on an index with a sequence of 2^29 bases or more (use impg_gpu_results_paf)"};
+    if (len >= (int64_t)OP_LEN_MASK + 1) throw Error{IMPG_E_UNSUPPORTED, "device-side " + what + " on an index with a sequence of 2^29 bases or more (use impg_gpu_results_paf)"};
   if (ix.tp_mode && !ix.opt.approximate_cigar)
     throw Error{IMPG_E_UNSUPPORTED, "store_cigar on a tracepoint index needs option approximate_cigar = 1 (the approximate mode's "
                                     "CIGAR is a pair of match / mismatch counts, not an alignment)"};
 }
+// ... and PAF: the reference prints no PAF in approximate mode (render_paf refuses it with the same words)
+void paf_refusals(const impg_gpu_index &ix) {
+  if (ix.tp_mode)
+    throw Error{IMPG_E_UNSUPPORTED, "PAF output of approximate-mode results: the reference offers bed and bedpe there (their CIGAR "
+                                    "is a pair of match / mismatch counts, not an alignment)"};
+  bedpe_refusals(ix, "PAF");
+}
 void text_batch(impg_gpu_index_t *ix, const impg_gpu_range_t *ranges, size_t n, const impg_gpu_params_t *params, const uint8_t *subset_keep,
                 int32_t merge_distance, const char *const *range_names, const std::function<void(const char *, size_t)> &sink,
-                double *seconds3, bool bedpe) {
+                double *seconds3, TextFormat format) {
   if (!ix || !params || (!ranges && n)) throw Error{IMPG_E_INVALID, "null argument"};
   check_ranges(ranges, n);
   Engine::check_params(*params);
   impg_gpu_params_t p = *params;
-  p.store_cigar = bedpe ? 1 : 0;  // BED never needs CIGARs, BEDPE rates them (main.rs:7447)
-  if (bedpe) bedpe_refusals(*ix);
+  p.store_cigar = format != TEXT_BED ? 1 : 0;  // BED never needs CIGARs, BEDPE rates them, PAF prints them (main.rs:7447)
+  if (format == TEXT_BEDPE) bedpe_refusals(*ix);
+  else if (format == TEXT_PAF) paf_refusals(*ix);
   else if (ix->shard || ix->cluster) { sharded_bed_batch(*ix, ranges, n, p, subset_keep, merge_distance, range_names, sink, seconds3); return; }
   IMPG_HIP(hipSetDevice(ix->device));
   EngineLease lease(*ix);
   Engine &E = *lease;
-  if (bedpe) ix->bedpe_stats_reset();
+  if (format == TEXT_BEDPE) ix->bedpe_stats_reset();
+  else if (format == TEXT_PAF) ix->paf_stats_reset();
   else ix->bed_stats_reset();
   apply_subset(E, *ix, subset_keep);
   const impg_gpu_range_t *d_ranges = upload_ranges(E.ranges_dev, ranges, n, &E.stream);
   double t3[3] = {0, 0, 0};  // engine, merge, text
-  for_chunks(E, n, [&](size_t b, size_t e) { run_chunk_bed(*ix, E, d_ranges, ranges, range_names, b, e, p, merge_distance, sink, t3, nullptr, bedpe); });
+  for_chunks(E, n, [&](size_t b, size_t e) { run_chunk_bed(*ix, E, d_ranges, ranges, range_names, b, e, p, merge_distance, sink, t3, nullptr, format); });
   if (seconds3) for (int k = 0; k < 3; k++) seconds3[k] = t3[k];
 }
 // a text as the caller gets it: malloc'ed and NUL-terminated behind its bytes
@@ -1344,7 +1363,7 @@ char *malloc_text(const std::string &s) {
 }
 // the text arrives in pieces; it is collected into one malloc'ed buffer that grows geometrically
 int text_batch_buffer(impg_gpu_index_t *ix, const impg_gpu_range_t *ranges, size_t n, const impg_gpu_params_t *params, const uint8_t *subset_keep,
-                      int32_t merge_distance, const char *const *range_names, char **text, size_t *len, double *seconds3, bool bedpe) {
+                      int32_t merge_distance, const char *const *range_names, char **text, size_t *len, double *seconds3, TextFormat format) {
   IMPG_TRY
   if (!text || !len) throw Error{IMPG_E_INVALID, "null argument"};
   char *buf = nullptr;
@@ -1359,7 +1378,7 @@ int text_batch_buffer(impg_gpu_index_t *ix, const impg_gpu_range_t *ranges, size
     }
     memcpy(buf + used, p, k);
     used += k;
-  }, seconds3, bedpe);
+  }, seconds3, format);
   if (!buf) buf = malloc_text(std::string());
   buf[used] = 0;
   guard.keep = true;
@@ -1369,7 +1388,7 @@ int text_batch_buffer(impg_gpu_index_t *ix, const impg_gpu_range_t *ranges, size
   IMPG_CATCH
 }
 int text_batch_fd(impg_gpu_index_t *ix, const impg_gpu_range_t *ranges, size_t n, const impg_gpu_params_t *params, const uint8_t *subset_keep,
-                  int32_t merge_distance, const char *const *range_names, int fd, uint64_t *bytes_written, double *seconds3, bool bedpe) {
+                  int32_t merge_distance, const char *const *range_names, int fd, uint64_t *bytes_written, double *seconds3, TextFormat format) {
   IMPG_TRY
   uint64_t total = 0;
   text_batch(ix, ranges, n, params, subset_keep, merge_distance, range_names, [&](const char *p, size_t k) {
@@ -1383,7 +1402,7 @@ int text_batch_fd(impg_gpu_index_t *ix, const impg_gpu_range_t *ranges, size_t n
       done += (size_t)w;
     }
     total += k;
-  }, seconds3, bedpe);
+  }, seconds3, format);
   if (bytes_written) *bytes_written = total;
   return IMPG_OK;
   IMPG_CATCH
@@ -1393,22 +1412,32 @@ int text_batch_fd(impg_gpu_index_t *ix, const impg_gpu_range_t *ranges, size_t n
 int impg_gpu_query_batch_bed(impg_gpu_index_t *ix, const impg_gpu_range_t *ranges, size_t n, const impg_gpu_params_t *params,
                              const uint8_t *subset_keep, int32_t merge_distance, const char *const *range_names, char **text,
                              size_t *len, double *seconds3) {
-  return text_batch_buffer(ix, ranges, n, params, subset_keep, merge_distance, range_names, text, len, seconds3, false);
+  return text_batch_buffer(ix, ranges, n, params, subset_keep, merge_distance, range_names, text, len, seconds3, TEXT_BED);
 }
 int impg_gpu_query_batch_bed_fd(impg_gpu_index_t *ix, const impg_gpu_range_t *ranges, size_t n, const impg_gpu_params_t *params,
                                 const uint8_t *subset_keep, int32_t merge_distance, const char *const *range_names, int fd,
                                 uint64_t *bytes_written, double *seconds3) {
-  return text_batch_fd(ix, ranges, n, params, subset_keep, merge_distance, range_names, fd, bytes_written, seconds3, false);
+  return text_batch_fd(ix, ranges, n, params, subset_keep, merge_distance, range_names, fd, bytes_written, seconds3, TEXT_BED);
 }
 int impg_gpu_query_batch_bedpe(impg_gpu_index_t *ix, const impg_gpu_range_t *ranges, size_t n, const impg_gpu_params_t *params,
                                const uint8_t *subset_keep, int32_t merge_distance, const char *const *range_names, char **text,
                                size_t *len, double *seconds3) {
-  return text_batch_buffer(ix, ranges, n, params, subset_keep, merge_distance, range_names, text, len, seconds3, true);
+  return text_batch_buffer(ix, ranges, n, params, subset_keep, merge_distance, range_names, text, len, seconds3, TEXT_BEDPE);
 }
 int impg_gpu_query_batch_bedpe_fd(impg_gpu_index_t *ix, const impg_gpu_range_t *ranges, size_t n, const impg_gpu_params_t *params,
                                   const uint8_t *subset_keep, int32_t merge_distance, const char *const *range_names, int fd,
                                   uint64_t *bytes_written, double *seconds3) {
-  return text_batch_fd(ix, ranges, n, params, subset_keep, merge_distance, range_names, fd, bytes_written, seconds3, true);
+  return text_batch_fd(ix, ranges, n, params, subset_keep, merge_distance, range_names, fd, bytes_written, seconds3, TEXT_BEDPE);
+}
+int impg_gpu_query_batch_paf(impg_gpu_index_t *ix, const impg_gpu_range_t *ranges, size_t n, const impg_gpu_params_t *params,
+                             const uint8_t *subset_keep, int32_t merge_distance, const char *const *range_names, char **text,
+                             size_t *len, double *seconds3) {
+  return text_batch_buffer(ix, ranges, n, params, subset_keep, merge_distance, range_names, text, len, seconds3, TEXT_PAF);
+}
+int impg_gpu_query_batch_paf_fd(impg_gpu_index_t *ix, const impg_gpu_range_t *ranges, size_t n, const impg_gpu_params_t *params,
+                                const uint8_t *subset_keep, int32_t merge_distance, const char *const *range_names, int fd,
+                                uint64_t *bytes_written, double *seconds3) {
+  return text_batch_fd(ix, ranges, n, params, subset_keep, merge_distance, range_names, fd, bytes_written, seconds3, TEXT_PAF);
 }
 
 int impg_gpu_results_paf(const impg_gpu_results_t *res, const impg_gpu_index_t *ix, const char *const *range_names,
@@ -1464,14 +1493,16 @@ int impg_gpu_selftest_bed_rows(impg_gpu_index_t *ix, const impg_gpu_interval_t *
   IMPG_CATCH
 }
 
-// The device BEDPE merge and text on rows and CIGARs the caller brings (diagnostics; tests/test_gpu_bedpe_device.py): what a
-// chunk of impg_gpu_query_batch_bedpe runs once its rows and their ops are placed (bedpe_device.hip), without a query in front.
-int impg_gpu_selftest_bedpe_rows(impg_gpu_index_t *ix, const impg_gpu_interval_t *rows, const uint32_t *row_range, size_t n_rows,
-                                 uint32_t n_ranges, const uint64_t *cigar_off, const uint32_t *cigar_ops, int32_t merge_distance,
-                                 int original_sequence_coordinates, const char *const *range_names, char **text, size_t *len) {
+// The device BEDPE / PAF merge and text on rows and CIGARs the caller brings (diagnostics; tests/test_gpu_bedpe_device.py,
+// tests/test_gpu_paf_device.py): what a chunk of impg_gpu_query_batch_bedpe / _paf runs once its rows and their ops are
+// placed (bedpe_device.hip, paf_device.inc), without a query in front.
+static int selftest_cigar_rows(impg_gpu_index_t *ix, const impg_gpu_interval_t *rows, const uint32_t *row_range, size_t n_rows, uint32_t n_ranges,
+                               const uint64_t *cigar_off, const uint32_t *cigar_ops, int32_t merge_distance, int original_sequence_coordinates,
+                               const char *const *range_names, char **text, size_t *len, bool paf) {
   IMPG_TRY
   if (!ix || !text || !len || !cigar_off || (n_rows && (!rows || !row_range))) throw Error{IMPG_E_INVALID, "null argument"};
-  bedpe_refusals(*ix);
+  if (paf) paf_refusals(*ix);
+  else bedpe_refusals(*ix);
   check_row_count(n_rows);
   if (cigar_off[0] != 0 || (cigar_off[n_rows] && !cigar_ops)) throw Error{IMPG_E_INVALID, "CIGAR offsets start at 0 and come with their ops"};
   for (size_t i = 0; i < n_rows; i++) {
@@ -1482,13 +1513,26 @@ int impg_gpu_selftest_bedpe_rows(impg_gpu_index_t *ix, const impg_gpu_interval_t
   const std::vector<std::string> rnames = default_range_names(n_ranges, range_names);
   IMPG_HIP(hipSetDevice(ix->device));
   EngineLease lease(*ix);
-  ix->bedpe_stats_reset();
+  if (paf) ix->paf_stats_reset();
+  else ix->bedpe_stats_reset();
   std::string out;
-  if (n_ranges) device_bedpe_selftest(*lease, *ix, rows, row_range, (uint32_t)n_rows, n_ranges, cigar_off, cigar_ops, merge_distance,
-                                      original_sequence_coordinates != 0, rnames, out);
+  if (n_ranges) (paf ? device_paf_selftest : device_bedpe_selftest)(*lease, *ix, rows, row_range, (uint32_t)n_rows, n_ranges, cigar_off, cigar_ops,
+                                                                    merge_distance, original_sequence_coordinates != 0, rnames, out);
   *text = malloc_text(out); *len = out.size();
   return IMPG_OK;
   IMPG_CATCH
+}
+int impg_gpu_selftest_bedpe_rows(impg_gpu_index_t *ix, const impg_gpu_interval_t *rows, const uint32_t *row_range, size_t n_rows,
+                                 uint32_t n_ranges, const uint64_t *cigar_off, const uint32_t *cigar_ops, int32_t merge_distance,
+                                 int original_sequence_coordinates, const char *const *range_names, char **text, size_t *len) {
+  return selftest_cigar_rows(ix, rows, row_range, n_rows, n_ranges, cigar_off, cigar_ops, merge_distance, original_sequence_coordinates, range_names,
+                             text, len, false);
+}
+int impg_gpu_selftest_paf_rows(impg_gpu_index_t *ix, const impg_gpu_interval_t *rows, const uint32_t *row_range, size_t n_rows,
+                               uint32_t n_ranges, const uint64_t *cigar_off, const uint32_t *cigar_ops, int32_t merge_distance,
+                               int original_sequence_coordinates, const char *const *range_names, char **text, size_t *len) {
+  return selftest_cigar_rows(ix, rows, row_range, n_rows, n_ranges, cigar_off, cigar_ops, merge_distance, original_sequence_coordinates, range_names,
+                             text, len, true);
 }
 
 // The lookup order's sort checked on its own (diagnostics; tests/test_gpu_parity.py): n pseudo-random keys of `end_bit` bits

@@ -506,7 +506,7 @@ int main(int argc, char **argv) {
     else if (a == "-l" || a == "--min-output-length") min_out = num(a, need("-l"), 0, 2147483647);
     else if (a == "--min-result-identity") min_ident = real(a, need(a.c_str()));
     else if (a == "--consider-strandness") consider_strandness = true;
-    else if (a == "--host-merge") host_merge = true;  // BED / BEDPE merges on the host (impg_gpu_results_bed / _paf) instead of the device
+    else if (a == "--host-merge") host_merge = true;  // BED / BEDPE / PAF merges on the host (impg_gpu_results_bed / _paf) instead of the device
     else if (a == "--subset-sequence-list") subset_list = need(a.c_str());
     else if (a == "--original-sequence-coordinates") original_coords = true;
     else if (a == "-o" || a == "--output-format") ofmt = need("-o");
@@ -625,14 +625,14 @@ int main(int argc, char **argv) {
   const double t0 = now();
   // BED and BEDPE: the merge and the text on the device, only text crosses PCIe.  An index the device BEDPE route does
   // not serve (a sequence of 2^29 bases or more) says so to an empty batch, before anything is printed: the host route takes it.
-  const bool device_bedpe = fmt == "bedpe" && !host_merge &&
-                            impg_gpu_query_batch_bedpe_fd(ix, nullptr, 0, &p, nullptr, merge_distance, nullptr, fileno(stdout), nullptr, nullptr) == IMPG_OK;
-  if ((fmt == "bed" && !host_merge) || device_bedpe) {
+  // PAF goes the same way: the merged CIGARs are fused and printed as cg:Z on the device (a tracepoint index is refused there as on the host).
+  const auto device_entry = fmt == "bed" ? impg_gpu_query_batch_bed_fd : fmt == "bedpe" ? impg_gpu_query_batch_bedpe_fd : impg_gpu_query_batch_paf_fd;
+  const bool device_route = !host_merge && (fmt == "bed" || device_entry(ix, nullptr, 0, &p, nullptr, merge_distance, nullptr, fileno(stdout), nullptr, nullptr) == IMPG_OK);
+  if (device_route) {
     uint64_t len = 0;
     double sec[3] = {0, 0, 0};
     fflush(stdout);
-    if ((device_bedpe ? impg_gpu_query_batch_bedpe_fd : impg_gpu_query_batch_bed_fd)(ix, ranges.data(), ranges.size(), &p, keep.empty() ? nullptr : keep.data(),
-                                                                                     merge_distance, names.data(), fileno(stdout), &len, sec) != IMPG_OK)
+    if (device_entry(ix, ranges.data(), ranges.size(), &p, keep.empty() ? nullptr : keep.data(), merge_distance, names.data(), fileno(stdout), &len, sec) != IMPG_OK)
       die(impg_gpu_last_error());
     const double t1 = now();
     if (verbose >= 1)

@@ -50,6 +50,13 @@ template <class In, class Out> inline void inclusive_max(DevBuf &tmp, In in, Out
   grow(tmp, sb);
   IMPG_HIP(rocprim::inclusive_scan(tmp.p, sb, in, out, n, rocprim::maximum<value_of<Out>>(), s));
 }
+// out[i] = in[0] (op) .. (op) in[i], op associative (it need not commute: the operands keep their order)
+template <class In, class Out, class Op> inline void inclusive_scan(DevBuf &tmp, In in, Out out, size_t n, Op op, hipStream_t s) {
+  size_t sb = 0;
+  IMPG_HIP(rocprim::inclusive_scan(nullptr, sb, in, out, n, op, s));
+  grow(tmp, sb);
+  IMPG_HIP(rocprim::inclusive_scan(tmp.p, sb, in, out, n, op, s));
+}
 // Stable sort of (key, value) pairs by the keys' bits [begin_bit, end_bit); query and sort also apart: the engine sizes its scratch up front.
 template <class KI, class KO, class VI, class VO, class Size> inline size_t radix_sort_pairs_bytes(Size n, unsigned begin_bit, unsigned end_bit) {
   size_t sb = 0;

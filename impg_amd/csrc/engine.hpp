@@ -343,12 +343,13 @@ bool run_chunk_rows(const impg_gpu_index &ix, Engine &E, const impg_gpu_range_t 
                     size_t e, const impg_gpu_params_t &p, impg_gpu_results &part, std::mutex *gpu_turn = nullptr,
                     uint64_t max_rows = ~0ull, hipEvent_t kernels_done = nullptr,
                     const std::function<void()> &on_kernels_done = nullptr);
+enum TextFormat { TEXT_BED = 0, TEXT_BEDPE = 1, TEXT_PAF = 2 };  // what the device text routes print
 // Its sibling for BED: the run, both merges and the text on the device (bed_device.hip); the three stages' seconds are
 // added to seconds3.  gpu_turn is held through the text.  false: an empty chunk, as above (no time is added).
 bool run_chunk_bed(const impg_gpu_index &ix, Engine &E, const impg_gpu_range_t *d_ranges, const impg_gpu_range_t *h_ranges,
                    const char *const *range_names, size_t b, size_t e, const impg_gpu_params_t &p, int32_t merge_distance,
                    const std::function<void(const char *, size_t)> &sink, double *seconds3, std::mutex *gpu_turn = nullptr,
-                   bool bedpe = false);  // bedpe: p.store_cigar set; the BEDPE merge and lines instead (bedpe_device.hip)
+                   TextFormat format = TEXT_BED);  // TEXT_BEDPE / TEXT_PAF: p.store_cigar set; that format's merge and lines instead
 // ---- result rows on the device (rows_device.hip) ---------------------------------------------------------------
 // Where every emitted slot of a chunk goes among the chunk's result rows (grouped by range, emission order within).
 struct RowPlan {
@@ -401,6 +402,18 @@ void device_bedpe_text(Engine &E, const impg_gpu_index &ix, const DevBuf &runs, 
 void device_bedpe_selftest(Engine &E, const impg_gpu_index &ix, const impg_gpu_interval_t *rows, const uint32_t *row_range, uint32_t n,
                            uint32_t n_ranges, const uint64_t *cigar_off, const uint32_t *cigar_ops, int32_t merge_distance, bool original_coords,
                            const std::vector<std::string> &rnames, std::string &text);
+// ---- PAF on the device (paf_device.inc, part of bedpe_device.hip): the same merge, then the merged CIGARs as cg:Z ----------
+// A chunk's rows, CIGAR pool, order and elements: they live from the rows call until the chunk's text is out.
+struct PafChunk;
+struct PafChunkFree { void operator()(PafChunk *c) const; };
+typedef std::unique_ptr<PafChunk, PafChunkFree> PafChunkPtr;
+PafChunkPtr device_paf_rows(Engine &E, const impg_gpu_index &ix, uint32_t n_ranges, const impg_gpu_params_t &p, int32_t merge_distance,
+                            std::vector<std::unique_ptr<LevelBufs>> &levels, DevBuf &self_dev);
+void device_paf_text(Engine &E, const impg_gpu_index &ix, PafChunk &chunk, uint32_t n_ranges, const std::vector<std::string> &rnames,
+                     bool original_coords, const std::function<void(const char *, size_t)> &sink);
+void device_paf_selftest(Engine &E, const impg_gpu_index &ix, const impg_gpu_interval_t *rows, const uint32_t *row_range, uint32_t n,
+                         uint32_t n_ranges, const uint64_t *cigar_off, const uint32_t *cigar_ops, int32_t merge_distance, bool original_coords,
+                         const std::vector<std::string> &rnames, std::string &text);
 // the diagnostic entry's device part: the caller's rows through the same merge and text (impg_gpu_selftest_bed_rows)
 struct BedGapRows { std::vector<uint32_t> range; std::vector<impg_gpu_interval_t> rows; };  // the rows between the two merges, in their order
 void device_bed_selftest(Engine &E, const impg_gpu_index &ix, const impg_gpu_interval_t *rows, const uint32_t *row_range, uint32_t n,

@@ -388,6 +388,8 @@ void for_each_rank(const impg_gpu_index &ix, const std::function<void(const impg
 enum BedStat { BED_ROWS, BED_GAP_ROOTS, BED_RUNS, BED_TEXT_PIECES, BED_TEXT_BYTES };  // impg_gpu_index::bed_stats
 // impg_gpu_index::bedpe_stats (bedpe_device.hip)
 enum BedpeStat { BEDPE_ROWS, BEDPE_RUNS, BEDPE_JOINS_CONTIGUOUS, BEDPE_JOINS_GAP, BEDPE_FUSED_OPS, BEDPE_SUMMARY_OPS, BEDPE_TEXT_PIECES, BEDPE_TEXT_BYTES };
+// impg_gpu_index::paf_stats (paf_device.inc)
+enum PafStat { PAF_ROWS, PAF_RUNS, PAF_JOINS_CONTIGUOUS, PAF_JOINS_GAP, PAF_OPS_READ, PAF_OPS_PRINTED, PAF_THROUGH_ROWS, PAF_TEXT_PIECES, PAF_TEXT_BYTES };
 size_t bed_merge(impg_gpu_interval_t *iv, size_t n, int32_t merge_distance, bool merge_strands);
 
 struct Engine;    // engine.hpp
@@ -461,6 +463,9 @@ struct impg_gpu_index {
   // ... and the last device BEDPE call (by impg::BedpeStat; bedpe_device.hip), kept like bed_stats
   mutable std::atomic<uint64_t> bedpe_stats[8] = {};
   void bedpe_stats_reset() const { for (auto &b : bedpe_stats) b = 0; }
+  // ... and the last device PAF call (by impg::PafStat; paf_device.inc), kept the same way
+  mutable std::atomic<uint64_t> paf_stats[9] = {};
+  void paf_stats_reset() const { for (auto &b : paf_stats) b = 0; }
   impg::ShardCtx *shard = nullptr;    // set: this index is one rank's shard; queries are collective calls
   impg::Cluster *cluster = nullptr;   // set: this handle fronts n_dev shards in this process (no arrays of its own)
   impg_gpu_index();

@@ -9,7 +9,8 @@
 namespace impg {
 
 // The name / shift / range-name tables of a chunk (text_device.hpp)
-TextTableBufs::TextTableBufs(Engine &E, const impg_gpu_index &ix, uint32_t n_ranges, const std::vector<std::string> &rnames, bool original_coords) {
+TextTableBufs::TextTableBufs(Engine &E, const impg_gpu_index &ix, uint32_t n_ranges, const std::vector<std::string> &rnames, bool original_coords,
+                             bool with_lengths) {
   hipStream_t s = E.stream;
   noff.assign(1, 0);
   for (const std::string &nm : ix.seq.names) {
@@ -24,7 +25,14 @@ TextTableBufs::TextTableBufs(Engine &E, const impg_gpu_index &ix, uint32_t n_ran
   };
   up(d_nb, nb.data(), nb.size()); up(d_noff, noff.data(), noff.size() * 4); up(d_shift, nshift.data(), nshift.size() * 4);
   up(d_rb, rb.data(), rb.size()); up(d_roff, roff.data(), roff.size() * 4);
-  t = TextTables{d_nb.as<char>(), d_noff.as<uint32_t>(), d_shift.as<uint32_t>(), (uint32_t)ix.seq.names.size(), d_rb.as<char>(), d_roff.as<uint32_t>()};
+  t = TextTables{d_nb.as<char>(), d_noff.as<uint32_t>(), d_shift.as<uint32_t>(), (uint32_t)ix.seq.names.size(), d_rb.as<char>(), d_roff.as<uint32_t>(),
+                 nullptr, 0u};
+  if (!with_lengths) return;
+  // "--original-sequence-coordinates": no sequence files to ask, the lengths print as 0 (main.rs:12014-12046)
+  for (const int64_t len : ix.seq.lens) lens.push_back(original_coords ? 0u : (uint32_t)len);
+  up(d_len, lens.data(), lens.size() * 4);
+  t.seq_len = d_len.as<uint32_t>();
+  t.n_lens = (uint32_t)lens.size();
 }
 
 void device_text_pieces(Engine &E, const uint32_t *d_len, uint32_t n_rows, const char *what,

@@ -22,6 +22,8 @@ struct TextTables {
   uint32_t n_names;             // 0: sequences print as their ids
   const char *rnames;           // the chunk's range names back to back
   const uint32_t *rname_off;    // [n_ranges + 1]
+  const uint32_t *seq_len;      // [n_lens] the sequence lengths PAF prints (all 0 under --original-sequence-coordinates); null unless asked for
+  uint32_t n_lens;              // an id from here on prints the length 0
 };
 __device__ __forceinline__ uint32_t dec_digits(uint32_t v) {
   uint32_t d = 1;
@@ -44,6 +46,7 @@ __device__ __forceinline__ char *put_seq(char *p, const TextTables &t, uint32_t 
   return p + nl;
 }
 __device__ __forceinline__ uint32_t seq_shift(const TextTables &t, uint32_t id) { return id < t.n_names ? t.shift[id] : 0u; }
+__device__ __forceinline__ uint32_t seq_len_of(const TextTables &t, uint32_t id) { return id < t.n_lens ? t.seq_len[id] : 0u; }
 __device__ __forceinline__ char *put_range_name(char *p, const TextTables &t, uint32_t q) {
   const char *rn = t.rnames + t.rname_off[q];
   const uint32_t rl = t.rname_off[q + 1] - t.rname_off[q];
@@ -53,13 +56,14 @@ __device__ __forceinline__ char *put_range_name(char *p, const TextTables &t, ui
 
 // The tables of one chunk on the device (uploaded on E.stream; they live as long as this object)
 struct TextTableBufs {
-  DevBuf d_nb, d_noff, d_shift, d_rb, d_roff;
+  DevBuf d_nb, d_noff, d_shift, d_rb, d_roff, d_len;
   TextTables t{};
-  TextTableBufs(Engine &E, const impg_gpu_index &ix, uint32_t n_ranges, const std::vector<std::string> &rnames, bool original_coords);
+  TextTableBufs(Engine &E, const impg_gpu_index &ix, uint32_t n_ranges, const std::vector<std::string> &rnames, bool original_coords,
+                bool with_lengths = false);  // with_lengths: PAF's two length columns
 
  private:
   std::string nb, rb;  // (the sources of the asynchronous uploads)
-  std::vector<uint32_t> noff, nshift, roff;
+  std::vector<uint32_t> noff, nshift, roff, lens;
 };
 
 // n_rows rows of d_len[r] bytes each as text, streamed to `sink(ptr, bytes)` in pieces of whole rows of at most PIECE

@@ -22,6 +22,11 @@ def make_params(transitive=False, dfs=False, max_depth=2, min_transitive_len=101
                   int(original_sequence_coordinates), int(consider_strandness))
 
 
+def _text_bytes(ptr, n):
+    """n bytes at ptr as bytes (ctypes.string_at takes its size as a C int: a PAF text of 2 GiB or more goes the other way)"""
+    return C.string_at(ptr, n) if n < (1 << 31) else bytes((C.c_char * n).from_address(ptr.value))
+
+
 class QueryResults:
     """Vec<AdjustedInterval> per range, in the reference's emission order."""
 
@@ -83,10 +88,10 @@ class QueryResults:
         finally:
             _lib.free(text)
 
-    def paf(self, range_names=None, merge_distance=0, params=None, fmt="paf"):
+    def paf(self, range_names=None, merge_distance=0, params=None, fmt="paf", raw=False):
         """output_results_paf / output_results_bedpe over every range (main.rs:11894-12103); the batch
         must have been queried with store_cigar = True.  Results of a tracepoint index print as "bedpe" only
-        (the reference refuses "paf" in approximate mode, main.rs:7387-7397)."""
+        (the reference refuses "paf" in approximate mode, main.rs:7387-7397).  raw: the text as bytes."""
         L = lib()
         p = params or make_params(store_cigar=True)
         arr = None
@@ -97,7 +102,8 @@ class QueryResults:
         check(L.impg_gpu_results_paf(self._h, self._owner._h, arr, C.byref(p), merge_distance, {"paf": 0, "bedpe": 1}[fmt],
                                      C.byref(text), C.byref(ln)))
         try:
-            return C.string_at(text, ln.value).decode()
+            out = _text_bytes(text, ln.value)
+            return out if raw else out.decode()
         finally:
             _lib.free(text)
 
@@ -564,6 +570,21 @@ class GpuImpg:
         if fd is None:
             return self._query_batch_text(lib().impg_gpu_query_batch_bedpe, ranges, params, merge_distance, range_names, subset_keep, timing,
                                           raw, kw)
+        return self._query_batch_text_fd(lib().impg_gpu_query_batch_bedpe_fd, ranges, params, merge_distance, range_names, subset_keep, timing,
+                                         fd, kw)
+
+    def query_batch_paf(self, ranges, params=None, merge_distance=0, range_names=None, subset_keep=None, timing=False, raw=False, fd=None,
+                        **kw):
+        """impg_gpu_query_batch_paf: the same merge, and every line's merged CIGAR fused and printed as cg:Z on the device
+        (what `impg query -o paf` prints); store_cigar is implied.  fd: impg_gpu_query_batch_paf_fd -- the text is
+        written there and the number of bytes returned in its place."""
+        if fd is None:
+            return self._query_batch_text(lib().impg_gpu_query_batch_paf, ranges, params, merge_distance, range_names, subset_keep, timing,
+                                          raw, kw)
+        return self._query_batch_text_fd(lib().impg_gpu_query_batch_paf_fd, ranges, params, merge_distance, range_names, subset_keep, timing,
+                                         fd, kw)
+
+    def _query_batch_text_fd(self, entry, ranges, params, merge_distance, range_names, subset_keep, timing, fd, kw):
         p = params or make_params(**kw)
         r = self._ranges(ranges)
         arr = None
@@ -572,8 +593,8 @@ class GpuImpg:
         keep = None if subset_keep is None else np.ascontiguousarray(subset_keep, dtype=np.uint8)
         done = C.c_uint64(0)
         sec = (C.c_double * 3)()
-        check(lib().impg_gpu_query_batch_bedpe_fd(self._h, r.ctypes.data, r.size, C.byref(p), None if keep is None else keep.ctypes.data,
-                                                  merge_distance, arr, fd, C.byref(done), sec))
+        check(entry(self._h, r.ctypes.data, r.size, C.byref(p), None if keep is None else keep.ctypes.data, merge_distance, arr, fd,
+                    C.byref(done), sec))
         return (done.value, list(sec)) if timing else done.value
 
     def _query_batch_text(self, entry, ranges, params, merge_distance, range_names, subset_keep, timing, raw, kw):
@@ -589,7 +610,7 @@ class GpuImpg:
         check(entry(self._h, r.ctypes.data, r.size, C.byref(p), None if keep is None else keep.ctypes.data, merge_distance, arr, C.byref(text),
                     C.byref(ln), sec))
         try:
-            out = C.string_at(text, ln.value)
+            out = _text_bytes(text, ln.value)
         finally:
             _lib.free(text)
         out = out if raw else out.decode()
@@ -634,6 +655,16 @@ class GpuImpg:
         """impg_gpu_selftest_bedpe_rows (diagnostics): the device BEDPE merge and text of query_batch_bedpe on the caller's
         rows (INTERVAL_DTYPE, grouped by range: row_range[i] = the range of rows[i], its first row the one that is dropped)
         and their packed CIGAR ops (cigars[i]: uint32 array of rows[i]).  Returns the text as bytes."""
+        return self._selftest_cigar_rows(lib().impg_gpu_selftest_bedpe_rows, rows, row_range, n_ranges, cigars, merge_distance,
+                                         original_sequence_coordinates, range_names)
+
+    def selftest_paf_rows(self, rows, row_range, n_ranges, cigars, merge_distance=0, original_sequence_coordinates=False, range_names=None):
+        """impg_gpu_selftest_paf_rows (diagnostics): the device PAF merge, CIGAR fusing and text of query_batch_paf on the
+        caller's rows and ops, given as for bedpe_rows.  Returns the text as bytes."""
+        return self._selftest_cigar_rows(lib().impg_gpu_selftest_paf_rows, rows, row_range, n_ranges, cigars, merge_distance,
+                                         original_sequence_coordinates, range_names)
+
+    def _selftest_cigar_rows(self, entry, rows, row_range, n_ranges, cigars, merge_distance, original_sequence_coordinates, range_names):
         a = np.ascontiguousarray(rows, dtype=INTERVAL_DTYPE)
         rr = np.ascontiguousarray(row_range, dtype=np.uint32)
         if a.size != rr.size or a.size != len(cigars):
@@ -645,8 +676,8 @@ class GpuImpg:
         if range_names is not None:
             arr = (C.c_char_p * len(range_names))(*[None if s is None else (s if isinstance(s, bytes) else s.encode()) for s in range_names])
         text, ln = C.c_void_p(None), C.c_size_t(0)
-        check(lib().impg_gpu_selftest_bedpe_rows(self._h, a.ctypes.data, rr.ctypes.data, a.size, n_ranges, off.ctypes.data, ops.ctypes.data,
-                                                 merge_distance, int(bool(original_sequence_coordinates)), arr, C.byref(text), C.byref(ln)))
+        check(entry(self._h, a.ctypes.data, rr.ctypes.data, a.size, n_ranges, off.ctypes.data, ops.ctypes.data, merge_distance,
+                    int(bool(original_sequence_coordinates)), arr, C.byref(text), C.byref(ln)))
         try:
             return C.string_at(text, ln.value)
         finally:

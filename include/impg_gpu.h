@@ -248,7 +248,8 @@ int impg_gpu_index_approximate(const impg_gpu_index_t *);
  * PCIe in pieces of whole rows of at most this many bytes, a piece of one row may be up to 4096 bytes longer; a row
  * beyond that is IMPG_E_UNSUPPORTED; the text is identical for every value; impg_gpu_query_batch_bedpe's text crosses the
  * same way), "bedpe_group_log2" (2 .. 6; 2 by default: impg_gpu_query_batch_bedpe sums a row's CIGAR ops with 2^value
- * lanes; results identical).  For tests of the multi-rank paths: "lane_schedule" (forced lane start / hand-over order of a sharded
+ * lanes; results identical), "paf_group_log2" (2 .. 6; 2 by default: impg_gpu_query_batch_paf fuses and prints a row's CIGAR
+ * ops with 2^value lanes; results identical).  For tests of the multi-rank paths: "lane_schedule" (forced lane start / hand-over order of a sharded
  * batch; 0 = off), "debug_fail_owner" / "debug_fail_home" (failure injection: (rank + 1) << 16 | hop of the batch at which
  * that rank throws on the owner / on the home side of the hop; 0 = off).
  * A multi-GPU handle hands "chunk_ranges", "pair_budget", "locality_min", "debug_fail_owner", "debug_fail_home",
@@ -294,7 +295,13 @@ const char *impg_gpu_counter_key(size_t i);
  * "bedpe_runs" = lines printed, "bedpe_joins_contiguous" / "bedpe_joins_gap" = rows joined to the row before them by either
  * arm of merge_adjusted_intervals, "bedpe_fused_ops" = I / D ops removed by fusing neighbours, at joins and inside joined
  * rows, "bedpe_summary_ops" = CIGAR ops the summary kernel read, "bedpe_text_pieces" = text pieces sent to the host,
- * "bedpe_text_bytes" = bytes printed.  Of the build of the index itself (a multi-GPU handle answers with the sum over its
+ * "bedpe_text_bytes" = bytes printed.  Of the last device PAF call on the handle (impg_gpu_query_batch_paf,
+ * impg_gpu_query_batch_paf_fd, impg_gpu_selftest_paf_rows; kept the same way): "paf_rows" = rows after each range's first is
+ * dropped, "paf_runs" = lines printed, "paf_joins_contiguous" / "paf_joins_gap" = rows joined to the row before them by
+ * either arm of merge_adjusted_intervals, "paf_ops_read" = CIGAR ops of those rows, "paf_ops_printed" = ops written into
+ * cg:Z (fused ops, and the raw ops of lines made of one row), "paf_through_rows" = rows that print no op of their own (one
+ * group of ops that started in a row before them and goes on), "paf_text_pieces" = text pieces sent to the host,
+ * "paf_text_bytes" = bytes printed.  Of the build of the index itself (a multi-GPU handle answers with the sum over its
  * ranks): "build_device" = 1 if the device builder produced it, 0 if the host builder did (IMPG_BUILD_HOST, tracepoints, a
  * loaded .impg file's entry order, a card short of memory for the build, an index loaded from a saved file);
  * "tokenized_device" = 1 if the device tokenised its CIGAR text (impg_gpu_index_create_from_paf on one GPU);
@@ -567,6 +574,20 @@ int impg_gpu_query_batch_bedpe(impg_gpu_index_t *, const impg_gpu_range_t *range
 int impg_gpu_query_batch_bedpe_fd(impg_gpu_index_t *, const impg_gpu_range_t *ranges, size_t n, const impg_gpu_params_t *params,
                                   const uint8_t *subset_keep, int32_t merge_distance, const char *const *range_names, int fd,
                                   uint64_t *bytes_written, double *seconds3);
+
+/* ---- PAF on the device (paf_device.inc): the same call for `impg query -o paf`, byte-identical to
+ *      impg_gpu_query_batch_filtered with store_cigar = 1 + impg_gpu_results_paf(IMPG_OUT_PAF).  The merge is BEDPE's; the
+ *      merged CIGAR of every line -- its rows' ops and the joins' gap ops, neighbours of one code fused -- is computed and
+ *      printed as cg:Z on the device (option "paf_group_log2"), so that only text crosses PCIe.  Arguments, seconds3 and
+ *      errors as impg_gpu_query_batch_bedpe, except that a tracepoint index is IMPG_E_UNSUPPORTED whatever its options (the
+ *      reference prints no PAF in approximate mode); a line longer than a text piece (option "bed_text_piece_bytes") is
+ *      IMPG_E_UNSUPPORTED. ---- */
+int impg_gpu_query_batch_paf(impg_gpu_index_t *, const impg_gpu_range_t *ranges, size_t n, const impg_gpu_params_t *params,
+                             const uint8_t *subset_keep, int32_t merge_distance, const char *const *range_names, char **text,
+                             size_t *len, double *seconds3);
+int impg_gpu_query_batch_paf_fd(impg_gpu_index_t *, const impg_gpu_range_t *ranges, size_t n, const impg_gpu_params_t *params,
+                                const uint8_t *subset_keep, int32_t merge_distance, const char *const *range_names, int fd,
+                                uint64_t *bytes_written, double *seconds3);
 
 /* ---- host-side ingest helpers (paf.rs, partition.rs parsers) -------------- */
 /* parse_cigar_to_delta (impg.rs:2935-2950): returns #ops or <0 */
@@ -931,6 +952,11 @@ typedef struct {
 int impg_gpu_selftest_bedpe_rows(impg_gpu_index_t *ix, const impg_gpu_interval_t *rows, const uint32_t *row_range, size_t n_rows,
                                  uint32_t n_ranges, const uint64_t *cigar_off, const uint32_t *cigar_ops, int32_t merge_distance,
                                  int original_sequence_coordinates, const char *const *range_names, char **text, size_t *len);
+/* The same for the device PAF merge and text of impg_gpu_query_batch_paf (impg_amd/csrc/paf_device.inc): same arguments, same
+ * rules; errors as impg_gpu_query_batch_paf.  Sets the "paf_*" counters. */
+int impg_gpu_selftest_paf_rows(impg_gpu_index_t *ix, const impg_gpu_interval_t *rows, const uint32_t *row_range, size_t n_rows,
+                               uint32_t n_ranges, const uint64_t *cigar_off, const uint32_t *cigar_ops, int32_t merge_distance,
+                               int original_sequence_coordinates, const char *const *range_names, char **text, size_t *len);
 int impg_gpu_selftest_bed_rows(impg_gpu_index_t *ix, const impg_gpu_interval_t *rows, const uint32_t *row_range, size_t n_rows,
                                uint32_t n_ranges, uint64_t n_seq, int32_t merge_distance, int merge_strands,
                                int original_sequence_coordinates, const char *const *range_names,
