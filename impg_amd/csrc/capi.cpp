@@ -42,6 +42,7 @@ static void engine_options(impg_gpu_index &ix, Engine *e) {
   e->seg_stats = ix.seg_stats;
   e->proj_stats = ix.proj_stats;
   e->upd_stats = ix.upd_stats;
+  e->dfs_stats = ix.dfs_stats;
   e->lk_stats = ix.lk_stats;
 }
 // The free engine used last, else a new one while the handle may have more; null: every engine is out.  (eng_m held.)
@@ -667,6 +668,7 @@ struct CounterRow { const char *key; const std::atomic<uint64_t> &(*at)(const im
 static const CounterRow COUNTER_TABLE[] = {
     CTR("walk_launches", walk_launches), CTR("walk_fallbacks", walk_fallbacks), CTR("walk_members", walk_last_members), CTR("walk_overflow", walk_last_overflow),
     CTR("small_batches", small_batches),
+    CTR("dfs_rounds", dfs_stats[0]), CTR("visited_compactions", dfs_stats[1]),
     CTR("segment_sliced_levels", seg_stats[0]), CTR("segment_retries", seg_stats[1]), CTR("segment_library_levels", seg_stats[2]),
     CTR("project_lane_levels", proj_stats[PROJ_ARM_LANE]), CTR("project_staged_levels", proj_stats[PROJ_ARM_STAGED]),
     CTR("project_staged_rows_levels", proj_stats[PROJ_ARM_STAGED_ROWS]), CTR("project_entries_slots_levels", proj_stats[PROJ_ARM_ENTRIES_SLOTS]),

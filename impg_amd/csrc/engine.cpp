@@ -1154,6 +1154,7 @@ void Engine::compact_tables() {
   IMPG_HIP(hipStreamSynchronize(stream));  // the old tables are read by the copy above
   tables.clear();
   tables.push_back(std::move(nt));
+  if (dfs_stats) dfs_stats[1]++;
 }
 
 // query_transitive_dfs (impg.rs:2057-2309) for a whole batch, in rounds: every
@@ -1193,6 +1194,7 @@ void Engine::run_dfs(const impg_gpu_index &ix, const RunSpec &spec) {
   bool unmerged = masked && mask_has_empty;
   for (;;) {
     const bool alive = n_stack > 0;
+    if (alive && dfs_stats) dfs_stats[0]++;
     // ---- pop the top of every query's stack -----------------------------------
     uint32_t n_fr = 0, n_keep = 0;
     frontier_b.reserve(256);

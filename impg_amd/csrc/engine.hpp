@@ -251,6 +251,7 @@ struct Engine {
   std::atomic<uint64_t> *seg_stats = nullptr;  // the handle's counters (impg_gpu_index::seg_stats), or null
   std::atomic<uint64_t> *proj_stats = nullptr;  // ... and its levels per projection kernel (impg_gpu_index::proj_stats, by ProjArm)
   std::atomic<uint64_t> *upd_stats = nullptr;  // ... and its groups per tier / rare path of the visited update (by UpdStat; option update_stats)
+  std::atomic<uint64_t> *dfs_stats = nullptr;  // ... and its DFS rounds and visited-table folds (impg_gpu_index::dfs_stats)
   void count_arm(int arm) { if (proj_stats && arm >= 0 && arm < PROJ_ARMS) proj_stats[arm]++; }
   uint32_t walk_group_size(const impg_gpu_index &ix, uint32_t n, const impg_gpu_params_t &p) const;
   char *small_in = nullptr;    // pinned: the ranges on their way in

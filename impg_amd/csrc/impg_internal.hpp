@@ -439,6 +439,8 @@ struct impg_gpu_index {
   struct RowsPool : impg::BufPool { RowsPool() { shared = true; } } rows_pool;
   mutable std::atomic<uint64_t> walk_launches{0}, walk_fallbacks{0}, walk_last_members{1}, walk_last_overflow{0};  // impg_gpu_get_counter
   mutable std::atomic<uint64_t> small_batches{0};  // ... and the batches Engine::run_small answered
+  // ... and the rounds of Engine::run_dfs in which a stack was alive, and the calls of Engine::compact_tables that folded ([0], [1])
+  mutable std::atomic<uint64_t> dfs_stats[2] = {};
   // ... and who built this index (by impg::BuildStat): 1 if build_index_device produced it (0: the host builder), 1 if the
   // device tokenised its CIGAR text, the tiles_kernel launches of its build.  A multi-GPU handle reports its ranks' sum.
   mutable std::atomic<uint64_t> build_stats[3] = {};

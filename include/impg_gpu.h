@@ -273,7 +273,9 @@ const char *impg_gpu_counter_key(size_t i);
  * member's share of the last level, 4 visited pool or a mask list, 8 piece scratch, 16 pieces of one level / pop, 32 DFS
  * stack (a BFS frontier is bounded by 16 first), 64 unnamed, 128 a grid hand-off timed out),
  * "small_batches" = plain batches of <= 64 ranges answered by the one-chain
- * small-batch path; how the visited updates grouped their hits: "segment_sliced_levels" =
+ * small-batch path; "dfs_rounds" = rounds of the batch engine's DFS / MultiImpg worklist (Engine::run_dfs) in which some
+ * query still had a stack -- a round that only drops too-deep records counts, a batch the walk answered adds none --,
+ * "visited_compactions" = times a transitive run folded its visited tables into one (Engine::compact_tables); how the visited updates grouped their hits: "segment_sliced_levels" =
  * levels whose queries were cut into slices of their frontier ranges, "segment_retries" = levels counted a second time
  * because one query held more hits than a wave should take, "segment_library_levels" = levels that went through the
  * library's radix sort instead; which kernel projected each level: "project_lane_levels", "project_staged_levels",

@@ -28,7 +28,7 @@ def test_abi_exports_every_declared_symbol():
 
 # the keys the if / else chains of impg_gpu_set_option and impg_gpu_get_counter accepted before they became tables
 # (there were 28 counter keys in that chain, not 29), and the keys added since: "walk_overflow", the option
-# "bed_text_piece_bytes" and the five "bed_*" counters of the last device BED call
+# "bed_text_piece_bytes", the five "bed_*" counters of the last device BED call, "dfs_rounds" and "visited_compactions"
 CHAIN_OPTION_KEYS = ["pair_budget", "chunk_ranges", "locality_min", "device_rows_pool_bytes", "fuse_final_level", "regroup_entries",
                      "walk_kernel", "segment_groups", "segment_parts", "walk_members", "filter_covered", "update_stats", "lookup_stats",
                      "wide_emit_cap", "wide_emit_bins", "approximate_cigar", "free_slot_order", "debug_fail_owner", "debug_fail_home",
@@ -40,13 +40,13 @@ CHAIN_COUNTER_KEYS = ["walk_launches", "walk_fallbacks", "walk_members", "walk_o
                       "update_wave_tiny_groups", "update_wave_small_groups", "update_wave_large_groups", "update_inplace_groups",
                       "update_tiled_sort_groups", "update_lane_spill_groups", "lookup_wide_windows", "lookup_wide_single",
                       "lookup_wide_grouped", "lookup_wide_group_passes", "lookup_wide_overflow", "bed_rows", "bed_gap_roots", "bed_runs",
-                      "bed_text_pieces", "bed_text_bytes"]
+                      "bed_text_pieces", "bed_text_bytes", "dfs_rounds", "visited_compactions"]
 
 
 def test_key_enumeration_keeps_every_key():
     """impg_gpu_option_key / impg_gpu_counter_key: NULL past the end, no key twice, no key of the old chains dropped."""
     L = impg_amd.lib()
-    assert len(CHAIN_OPTION_KEYS) == 23 and len(CHAIN_COUNTER_KEYS) == 34
+    assert len(CHAIN_OPTION_KEYS) == 23 and len(CHAIN_COUNTER_KEYS) == 36
     for fn, keys, chain in ((L.impg_gpu_option_key, impg_amd.option_keys(), CHAIN_OPTION_KEYS),
                             (L.impg_gpu_counter_key, impg_amd.counter_keys(), CHAIN_COUNTER_KEYS)):
         assert fn(len(keys)) is None and fn(len(keys) + 1) is None and fn(2 ** 40) is None
