@@ -3057,44 +3057,68 @@ __global__ __launch_bounds__(256) void query_bounds_kernel(const FrontierRec *__
   }
   if (i + 1u == n_fr || fr[i + 1u].qidx != q) qlast[q] = i + 1u;
 }
-// The slots of the ranges [f0, f1) of one query, 64 at a time in frontier order x slot order (one wave): f(qid, hc, active)
-// per chunk, the next chunk's loads already under way (a chunk is one or two memory round trips, and a query's ~20 runs
-// of ~40 slots were that many trips in a row).  WITH_HC: the hit's coordinates are loaded beside its sequence id.
+// The slots of the ranges [f0, f1) of one query as ONE stream in frontier order x slot order (one wave).  Per base of 64
+// ranges, a lane each, an inclusive scan over the runs' lengths numbers the base's slots 0 .. total; the lane of flat
+// index x finds its run -- the first j with incl[j] > x -- with six probes of the scan where it lies (ds_bpermute: no LDS
+// of the wave's own) and reads that run's first slot and target the same way.  So a chunk of 64 slots is full whatever
+// the runs' lengths (all but a base's last one), an empty run costs nothing, and a chunk's lanes may belong to several
+// ranges: `active` compares a hit with the target of its OWN range.  f(qid, hc, active) once per chunk that holds slots,
+// in stream order.  The chunks are loaded SEG_U at a time, back to back, a group ahead of the one that is consumed; the
+// next base's runs are asked for as soon as this base's are in registers.  (The walk this replaces took a run at a time,
+// one chunk ahead: a query's ~27 runs of ~30 slots were that many half-empty chunks and dependent round trips.)
+// WITH_HC: the hit's query-side coordinates (q_first, q_last: what the place pass stores) are loaded beside its id.
+// (SEG_U = 2 | 4 | 8 on the headline step: update 5.46 | 5.41 | 5.35 ms, the step 27.35 | 27.18 | 27.29, all inside the ±0.15
+// spread; 8 takes the place pass from 56 to 92 VGPRs and from 8 to 5 waves a SIMD, 4 keeps both passes at 8.)
+constexpr uint32_t SEG_U = 4;
+__device__ __forceinline__ uint32_t wave_read(uint32_t x, uint32_t src_lane) { return (uint32_t)__shfl((int)x, (int)src_lane); }
 template <bool WITH_HC, class F>
 __device__ __forceinline__ void seg_for_chunks(const FrontierRec *__restrict__ fr, const uint32_t *__restrict__ run_start,
                                                const uint32_t *__restrict__ run_end, const HitArrays &h, uint32_t f0, uint32_t f1, F f) {
   const uint32_t lane = lane_id();
-  for (uint32_t base = f0; base < f1; base += 64u) {
+  auto load_base = [&](uint32_t base, uint32_t &rs, uint32_t &re, uint32_t &tg) {
     const uint32_t i = base + lane;
     const bool have = i < f1;
-    const uint32_t rs = have ? run_start[i] : 0u, re = have ? run_end[i] : 0u, tg = have ? fr[i].target_id : 0u;
-    const uint32_t m = min(64u, f1 - base);
-    uint32_t j = 0, c0 = 0, e = 0, t = 0;
-    auto seek = [&](uint32_t &jj, uint32_t &cc, uint32_t &ee, uint32_t &tt) {  // the first chunk at or after (jj, cc) that holds slots
-      while (jj < m && cc >= ee) {
-        jj += 1u;
-        if (jj < m) {
-          cc = (uint32_t)__builtin_amdgcn_readlane((int)rs, (int)jj);
-          ee = (uint32_t)__builtin_amdgcn_readlane((int)re, (int)jj);
-          tt = (uint32_t)__builtin_amdgcn_readlane((int)tg, (int)jj);
-        }
+    rs = have ? run_start[i] : 0u; re = have ? run_end[i] : 0u; tg = have ? fr[i].target_id : 0u;
+  };
+  uint32_t rs, re, tg;
+  load_base(f0, rs, re, tg);
+  for (uint32_t base = f0; base < f1; base += 64u) {
+    const uint32_t len = re > rs ? re - rs : 0u, incl = wave_incl_scan(len);
+    const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+    const uint32_t first = rs - (incl - len), tgt = tg;  // (flat index x of this lane's run is slot first + x, modulo 2^32)
+    if (base + 64u < f1) load_base(base + 64u, rs, re, tg);
+    // the chunk of flat indices [x0, x0 + 64): its loads issued, nothing waited for (x0 and total are wave-uniform)
+    auto fetch = [&](uint32_t x0, uint32_t &qid, int2 &hc, uint32_t &t) {
+      qid = HIT_NONE; hc = make_int2(0, 0); t = 0u;
+      if (x0 >= total) return;
+      const uint32_t x = x0 + lane;
+      uint32_t j = 0;  // (the runs that end at or before x; 63 at most for x < total, and a lane past total stays inside the wave)
+#pragma unroll
+      for (uint32_t s = 32u; s; s >>= 1) {
+        const uint32_t v = wave_read(incl, j + s - 1u);
+        j += v <= x ? s : 0u;
+      }
+      const uint32_t slot = wave_read(first, j) + x;
+      t = wave_read(tgt, j);
+      if (x < total) {
+        qid = h.qid[slot];
+        if (WITH_HC) hc = *reinterpret_cast<const int2 *>(h.c + slot);
       }
     };
-    c0 = (uint32_t)__builtin_amdgcn_readlane((int)rs, 0);
-    e = (uint32_t)__builtin_amdgcn_readlane((int)re, 0);
-    t = (uint32_t)__builtin_amdgcn_readlane((int)tg, 0);
-    seek(j, c0, e, t);
-    uint32_t qid = HIT_NONE;
-    int4 hc = make_int4(0, 0, 0, 0);
-    if (j < m && c0 + lane < e) { qid = h.qid[c0 + lane]; if (WITH_HC) hc = h.c[c0 + lane]; }
-    while (j < m) {
-      uint32_t nj = j, nc = c0 + 64u, ne = e, nt = t;
-      seek(nj, nc, ne, nt);
-      uint32_t nqid = HIT_NONE;
-      int4 nhc = make_int4(0, 0, 0, 0);
-      if (nj < m && nc + lane < ne) { nqid = h.qid[nc + lane]; if (WITH_HC) nhc = h.c[nc + lane]; }
-      f(qid, hc, qid != HIT_NONE && qid != t);  // impg.rs:2507
-      j = nj; c0 = nc; e = ne; t = nt; qid = nqid; hc = nhc;
+    uint32_t qid[SEG_U], t[SEG_U];
+    int2 hc[SEG_U];
+#pragma unroll
+    for (uint32_t u = 0; u < SEG_U; u++) fetch(64u * u, qid[u], hc[u], t[u]);
+    for (uint32_t x0 = 0; x0 < total; x0 += 64u * SEG_U) {
+      uint32_t nqid[SEG_U], nt[SEG_U];
+      int2 nhc[SEG_U];
+#pragma unroll
+      for (uint32_t u = 0; u < SEG_U; u++) fetch(x0 + 64u * (SEG_U + u), nqid[u], nhc[u], nt[u]);
+#pragma unroll
+      for (uint32_t u = 0; u < SEG_U; u++)
+        if (x0 + 64u * u < total) f(qid[u], hc[u], qid[u] != HIT_NONE && qid[u] != t[u]);  // impg.rs:2507
+#pragma unroll
+      for (uint32_t u = 0; u < SEG_U; u++) { qid[u] = nqid[u]; hc[u] = nhc[u]; t[u] = nt[u]; }
     }
   }
 }
@@ -3125,7 +3149,7 @@ __global__ __launch_bounds__(64 * SEG_WAVES) void seg_group_kernel(const Frontie
   if (COUNT_ONLY || !qbins) {
     for (uint32_t b = lane; b < nb; b += 64u) bins[b] = 0u;
     __builtin_amdgcn_wave_barrier();
-    seg_for_chunks<false>(fr, run_start, run_end, h, f0, f1, [&](uint32_t qid, const int4 &, bool active) { if (active) atomicAdd(&bins[qid], 1u); });
+    seg_for_chunks<false>(fr, run_start, run_end, h, f0, f1, [&](uint32_t qid, const int2 &, bool active) { if (active) atomicAdd(&bins[qid], 1u); });
   } else if (!sliced) {
     for (uint32_t b = lane; b < nb; b += 64u) bins[b] = qbins[(size_t)q * nb + b];
   }
@@ -3167,7 +3191,7 @@ __global__ __launch_bounds__(64 * SEG_WAVES) void seg_group_kernel(const Frontie
   }
   __builtin_amdgcn_wave_barrier();
   // pass B: a hit's place = its sequence's counter + its rank among the chunk's earlier hits of that sequence
-  seg_for_chunks<true>(fr, run_start, run_end, h, f0, f1, [&](uint32_t qid, const int4 &hc, bool active) {
+  seg_for_chunks<true>(fr, run_start, run_end, h, f0, f1, [&](uint32_t qid, const int2 &hc, bool active) {
     const unsigned long long am = __ballot(active);
     if (!am) return;
     unsigned long long mask = am;  // the chunk's hits of this lane's sequence
