@@ -253,6 +253,20 @@ SYMBOLS = [
                                                C.POINTER(C.c_size_t)]),
     ("impg_gpu_selftest_paf_rows", C.c_int, [_P, _P, _P, C.c_size_t, C.c_uint32, _P, _P, C.c_int32, C.c_int, _P, C.POINTER(_P),
                                              C.POINTER(C.c_size_t)]),
+    ("impg_gpu_sequences_from_fasta", C.c_int, [_P, C.c_size_t, C.POINTER(_P)]),
+    ("impg_gpu_sequences_from_memory", C.c_int, [_P, _P, _P, C.c_size_t, C.POINTER(_P)]),
+    ("impg_gpu_sequences_num", C.c_size_t, [_P]),
+    ("impg_gpu_sequences_name", C.c_char_p, [_P, C.c_size_t]),
+    ("impg_gpu_sequences_bases", _P, [_P, C.c_size_t, C.POINTER(C.c_uint64)]),
+    ("impg_gpu_sequences_free", None, [_P]),
+    ("impg_gpu_index_set_sequences", C.c_int, [_P, _P]),
+    ("impg_gpu_query_batch_fasta", C.c_int, [_P, _P, C.c_size_t, C.POINTER(Params), _P, C.c_int32, _P, C.c_int, C.POINTER(_P),
+                                             C.POINTER(C.c_size_t), _P]),
+    ("impg_gpu_query_batch_fasta_fd", C.c_int, [_P, _P, C.c_size_t, C.POINTER(Params), _P, C.c_int32, _P, C.c_int, C.c_int,
+                                                C.POINTER(C.c_uint64), _P]),
+    ("impg_gpu_results_fasta", C.c_int, [_P, _P, C.POINTER(Params), C.c_int32, C.c_int, C.POINTER(_P), C.POINTER(C.c_size_t)]),
+    ("impg_gpu_fasta_text", C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t, C.c_int32, C.c_int, C.POINTER(_P), C.POINTER(C.c_size_t)]),
+    ("impg_gpu_selftest_fasta_rows", C.c_int, [_P, _P, _P, C.c_size_t, C.c_uint32, C.c_int32, C.c_int, C.POINTER(_P), C.POINTER(C.c_size_t)]),
     ("impg_synth_seq_name", C.c_int, [C.c_uint32, C.c_char_p, C.c_size_t]),
     ("impg_synth_bed", C.c_int, [C.c_uint64, C.c_size_t, C.c_uint32, C.c_int32, C.c_int32, _P]),
 ]

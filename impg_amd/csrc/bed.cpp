@@ -134,6 +134,10 @@ void merge_query_axis(std::vector<impg_gpu_interval_t> &r, int32_t merge_distanc
 
 }  // namespace
 
+void query_axis_merge(std::vector<impg_gpu_interval_t> &rows, int32_t merge_distance, bool merge_strands) {
+  merge_query_axis(rows, merge_distance, merge_strands);
+}
+
 size_t bed_merge(impg_gpu_interval_t *iv, size_t n, int32_t merge_distance, bool merge_strands) {
   std::vector<impg_gpu_interval_t> v(iv, iv + n);
   gap_2d(v, merge_distance);  // BED: every CIGAR is empty (main.rs:11858-11865)

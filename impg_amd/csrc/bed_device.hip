@@ -157,11 +157,6 @@ __global__ __launch_bounds__(256) void axis_run_heads_kernel(ConstRows R, const 
   }
   run_head[k] = head ? 1u : 0u;
 }
-struct BedRow {  // a merged row, 16 bytes
-  uint32_t q_strand;  // range index | reverse strand << 31
-  uint32_t query_id;
-  int32_t start, end;  // (printed as u32, like the reference: an inconsistent CIGAR can project below zero)
-};
 // one thread per sorted row; run r = run_id[k] (exclusive scan of the heads + own flag - 1)
 __global__ __launch_bounds__(256) void axis_emit_kernel(ConstRows R, const uint32_t *__restrict__ perm, const uint32_t *__restrict__ run_head,
                                                         const uint32_t *__restrict__ run_pos, const unsigned long long *__restrict__ pmax,
@@ -308,8 +303,10 @@ static uint32_t query_axis(Engine &E, ConstRows R, uint32_t m, unsigned seq_bits
 // number.  R: n rows numbered in emission order (within a range: the reference's; rows of different ranges may
 // interleave), ids < n_seq, range indices < n_ranges.  Counts into the handle's bed_* counters.  gap (diagnostics):
 // the rows between the two merges, copied to the host in their order -- a chain stands where its first row stood.
+// bed = false (FASTA, output_results_fasta: main.rs:12362): the sweep along the query axis alone, no gap_2d before it,
+// and the bed_* counters stay as they are.
 static uint32_t merge_rows(Engine &E, const impg_gpu_index &ix, Rows R, uint32_t n, uint64_t n_seq, uint32_t n_ranges, int32_t merge_distance,
-                           bool merge_strands, DevBuf &out, BedGapRows *gap = nullptr) {
+                           bool merge_strands, DevBuf &out, BedGapRows *gap = nullptr, bool bed = true) {
   hipStream_t s = E.stream;
   const unsigned seq_bits = bits_for(n_seq), q_bits = bits_for(n_ranges);
   // (with no merge at all the rows are only grouped by range: no key holds a sequence id)
@@ -320,7 +317,7 @@ static uint32_t merge_rows(Engine &E, const impg_gpu_index &ix, Rows R, uint32_t
   DevRows chains;
   Rows cur = R;
   uint32_t m = n;
-  if (merge_distance >= 0 && n > 1) {
+  if (bed && merge_distance >= 0 && n > 1) {
     m = gap_2d(E, R, n, seq_bits, q_bits, merge_distance, ks, k32, k64a, chains);
     cur = chains.view();
   }
@@ -337,6 +334,7 @@ static uint32_t merge_rows(Engine &E, const impg_gpu_index &ix, Rows R, uint32_t
     for (uint32_t i = 0; i < m; i++) gap->rows[i] = impg_gpu_interval_t{hqid[i], hc[i].x, hc[i].y, htid[i], hc[i].z, hc[i].w};
   }
   const uint32_t n_runs = query_axis(E, cur, m, seq_bits, q_bits, merge_distance, merge_strands, ks, k64a, k64b, out);
+  if (!bed) return n_runs;
   ix.bed_stats[BED_ROWS] += n;
   ix.bed_stats[BED_GAP_ROOTS] += m;
   ix.bed_stats[BED_RUNS] += n_runs;
@@ -344,8 +342,10 @@ static uint32_t merge_rows(Engine &E, const impg_gpu_index &ix, Rows R, uint32_t
 }
 
 // Rows of one chunk -> merged BED rows (merge_rows).  levels / self_dev: what Engine::run kept for the chunk.
-uint32_t device_bed_rows(Engine &E, const impg_gpu_index &ix, uint32_t n_ranges, const impg_gpu_params_t &p, int32_t merge_distance,
-                         std::vector<std::unique_ptr<LevelBufs>> &levels, DevBuf &self_dev, DevBuf &out) {
+// fasta_rows_in (FASTA): the rows go through the sweep alone, strands apart (merge_rows with bed = false); their number
+// before it is left there.
+static uint32_t chunk_rows_merged(Engine &E, const impg_gpu_index &ix, uint32_t n_ranges, const impg_gpu_params_t &p, int32_t merge_distance,
+                                  std::vector<std::unique_ptr<LevelBufs>> &levels, DevBuf &self_dev, DevBuf &out, uint32_t *fasta_rows_in) {
   // ---- rows: range-major, the reference's emission order within a range (rows_device.hip) ---------------------------
   uint32_t n = 0;
   DevRows rows;
@@ -360,7 +360,31 @@ uint32_t device_bed_rows(Engine &E, const impg_gpu_index &ix, uint32_t n_ranges,
   }
   // the levels' slots are not needed any more: give their memory back before the sorts take theirs
   levels.clear();
+  if (fasta_rows_in) {
+    *fasta_rows_in = n;
+    return merge_rows(E, ix, rows.view(), n, ix.view.n_seq, n_ranges, merge_distance, /*merge_strands=*/false, out, nullptr, /*bed=*/false);
+  }
   return merge_rows(E, ix, rows.view(), n, ix.view.n_seq, n_ranges, merge_distance, p.consider_strandness == 0, out);
+}
+
+uint32_t device_bed_rows(Engine &E, const impg_gpu_index &ix, uint32_t n_ranges, const impg_gpu_params_t &p, int32_t merge_distance,
+                         std::vector<std::unique_ptr<LevelBufs>> &levels, DevBuf &self_dev, DevBuf &out) {
+  return chunk_rows_merged(E, ix, n_ranges, p, merge_distance, levels, self_dev, out, nullptr);
+}
+uint32_t device_fasta_rows(Engine &E, const impg_gpu_index &ix, uint32_t n_ranges, const impg_gpu_params_t &p, int32_t merge_distance,
+                           std::vector<std::unique_ptr<LevelBufs>> &levels, DevBuf &self_dev, DevBuf &out, uint32_t &rows_in) {
+  rows_in = 0;
+  return chunk_rows_merged(E, ix, n_ranges, p, merge_distance, levels, self_dev, out, &rows_in);
+}
+
+// The FASTA sweep on rows the caller brings (impg_gpu_selftest_fasta_rows): uploaded as they are, then merge_rows as a
+// chunk of impg_gpu_query_batch_fasta runs it; returns the merged rows' number, the rows in `out`.
+uint32_t device_fasta_selftest_rows(Engine &E, const impg_gpu_index &ix, const impg_gpu_interval_t *rows, const uint32_t *row_range, uint32_t n,
+                                    uint32_t n_ranges, int32_t merge_distance, DevBuf &out) {
+  if (!n) return 0;
+  DevRows dev;
+  dev.upload(E, rows, row_range, n);
+  return merge_rows(E, ix, dev.view(), n, ix.view.n_seq, n_ranges, merge_distance, /*merge_strands=*/false, out, nullptr, /*bed=*/false);
 }
 
 // The merge and the text on rows the caller brings (impg_gpu_selftest_bed_rows): uploaded as they are, then merge_rows

@@ -25,6 +25,8 @@ void render_paf(const impg_gpu_results &res, const impg_gpu_index &ix, const cha
 void render_bed(const impg_gpu_results &res, const impg_gpu_index &ix, const char *const *range_names,
                 const impg_gpu_params_t &p, int32_t merge_distance, std::vector<std::string> &parts);
 char *join_parts(std::vector<std::string> &parts, size_t *len);  // bed.cpp
+void render_fasta(const impg_gpu_results &res, const impg_gpu_index &ix, const impg_gpu_params_t &p, int32_t merge_distance, bool reverse_complement,
+                  std::vector<std::string> &parts);  // sequences.cpp
 }  // namespace impg
 
 using namespace impg;
@@ -219,12 +221,20 @@ bool run_chunk_bed(const impg_gpu_index &ix, Engine &E, const impg_gpu_range_t *
   const auto c1 = std::chrono::steady_clock::now();
   if (e == b) return false;
   uint32_t n_rows = 0;
+  const bool fasta = format == TEXT_FASTA || format == TEXT_FASTA_RC;
   if (format == TEXT_PAF) paf = device_paf_rows(E, ix, (uint32_t)(e - b), p, merge_distance, levels, self_dev);
+  else if (fasta) {
+    uint32_t n_in = 0;
+    n_rows = device_fasta_rows(E, ix, (uint32_t)(e - b), p, merge_distance, levels, self_dev, rows, n_in);
+    ix.fasta_stats[FASTA_ROWS] += n_in;
+    ix.fasta_stats[FASTA_RECORDS] += n_rows;
+  }
   else n_rows = (format == TEXT_BEDPE ? device_bedpe_rows : device_bed_rows)(E, ix, (uint32_t)(e - b), p, merge_distance, levels, self_dev, rows);
   const auto c2 = std::chrono::steady_clock::now();
   const std::vector<std::string> rnames = bed_range_names(ix, h_ranges, range_names, b, e);
   const bool orig = p.original_sequence_coordinates != 0;
   if (format == TEXT_PAF) device_paf_text(E, ix, *paf, (uint32_t)(e - b), rnames, orig, sink);
+  else if (fasta) device_fasta_text(E, ix, rows, n_rows, format == TEXT_FASTA_RC, sink);
   else (format == TEXT_BEDPE ? device_bedpe_text : device_bed_text)(E, ix, rows, n_rows, (uint32_t)(e - b), rnames, orig, sink);
   const auto c3 = std::chrono::steady_clock::now();
   seconds3[0] += std::chrono::duration<double>(c1 - c0).count();
@@ -694,6 +704,9 @@ static const CounterRow COUNTER_TABLE[] = {
     CTR("paf_ops_read", paf_stats[PAF_OPS_READ]), CTR("paf_ops_printed", paf_stats[PAF_OPS_PRINTED]),
     CTR("paf_through_rows", paf_stats[PAF_THROUGH_ROWS]), CTR("paf_text_pieces", paf_stats[PAF_TEXT_PIECES]),
     CTR("paf_text_bytes", paf_stats[PAF_TEXT_BYTES]),
+    CTR("fasta_rows", fasta_stats[FASTA_ROWS]), CTR("fasta_records", fasta_stats[FASTA_RECORDS]),
+    CTR("fasta_text_pieces", fasta_stats[FASTA_TEXT_PIECES]), CTR("fasta_text_bytes", fasta_stats[FASTA_TEXT_BYTES]),
+    CTR("fasta_store_bytes", fasta_stats[FASTA_STORE_BYTES]),
     CTR_RANKS("build_device", build_stats[BUILD_DEVICE]), CTR_RANKS("tokenized_device", build_stats[BUILD_TOKENIZED_DEVICE]),
     CTR_RANKS("build_batches", build_stats[BUILD_BATCHES]),
 };
@@ -1332,6 +1345,11 @@ void paf_refusals(const impg_gpu_index &ix) {
                                     "is a pair of match / mismatch counts, not an alignment)"};
   bedpe_refusals(ix, "PAF");
 }
+// ... and FASTA: raised before anything runs
+void fasta_refusals(const impg_gpu_index &ix) {
+  if (ix.shard || ix.cluster) throw Error{IMPG_E_UNSUPPORTED, "device-side FASTA on a sharded index"};
+  if (!ix.seq_store) throw Error{IMPG_E_INVALID, "FASTA output needs a sequence store (impg_gpu_index_set_sequences)"};
+}
 void text_batch(impg_gpu_index_t *ix, const impg_gpu_range_t *ranges, size_t n, const impg_gpu_params_t *params, const uint8_t *subset_keep,
                 int32_t merge_distance, const char *const *range_names, const std::function<void(const char *, size_t)> &sink,
                 double *seconds3, TextFormat format) {
@@ -1339,14 +1357,17 @@ void text_batch(impg_gpu_index_t *ix, const impg_gpu_range_t *ranges, size_t n, 
   check_ranges(ranges, n);
   Engine::check_params(*params);
   impg_gpu_params_t p = *params;
-  p.store_cigar = format != TEXT_BED ? 1 : 0;  // BED never needs CIGARs, BEDPE rates them, PAF prints them (main.rs:7447)
-  if (format == TEXT_BEDPE) bedpe_refusals(*ix);
+  const bool fasta = format == TEXT_FASTA || format == TEXT_FASTA_RC;
+  p.store_cigar = format != TEXT_BED && !fasta ? 1 : 0;  // BED and FASTA never need CIGARs, BEDPE rates them, PAF prints them (main.rs:7447)
+  if (fasta) fasta_refusals(*ix);
+  else if (format == TEXT_BEDPE) bedpe_refusals(*ix);
   else if (format == TEXT_PAF) paf_refusals(*ix);
   else if (ix->shard || ix->cluster) { sharded_bed_batch(*ix, ranges, n, p, subset_keep, merge_distance, range_names, sink, seconds3); return; }
   IMPG_HIP(hipSetDevice(ix->device));
   EngineLease lease(*ix);
   Engine &E = *lease;
-  if (format == TEXT_BEDPE) ix->bedpe_stats_reset();
+  if (fasta) ix->fasta_stats_reset();
+  else if (format == TEXT_BEDPE) ix->bedpe_stats_reset();
   else if (format == TEXT_PAF) ix->paf_stats_reset();
   else ix->bed_stats_reset();
   apply_subset(E, *ix, subset_keep);
@@ -1442,6 +1463,30 @@ int impg_gpu_query_batch_paf_fd(impg_gpu_index_t *ix, const impg_gpu_range_t *ra
   return text_batch_fd(ix, ranges, n, params, subset_keep, merge_distance, range_names, fd, bytes_written, seconds3, TEXT_PAF);
 }
 
+// FASTA (fasta_device.hip): range_names is accepted and unused -- a record is named after its own sequence
+int impg_gpu_query_batch_fasta(impg_gpu_index_t *ix, const impg_gpu_range_t *ranges, size_t n, const impg_gpu_params_t *params,
+                               const uint8_t *subset_keep, int32_t merge_distance, const char *const *range_names, int reverse_complement,
+                               char **text, size_t *len, double *seconds3) {
+  (void)range_names;
+  return text_batch_buffer(ix, ranges, n, params, subset_keep, merge_distance, nullptr, text, len, seconds3, reverse_complement ? TEXT_FASTA_RC : TEXT_FASTA);
+}
+int impg_gpu_query_batch_fasta_fd(impg_gpu_index_t *ix, const impg_gpu_range_t *ranges, size_t n, const impg_gpu_params_t *params,
+                                  const uint8_t *subset_keep, int32_t merge_distance, const char *const *range_names, int reverse_complement,
+                                  int fd, uint64_t *bytes_written, double *seconds3) {
+  (void)range_names;
+  return text_batch_fd(ix, ranges, n, params, subset_keep, merge_distance, nullptr, fd, bytes_written, seconds3, reverse_complement ? TEXT_FASTA_RC : TEXT_FASTA);
+}
+int impg_gpu_results_fasta(const impg_gpu_results_t *res, const impg_gpu_index_t *ix, const impg_gpu_params_t *params, int32_t merge_distance,
+                           int reverse_complement, char **text, size_t *len) {
+  IMPG_TRY
+  if (!res || !ix || !params || !text || !len) throw Error{IMPG_E_INVALID, "null argument"};
+  std::vector<std::string> parts;
+  render_fasta(*res, *ix, *params, merge_distance, reverse_complement != 0, parts);
+  *text = join_parts(parts, len);
+  return IMPG_OK;
+  IMPG_CATCH
+}
+
 int impg_gpu_results_paf(const impg_gpu_results_t *res, const impg_gpu_index_t *ix, const char *const *range_names,
                          const impg_gpu_params_t *params, int32_t merge_distance, int format, char **text, size_t *len) {
   IMPG_TRY
@@ -1491,6 +1536,32 @@ int impg_gpu_selftest_bed_rows(impg_gpu_index_t *ix, const impg_gpu_interval_t *
   }
   if (!merged.empty()) memcpy(m, merged.data(), merged.size() * sizeof(impg_gpu_bed_row_t));
   *merged_out = m; *n_merged = merged.size(); *text = t; *len = out.size();
+  return IMPG_OK;
+  IMPG_CATCH
+}
+
+// The device FASTA sweep and writer on rows the caller brings (diagnostics; tests/test_gpu_fasta_device.py): what a chunk of
+// impg_gpu_query_batch_fasta runs once its rows are placed (bed_device.hip's sweep, fasta_device.hip), without a query in front.
+int impg_gpu_selftest_fasta_rows(impg_gpu_index_t *ix, const impg_gpu_interval_t *rows, const uint32_t *row_range, size_t n_rows, uint32_t n_ranges,
+                                 int32_t merge_distance, int reverse_complement, char **text, size_t *len) {
+  IMPG_TRY
+  if (!ix || !text || !len || (n_rows && (!rows || !row_range))) throw Error{IMPG_E_INVALID, "null argument"};
+  fasta_refusals(*ix);
+  check_row_count(n_rows);
+  for (size_t i = 0; i < n_rows; i++) {
+    if (rows[i].query_id >= ix->view.n_seq || rows[i].target_id >= ix->view.n_seq) throw Error{IMPG_E_INVALID, "a row's sequence id is not one of the index's"};
+    if (row_range[i] >= n_ranges) throw Error{IMPG_E_INVALID, "a row's range index is not below n_ranges"};
+  }
+  IMPG_HIP(hipSetDevice(ix->device));
+  EngineLease lease(*ix);
+  ix->fasta_stats_reset();
+  std::string out;
+  DevBuf merged;
+  const uint32_t n_rec = device_fasta_selftest_rows(*lease, *ix, rows, row_range, (uint32_t)n_rows, n_ranges, merge_distance, merged);
+  ix->fasta_stats[FASTA_ROWS] += n_rows;
+  ix->fasta_stats[FASTA_RECORDS] += n_rec;
+  device_fasta_text(*lease, *ix, merged, n_rec, reverse_complement != 0, [&](const char *p, size_t k) { out.append(p, k); });
+  *text = malloc_text(out); *len = out.size();
   return IMPG_OK;
   IMPG_CATCH
 }

@@ -12,6 +12,7 @@
 #include <chrono>
 #include <cstring>
 #include <fstream>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -96,7 +97,8 @@ void usage() {
           "impg-gpu query (-a <paf>... | -i <file>) (-r seq:start-end | -b <bed>) (-d <bp> | --no-merge) [-x] [-m N]\n"
           "               [--transitive-dfs] [--multi-impg] [--min-transitive-len N] [--min-distance-between-ranges N]\n"
           "               [-l N] [--min-result-identity F] [--subset-sequence-list FILE] [--original-sequence-coordinates]\n"
-          "               [--consider-strandness] [-o auto|bed|bedpe|paf] [--unidirectional] [--order coitrees|sorted]\n"
+          "               [--consider-strandness] [-o auto|bed|bedpe|paf|fasta] [--sequence-files F... | --sequence-list FILE]\n"
+          "               [--reverse-complement] [--host-merge] [--unidirectional] [--order coitrees|sorted]\n"
           "               [--device N]\n"
           "impg-gpu partition (-a <paf>... | -i <file>) -w <bp> -d <bp> [--min-missing-size N] [--min-boundary-distance N]\n"
           "               [--selection-mode longest|total|sample[,sep]|haplotype[,sep]] [--starting-sequences-file FILE]\n"
@@ -482,6 +484,9 @@ int main(int argc, char **argv) {
   };
   bool consider_strandness = false;  // main.rs:4380
   bool host_merge = false;
+  std::vector<std::string> seq_files;  // --sequence-files / --sequence-list (main.rs:4116-4121): what -o fasta prints from
+  std::string seq_list;
+  bool reverse_complement = false;
   for (int i = 2; i < argc; i++) {
     std::string a = argv[i];
     auto need = [&](const char *f) -> const char * {
@@ -506,7 +511,12 @@ int main(int argc, char **argv) {
     else if (a == "-l" || a == "--min-output-length") min_out = num(a, need("-l"), 0, 2147483647);
     else if (a == "--min-result-identity") min_ident = real(a, need(a.c_str()));
     else if (a == "--consider-strandness") consider_strandness = true;
-    else if (a == "--host-merge") host_merge = true;  // BED / BEDPE / PAF merges on the host (impg_gpu_results_bed / _paf) instead of the device
+    else if (a == "--host-merge") host_merge = true;  // BED / BEDPE / PAF / FASTA merges and text on the host (impg_gpu_results_bed / _paf / _fasta) instead of the device
+    else if (a == "--sequence-files") {
+      seq_files.push_back(need(a.c_str()));
+      while (i + 1 < argc && argv[i + 1][0] != '-') seq_files.push_back(argv[++i]);
+    } else if (a == "--sequence-list") seq_list = need(a.c_str());
+    else if (a == "--reverse-complement") reverse_complement = true;
     else if (a == "--subset-sequence-list") subset_list = need(a.c_str());
     else if (a == "--original-sequence-coordinates") original_coords = true;
     else if (a == "-o" || a == "--output-format") ofmt = need("-o");
@@ -543,8 +553,20 @@ int main(int argc, char **argv) {
   const int32_t merge_distance = no_merge ? -1 : (int32_t)merge_d;
   // -o auto: bed for -r, bedpe for -b (main.rs:7365-7373)
   std::string fmt = ofmt == "auto" ? (bed.empty() ? "bed" : "bedpe") : ofmt;
-  if (fmt != "bed" && fmt != "bedpe" && fmt != "paf")
-    die("output format '" + fmt + "' is not built in impg-gpu (bed, bedpe, paf)");
+  if (fmt != "bed" && fmt != "bedpe" && fmt != "paf" && fmt != "fasta")
+    die("output format '" + fmt + "' is not built in impg-gpu (bed, bedpe, paf, fasta)");
+  if (!seq_files.empty() && !seq_list.empty()) die("Cannot specify both --sequence-files and --sequence-list");
+  if (!seq_list.empty()) {  // one path per line (main.rs:4130-4145)
+    std::ifstream in(seq_list);
+    if (!in) die("No such file or directory: " + seq_list);
+    std::string line;
+    while (std::getline(in, line)) {
+      while (!line.empty() && (line.back() == '\r' || line.back() == ' ' || line.back() == '\t')) line.pop_back();
+      if (!line.empty()) seq_files.push_back(line);
+    }
+  }
+  if (fmt == "fasta" && seq_files.empty())  // main.rs:4243
+    die("Sequence files (FASTA/AGC) are required for 'fasta' output format. Use --sequence-files or --sequence-list");
 
   std::vector<const char *> pp;
   for (auto &p : pafs) pp.push_back(p.c_str());
@@ -569,6 +591,15 @@ int main(int argc, char **argv) {
     if (impg_gpu_index_create_from_paf(pp.data(), (int)pp.size(), unidirectional ? 0 : 1, order, device, &ix) != IMPG_OK)
       die(impg_gpu_last_error());
     if (!index_file.empty() && impg_gpu_index_save(ix, index_file.c_str()) != IMPG_OK) die(impg_gpu_last_error());
+  }
+
+  if (fmt == "fasta") {
+    std::vector<const char *> sp;
+    for (auto &f : seq_files) sp.push_back(f.c_str());
+    impg_gpu_sequences_t *seqs = nullptr;
+    if (impg_gpu_sequences_from_fasta(sp.data(), sp.size(), &seqs) != IMPG_OK) die(impg_gpu_last_error());
+    if (impg_gpu_index_set_sequences(ix, seqs) != IMPG_OK) die(impg_gpu_last_error());
+    impg_gpu_sequences_free(seqs);  // (the handle shares the store)
   }
 
   std::vector<Target> targets;
@@ -615,7 +646,7 @@ int main(int argc, char **argv) {
   p.min_distance_between_ranges = (int32_t)mdbr;
   p.min_output_length = min_out < 0 ? -1 : (int32_t)min_out;
   p.min_identity = min_ident;
-  p.store_cigar = fmt != "bed";  // CIGARs for PAF / BEDPE only (main.rs:7447)
+  p.store_cigar = fmt != "bed" && fmt != "fasta";  // CIGARs for PAF / BEDPE only (main.rs:7447)
   p.original_sequence_coordinates = original_coords;
   p.consider_strandness = consider_strandness;
   impg_gpu_results_t *res = nullptr;
@@ -626,7 +657,14 @@ int main(int argc, char **argv) {
   // BED and BEDPE: the merge and the text on the device, only text crosses PCIe.  An index the device BEDPE route does
   // not serve (a sequence of 2^29 bases or more) says so to an empty batch, before anything is printed: the host route takes it.
   // PAF goes the same way: the merged CIGARs are fused and printed as cg:Z on the device (a tracepoint index is refused there as on the host).
-  const auto device_entry = fmt == "bed" ? impg_gpu_query_batch_bed_fd : fmt == "bedpe" ? impg_gpu_query_batch_bedpe_fd : impg_gpu_query_batch_paf_fd;
+  // FASTA: the records are written on the device from the sequences in HBM (range names play no part in them).
+  const int rc_flag = reverse_complement ? 1 : 0;
+  typedef std::function<int(impg_gpu_index_t *, const impg_gpu_range_t *, size_t, const impg_gpu_params_t *, const uint8_t *, int32_t, const char *const *, int,
+                            uint64_t *, double *)> TextEntry;
+  const TextEntry device_entry =
+      fmt == "bed" ? TextEntry(impg_gpu_query_batch_bed_fd) : fmt == "bedpe" ? TextEntry(impg_gpu_query_batch_bedpe_fd) : fmt == "paf" ? TextEntry(impg_gpu_query_batch_paf_fd)
+      : TextEntry([rc_flag](impg_gpu_index_t *x, const impg_gpu_range_t *r, size_t n, const impg_gpu_params_t *pp, const uint8_t *k, int32_t d,
+                            const char *const *nm, int fd, uint64_t *w, double *s3) { return impg_gpu_query_batch_fasta_fd(x, r, n, pp, k, d, nm, rc_flag, fd, w, s3); });
   const bool device_route = !host_merge && (fmt == "bed" || device_entry(ix, nullptr, 0, &p, nullptr, merge_distance, nullptr, fileno(stdout), nullptr, nullptr) == IMPG_OK);
   if (device_route) {
     uint64_t len = 0;
@@ -646,6 +684,7 @@ int main(int argc, char **argv) {
   char *text = nullptr;
   size_t len = 0;
   const int rc = fmt == "bed" ? impg_gpu_results_bed(res, ix, names.data(), &p, merge_distance, &text, &len)
+                 : fmt == "fasta" ? impg_gpu_results_fasta(res, ix, &p, merge_distance, rc_flag, &text, &len)
                               : impg_gpu_results_paf(res, ix, names.data(), &p, merge_distance,
                                                      fmt == "paf" ? IMPG_OUT_PAF : IMPG_OUT_BEDPE, &text, &len);
   if (rc != IMPG_OK) die(impg_gpu_last_error());

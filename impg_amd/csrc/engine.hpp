@@ -344,7 +344,7 @@ bool run_chunk_rows(const impg_gpu_index &ix, Engine &E, const impg_gpu_range_t 
                     size_t e, const impg_gpu_params_t &p, impg_gpu_results &part, std::mutex *gpu_turn = nullptr,
                     uint64_t max_rows = ~0ull, hipEvent_t kernels_done = nullptr,
                     const std::function<void()> &on_kernels_done = nullptr);
-enum TextFormat { TEXT_BED = 0, TEXT_BEDPE = 1, TEXT_PAF = 2 };  // what the device text routes print
+enum TextFormat { TEXT_BED = 0, TEXT_BEDPE = 1, TEXT_PAF = 2, TEXT_FASTA = 3, TEXT_FASTA_RC = 4 };  // what the device text routes print (_RC: --reverse-complement)
 // Its sibling for BED: the run, both merges and the text on the device (bed_device.hip); the three stages' seconds are
 // added to seconds3.  gpu_turn is held through the text.  false: an empty chunk, as above (no time is added).
 bool run_chunk_bed(const impg_gpu_index &ix, Engine &E, const impg_gpu_range_t *d_ranges, const impg_gpu_range_t *h_ranges,
@@ -420,6 +420,17 @@ struct BedGapRows { std::vector<uint32_t> range; std::vector<impg_gpu_interval_t
 void device_bed_selftest(Engine &E, const impg_gpu_index &ix, const impg_gpu_interval_t *rows, const uint32_t *row_range, uint32_t n,
                          uint32_t n_ranges, uint64_t n_seq, int32_t merge_distance, bool merge_strands, bool original_coords,
                          const std::vector<std::string> &rnames, std::vector<impg_gpu_bed_row_t> &merged, std::string &text, BedGapRows *gap);
+// ---- FASTA on the device (fasta_device.hip): the sweep alone (bed_device.hip), then records of bases ----
+uint32_t device_fasta_rows(Engine &E, const impg_gpu_index &ix, uint32_t n_ranges, const impg_gpu_params_t &p, int32_t merge_distance,
+                           std::vector<std::unique_ptr<LevelBufs>> &levels, DevBuf &self_dev, DevBuf &out, uint32_t &rows_in);
+uint32_t device_fasta_selftest_rows(Engine &E, const impg_gpu_index &ix, const impg_gpu_interval_t *rows, const uint32_t *row_range, uint32_t n,
+                                    uint32_t n_ranges, int32_t merge_distance, DevBuf &out);
+// the merged rows (BedRow, text_device.hpp) as FASTA records; refusals (no store, a sequence the store lacks, a row that leaves
+// its sequence) are raised before any text is delivered.  Counts into the handle's fasta_* counters.
+void device_fasta_text(Engine &E, const impg_gpu_index &ix, const DevBuf &rows, uint32_t n_rows, bool reverse_complement,
+                       const std::function<void(const char *, size_t)> &sink);
+// the store's bases in HBM for the handle's ids (impg_gpu_index_set_sequences); the handle's seq_store is set
+void upload_sequences(impg_gpu_index &ix);
 // the names BED rows print for ranges [b, e): the caller's, else "{chrom}:{start}-{end}" (partition.rs:1741, :1762)
 std::vector<std::string> bed_range_names(const impg_gpu_index &ix, const impg_gpu_range_t *ranges, const char *const *range_names,
                                          size_t b, size_t e);

@@ -1,0 +1,319 @@
+// FASTA records on the device (output_results_fasta, main.rs:12351-12415): the merged rows of the query-axis sweep
+// (bed_device.hip, strands apart, no gap_2d) printed as ">{name}:{start}-{end}[/rc]\n" and their bases in lines of 80, from a
+// sequence store that lives in HBM (one byte per base).  sequences.cpp holds the host side of the same text.
+//
+//   store     SEQ_PAD zero bytes, the present sequences back to back in id order, padding behind them; off[id] = the place
+//             of the sequence's first base, SEQ_NOT_IN_HBM where the store lacks it.  The padding lets the writer's aligned
+//             16-byte loads read past either end of a sequence.
+//   lengths   one thread per record: header + body, body = L + ceil(L / 80) bytes (a single '\n' for L = 0); the same thread
+//             marks the first record whose sequence the store lacks, or whose row leaves its sequence -- refused before any
+//             text is written.
+//   text      a record is megabytes of bases, not forty bytes of fields: the write kernel's grid covers the piece's BYTES,
+//             each lane 16 consecutive ones, aligned in the piece buffer.  A lane finds its record in the piece's offsets
+//             (one search for the wave's first byte and one for its last; a search of its own only when those differ).  A
+//             lane whose 16 bytes lie inside one body, short of its last byte, holds at most one line break: the bases
+//             before and behind it are one contiguous run of the source, read with two aligned 16-byte loads and shifted
+//             into place (read backwards and complemented for "/rc"), the '\n' spliced in, one 16-byte store.  Every other
+//             lane -- headers, a record's last bytes, records a few bytes long -- computes its bytes one at a time.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdio>
+#include <functional>
+#include <string>
+
+#include "device_prims.hpp"
+#include "engine.hpp"
+#include "text_device.hpp"
+
+namespace impg {
+
+namespace {
+
+using prims::cdiv;
+typedef unsigned long long u64;
+typedef unsigned __int128 u128;
+
+struct FastaStore {
+  const unsigned char *bases;  // 16-byte aligned
+  const u64 *off;              // [n_ids]
+  const uint32_t *len;         // [n_ids] the index's sequence lengths
+  uint32_t n_ids;
+};
+constexpr uint32_t FASTA_OK = 0xFFFFFFFFu;  // no record to refuse
+
+__device__ __forceinline__ uint32_t fasta_header_len(const TextTables &t, const BedRow &x, bool flip) {
+  return 1u + seq_text_len(t, x.query_id) + 1u + dec_digits((uint32_t)x.start) + 1u + dec_digits((uint32_t)x.end) + (flip ? 3u : 0u) + 1u;
+}
+__device__ __forceinline__ uint32_t fasta_body_len(uint32_t L) { return L ? L + (L + 79u) / 80u : 1u; }
+
+// bad[0] / bad[1]: the first record on a sequence the store lacks / that leaves its sequence
+__global__ __launch_bounds__(256) void fasta_len_kernel(const BedRow *__restrict__ rows, uint32_t n, TextTables t, FastaStore st, int reverse_complement,
+                                                        uint32_t *__restrict__ len, uint32_t *__restrict__ bad) {
+  const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+  if (r >= n) return;
+  const BedRow x = rows[r];
+  const bool present = x.query_id < st.n_ids && st.off[x.query_id] != SEQ_NOT_IN_HBM;
+  if (!present) atomicMin(&bad[0], r);
+  else if (x.start < 0 || x.end < x.start || (uint32_t)x.end > st.len[x.query_id]) atomicMin(&bad[1], r);
+  const bool flip = reverse_complement && (x.q_strand >> 31);
+  const uint32_t L = x.end >= x.start ? (uint32_t)(x.end - x.start) : 0u;
+  len[r] = fasta_header_len(t, x, flip) + fasta_body_len(L);
+}
+
+// digit `pos` (0 = the leading one) of v, which prints with `digits` digits
+__device__ __forceinline__ char dec_char(uint32_t v, uint32_t digits, uint32_t pos) {
+  for (uint32_t k = digits - 1u - pos; k > 0; k--) v /= 10u;
+  return (char)('0' + v % 10u);
+}
+__device__ __forceinline__ unsigned char base_complement(unsigned char c) {  // graph.rs:814-828
+  return c == 'A' ? 'T' : c == 'T' ? 'A' : c == 'C' ? 'G' : c == 'G' ? 'C' : c;
+}
+// byte x of a record: its header, then its body
+__device__ unsigned char fasta_byte(const TextTables &t, const FastaStore &st, const BedRow &row, bool flip, uint32_t hl, u64 rec_len, u64 x) {
+  if (x >= hl) {
+    const u64 j = x - hl;
+    if (j + 1 == rec_len - hl || j % 81u == 80u) return '\n';
+    const u64 idx = j - j / 81u;
+    const u64 so = st.off[row.query_id];
+    const unsigned char c = st.bases[flip ? so + (u64)row.end - 1u - idx : so + (u64)row.start + idx];
+    return flip ? base_complement(c) : c;
+  }
+  uint32_t h = (uint32_t)x;
+  if (h == 0) return '>';
+  h -= 1u;
+  const uint32_t nl = seq_text_len(t, row.query_id);
+  if (h < nl) return row.query_id < t.n_names ? (unsigned char)t.names[t.name_off[row.query_id] + h] : (unsigned char)dec_char(row.query_id, nl, h);
+  h -= nl;
+  if (h == 0) return ':';
+  h -= 1u;
+  const uint32_t d1 = dec_digits((uint32_t)row.start), d2 = dec_digits((uint32_t)row.end);
+  if (h < d1) return (unsigned char)dec_char((uint32_t)row.start, d1, h);
+  h -= d1;
+  if (h == 0) return '-';
+  h -= 1u;
+  if (h < d2) return (unsigned char)dec_char((uint32_t)row.end, d2, h);
+  h -= d2;
+  if (flip && h < 3u) return h == 0 ? '/' : h == 1 ? 'r' : 'c';
+  return '\n';
+}
+// the record that holds byte g (absolute): the last r in [lo, hi) with off[r] <= g; off[lo] <= g
+__device__ __forceinline__ uint32_t fasta_find(const u64 *__restrict__ off, uint32_t lo, uint32_t hi, u64 g) {
+  while (hi - lo > 1u) {
+    const uint32_t mid = lo + (hi - lo) / 2u;
+    if (off[mid] <= g) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+__device__ __forceinline__ u128 load16(const unsigned char *p) {  // p 16-byte aligned
+  const uint4 v = *reinterpret_cast<const uint4 *>(p);
+  return ((u128)(((u64)v.w << 32) | v.z) << 64) | (((u64)v.y << 32) | v.x);
+}
+// the 16 bytes at p, of any alignment: two aligned loads (the store's padding covers what they read beyond a sequence)
+__device__ __forceinline__ u128 load16_any(const unsigned char *base, u64 at) {
+  const u64 a0 = at & ~15ull;
+  const unsigned sh = (unsigned)(at & 15ull) * 8u;
+  const u128 lo = load16(base + a0), hi = load16(base + a0 + 16u);
+  return sh ? (lo >> sh) | (hi << (128u - sh)) : lo;
+}
+
+// records [0, n_rec) of a piece: record r at out + (off[r] - base), the piece n_bytes long.  One lane per 16 bytes.
+__global__ __launch_bounds__(256) void fasta_write_kernel(const BedRow *__restrict__ rows, uint32_t n_rec, TextTables t, FastaStore st,
+                                                          int reverse_complement, const u64 *__restrict__ off, u64 base, u64 n_bytes,
+                                                          char *__restrict__ out) {
+  const u64 lane = (u64)blockIdx.x * 256u + threadIdx.x;
+  const u64 p = lane * 16u;
+  // the wave's first and last byte: if one record holds both, it holds every lane's
+  const u64 w0 = (lane & ~63ull) * 16u;
+  if (w0 >= n_bytes) return;
+  const u64 w1 = min(w0 + 64u * 16u, n_bytes) - 1u;
+  const uint32_t rf = fasta_find(off, 0u, n_rec, base + w0);
+  const uint32_t rl = fasta_find(off, rf, n_rec, base + w1);
+  if (p >= n_bytes) return;
+  uint32_t r = rf == rl ? rf : fasta_find(off, rf, rl + 1u, base + p);
+  BedRow row = rows[r];
+  bool flip = reverse_complement && (row.q_strand >> 31);
+  uint32_t hl = fasta_header_len(t, row, flip);
+  u64 rec_at = off[r] - base;                                              // the record's first byte in the piece
+  u64 rec_len = (r + 1u < n_rec ? off[r + 1u] - base : n_bytes) - rec_at;
+  const u64 x0 = p - rec_at;
+  if (x0 >= hl && x0 + 16u < rec_len) {
+    // 16 bytes of one body, its last byte not among them: at most one line break, at k (16: none)
+    const u64 j0 = x0 - hl;
+    const u64 line0 = j0 / 81u;
+    const unsigned col0 = (unsigned)(j0 - line0 * 81u);
+    const unsigned k = 80u - col0 < 16u ? 80u - col0 : 16u;
+    const u64 s0 = j0 - line0;  // the base index of byte 0 (of byte 1 where byte 0 is the break)
+    const u64 so = st.off[row.query_id];
+    u128 S;
+    if (!flip) S = load16_any(st.bases, so + (u64)row.start + s0);
+    else {
+      // bytes hi, hi - 1, ...: read the 16 bytes that end at hi, turn them round, complement each
+      const u128 F = load16_any(st.bases, so + (u64)row.end - 1u - s0 - 15u);
+      const u64 f_lo = (u64)F, f_hi = (u64)(F >> 64);
+      u64 r_lo = __builtin_bswap64(f_hi), r_hi = __builtin_bswap64(f_lo);
+      u64 c_lo = 0, c_hi = 0;
+#pragma unroll
+      for (unsigned i = 0; i < 8u; i++) {
+        c_lo |= (u64)base_complement((unsigned char)(r_lo >> (8u * i))) << (8u * i);
+        c_hi |= (u64)base_complement((unsigned char)(r_hi >> (8u * i))) << (8u * i);
+      }
+      S = ((u128)c_hi << 64) | c_lo;
+    }
+    if (k < 16u) {
+      const unsigned kb = k * 8u;
+      const u128 below = kb ? S & (((u128)1 << kb) - 1u) : (u128)0;
+      const u128 above = k < 15u ? (S >> kb) << (kb + 8u) : (u128)0;
+      S = below | ((u128)'\n' << kb) | above;
+    }
+    const u64 s_lo = (u64)S, s_hi = (u64)(S >> 64);
+    *reinterpret_cast<uint4 *>(out + p) = make_uint4((uint32_t)s_lo, (uint32_t)(s_lo >> 32), (uint32_t)s_hi, (uint32_t)(s_hi >> 32));
+    return;
+  }
+  // headers, a record's last bytes, several records in one lane: byte by byte
+  uint32_t w[4] = {0u, 0u, 0u, 0u};
+  const unsigned n_own = (unsigned)min((u64)16u, n_bytes - p);
+#pragma unroll
+  for (unsigned i = 0; i < 16u; i++) {
+    if (i < n_own) {
+      const u64 g = p + i;
+      while (g >= rec_at + rec_len) {  // (a record is never empty: its header alone is 6 bytes)
+        r++;
+        row = rows[r];
+        flip = reverse_complement && (row.q_strand >> 31);
+        hl = fasta_header_len(t, row, flip);
+        rec_at += rec_len;
+        rec_len = (r + 1u < n_rec ? off[r + 1u] - base : n_bytes) - rec_at;
+      }
+      w[i >> 2] |= (uint32_t)fasta_byte(t, st, row, flip, hl, rec_len, g - rec_at) << (8u * (i & 3u));
+    }
+  }
+  if (n_own == 16u) *reinterpret_cast<uint4 *>(out + p) = make_uint4(w[0], w[1], w[2], w[3]);
+  else {
+    // the piece's last lane: the buffer is not promised to reach 16 bytes beyond the text
+#pragma unroll
+    for (unsigned i = 0; i < 16u; i++)
+      if (i < n_own) out[p + i] = (char)(w[i >> 2] >> (8u * (i & 3u)));
+  }
+}
+
+// IMPG_FASTA_PIECE_TIMING=<file> (a probe's switch, read on every call): every piece's write kernel between two events, and
+// a second copy of the same piece into a pinned buffer of the probe's own between two more, so that the kernel can be held
+// against the copy it is meant to hide behind.  "bytes kernel_ms copy_ms" per piece is appended to the file.
+struct PieceTiming {
+  const char *path = getenv("IMPG_FASTA_PIECE_TIMING");
+  std::vector<hipEvent_t> ev;  // four per piece
+  std::vector<u64> bytes;
+  char *pin = nullptr;
+  size_t pin_cap = 0;
+  bool on() const { return path && *path; }
+  hipEvent_t mark(hipStream_t s) {
+    hipEvent_t e;
+    IMPG_HIP(hipEventCreate(&e));
+    ev.push_back(e);
+    IMPG_HIP(hipEventRecord(e, s));
+    return e;
+  }
+  void copy(const char *src, u64 n, hipStream_t s) {
+    if (n > pin_cap) {
+      if (pin) { IMPG_HIP(hipStreamSynchronize(s)); (void)hipHostFree(pin); pin = nullptr; }
+      IMPG_HIP(hipHostMalloc((void **)&pin, (size_t)n, hipHostMallocDefault));
+      pin_cap = (size_t)n;
+    }
+    mark(s);
+    IMPG_HIP(hipMemcpyAsync(pin, src, (size_t)n, hipMemcpyDeviceToHost, s));
+    mark(s);
+    bytes.push_back(n);
+  }
+  void report() {  // (the stream is idle)
+    FILE *f = fopen(path, "a");
+    for (size_t k = 0; f && k < bytes.size(); k++) {
+      float kernel_ms = 0, copy_ms = 0;
+      if (hipEventElapsedTime(&kernel_ms, ev[4 * k], ev[4 * k + 1]) != hipSuccess || hipEventElapsedTime(&copy_ms, ev[4 * k + 2], ev[4 * k + 3]) != hipSuccess) break;
+      fprintf(f, "%llu %.6f %.6f\n", bytes[k], (double)kernel_ms, (double)copy_ms);
+    }
+    if (f) fclose(f);
+  }
+  ~PieceTiming() {
+    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+    if (pin) (void)hipHostFree(pin);
+  }
+};
+
+}  // namespace
+
+// The store's bases in HBM, in the handle's id order (impg_gpu_index_set_sequences; the device is current)
+void upload_sequences(impg_gpu_index &ix) {
+  const SeqStore &st = *ix.seq_store;
+  const size_t n_ids = ix.store_of_id.size();
+  std::vector<u64> off(std::max<size_t>(n_ids, 1), SEQ_NOT_IN_HBM);
+  u64 at = SEQ_PAD;
+  for (size_t id = 0; id < n_ids; id++) {
+    const uint32_t s = ix.store_of_id[id];
+    if (s == SEQ_ABSENT) continue;
+    off[id] = at;
+    at += st.off[s + 1] - st.off[s];
+  }
+  const size_t bytes = (size_t)((at + 15u) & ~15ull) + 64;  // (an aligned load that starts at the last base reads 32 bytes from there)
+  ix.d_seq_bases.reserve(bytes);
+  ix.d_seq_off.reserve(off.size() * 8);
+  IMPG_HIP(hipMemset(ix.d_seq_bases.p, 0, bytes));
+  for (size_t id = 0; id < n_ids; id++) {
+    const uint32_t s = ix.store_of_id[id];
+    if (s == SEQ_ABSENT || st.off[s + 1] == st.off[s]) continue;
+    IMPG_HIP(hipMemcpy(ix.d_seq_bases.as<char>() + off[id], st.bases.data() + st.off[s], (size_t)(st.off[s + 1] - st.off[s]), hipMemcpyHostToDevice));
+  }
+  IMPG_HIP(hipMemcpy(ix.d_seq_off.p, off.data(), off.size() * 8, hipMemcpyHostToDevice));
+  ix.fasta_stats[FASTA_STORE_BYTES] = bytes;
+}
+
+void device_fasta_text(Engine &E, const impg_gpu_index &ix, const DevBuf &rows, uint32_t n_rows, bool reverse_complement,
+                       const std::function<void(const char *, size_t)> &sink) {
+  if (!ix.seq_store) throw Error{IMPG_E_INVALID, "FASTA output needs a sequence store (impg_gpu_index_set_sequences)"};
+  if (!n_rows) return;
+  hipStream_t s = E.stream;
+  // (no range names, and the names as the index has them: --original-sequence-coordinates does not touch FASTA)
+  TextTableBufs tb(E, ix, 0, std::vector<std::string>(), false, /*with_lengths=*/true);
+  const TextTables t = tb.t;
+  const FastaStore st{ix.d_seq_bases.as<unsigned char>(), ix.d_seq_off.as<u64>(), t.seq_len, std::min<uint32_t>((uint32_t)ix.store_of_id.size(), t.n_lens)};
+  const int rc = reverse_complement ? 1 : 0;
+  DevBuf len, bad;
+  len.reserve((size_t)n_rows * 4);
+  bad.reserve(256);
+  IMPG_HIP(hipMemsetAsync(bad.p, 0xFF, 8, s));
+  fasta_len_kernel<<<cdiv(n_rows, 256), 256, 0, s>>>(rows.as<BedRow>(), n_rows, t, st, rc, len.as<uint32_t>(), bad.as<uint32_t>());
+  uint32_t h_bad[2];
+  std::vector<uint32_t> h_len(n_rows);
+  IMPG_HIP(hipMemcpyAsync(h_bad, bad.p, 8, hipMemcpyDeviceToHost, s));
+  IMPG_HIP(hipMemcpyAsync(h_len.data(), len.p, (size_t)n_rows * 4, hipMemcpyDeviceToHost, s));
+  IMPG_HIP(hipStreamSynchronize(s));
+  if (h_bad[0] != FASTA_OK || h_bad[1] != FASTA_OK) {
+    const bool lacks = h_bad[0] != FASTA_OK;
+    BedRow x;
+    IMPG_HIP(hipMemcpy(&x, rows.as<BedRow>() + h_bad[lacks ? 0 : 1], sizeof x, hipMemcpyDeviceToHost));
+    const std::string name = x.query_id < ix.seq.names.size() ? ix.seq.names[x.query_id] : std::to_string(x.query_id);
+    if (lacks) throw Error{IMPG_E_INVALID, "Sequence '" + name + "' not found in the sequence store"};
+    throw Error{IMPG_E_INVALID, "row " + name + ":" + std::to_string(x.start) + "-" + std::to_string(x.end) + " leaves its sequence of " +
+                                    std::to_string(x.query_id < ix.seq.lens.size() ? ix.seq.lens[x.query_id] : 0) + " bases"};
+  }
+  // the pieces' sizes, which the byte-centric grid needs: the records' offsets on the host
+  std::vector<u64> h_off((size_t)n_rows + 1, 0);
+  for (uint32_t r = 0; r < n_rows; r++) h_off[r + 1] = h_off[r] + h_len[r];
+  PieceTiming timing;
+  device_text_pieces(E, len.as<uint32_t>(), n_rows, "FASTA",
+                     [&](uint32_t r0, uint32_t r1, const unsigned long long *off, unsigned long long base, char *out) {
+                       const u64 n_bytes = h_off[r1] - h_off[r0];
+                       if (timing.on()) {
+                         timing.mark(s);
+                         fasta_write_kernel<<<cdiv(n_bytes, 16u * 256u), 256, 0, s>>>(rows.as<BedRow>() + r0, r1 - r0, t, st, rc, off, base, n_bytes, out);
+                         timing.mark(s);
+                         timing.copy(out, n_bytes, s);
+                         return;
+                       }
+                       fasta_write_kernel<<<cdiv(n_bytes, 16u * 256u), 256, 0, s>>>(rows.as<BedRow>() + r0, r1 - r0, t, st, rc, off, base, n_bytes, out);
+                     },
+                     sink, ix.fasta_stats[FASTA_TEXT_PIECES], ix.fasta_stats[FASTA_TEXT_BYTES]);
+  if (timing.on()) timing.report();
+}
+
+}  // namespace impg

@@ -391,6 +391,27 @@ enum BedpeStat { BEDPE_ROWS, BEDPE_RUNS, BEDPE_JOINS_CONTIGUOUS, BEDPE_JOINS_GAP
 // impg_gpu_index::paf_stats (paf_device.inc)
 enum PafStat { PAF_ROWS, PAF_RUNS, PAF_JOINS_CONTIGUOUS, PAF_JOINS_GAP, PAF_OPS_READ, PAF_OPS_PRINTED, PAF_THROUGH_ROWS, PAF_TEXT_PIECES, PAF_TEXT_BYTES };
 size_t bed_merge(impg_gpu_interval_t *iv, size_t n, int32_t merge_distance, bool merge_strands);
+// merge_query_adjusted_intervals alone (bed.cpp): what FASTA output runs on a range's rows (main.rs:12362)
+void query_axis_merge(std::vector<impg_gpu_interval_t> &rows, int32_t merge_distance, bool merge_strands);
+
+// ---- sequences (sequences.cpp): the bases FASTA output prints ---------------------------------------------------------
+// impg_gpu_index::fasta_stats (fasta_device.hip)
+enum FastaStat { FASTA_ROWS, FASTA_RECORDS, FASTA_TEXT_PIECES, FASTA_TEXT_BYTES, FASTA_STORE_BYTES };
+struct SeqStore {  // one byte per base, upper-cased at load, back to back
+  std::vector<std::string> names;
+  std::vector<uint64_t> off;  // [n + 1]
+  std::string bases;
+  std::unordered_map<std::string, uint32_t> by_name;
+  void add(const std::string &name, const char *b, size_t n);  // IMPG_E_INVALID for a name it already holds
+};
+constexpr uint32_t SEQ_ABSENT = 0xFFFFFFFFu;      // impg_gpu_index::store_of_id: the store lacks the sequence
+constexpr uint64_t SEQ_NOT_IN_HBM = ~0ull;        // the device offsets' mark of the same
+constexpr size_t SEQ_PAD = 16;                    // bytes in front of the first base in HBM (and at least as many behind the last)
+// One range's rows -> FASTA records appended to `text` (output_results_fasta, main.rs:12351-12415): the sweep, then per merged
+// row the header and the bases in lines of 80.  fetch(id, name): the sequence's bases in the store, null if it lacks them.
+struct SeqRef { const char *bases; uint64_t len; };
+void fasta_range_text(std::vector<impg_gpu_interval_t> &rows, int32_t merge_distance, bool reverse_complement,
+                      const std::function<bool(uint32_t, std::string &, SeqRef &)> &fetch, std::string &text);
 
 struct Engine;    // engine.hpp
 struct ShardCtx;  // sharded.cpp: this rank's part of an index sharded over GPUs
@@ -468,6 +489,16 @@ struct impg_gpu_index {
   // ... and the last device PAF call (by impg::PafStat; paf_device.inc), kept the same way
   mutable std::atomic<uint64_t> paf_stats[9] = {};
   void paf_stats_reset() const { for (auto &b : paf_stats) b = 0; }
+  // ... and the last device FASTA call (by impg::FastaStat; fasta_device.hip), kept the same way
+  mutable std::atomic<uint64_t> fasta_stats[5] = {};
+  void fasta_stats_reset() const { for (int k = 0; k < impg::FASTA_STORE_BYTES; k++) fasta_stats[k] = 0; }  // (the store's size stays: set when it is attached)
+  // The sequence store attached by impg_gpu_index_set_sequences (null: none): the host copy the host route reads, which
+  // of its sequences every index id is (impg::SEQ_ABSENT: none), and the same bases in HBM for the device route -- SEQ_PAD
+  // zero bytes, the present sequences back to back in id order, padding; d_seq_off[id] = the first base's place, or
+  // impg::SEQ_NOT_IN_HBM.  Attach and detach while no query runs on the handle.
+  std::shared_ptr<const impg::SeqStore> seq_store;
+  std::vector<uint32_t> store_of_id;
+  impg::DevBuf d_seq_bases, d_seq_off;
   impg::ShardCtx *shard = nullptr;    // set: this index is one rank's shard; queries are collective calls
   impg::Cluster *cluster = nullptr;   // set: this handle fronts n_dev shards in this process (no arrays of its own)
   impg_gpu_index();

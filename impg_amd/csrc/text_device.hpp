@@ -54,6 +54,13 @@ __device__ __forceinline__ char *put_range_name(char *p, const TextTables &t, ui
   return p + rl;
 }
 
+// A merged row as the query-axis sweep of bed_device.hip leaves it (BED prints it as a line, FASTA as a record), 16 bytes
+struct BedRow {
+  uint32_t q_strand;  // range index | reverse strand << 31
+  uint32_t query_id;
+  int32_t start, end;  // (printed as u32, like the reference: an inconsistent CIGAR can project below zero)
+};
+
 // The tables of one chunk on the device (uploaded on E.stream; they live as long as this object)
 struct TextTableBufs {
   DevBuf d_nb, d_noff, d_shift, d_rb, d_roff, d_len;

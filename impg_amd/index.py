@@ -88,6 +88,20 @@ class QueryResults:
         finally:
             _lib.free(text)
 
+    def fasta(self, merge_distance=0, params=None, reverse_complement=False, raw=False):
+        """output_results_fasta over every range (main.rs:12351-12415), from the host copy of the store the index
+        has attached (GpuImpg.set_sequences).  raw: the text as bytes."""
+        p = params or make_params()
+        text = C.c_void_p(None)
+        ln = C.c_size_t(0)
+        check(lib().impg_gpu_results_fasta(self._h, self._owner._h, C.byref(p), merge_distance, int(bool(reverse_complement)),
+                                           C.byref(text), C.byref(ln)))
+        try:
+            out = _text_bytes(text, ln.value)
+            return out if raw else out.decode()
+        finally:
+            _lib.free(text)
+
     def paf(self, range_names=None, merge_distance=0, params=None, fmt="paf", raw=False):
         """output_results_paf / output_results_bedpe over every range (main.rs:11894-12103); the batch
         must have been queried with store_cigar = True.  Results of a tracepoint index print as "bedpe" only
@@ -243,6 +257,76 @@ class PreparedMask:
 
 def prepare_mask(masked_regions):
     return PreparedMask(*GpuImpg._mask(masked_regions))
+
+
+class Sequences:
+    """The sequences FASTA output prints (impg_gpu_sequences_t): one byte per base, upper-cased at load."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    @classmethod
+    def from_fasta(cls, paths):
+        """Plain FASTA files (a path or a list of them); gzip input is IMPG_E_UNSUPPORTED, a name twice IMPG_E_INVALID."""
+        if isinstance(paths, (str, bytes, os.PathLike)):
+            paths = [paths]
+        arr = (C.c_char_p * len(paths))(*[os.fsencode(q) for q in paths])
+        h = C.c_void_p(None)
+        check(lib().impg_gpu_sequences_from_fasta(arr, len(paths), C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def from_arrays(cls, names, sequences):
+        """names[i] -> sequences[i] (bytes or str)."""
+        seqs = [q.encode() if isinstance(q, str) else bytes(q) for q in sequences]
+        if len(names) != len(seqs):
+            raise _lib.ImpgGpuError(_lib.IMPG_E_INVALID, "one name per sequence")
+        off = np.zeros(len(seqs) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(q) for q in seqs], dtype=np.uint64)
+        bases = b"".join(seqs)
+        arr = (C.c_char_p * len(names))(*[q.encode() if isinstance(q, str) else q for q in names])
+        h = C.c_void_p(None)
+        check(lib().impg_gpu_sequences_from_memory(arr, off.ctypes.data, bases, len(seqs), C.byref(h)))
+        return cls(h)
+
+    def __len__(self):
+        return lib().impg_gpu_sequences_num(self._h)
+
+    def name(self, i):
+        s = lib().impg_gpu_sequences_name(self._h, i)
+        return None if s is None else s.decode()
+
+    def bases(self, i):
+        n = C.c_uint64(0)
+        q = lib().impg_gpu_sequences_bases(self._h, i, C.byref(n))
+        if q is None and n.value == 0 and i >= len(self):
+            raise IndexError(i)
+        return C.string_at(q, n.value) if n.value else b""
+
+    def items(self):
+        return [(self.name(i), self.bases(i)) for i in range(len(self))]
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            try:
+                lib().impg_gpu_sequences_free(self._h)
+            except Exception:
+                pass
+            self._h = None
+
+
+def fasta_text(sequences, names, rows, merge_distance=0, reverse_complement=False):
+    """impg_gpu_fasta_text (host-only): one range's rows (INTERVAL_DTYPE) -> its FASTA records as bytes: the sweep of
+    merge_query_adjusted_intervals with the strands apart, then the text.  names[id] = the name of sequence id."""
+    a = np.ascontiguousarray(rows, dtype=INTERVAL_DTYPE)
+    arr = (C.c_char_p * max(len(names), 1))(*[q.encode() if isinstance(q, str) else q for q in names])
+    text, ln = C.c_void_p(None), C.c_size_t(0)
+    check(lib().impg_gpu_fasta_text(sequences._h, arr, len(names), a.ctypes.data, a.size, merge_distance, int(bool(reverse_complement)),
+                                    C.byref(text), C.byref(ln)))
+    try:
+        return _text_bytes(text, ln.value)
+    finally:
+        _lib.free(text)
 
 
 class GpuImpg:
@@ -583,6 +667,37 @@ class GpuImpg:
                                           raw, kw)
         return self._query_batch_text_fd(lib().impg_gpu_query_batch_paf_fd, ranges, params, merge_distance, range_names, subset_keep, timing,
                                          fd, kw)
+
+    def set_sequences(self, sequences):
+        """impg_gpu_index_set_sequences: attach a Sequences store (its bases go to HBM), or detach with None."""
+        check(lib().impg_gpu_index_set_sequences(self._h, None if sequences is None else sequences._h))
+
+    def query_batch_fasta(self, ranges, params=None, merge_distance=0, range_names=None, subset_keep=None, timing=False, raw=False,
+                          reverse_complement=False, fd=None, **kw):
+        """impg_gpu_query_batch_fasta: query + the query-axis sweep + the records written on the device from the store in
+        HBM (what `impg query -o fasta` prints).  fd: impg_gpu_query_batch_fasta_fd -- the text is written there and the
+        number of bytes returned in its place."""
+        rc = int(bool(reverse_complement))
+        if fd is None:
+            entry = lambda h, r, n, p, keep, d, names, text, ln, sec: lib().impg_gpu_query_batch_fasta(h, r, n, p, keep, d, names, rc, text, ln, sec)
+            return self._query_batch_text(entry, ranges, params, merge_distance, range_names, subset_keep, timing, raw, kw)
+        entry = lambda h, r, n, p, keep, d, names, f, done, sec: lib().impg_gpu_query_batch_fasta_fd(h, r, n, p, keep, d, names, rc, f, done, sec)
+        return self._query_batch_text_fd(entry, ranges, params, merge_distance, range_names, subset_keep, timing, fd, kw)
+
+    def fasta_rows(self, rows, row_range, n_ranges, merge_distance=0, reverse_complement=False):
+        """impg_gpu_selftest_fasta_rows (diagnostics): the device sweep and FASTA writer of query_batch_fasta on the caller's
+        rows (INTERVAL_DTYPE; row_range[i] = the range of rows[i]).  Returns the text as bytes."""
+        a = np.ascontiguousarray(rows, dtype=INTERVAL_DTYPE)
+        rr = np.ascontiguousarray(row_range, dtype=np.uint32)
+        if a.size != rr.size:
+            raise _lib.ImpgGpuError(_lib.IMPG_E_INVALID, "one range index per row")
+        text, ln = C.c_void_p(None), C.c_size_t(0)
+        check(lib().impg_gpu_selftest_fasta_rows(self._h, a.ctypes.data, rr.ctypes.data, a.size, n_ranges, merge_distance,
+                                                 int(bool(reverse_complement)), C.byref(text), C.byref(ln)))
+        try:
+            return _text_bytes(text, ln.value)
+        finally:
+            _lib.free(text)
 
     def _query_batch_text_fd(self, entry, ranges, params, merge_distance, range_names, subset_keep, timing, fd, kw):
         p = params or make_params(**kw)

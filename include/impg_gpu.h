@@ -303,7 +303,10 @@ const char *impg_gpu_counter_key(size_t i);
  * either arm of merge_adjusted_intervals, "paf_ops_read" = CIGAR ops of those rows, "paf_ops_printed" = ops written into
  * cg:Z (fused ops, and the raw ops of lines made of one row), "paf_through_rows" = rows that print no op of their own (one
  * group of ops that started in a row before them and goes on), "paf_text_pieces" = text pieces sent to the host,
- * "paf_text_bytes" = bytes printed.  Of the build of the index itself (a multi-GPU handle answers with the sum over its
+ * "paf_text_bytes" = bytes printed.  Of the last device FASTA call on the handle (impg_gpu_query_batch_fasta,
+ * impg_gpu_query_batch_fasta_fd, impg_gpu_selftest_fasta_rows; kept the same way): "fasta_rows" = rows entering the sweep,
+ * "fasta_records" = records printed, "fasta_text_pieces" = text pieces sent to the host, "fasta_text_bytes" = bytes printed;
+ * "fasta_store_bytes" = bytes of HBM the attached sequence store takes (0: none attached).  Of the build of the index itself (a multi-GPU handle answers with the sum over its
  * ranks): "build_device" = 1 if the device builder produced it, 0 if the host builder did (IMPG_BUILD_HOST, tracepoints, a
  * loaded .impg file's entry order, a card short of memory for the build, an index loaded from a saved file);
  * "tokenized_device" = 1 if the device tokenised its CIGAR text (impg_gpu_index_create_from_paf on one GPU);
@@ -590,6 +593,58 @@ int impg_gpu_query_batch_paf(impg_gpu_index_t *, const impg_gpu_range_t *ranges,
 int impg_gpu_query_batch_paf_fd(impg_gpu_index_t *, const impg_gpu_range_t *ranges, size_t n, const impg_gpu_params_t *params,
                                 const uint8_t *subset_keep, int32_t merge_distance, const char *const *range_names, int fd,
                                 uint64_t *bytes_written, double *seconds3);
+
+/* ---- FASTA: `impg query -o fasta` (output_results_fasta, main.rs:12351-12415) -------------------------------------
+ * The sequences: plain FASTA files (the name runs to the first whitespace of the '>' line; body lines of any length; '\r'
+ * dropped; bytes upper-cased at load; an empty sequence and a last line without a newline are accepted), or arrays of the
+ * caller's (names[n], off[n + 1] into bases; upper-cased too).  One byte per base, so IUPAC codes and N stay exact.
+ * IMPG_E_UNSUPPORTED for a file that starts with the gzip magic 1f 8b (no codec here: decompress first); IMPG_E_INVALID,
+ * naming it, for a name that occurs twice, in one file or across files (the reference lets the last file win);
+ * IMPG_E_IO for a file that cannot be read.  Host-only.  _name / _bases: sequence i as the store holds it (NULL past the
+ * last; the bases are not NUL-terminated, *len = their number). */
+typedef struct impg_gpu_sequences impg_gpu_sequences_t;
+int impg_gpu_sequences_from_fasta(const char *const *paths, size_t n_paths, impg_gpu_sequences_t **out);
+int impg_gpu_sequences_from_memory(const char *const *names, const uint64_t *off, const char *bases, size_t n, impg_gpu_sequences_t **out);
+size_t impg_gpu_sequences_num(const impg_gpu_sequences_t *);
+const char *impg_gpu_sequences_name(const impg_gpu_sequences_t *, size_t i);
+const char *impg_gpu_sequences_bases(const impg_gpu_sequences_t *, size_t i, uint64_t *len);
+void impg_gpu_sequences_free(impg_gpu_sequences_t *);
+/* Attaches the store to an index handle: its sequences are matched to the index's by name and their bases uploaded to the
+ * handle's device (back to back, one byte per base, padded by 16 bytes or more at both ends; a 64-bit offset per index id,
+ * all ones where the store lacks the sequence).  Index sequences the store lacks, and store sequences the index lacks, are
+ * tolerated; a sequence whose length differs from impg_gpu_seq_len is IMPG_E_INVALID, naming it.  The handle shares the
+ * store's host copy (the host route reads it): the caller may free its own handle at once.  seqs == NULL detaches.  A
+ * tracepoint index (it has no names) and a sharded handle: IMPG_E_UNSUPPORTED.  Not to be called while a query runs. */
+int impg_gpu_index_set_sequences(impg_gpu_index_t *, const impg_gpu_sequences_t *seqs);
+/* perform_query + output_results_fasta for a whole batch, the sweep (merge_query_adjusted_intervals alone, strands kept
+ * apart: main.rs:12362, :4395-4409) and the records written ON THE DEVICE (fasta_device.hip) from the store in HBM: per merged
+ * row ">{name}:{start}-{end}" ("/rc" appended and the bases reverse-complemented -- A/T/C/G/N, other bytes as they are -- on
+ * a reverse-strand row under reverse_complement), then the bases in lines of 80; a zero-length row prints its header and an
+ * empty line.  Arguments as impg_gpu_query_batch_bed plus reverse_complement; range_names is accepted and unused;
+ * params->store_cigar is taken as 0 and original_sequence_coordinates does not touch the text; seconds3 = {engine, rows +
+ * merge, text}.  The text crosses PCIe as BED's does (option "bed_text_piece_bytes"): a record longer than a piece is
+ * IMPG_E_UNSUPPORTED.  Raised before any text of the chunk that holds it is delivered: IMPG_E_INVALID, naming the sequence,
+ * for a merged row on a sequence the store lacks (the reference fails with NotFound) or a row that leaves its sequence;
+ * before anything runs: IMPG_E_INVALID without a store, IMPG_E_UNSUPPORTED for a sharded or multi-GPU handle. */
+int impg_gpu_query_batch_fasta(impg_gpu_index_t *, const impg_gpu_range_t *ranges, size_t n, const impg_gpu_params_t *params,
+                               const uint8_t *subset_keep, int32_t merge_distance, const char *const *range_names, int reverse_complement,
+                               char **text, size_t *len, double *seconds3);
+int impg_gpu_query_batch_fasta_fd(impg_gpu_index_t *, const impg_gpu_range_t *ranges, size_t n, const impg_gpu_params_t *params,
+                                  const uint8_t *subset_keep, int32_t merge_distance, const char *const *range_names, int reverse_complement,
+                                  int fd, uint64_t *bytes_written, double *seconds3);
+/* The host twin: the same text from the rows of impg_gpu_query_batch[_filtered] (store_cigar = 0) and the handle's host copy
+ * of the store, with the min_output_length retain of impg_gpu_results_bed.  *text is malloc'ed; free() it. */
+int impg_gpu_results_fasta(const impg_gpu_results_t *, const impg_gpu_index_t *, const impg_gpu_params_t *params, int32_t merge_distance,
+                           int reverse_complement, char **text, size_t *len);
+/* One range's rows -> its records, host-only (no handle, no GPU call): the sweep, then the text.  names_of_ids[n_ids]: the
+ * name of every sequence id the rows use.  Errors as above.  *text is malloc'ed; free() it. */
+int impg_gpu_fasta_text(const impg_gpu_sequences_t *seqs, const char *const *names_of_ids, size_t n_ids, const impg_gpu_interval_t *rows, size_t n,
+                        int32_t merge_distance, int reverse_complement, char **text, size_t *len);
+/* Diagnostics: the device sweep and writer of impg_gpu_query_batch_fasta on rows the caller brings (row_range[i] = the range
+ * of rows[i], below n_ranges; ids below the index's number of sequences), without a query in front.  Errors as
+ * impg_gpu_query_batch_fasta.  *text is malloc'ed; free() it.  Sets the "fasta_*" counters. */
+int impg_gpu_selftest_fasta_rows(impg_gpu_index_t *ix, const impg_gpu_interval_t *rows, const uint32_t *row_range, size_t n_rows, uint32_t n_ranges,
+                                 int32_t merge_distance, int reverse_complement, char **text, size_t *len);
 
 /* ---- host-side ingest helpers (paf.rs, partition.rs parsers) -------------- */
 /* parse_cigar_to_delta (impg.rs:2935-2950): returns #ops or <0 */
