@@ -258,6 +258,7 @@ SYMBOLS = [
     ("impg_gpu_sequences_num", C.c_size_t, [_P]),
     ("impg_gpu_sequences_name", C.c_char_p, [_P, C.c_size_t]),
     ("impg_gpu_sequences_bases", _P, [_P, C.c_size_t, C.POINTER(C.c_uint64)]),
+    ("impg_gpu_sequences_exceptions", C.c_int, [_P, C.c_size_t, _P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("impg_gpu_sequences_free", None, [_P]),
     ("impg_gpu_index_set_sequences", C.c_int, [_P, _P]),
     ("impg_gpu_query_batch_fasta", C.c_int, [_P, _P, C.c_size_t, C.POINTER(Params), _P, C.c_int32, _P, C.c_int, C.POINTER(_P),

@@ -706,7 +706,8 @@ static const CounterRow COUNTER_TABLE[] = {
     CTR("paf_text_bytes", paf_stats[PAF_TEXT_BYTES]),
     CTR("fasta_rows", fasta_stats[FASTA_ROWS]), CTR("fasta_records", fasta_stats[FASTA_RECORDS]),
     CTR("fasta_text_pieces", fasta_stats[FASTA_TEXT_PIECES]), CTR("fasta_text_bytes", fasta_stats[FASTA_TEXT_BYTES]),
-    CTR("fasta_store_bytes", fasta_stats[FASTA_STORE_BYTES]),
+    CTR("fasta_store_bytes", fasta_stats[FASTA_STORE_BYTES]), CTR("fasta_store_packed", fasta_stats[FASTA_STORE_PACKED]),
+    CTR("fasta_store_exception_runs", fasta_stats[FASTA_STORE_EXCEPTION_RUNS]),
     CTR_RANKS("build_device", build_stats[BUILD_DEVICE]), CTR_RANKS("tokenized_device", build_stats[BUILD_TOKENIZED_DEVICE]),
     CTR_RANKS("build_batches", build_stats[BUILD_BATCHES]),
 };

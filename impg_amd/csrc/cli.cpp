@@ -98,8 +98,8 @@ void usage() {
           "               [--transitive-dfs] [--multi-impg] [--min-transitive-len N] [--min-distance-between-ranges N]\n"
           "               [-l N] [--min-result-identity F] [--subset-sequence-list FILE] [--original-sequence-coordinates]\n"
           "               [--consider-strandness] [-o auto|bed|bedpe|paf|fasta] [--sequence-files F... | --sequence-list FILE]\n"
-          "               [--reverse-complement] [--host-merge] [--unidirectional] [--order coitrees|sorted]\n"
-          "               [--device N]\n"
+          "               [--reverse-complement] [--sequence-store bytes|packed|auto] [--host-merge] [--unidirectional]\n"
+          "               [--order coitrees|sorted] [--device N]\n"
           "impg-gpu partition (-a <paf>... | -i <file>) -w <bp> -d <bp> [--min-missing-size N] [--min-boundary-distance N]\n"
           "               [--selection-mode longest|total|sample[,sep]|haplotype[,sep]] [--starting-sequences-file FILE]\n"
           "               [--separate-files] [--no-rehome-singletons] [--output-folder DIR] [-o bed] [--host-state] [-m N]\n"
@@ -487,6 +487,7 @@ int main(int argc, char **argv) {
   std::vector<std::string> seq_files;  // --sequence-files / --sequence-list (main.rs:4116-4121): what -o fasta prints from
   std::string seq_list;
   bool reverse_complement = false;
+  int sequence_store = 0;
   for (int i = 2; i < argc; i++) {
     std::string a = argv[i];
     auto need = [&](const char *f) -> const char * {
@@ -517,6 +518,11 @@ int main(int argc, char **argv) {
       while (i + 1 < argc && argv[i + 1][0] != '-') seq_files.push_back(argv[++i]);
     } else if (a == "--sequence-list") seq_list = need(a.c_str());
     else if (a == "--reverse-complement") reverse_complement = true;
+    else if (a == "--sequence-store") {  // the form the sequences take in HBM (option "sequence_store_packed"); --host-merge prints from the host copy
+      const std::string v = need(a.c_str());
+      if (v != "bytes" && v != "packed" && v != "auto") die("invalid value '" + v + "' for '--sequence-store'", 2);
+      sequence_store = v == "bytes" ? 0 : v == "packed" ? 1 : 2;
+    }
     else if (a == "--subset-sequence-list") subset_list = need(a.c_str());
     else if (a == "--original-sequence-coordinates") original_coords = true;
     else if (a == "-o" || a == "--output-format") ofmt = need("-o");
@@ -598,6 +604,7 @@ int main(int argc, char **argv) {
     for (auto &f : seq_files) sp.push_back(f.c_str());
     impg_gpu_sequences_t *seqs = nullptr;
     if (impg_gpu_sequences_from_fasta(sp.data(), sp.size(), &seqs) != IMPG_OK) die(impg_gpu_last_error());
+    if (impg_gpu_set_option(ix, "sequence_store_packed", sequence_store) != IMPG_OK) die(impg_gpu_last_error());
     if (impg_gpu_index_set_sequences(ix, seqs) != IMPG_OK) die(impg_gpu_last_error());
     impg_gpu_sequences_free(seqs);  // (the handle shares the store)
   }

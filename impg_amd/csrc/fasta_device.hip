@@ -1,10 +1,16 @@
 // FASTA records on the device (output_results_fasta, main.rs:12351-12415): the merged rows of the query-axis sweep
 // (bed_device.hip, strands apart, no gap_2d) printed as ">{name}:{start}-{end}[/rc]\n" and their bases in lines of 80, from a
-// sequence store that lives in HBM (one byte per base).  sequences.cpp holds the host side of the same text.
+// sequence store that lives in HBM (one byte per base, or two bits per base).  sequences.cpp holds the host side of the
+// same text.
 //
 //   store     SEQ_PAD zero bytes, the present sequences back to back in id order, padding behind them; off[id] = the place
 //             of the sequence's first base, SEQ_NOT_IN_HBM where the store lacks it.  The padding lets the writer's aligned
 //             16-byte loads read past either end of a sequence.
+//   packed    the same store at a quarter of the size (option "sequence_store_packed", read at attach; PackedStore below):
+//             2 bits a base, the bytes that are not A/C/G/T kept as runs beside them, packed on the device chunk by chunk
+//             (fasta_pack_kernel, upload_packed).  The kernels below are the same ones: the write kernel is a template on
+//             the store's form and differs in where a lane's 16 source bases come from -- 32 bits of the stream turned into
+//             letters in registers, the runs' bytes laid over them -- and nowhere else; the text is the same byte for byte.
 //   lengths   one thread per record: header + body, body = L + ceil(L / 80) bytes (a single '\n' for L = 0); the same thread
 //             marks the first record whose sequence the store lacks, or whose row leaves its sequence -- refused before any
 //             text is written.
@@ -39,7 +45,28 @@ struct FastaStore {
   const u64 *off;              // [n_ids]
   const uint32_t *len;         // [n_ids] the index's sequence lengths
   uint32_t n_ids;
+  static constexpr bool packed = false;
 };
+// The packed form (option "sequence_store_packed"): 2 bits a base, A C G T = 0 1 2 3, base i of the stream in bits
+// 2 * (i & 15) and up of word i >> 4 (bits 2 * (i & 3) of byte i >> 2).  64 zero bases in front, every present sequence
+// from a multiple of 64 bases on, 64 zero bytes or more behind the last; off[id] counts BASES.  A byte that is not A/C/G/T
+// packs as 0 and is kept in a run: a maximal stretch of one such byte, (start, end) in its sequence, the runs sorted, a CSR
+// offset per id.  A sequence that has runs also has a table over its blocks of 1 024 bases, first[b] = its runs that end at
+// or before base 1 024 * b: the runs that can touch bases [a, b) are first[a / 1024] .. first[(b - 1) / 1024 + 1] inclusive,
+// one candidate where no run lies near, none to look at where the sequence has no runs.
+struct PackedStore {
+  const uint32_t *words;  // 16-byte aligned
+  const u64 *off;         // [n_ids] the sequence's first base in the stream
+  const uint32_t *len;
+  uint32_t n_ids;
+  const u64 *run_off;             // [n_ids + 1]
+  const uint2 *runs;              // (start, end) in the sequence
+  const unsigned char *run_byte;  // what the run's bases print as
+  const u64 *blk_off;             // [n_ids] where the block table of a sequence with runs starts in blk
+  const uint32_t *blk;            // first[0 .. ceil(len / 1024)] per such sequence
+  static constexpr bool packed = true;
+};
+constexpr uint32_t ACGT = 0x54474341u;      // code c prints as byte c of it
 constexpr uint32_t FASTA_OK = 0xFFFFFFFFu;  // no record to refuse
 
 __device__ __forceinline__ uint32_t fasta_header_len(const TextTables &t, const BedRow &x, bool flip) {
@@ -69,15 +96,82 @@ __device__ __forceinline__ char dec_char(uint32_t v, uint32_t digits, uint32_t p
 __device__ __forceinline__ unsigned char base_complement(unsigned char c) {  // graph.rs:814-828
   return c == 'A' ? 'T' : c == 'T' ? 'A' : c == 'C' ? 'G' : c == 'G' ? 'C' : c;
 }
+// ---- the packed store's readers
+// The runs of sequence `id` that can touch its bases [a, b), 0 <= a < b <= its length: [lo, hi) of st.runs, every run
+// before lo ends at or before a.  Two words for a sequence without runs; two more and the table's two where it has some,
+// and a search only where more than one run remains.
+__device__ __forceinline__ void runs_near(const PackedStore &st, uint32_t id, uint32_t a, uint32_t b, u64 &lo, u64 &hi) {
+  const u64 r0 = st.run_off[id], r1 = st.run_off[id + 1];
+  lo = hi = r0;
+  if (r0 == r1) return;
+  const uint32_t *first = st.blk + st.blk_off[id];
+  lo = r0 + first[a >> 10];
+  hi = min(r0 + first[((b - 1u) >> 10) + 1u] + 1u, r1);  // (the run behind that one starts in a later block)
+  u64 top = hi;
+  while (top - lo > 1u) {  // the first run that ends behind a; `hi - 1` if none does
+    const u64 mid = lo + (top - lo) / 2u;
+    if (st.runs[mid - 1u].y > a) top = mid; else lo = mid;
+  }
+}
+// the 16 bases from place P of the stream on: 32 bits from two aligned words (the padding covers a read beyond a sequence)
+__device__ __forceinline__ uint32_t load_codes16(const uint32_t *__restrict__ words, u64 P) {
+  const u64 w = P >> 4;
+  const u64 v = ((u64)words[w + 1u] << 32) | words[w];
+  return (uint32_t)(v >> ((unsigned)(P & 15ull) * 2u));
+}
+__device__ __forceinline__ u64 expand8(uint32_t c) {  // eight codes in the low 16 bits -> their letters
+  u64 r = 0;
+#pragma unroll
+  for (unsigned i = 0; i < 8u; i++) r |= (u64)((ACGT >> (8u * ((c >> (2u * i)) & 3u))) & 0xFFu) << (8u * i);
+  return r;
+}
+// S holds 16 bases of sequence `id`, byte i base wa + i of it (forward) or base wb - 1 - i (turned round), wb = wa + 16; a
+// byte outside the sequence is one the caller drops.  The bytes under a run become the run's byte -- the same on either
+// strand: the complement leaves every byte that is not A/C/G/T as it is.
+__device__ __forceinline__ u128 overlay_runs(const PackedStore &st, uint32_t id, u128 S, long long wa, bool turned) {
+  const long long wb = wa + 16;
+  const uint32_t ca = (uint32_t)max(wa, 0ll), cb = (uint32_t)min(wb, (long long)st.len[id]);
+  u64 k, hi;
+  runs_near(st, id, ca, cb, k, hi);
+  for (; k < hi; k++) {
+    const uint2 run = st.runs[k];
+    if (run.x >= cb) break;
+    const uint32_t s = max(run.x, ca), e = min(run.y, cb);
+    if (s >= e) continue;
+    const unsigned i0 = (unsigned)(turned ? wb - (long long)e : (long long)s - wa), n = e - s;
+    const u64 fill = 0x0101010101010101ull * st.run_byte[k];
+    const u128 m = (n < 16u ? ((u128)1 << (8u * n)) - 1u : ~(u128)0) << (8u * i0);
+    S = (S & ~m) | ((((u128)fill << 64) | fill) & m);
+  }
+  return S;
+}
+// base `pos` of sequence `id`, one at a time (the slow path)
+__device__ __forceinline__ unsigned char store_base(const PackedStore &st, uint32_t id, uint32_t pos) {
+  const u64 P = st.off[id] + pos;
+  u64 k, hi;
+  runs_near(st, id, pos, pos + 1u, k, hi);
+  if (k < hi) {
+    const uint2 run = st.runs[k];
+    if (run.x <= pos && pos < run.y) return st.run_byte[k];
+  }
+  return (unsigned char)(ACGT >> (8u * ((st.words[P >> 4] >> ((unsigned)(P & 15ull) * 2u)) & 3u)));
+}
+
 // byte x of a record: its header, then its body
-__device__ unsigned char fasta_byte(const TextTables &t, const FastaStore &st, const BedRow &row, bool flip, uint32_t hl, u64 rec_len, u64 x) {
+template <class Store>
+__device__ unsigned char fasta_byte(const TextTables &t, const Store &st, const BedRow &row, bool flip, uint32_t hl, u64 rec_len, u64 x) {
   if (x >= hl) {
     const u64 j = x - hl;
     if (j + 1 == rec_len - hl || j % 81u == 80u) return '\n';
     const u64 idx = j - j / 81u;
-    const u64 so = st.off[row.query_id];
-    const unsigned char c = st.bases[flip ? so + (u64)row.end - 1u - idx : so + (u64)row.start + idx];
-    return flip ? base_complement(c) : c;
+    if constexpr (Store::packed) {
+      const unsigned char c = store_base(st, row.query_id, (uint32_t)(flip ? (u64)row.end - 1u - idx : (u64)row.start + idx));
+      return flip ? base_complement(c) : c;
+    } else {
+      const u64 so = st.off[row.query_id];
+      const unsigned char c = st.bases[flip ? so + (u64)row.end - 1u - idx : so + (u64)row.start + idx];
+      return flip ? base_complement(c) : c;
+    }
   }
   uint32_t h = (uint32_t)x;
   if (h == 0) return '>';
@@ -118,7 +212,9 @@ __device__ __forceinline__ u128 load16_any(const unsigned char *base, u64 at) {
 }
 
 // records [0, n_rec) of a piece: record r at out + (off[r] - base), the piece n_bytes long.  One lane per 16 bytes.
-__global__ __launch_bounds__(256) void fasta_write_kernel(const BedRow *__restrict__ rows, uint32_t n_rec, TextTables t, FastaStore st,
+// Store: FastaStore or PackedStore -- the two differ in where a lane's 16 source bases come from, and in fasta_byte's.
+template <class Store>
+__global__ __launch_bounds__(256) void fasta_write_kernel(const BedRow *__restrict__ rows, uint32_t n_rec, TextTables t, Store st,
                                                           int reverse_complement, const u64 *__restrict__ off, u64 base, u64 n_bytes,
                                                           char *__restrict__ out) {
   const u64 lane = (u64)blockIdx.x * 256u + threadIdx.x;
@@ -146,7 +242,21 @@ __global__ __launch_bounds__(256) void fasta_write_kernel(const BedRow *__restri
     const u64 s0 = j0 - line0;  // the base index of byte 0 (of byte 1 where byte 0 is the break)
     const u64 so = st.off[row.query_id];
     u128 S;
-    if (!flip) S = load16_any(st.bases, so + (u64)row.start + s0);
+    if constexpr (Store::packed) {
+      // 32 bits of the stream: the 16 bases from `start + s0` on, or the 16 that end at `end - 1 - s0` with their fields
+      // turned round and every code ^ 3; their letters; then the runs' bytes over them, before the break goes in
+      uint32_t c;
+      long long wa;
+      if (!flip) {
+        wa = (long long)row.start + (long long)s0;
+        c = load_codes16(st.words, so + (u64)wa);
+      } else {
+        wa = (long long)row.end - 1 - (long long)s0 - 15;
+        c = __builtin_bitreverse32(load_codes16(st.words, so + (u64)row.end - 1u - s0 - 15u));
+        c = ~(((c >> 1) & 0x55555555u) | ((c & 0x55555555u) << 1));
+      }
+      S = overlay_runs(st, row.query_id, ((u128)expand8(c >> 16) << 64) | expand8(c), wa, flip);
+    } else if (!flip) S = load16_any(st.bases, so + (u64)row.start + s0);
     else {
       // bytes hi, hi - 1, ...: read the 16 bytes that end at hi, turn them round, complement each
       const u128 F = load16_any(st.bases, so + (u64)row.end - 1u - s0 - 15u);
@@ -197,6 +307,22 @@ __global__ __launch_bounds__(256) void fasta_write_kernel(const BedRow *__restri
   }
 }
 
+// A staged chunk of the byte stream into the packed one: a lane reads 16 bytes and writes their 32 bits, word `lane` of out.
+// Every byte that is not A/C/G/T (a run's, the zero bytes between two sequences) packs as 0.
+__global__ __launch_bounds__(256) void fasta_pack_kernel(const uint4 *__restrict__ stage, u64 n_words, uint32_t *__restrict__ out) {
+  const u64 lane = (u64)blockIdx.x * 256u + threadIdx.x;
+  if (lane >= n_words) return;
+  const uint4 v = stage[lane];
+  const uint32_t in[4] = {v.x, v.y, v.z, v.w};
+  uint32_t w = 0;
+#pragma unroll
+  for (unsigned i = 0; i < 16u; i++) {
+    const uint32_t c = (in[i >> 2] >> (8u * (i & 3u))) & 0xFFu;
+    w |= (c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : 0u) << (2u * i);
+  }
+  out[lane] = w;
+}
+
 // IMPG_FASTA_PIECE_TIMING=<file> (a probe's switch, read on every call): every piece's write kernel between two events, and
 // a second copy of the same piece into a pinned buffer of the probe's own between two more, so that the kernel can be held
 // against the copy it is meant to hide behind.  "bytes kernel_ms copy_ms" per piece is appended to the file.
@@ -242,9 +368,138 @@ struct PieceTiming {
 
 }  // namespace
 
-// The store's bases in HBM, in the handle's id order (impg_gpu_index_set_sequences; the device is current)
+namespace {
+
+constexpr u64 PACK_CHUNK_BASES = 64ull << 20;  // IMPG_SEQ_PACK_CHUNK=<bases> sets another (tests: a chunk's end inside a sequence)
+constexpr size_t RUN_BYTES = sizeof(uint2) + 1;  // a run in HBM
+
+// What the packed form of the attached store would hold: the places, the runs and the block tables, all on the host
+struct PackedPlan {
+  std::vector<u64> off, run_off, blk_off;  // [n_ids], [n_ids + 1], [n_ids]
+  std::vector<uint2> runs;
+  std::vector<unsigned char> run_byte;
+  std::vector<uint32_t> blk;
+  u64 end = 64;  // the stream's bases, the alignment of every sequence included
+  size_t stream_bytes() const { return (size_t)(end / 4u) + 64; }
+  size_t bytes() const { return stream_bytes() + runs.size() * RUN_BYTES + blk.size() * 4; }
+};
+PackedPlan plan_packed(const impg_gpu_index &ix) {
+  const SeqStore &st = *ix.seq_store;
+  const size_t n_ids = ix.store_of_id.size();
+  PackedPlan p;
+  p.off.assign(std::max<size_t>(n_ids, 1), SEQ_NOT_IN_HBM);
+  p.run_off.assign(n_ids + 1, 0);
+  p.blk_off.assign(std::max<size_t>(n_ids, 1), 0);
+  std::vector<SeqRun> runs;
+  for (size_t id = 0; id < n_ids; id++) {
+    p.run_off[id + 1] = p.run_off[id];
+    const uint32_t s = ix.store_of_id[id];
+    if (s == SEQ_ABSENT) continue;
+    const u64 len = st.off[s + 1] - st.off[s];  // (the index's length: below 2^31)
+    p.off[id] = p.end;
+    p.end += (len + 63u) & ~63ull;
+    runs.clear();
+    seq_exception_runs(st.bases.data() + st.off[s], (size_t)len, runs);
+    if (runs.empty()) continue;
+    p.run_off[id + 1] += runs.size();
+    p.blk_off[id] = p.blk.size();
+    size_t k = 0;  // first[b] = the runs that end at or before base 1024 * b
+    for (u64 b = 0; b <= (len + 1023u) >> 10; b++) {
+      while (k < runs.size() && (u64)runs[k].end <= b << 10) k++;
+      p.blk.push_back((uint32_t)k);
+    }
+    for (const SeqRun &r : runs) {
+      p.runs.push_back(make_uint2(r.start, r.end));
+      p.run_byte.push_back(r.byte);
+    }
+  }
+  return p;
+}
+
+void upload(DevBuf &d, const void *src, size_t bytes) {  // (never an empty buffer: a kernel argument points into it)
+  d.reserve(std::max<size_t>(bytes, 16));
+  if (bytes) IMPG_HIP(hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice));
+}
+
+// The packed stream is made on the device chunk by chunk: the host lays a window of the stream out one byte per base in a
+// pinned block -- the sequences at their places, zero bytes between them --, the block goes to a staging buffer in HBM and
+// fasta_pack_kernel packs it into place.  A window starts and ends at a multiple of 64 bases of the stream, and so of every
+// sequence.  Peak HBM during attach: the packed stream, the run tables and this ONE staging chunk -- never the store at a
+// byte per base.
+void upload_packed(impg_gpu_index &ix, const PackedPlan &p) {
+  const SeqStore &st = *ix.seq_store;
+  const size_t n_ids = ix.store_of_id.size();
+  const char *env = getenv("IMPG_SEQ_PACK_CHUNK");
+  const u64 asked = env ? strtoull(env, nullptr, 10) : 0ull;
+  const u64 chunk = std::max<u64>(((asked ? asked : PACK_CHUNK_BASES) + 63u) & ~63ull, 64);
+  ix.d_seq_bases.reserve(p.stream_bytes());
+  IMPG_HIP(hipMemset(ix.d_seq_bases.p, 0, p.stream_bytes()));
+  upload(ix.d_seq_off, p.off.data(), p.off.size() * 8);
+  upload(ix.d_seq_run_off, p.run_off.data(), p.run_off.size() * 8);
+  upload(ix.d_seq_blk_off, p.blk_off.data(), p.blk_off.size() * 8);
+  upload(ix.d_seq_runs, p.runs.data(), p.runs.size() * sizeof(uint2));
+  upload(ix.d_seq_run_byte, p.run_byte.data(), p.run_byte.size());
+  upload(ix.d_seq_blk, p.blk.data(), p.blk.size() * 4);
+  const u64 stage_bytes = std::min<u64>(chunk, p.end - 64u);
+  if (stage_bytes) {
+    DevBuf d_stage;
+    d_stage.reserve((size_t)stage_bytes);
+    size_t pin_cap = 0;
+    char *pin = (char *)pinned_take((size_t)stage_bytes, pin_cap);
+    try {
+      size_t id = 0;  // the first sequence that reaches into the window
+      for (u64 b0 = 64; b0 < p.end; b0 += chunk) {
+        const u64 b1 = std::min<u64>(b0 + chunk, p.end);
+        u64 cur = b0;
+        for (size_t j = id; j < n_ids; j++) {
+          const uint32_t s = ix.store_of_id[j];
+          if (s == SEQ_ABSENT) continue;
+          if (p.off[j] >= b1) break;
+          const u64 a = std::max<u64>(p.off[j], b0), b = std::min<u64>(p.off[j] + (st.off[s + 1] - st.off[s]), b1);
+          if (a < b) {
+            memset(pin + (cur - b0), 0, (size_t)(a - cur));
+            memcpy(pin + (a - b0), st.bases.data() + st.off[s] + (a - p.off[j]), (size_t)(b - a));
+            cur = b;
+          }
+          if (p.off[j] + (st.off[s + 1] - st.off[s]) <= b1) id = j + 1;
+        }
+        memset(pin + (cur - b0), 0, (size_t)(b1 - cur));
+        IMPG_HIP(hipMemcpy(d_stage.p, pin, (size_t)(b1 - b0), hipMemcpyHostToDevice));
+        const u64 n_words = (b1 - b0) / 16u;
+        fasta_pack_kernel<<<cdiv(n_words, 256), 256>>>(d_stage.as<uint4>(), n_words, ix.d_seq_bases.as<uint32_t>() + b0 / 16u);
+        IMPG_HIP(hipGetLastError());
+        IMPG_HIP(hipDeviceSynchronize());  // (the next window overwrites the pinned block and the staging buffer)
+      }
+    } catch (...) {
+      pinned_give(pin, pin_cap);
+      throw;
+    }
+    pinned_give(pin, pin_cap);
+  }
+  ix.seq_packed = true;
+  ix.fasta_stats[FASTA_STORE_BYTES] = p.bytes();
+  ix.fasta_stats[FASTA_STORE_PACKED] = 1;
+  ix.fasta_stats[FASTA_STORE_EXCEPTION_RUNS] = p.runs.size();
+}
+
+}  // namespace
+
+// The store's bases in HBM, in the handle's id order (impg_gpu_index_set_sequences; the device is current), in the form
+// option "sequence_store_packed" asks for: 0 a byte per base, 1 packed, 2 whichever takes fewer bytes -- decided on the
+// host, from the runs, before anything is uploaded
 void upload_sequences(impg_gpu_index &ix) {
   const SeqStore &st = *ix.seq_store;
+  ix.seq_packed = false;
+  ix.fasta_stats[FASTA_STORE_PACKED] = 0;
+  ix.fasta_stats[FASTA_STORE_EXCEPTION_RUNS] = 0;
+  if (ix.opt.sequence_store_packed) {
+    const PackedPlan p = plan_packed(ix);
+    u64 as_bytes = SEQ_PAD;
+    for (const uint32_t s : ix.store_of_id)
+      if (s != SEQ_ABSENT) as_bytes += st.off[s + 1] - st.off[s];
+    if (ix.opt.sequence_store_packed == 1 || p.bytes() < (size_t)((as_bytes + 15u) & ~15ull) + 64) return upload_packed(ix, p);
+  }
+  for (DevBuf *d : {&ix.d_seq_run_off, &ix.d_seq_runs, &ix.d_seq_run_byte, &ix.d_seq_blk_off, &ix.d_seq_blk}) d->release();
   const size_t n_ids = ix.store_of_id.size();
   std::vector<u64> off(std::max<size_t>(n_ids, 1), SEQ_NOT_IN_HBM);
   u64 at = SEQ_PAD;
@@ -276,6 +531,9 @@ void device_fasta_text(Engine &E, const impg_gpu_index &ix, const DevBuf &rows, 
   TextTableBufs tb(E, ix, 0, std::vector<std::string>(), false, /*with_lengths=*/true);
   const TextTables t = tb.t;
   const FastaStore st{ix.d_seq_bases.as<unsigned char>(), ix.d_seq_off.as<u64>(), t.seq_len, std::min<uint32_t>((uint32_t)ix.store_of_id.size(), t.n_lens)};
+  // (the length kernel asks the store for presence and bounds only: one kernel for both forms)
+  const PackedStore pst{ix.d_seq_bases.as<uint32_t>(), st.off, st.len, st.n_ids, ix.d_seq_run_off.as<u64>(), ix.d_seq_runs.as<uint2>(),
+                        ix.d_seq_run_byte.as<unsigned char>(), ix.d_seq_blk_off.as<u64>(), ix.d_seq_blk.as<uint32_t>()};
   const int rc = reverse_complement ? 1 : 0;
   DevBuf len, bad;
   len.reserve((size_t)n_rows * 4);
@@ -303,14 +561,20 @@ void device_fasta_text(Engine &E, const impg_gpu_index &ix, const DevBuf &rows, 
   device_text_pieces(E, len.as<uint32_t>(), n_rows, "FASTA",
                      [&](uint32_t r0, uint32_t r1, const unsigned long long *off, unsigned long long base, char *out) {
                        const u64 n_bytes = h_off[r1] - h_off[r0];
+                       auto write = [&]() {  // the kernel of the form the attached store has
+                         if (ix.seq_packed)
+                           fasta_write_kernel<PackedStore><<<cdiv(n_bytes, 16u * 256u), 256, 0, s>>>(rows.as<BedRow>() + r0, r1 - r0, t, pst, rc, off, base, n_bytes, out);
+                         else
+                           fasta_write_kernel<FastaStore><<<cdiv(n_bytes, 16u * 256u), 256, 0, s>>>(rows.as<BedRow>() + r0, r1 - r0, t, st, rc, off, base, n_bytes, out);
+                       };
                        if (timing.on()) {
                          timing.mark(s);
-                         fasta_write_kernel<<<cdiv(n_bytes, 16u * 256u), 256, 0, s>>>(rows.as<BedRow>() + r0, r1 - r0, t, st, rc, off, base, n_bytes, out);
+                         write();
                          timing.mark(s);
                          timing.copy(out, n_bytes, s);
                          return;
                        }
-                       fasta_write_kernel<<<cdiv(n_bytes, 16u * 256u), 256, 0, s>>>(rows.as<BedRow>() + r0, r1 - r0, t, st, rc, off, base, n_bytes, out);
+                       write();
                      },
                      sink, ix.fasta_stats[FASTA_TEXT_PIECES], ix.fasta_stats[FASTA_TEXT_BYTES]);
   if (timing.on()) timing.report();

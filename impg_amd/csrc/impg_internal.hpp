@@ -396,7 +396,7 @@ void query_axis_merge(std::vector<impg_gpu_interval_t> &rows, int32_t merge_dist
 
 // ---- sequences (sequences.cpp): the bases FASTA output prints ---------------------------------------------------------
 // impg_gpu_index::fasta_stats (fasta_device.hip)
-enum FastaStat { FASTA_ROWS, FASTA_RECORDS, FASTA_TEXT_PIECES, FASTA_TEXT_BYTES, FASTA_STORE_BYTES };
+enum FastaStat { FASTA_ROWS, FASTA_RECORDS, FASTA_TEXT_PIECES, FASTA_TEXT_BYTES, FASTA_STORE_BYTES, FASTA_STORE_PACKED, FASTA_STORE_EXCEPTION_RUNS };
 struct SeqStore {  // one byte per base, upper-cased at load, back to back
   std::vector<std::string> names;
   std::vector<uint64_t> off;  // [n + 1]
@@ -407,6 +407,10 @@ struct SeqStore {  // one byte per base, upper-cased at load, back to back
 constexpr uint32_t SEQ_ABSENT = 0xFFFFFFFFu;      // impg_gpu_index::store_of_id: the store lacks the sequence
 constexpr uint64_t SEQ_NOT_IN_HBM = ~0ull;        // the device offsets' mark of the same
 constexpr size_t SEQ_PAD = 16;                    // bytes in front of the first base in HBM (and at least as many behind the last)
+// What the packed store (fasta_device.hip) keeps beside its 2 bits a base: a maximal stretch [start, end) of ONE byte that
+// is not A/C/G/T.  The runs of a sequence (upper-cased, as the store holds it) appended to `runs`, in order; "NNNRR" is two.
+struct SeqRun { uint32_t start, end; uint8_t byte; };
+void seq_exception_runs(const char *bases, size_t n, std::vector<SeqRun> &runs);
 // One range's rows -> FASTA records appended to `text` (output_results_fasta, main.rs:12351-12415): the sweep, then per merged
 // row the header and the bases in lines of 80.  fetch(id, name): the sequence's bases in the store, null if it lacks them.
 struct SeqRef { const char *bases; uint64_t len; };
@@ -490,15 +494,21 @@ struct impg_gpu_index {
   mutable std::atomic<uint64_t> paf_stats[9] = {};
   void paf_stats_reset() const { for (auto &b : paf_stats) b = 0; }
   // ... and the last device FASTA call (by impg::FastaStat; fasta_device.hip), kept the same way
-  mutable std::atomic<uint64_t> fasta_stats[5] = {};
+  mutable std::atomic<uint64_t> fasta_stats[7] = {};
   void fasta_stats_reset() const { for (int k = 0; k < impg::FASTA_STORE_BYTES; k++) fasta_stats[k] = 0; }  // (the store's size stays: set when it is attached)
   // The sequence store attached by impg_gpu_index_set_sequences (null: none): the host copy the host route reads, which
   // of its sequences every index id is (impg::SEQ_ABSENT: none), and the same bases in HBM for the device route -- SEQ_PAD
   // zero bytes, the present sequences back to back in id order, padding; d_seq_off[id] = the first base's place, or
   // impg::SEQ_NOT_IN_HBM.  Attach and detach while no query runs on the handle.
+  // seq_packed (option "sequence_store_packed" as it stood at attach): d_seq_bases holds 2 bits a base instead, d_seq_off
+  // counts bases, and the bytes that are not A/C/G/T are runs -- d_seq_run_off[id] .. [id + 1] of d_seq_runs (start, end) and
+  // d_seq_run_byte, found through the block table d_seq_blk + d_seq_blk_off[id] (PackedStore, fasta_device.hip).
   std::shared_ptr<const impg::SeqStore> seq_store;
   std::vector<uint32_t> store_of_id;
   impg::DevBuf d_seq_bases, d_seq_off;
+  bool seq_packed = false;
+  impg::DevBuf d_seq_run_off, d_seq_runs, d_seq_run_byte, d_seq_blk_off, d_seq_blk;
+  void drop_device_sequences();  // (sequences.cpp: the buffers above released, the store's three counters zero)
   impg::ShardCtx *shard = nullptr;    // set: this index is one rank's shard; queries are collective calls
   impg::Cluster *cluster = nullptr;   // set: this handle fronts n_dev shards in this process (no arrays of its own)
   impg_gpu_index();

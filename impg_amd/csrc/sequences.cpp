@@ -27,6 +27,17 @@ void SeqStore::add(const std::string &name, const char *b, size_t n) {
   off.push_back(bases.size());
 }
 
+void seq_exception_runs(const char *bases, size_t n, std::vector<SeqRun> &runs) {
+  for (size_t i = 0; i < n;) {
+    const char c = bases[i];
+    if (c == 'A' || c == 'C' || c == 'G' || c == 'T') { i++; continue; }
+    size_t j = i + 1;
+    while (j < n && bases[j] == c) j++;
+    runs.push_back(SeqRun{(uint32_t)i, (uint32_t)j, (uint8_t)c});
+    i = j;
+  }
+}
+
 namespace {
 
 // One plain FASTA file into the store: the name runs to the first whitespace of the '>' line, body lines of any length,
@@ -123,6 +134,12 @@ void fasta_range_text(std::vector<impg_gpu_interval_t> &rows, int32_t merge_dist
 
 using namespace impg;
 
+void impg_gpu_index::drop_device_sequences() {
+  for (DevBuf *d : {&d_seq_bases, &d_seq_off, &d_seq_run_off, &d_seq_runs, &d_seq_run_byte, &d_seq_blk_off, &d_seq_blk}) d->release();
+  seq_packed = false;
+  for (int k : {FASTA_STORE_BYTES, FASTA_STORE_PACKED, FASTA_STORE_EXCEPTION_RUNS}) fasta_stats[k] = 0;
+}
+
 extern "C" {
 
 int impg_gpu_sequences_from_fasta(const char *const *paths, size_t n_paths, impg_gpu_sequences_t **out) {
@@ -165,6 +182,24 @@ const char *impg_gpu_sequences_bases(const impg_gpu_sequences_t *s, size_t i, ui
   return s->s->bases.data() + s->s->off[i];
 }
 
+int impg_gpu_sequences_exceptions(const impg_gpu_sequences_t *s, size_t i, uint32_t *start, uint32_t *len, uint8_t *byte, size_t cap, size_t *n_runs) {
+  IMPG_TRY
+  if (!s || !n_runs || (cap && (!start || !len || !byte))) throw Error{IMPG_E_INVALID, "null argument"};
+  if (i >= s->s->names.size()) throw Error{IMPG_E_INVALID, "no such sequence in the store"};
+  const uint64_t n = s->s->off[i + 1] - s->s->off[i];
+  if (n > 0xFFFFFFFFull) throw Error{IMPG_E_UNSUPPORTED, "a sequence of 2^32 bases or more"};
+  std::vector<SeqRun> runs;
+  seq_exception_runs(s->s->bases.data() + s->s->off[i], (size_t)n, runs);
+  for (size_t k = 0; k < runs.size() && k < cap; k++) {
+    start[k] = runs[k].start;
+    len[k] = runs[k].end - runs[k].start;
+    byte[k] = runs[k].byte;
+  }
+  *n_runs = runs.size();
+  return IMPG_OK;
+  IMPG_CATCH
+}
+
 void impg_gpu_sequences_free(impg_gpu_sequences_t *s) { delete s; }
 
 int impg_gpu_index_set_sequences(impg_gpu_index_t *ix, const impg_gpu_sequences_t *seqs) {
@@ -175,9 +210,7 @@ int impg_gpu_index_set_sequences(impg_gpu_index_t *ix, const impg_gpu_sequences_
   if (!seqs) {
     ix->seq_store.reset();
     ix->store_of_id.clear();
-    ix->d_seq_bases.release();
-    ix->d_seq_off.release();
-    ix->fasta_stats[FASTA_STORE_BYTES] = 0;
+    ix->drop_device_sequences();
     return IMPG_OK;
   }
   if (ix->tp_mode) throw Error{IMPG_E_UNSUPPORTED, "a sequence store on a tracepoint index (it has no sequence names)"};
@@ -201,8 +234,7 @@ int impg_gpu_index_set_sequences(impg_gpu_index_t *ix, const impg_gpu_sequences_
   } catch (...) {
     ix->seq_store.reset();
     ix->store_of_id.clear();
-    ix->d_seq_bases.release();
-    ix->d_seq_off.release();
+    ix->drop_device_sequences();
     throw;
   }
   return IMPG_OK;

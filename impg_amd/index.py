@@ -306,6 +306,18 @@ class Sequences:
     def items(self):
         return [(self.name(i), self.bases(i)) for i in range(len(self))]
 
+    def exceptions(self, i):
+        """impg_gpu_sequences_exceptions (host-only): sequence i's maximal runs of one byte that is not A/C/G/T, as the
+        packed store keeps them -> (start, length, byte) arrays (uint32, uint32, uint8), in order."""
+        if not 0 <= i < len(self):
+            raise IndexError(i)
+        n = C.c_size_t(0)
+        check(lib().impg_gpu_sequences_exceptions(self._h, i, None, None, None, 0, C.byref(n)))
+        start, length, byte = np.zeros(n.value, dtype=np.uint32), np.zeros(n.value, dtype=np.uint32), np.zeros(n.value, dtype=np.uint8)
+        if n.value:
+            check(lib().impg_gpu_sequences_exceptions(self._h, i, start.ctypes.data, length.ctypes.data, byte.ctypes.data, n.value, C.byref(n)))
+        return start, length, byte
+
     def __del__(self):
         if getattr(self, "_h", None):
             try:
@@ -668,8 +680,14 @@ class GpuImpg:
         return self._query_batch_text_fd(lib().impg_gpu_query_batch_paf_fd, ranges, params, merge_distance, range_names, subset_keep, timing,
                                          fd, kw)
 
-    def set_sequences(self, sequences):
-        """impg_gpu_index_set_sequences: attach a Sequences store (its bases go to HBM), or detach with None."""
+    def set_sequences(self, sequences, packed=None):
+        """impg_gpu_index_set_sequences: attach a Sequences store (its bases go to HBM), or detach with None.  packed:
+        option "sequence_store_packed" set first -- False one byte per base, True two bits per base with the bytes that
+        are not A/C/G/T kept as runs, "auto" whichever takes fewer bytes in HBM; None leaves the option as it is."""
+        if packed is not None:
+            if not any(packed is v for v in (False, True)) and packed != "auto":
+                raise ValueError("packed is None, False, True or 'auto'")
+            self.set_option("sequence_store_packed", 2 if packed == "auto" else int(packed))
         check(lib().impg_gpu_index_set_sequences(self._h, None if sequences is None else sequences._h))
 
     def query_batch_fasta(self, ranges, params=None, merge_distance=0, range_names=None, subset_keep=None, timing=False, raw=False,

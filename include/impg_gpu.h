@@ -249,7 +249,11 @@ int impg_gpu_index_approximate(const impg_gpu_index_t *);
  * beyond that is IMPG_E_UNSUPPORTED; the text is identical for every value; impg_gpu_query_batch_bedpe's text crosses the
  * same way), "bedpe_group_log2" (2 .. 6; 2 by default: impg_gpu_query_batch_bedpe sums a row's CIGAR ops with 2^value
  * lanes; results identical), "paf_group_log2" (2 .. 6; 2 by default: impg_gpu_query_batch_paf fuses and prints a row's CIGAR
- * ops with 2^value lanes; results identical).  For tests of the multi-rank paths: "lane_schedule" (forced lane start / hand-over order of a sharded
+ * ops with 2^value lanes; results identical), "sequence_store_packed" (the form impg_gpu_index_set_sequences uploads the
+ * sequence store in: 0, the default, one byte per base; 1 two bits per base and a table of runs for every byte that is not
+ * A/C/G/T; 2 whichever of the two takes fewer bytes in HBM for the store at hand -- see impg_gpu_index_set_sequences.  Read
+ * at attach: changing it does not repack an attached store, detach and attach again for that.  The text is identical for
+ * every value).  For tests of the multi-rank paths: "lane_schedule" (forced lane start / hand-over order of a sharded
  * batch; 0 = off), "debug_fail_owner" / "debug_fail_home" (failure injection: (rank + 1) << 16 | hop of the batch at which
  * that rank throws on the owner / on the home side of the hop; 0 = off).
  * A multi-GPU handle hands "chunk_ranges", "pair_budget", "locality_min", "debug_fail_owner", "debug_fail_home",
@@ -306,7 +310,10 @@ const char *impg_gpu_counter_key(size_t i);
  * "paf_text_bytes" = bytes printed.  Of the last device FASTA call on the handle (impg_gpu_query_batch_fasta,
  * impg_gpu_query_batch_fasta_fd, impg_gpu_selftest_fasta_rows; kept the same way): "fasta_rows" = rows entering the sweep,
  * "fasta_records" = records printed, "fasta_text_pieces" = text pieces sent to the host, "fasta_text_bytes" = bytes printed;
- * "fasta_store_bytes" = bytes of HBM the attached sequence store takes (0: none attached).  Of the build of the index itself (a multi-GPU handle answers with the sum over its
+ * "fasta_store_bytes" = bytes of HBM the attached sequence store takes, in whichever form it has -- the bases, and the
+ * packed form's runs and block tables (0: none attached), "fasta_store_packed" = 1 if the attached store is the packed
+ * form (0: one byte per base, or none attached), "fasta_store_exception_runs" = the runs of bytes other than A/C/G/T the
+ * packed form keeps (0 for the byte form, and with none attached).  Of the build of the index itself (a multi-GPU handle answers with the sum over its
  * ranks): "build_device" = 1 if the device builder produced it, 0 if the host builder did (IMPG_BUILD_HOST, tracepoints, a
  * loaded .impg file's entry order, a card short of memory for the build, an index loaded from a saved file);
  * "tokenized_device" = 1 if the device tokenised its CIGAR text (impg_gpu_index_create_from_paf on one GPU);
@@ -597,7 +604,8 @@ int impg_gpu_query_batch_paf_fd(impg_gpu_index_t *, const impg_gpu_range_t *rang
 /* ---- FASTA: `impg query -o fasta` (output_results_fasta, main.rs:12351-12415) -------------------------------------
  * The sequences: plain FASTA files (the name runs to the first whitespace of the '>' line; body lines of any length; '\r'
  * dropped; bytes upper-cased at load; an empty sequence and a last line without a newline are accepted), or arrays of the
- * caller's (names[n], off[n + 1] into bases; upper-cased too).  One byte per base, so IUPAC codes and N stay exact.
+ * caller's (names[n], off[n + 1] into bases; upper-cased too).  One byte per base on the host, so IUPAC codes and N stay
+ * exact; in HBM one byte per base too, or two bits per base with those bytes kept aside (option "sequence_store_packed").
  * IMPG_E_UNSUPPORTED for a file that starts with the gzip magic 1f 8b (no codec here: decompress first); IMPG_E_INVALID,
  * naming it, for a name that occurs twice, in one file or across files (the reference lets the last file win);
  * IMPG_E_IO for a file that cannot be read.  Host-only.  _name / _bases: sequence i as the store holds it (NULL past the
@@ -608,13 +616,25 @@ int impg_gpu_sequences_from_memory(const char *const *names, const uint64_t *off
 size_t impg_gpu_sequences_num(const impg_gpu_sequences_t *);
 const char *impg_gpu_sequences_name(const impg_gpu_sequences_t *, size_t i);
 const char *impg_gpu_sequences_bases(const impg_gpu_sequences_t *, size_t i, uint64_t *len);
+/* Sequence i's exceptions as the packed form of the store keeps them (host-only; impg_gpu_index_set_sequences extracts the
+ * same at attach): the maximal runs of ONE byte that is not A/C/G/T after upper-casing, in order -- "NNNRR" is two runs --,
+ * run k = bases [start[k], start[k] + len[k]) printing as byte[k].  *n_runs = their number; the first min(cap, *n_runs) are
+ * written (cap = 0: the arrays may be NULL).  IMPG_E_INVALID past the last sequence. */
+int impg_gpu_sequences_exceptions(const impg_gpu_sequences_t *, size_t i, uint32_t *start, uint32_t *len, uint8_t *byte, size_t cap, size_t *n_runs);
 void impg_gpu_sequences_free(impg_gpu_sequences_t *);
 /* Attaches the store to an index handle: its sequences are matched to the index's by name and their bases uploaded to the
  * handle's device (back to back, one byte per base, padded by 16 bytes or more at both ends; a 64-bit offset per index id,
  * all ones where the store lacks the sequence).  Index sequences the store lacks, and store sequences the index lacks, are
  * tolerated; a sequence whose length differs from impg_gpu_seq_len is IMPG_E_INVALID, naming it.  The handle shares the
  * store's host copy (the host route reads it): the caller may free its own handle at once.  seqs == NULL detaches.  A
- * tracepoint index (it has no names) and a sharded handle: IMPG_E_UNSUPPORTED.  Not to be called while a query runs. */
+ * tracepoint index (it has no names) and a sharded handle: IMPG_E_UNSUPPORTED.  Not to be called while a query runs.
+ * Under option "sequence_store_packed" = 1 (or 2, where that is smaller) the bases go to HBM packed instead: two bits per
+ * base (A C G T = 0 1 2 3, base i in bits 2 * (i & 3) and up of byte i >> 2), 16 zero bytes in front, every sequence from a
+ * multiple of 64 bases on, 64 zero bytes or more behind the last, the offsets counting bases; every other byte packs as 0
+ * and is kept as a run (impg_gpu_sequences_exceptions) with a table over each sequence's blocks of 1 024 bases to find its
+ * runs by: bases / 4 + 9 bytes per run + 16 bytes per sequence, + 4 bytes per 1 024 bases of a sequence that has runs.  The
+ * bases are packed on the device chunk by chunk through one staging buffer (64 MiB), so the attach never holds the store
+ * at a byte per base in HBM.  The text every FASTA call prints is the same, byte for byte; the host copy stays as it is. */
 int impg_gpu_index_set_sequences(impg_gpu_index_t *, const impg_gpu_sequences_t *seqs);
 /* perform_query + output_results_fasta for a whole batch, the sweep (merge_query_adjusted_intervals alone, strands kept
  * apart: main.rs:12362, :4395-4409) and the records written ON THE DEVICE (fasta_device.hip) from the store in HBM: per merged
