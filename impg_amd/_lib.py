@@ -90,6 +90,10 @@ class RefineOpts(C.Structure):  # impg_gpu_refine_opts_t
                 ("use_max_entities", C.c_int32), ("support_on_host", C.c_int32)]
 
 
+class SortPass(C.Structure):  # impg_gpu_sort_pass_t
+    _fields_ = [("keys", C.c_void_p), ("wide", C.c_int), ("bits", C.c_uint)]
+
+
 REFINE_RECORD_DTYPE = np.dtype([("target_id", "<u4"), ("refined_start", "<i4"), ("refined_end", "<i4"), ("original_start", "<i4"),
                                 ("original_end", "<i4"), ("left_extension", "<i4"), ("right_extension", "<i4"), ("support_count", "<u4"),
                                 ("original_support_count", "<u4")])  # impg_gpu_refine_record_t
@@ -246,6 +250,9 @@ SYMBOLS = [
     ("impg_synth_paf_text", C.c_int, [C.c_uint64, C.c_size_t, C.c_uint32, C.c_int32, C.c_int32, C.c_uint32, C.c_char_p]),
     ("impg_synth_skewed_paf_text", C.c_int, [C.c_uint64, C.c_size_t, C.c_uint32, C.c_int32, C.c_char_p, C.POINTER(C.c_uint64)]),
     ("impg_gpu_selftest_order_sort", C.c_int, [C.c_int, C.c_uint32, C.c_uint, C.c_uint64]),
+    ("impg_gpu_selftest_scan", C.c_int, [C.c_int, C.c_int, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, C.POINTER(C.c_uint64), _P]),
+    ("impg_gpu_selftest_offsets", C.c_int, [C.c_int, _P, C.c_uint32, C.c_int, _P, C.POINTER(C.c_uint64)]),
+    ("impg_gpu_selftest_key_sort", C.c_int, [C.c_int, C.c_uint32, _P, C.c_uint32, C.c_int, _P, C.c_uint32, _P, _P]),
     ("impg_gpu_selftest_bed_rows", C.c_int, [_P, _P, _P, C.c_size_t, C.c_uint32, C.c_uint64, C.c_int32, C.c_int, C.c_int, _P, C.POINTER(_P),
                                              C.POINTER(C.c_size_t), C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(_P), C.POINTER(_P),
                                              C.POINTER(C.c_size_t)]),

@@ -1020,13 +1020,13 @@ __global__ __launch_bounds__(LB_BLOCK) void scan_lookback_kernel(const uint32_t 
   if (tile == n_tiles - 1u && threadIdx.x == 0) *total = prefix + tot;
 }
 
-void launch_exclusive_scan(const uint32_t *d_in, uint32_t *d_out, uint32_t n, unsigned long long *d_bsum,
-                           unsigned long long *d_total, hipStream_t s) {
+int launch_exclusive_scan(const uint32_t *d_in, uint32_t *d_out, uint32_t n, unsigned long long *d_bsum,
+                          unsigned long long *d_total, hipStream_t s) {
   if (((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_out)) & 15u) == 0u) {
     const uint32_t nt = std::max<uint32_t>((n + LB_TILE - 1) / LB_TILE, 1u);
     IMPG_HIP(hipMemsetAsync(d_bsum, 0, ((size_t)nt + 1) * sizeof(unsigned long long), s));
     scan_lookback_kernel<<<nt, LB_BLOCK, 0, s>>>(d_in, d_out, n, d_bsum, nt, d_total);
-    return;
+    return SCAN_FORM_LOOKBACK;
   }
   uint32_t nb = (n + SCAN_TILE - 1) / SCAN_TILE;
   if (nb == 0) nb = 1;
@@ -1035,8 +1035,10 @@ void launch_exclusive_scan(const uint32_t *d_in, uint32_t *d_out, uint32_t n, un
   scan_block_sums<<<nb, SCAN_BLOCK, 0, s>>>(d_in, n, d_bsum);
   scan_of_sums<<<1, 1024, 0, s>>>(d_bsum, nb, d_total);
   scan_apply<<<nb, SCAN_BLOCK, 0, s>>>(d_in, n, d_bsum, d_out);
+  return SCAN_FORM_THREE_KERNEL;
 }
 size_t scan_scratch_bytes(uint32_t n) { return ((size_t)(n + SCAN_TILE - 1) / SCAN_TILE + 2) * sizeof(unsigned long long); }  // (block sums, or tile words + the ticket)
+void scan_tile_sizes(uint32_t *lookback_tile, uint32_t *three_kernel_tile) { *lookback_tile = LB_TILE; *three_kernel_tile = SCAN_TILE; }
 
 // ---------------------------------------------------------------------------
 // K2: projection, one lane per (range, entry) pair

@@ -156,9 +156,13 @@ void launch_reorder_runs(const uint32_t *hits, uint32_t n, uint32_t words, uint3
 void launch_order_keys(const DeviceIndexView &v, const FrontierRec *fr, uint32_t n, uint32_t *key, uint32_t *idx, hipStream_t s,
                        const uint32_t *bounds = nullptr, uint32_t n_blocks = 0, uint32_t block_shift = 0);
 void launch_scatter_u32(const uint32_t *in, const uint32_t *perm, uint32_t n, uint32_t *out, hipStream_t s);
-void launch_exclusive_scan(const uint32_t *d_in, uint32_t *d_out, uint32_t n, unsigned long long *d_bsum,
-                           unsigned long long *d_total, hipStream_t s);
+// Returns the form it ran: the single-pass look-back kernel when both pointers are 16-byte aligned, else the three kernels
+// (the engine ignores the value; impg_gpu_selftest_scan reports it).
+enum ScanForm : int { SCAN_FORM_LOOKBACK = 0, SCAN_FORM_THREE_KERNEL = 1 };
+int launch_exclusive_scan(const uint32_t *d_in, uint32_t *d_out, uint32_t n, unsigned long long *d_bsum,
+                          unsigned long long *d_total, hipStream_t s);
 size_t scan_scratch_bytes(uint32_t n);
+void scan_tile_sizes(uint32_t *lookback_tile, uint32_t *three_kernel_tile);  // LB_TILE, SCAN_TILE (diagnostics)
 // Which kernel launch_project ran a level on (its return value; PROJ_ARM_NONE: no pairs, nothing launched).  The handle counts
 // them per arm (impg_gpu_get_counter "project_*_levels"), on the host.
 enum ProjArm : int {

@@ -1474,3 +1474,47 @@ def synth_bed(seed, n, n_seq=200, seq_len=5_000_000, range_len=5_000):
     out = np.zeros(n, dtype=RANGE_DTYPE)
     check(lib().impg_synth_bed(seed, n, n_seq, seq_len, range_len, out.ctypes.data))
     return out
+
+
+# ---- the device primitives on the caller's arrays (diagnostics; tests/test_gpu_prims.py) ---------------------------
+SCAN_LOOKBACK, SCAN_THREE_KERNEL, SCAN_SMALL = 0, 1, 2
+
+
+def selftest_scan(values, which=0, in_shift=0, out_shift=0, device=0):
+    """impg_gpu_selftest_scan: the engine's exclusive scan (which=0) or the small-batch path's single-block one (which=1)
+    of `values` (u32), the device arrays in_shift / out_shift words behind a 256-byte boundary.  Returns (out, total, info):
+    the offsets written, the total, and info = dict(form, in_low4, out_low4, lookback_tile, three_kernel_tile)."""
+    a = np.ascontiguousarray(values, dtype=np.uint32)
+    out = np.empty(a.size, dtype=np.uint32)
+    total = C.c_uint64(0)
+    info = np.zeros(5, dtype=np.uint32)
+    check(lib().impg_gpu_selftest_scan(device, which, a.ctypes.data, a.size, in_shift, out_shift, out.ctypes.data, C.byref(total),
+                                       info.ctypes.data))
+    return out, int(total.value), dict(zip(("form", "in_low4", "out_low4", "lookback_tile", "three_kernel_tile"), map(int, info)))
+
+
+def selftest_offsets(lengths, with_host_copy=False, device=0):
+    """impg_gpu_selftest_offsets: the 64-bit offsets of `lengths` (u32) and their total, by prims::offsets_and_total --
+    with_host_copy: through the form that copies the offsets home itself."""
+    a = np.ascontiguousarray(lengths, dtype=np.uint32)
+    off = np.empty(a.size, dtype=np.uint64)
+    total = C.c_uint64(0)
+    check(lib().impg_gpu_selftest_offsets(device, a.ctypes.data, a.size, int(with_host_copy), off.ctypes.data, C.byref(total)))
+    return off, int(total.value)
+
+
+def selftest_key_sort(n_keys, perm, passes, first_in_order, device=0):
+    """impg_gpu_selftest_key_sort: prims::KeySort::run over passes = [(keys, bits), ...], least significant first; keys:
+    n_keys of uint32 or (a wide pass) uint64, at the rows' own indices.  Returns (order, sorted_keys)."""
+    p = np.ascontiguousarray(perm, dtype=np.uint32)
+    arrays = [np.ascontiguousarray(k) for k, _ in passes]
+    for k in arrays:
+        if k.dtype not in (np.uint32, np.uint64) or k.size != n_keys:
+            raise ValueError("a pass's keys are n_keys of uint32 or uint64")
+    sp = (_lib.SortPass * len(passes))(*[_lib.SortPass(k.ctypes.data, int(k.dtype == np.uint64), bits)
+                                         for k, (_, bits) in zip(arrays, passes)])
+    order = np.empty(p.size, dtype=np.uint32)
+    sorted_keys = np.empty(p.size, dtype=arrays[-1].dtype)
+    check(lib().impg_gpu_selftest_key_sort(device, n_keys, p.ctypes.data, p.size, int(first_in_order), C.cast(sp, C.c_void_p), len(passes),
+                                           order.ctypes.data, sorted_keys.ctypes.data))
+    return order, sorted_keys

@@ -1003,6 +1003,36 @@ int impg_synth_bed(uint64_t seed, size_t n, uint32_t n_seq, int32_t seq_len, int
  * pseudo-random keys of `end_bit` bits on `device` and checked on the host: a permutation, keys non-decreasing, equal keys
  * in index order.  IMPG_OK or IMPG_E_INVALID with the first offending place in impg_gpu_last_error(). */
 int impg_gpu_selftest_order_sort(int device, uint32_t n, unsigned end_bit, uint64_t seed);
+/* Diagnostics: the device primitives under every stage on arrays the caller brings (impg_amd/csrc/prims_selftest.hip).  Each
+ * returns the device's raw answer and compares nothing, but for the scan's guards.
+ *
+ * impg_gpu_selftest_scan: the exclusive scan of in[n] (n > 0).  which = 0: launch_exclusive_scan as the engine's scans call
+ * it (scratch of scan_scratch_bytes(n), a stream of its own, one synchronisation); which = 1: launch_small_scan, the
+ * small-batch path's single block (n <= 1024; its total is 32-bit).  The device copies of in and out start in_shift /
+ * out_shift words (0 .. 4) behind a 256-byte boundary: which = 0 runs the single-pass look-back kernel when both are
+ * 16-byte aligned and the three kernels otherwise.  out[n]: the offsets written (the low 32 bits of the 64-bit prefixes),
+ * *total: the sum.  info[5] = {the form that ran -- 0 look-back, 1 three kernels, 2 the small scan --, the low four bits of
+ * in's device address, of out's, the look-back tile, the three-kernel tile (items)}.  64 words of 0xA5A5A5A5 stand in front
+ * of out, behind out and behind the scratch: IMPG_E_INVALID, naming the guard, if one of them changed.
+ *
+ * impg_gpu_selftest_offsets: prims::offsets_and_total on len[n] (n > 0) -- off[n] = the exclusive sums in 64 bits, *total
+ * their total; with_host_copy: through the form that brings the offsets home itself (it reads the total from that copy).
+ *
+ * impg_gpu_selftest_key_sort: prims::KeySort::run, the stable sort by 1 .. 3 keys, least significant first.  A pass's keys
+ * (n_keys of 32 or, wide, 64 bits) stand at the rows' own indices, only their low `bits` bits count; perm[m] lists the rows
+ * to sort (each < n_keys; first_in_order: the identity with m = n_keys, the first pass then sorts in place).  order[m] = the
+ * sorted permutation, ties in incoming order; sorted_keys[m] (of the last pass's width) = the last pass's keys in that order.
+ * The keys are copied: the caller's arrays stay as they are. */
+typedef struct {
+  const void *keys;
+  int wide;
+  unsigned bits;
+} impg_gpu_sort_pass_t;
+int impg_gpu_selftest_scan(int device, int which, const uint32_t *in, uint32_t n, uint32_t in_shift, uint32_t out_shift, uint32_t *out,
+                           uint64_t *total, uint32_t *info);
+int impg_gpu_selftest_offsets(int device, const uint32_t *len, uint32_t n, int with_host_copy, uint64_t *off, uint64_t *total);
+int impg_gpu_selftest_key_sort(int device, uint32_t n_keys, const uint32_t *perm, uint32_t m, int first_in_order,
+                               const impg_gpu_sort_pass_t *passes, uint32_t n_passes, uint32_t *order, void *sorted_keys);
 /* Diagnostics: the device BED merges and text of impg_gpu_query_batch_bed (impg_amd/csrc/bed_device.hip) on rows the
  * caller brings instead of a query's.  rows[i] belongs to range row_range[i] < n_ranges; array order within a range is
  * the emission order the reference's tie rules refer to, rows of different ranges may interleave.  n_seq: the id
