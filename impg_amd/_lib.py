@@ -229,6 +229,10 @@ SYMBOLS = [
     ("impg_gpu_partition_next_windows", C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("impg_gpu_partition_window", C.c_int, [_P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("impg_gpu_partition_run", C.c_int, [_P, C.c_char_p, C.c_int, C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]),
+    ("impg_gpu_partition_run_fasta", C.c_int, [_P, C.c_char_p, C.POINTER(C.c_uint64)]),
+    ("impg_gpu_partition_window_fasta", C.c_int, [_P, _P, C.c_int, C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    ("impg_gpu_partition_rows_fasta", C.c_int, [_P, _P, C.c_size_t, C.c_int, C.POINTER(_P), C.POINTER(C.c_size_t)]),
+    ("impg_gpu_partition_fasta_text", C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t, C.POINTER(_P), C.POINTER(C.c_size_t)]),
     ("impg_gpu_partition_regions", _P, [_P]),
     ("impg_gpu_partition_counter", C.c_int, [_P, C.c_char_p, C.POINTER(C.c_int64)]),
     ("impg_gpu_partition_destroy", None, [_P]),

@@ -102,7 +102,8 @@ void usage() {
           "               [--order coitrees|sorted] [--device N]\n"
           "impg-gpu partition (-a <paf>... | -i <file>) -w <bp> -d <bp> [--min-missing-size N] [--min-boundary-distance N]\n"
           "               [--selection-mode longest|total|sample[,sep]|haplotype[,sep]] [--starting-sequences-file FILE]\n"
-          "               [--separate-files] [--no-rehome-singletons] [--output-folder DIR] [-o bed] [--host-state] [-m N]\n"
+          "               [--separate-files] [--no-rehome-singletons] [--output-folder DIR] [-o bed|fasta] [--host-state] [-m N]\n"
+          "               [--sequence-files F... | --sequence-list FILE] [--sequence-store bytes|packed|auto] [--reverse-complement]\n"
           "               [--transitive-dfs] [--min-transitive-len N] [--min-distance-between-ranges N] [--min-identity F]\n"
           "               [--unidirectional] [--order coitrees|sorted] [--device N]\n"
           "impg-gpu refine (-a <paf>... | -i <file>) (-r seq:start-end | -b <bed>) (-d <bp> | --no-merge) [--span-bp N]\n"
@@ -149,12 +150,16 @@ std::vector<uint8_t> load_subset_keep(impg_gpu_index_t *ix, const std::string &s
 }
 
 // `impg partition` (reference src/main.rs partition arguments; src/commands/partition.rs:158-712) with BED output:
-// partitions.bed (or partition{N}.bed with --separate-files) in --output-folder, as the reference writes them.
+// partitions.bed (or partition{N}.bed with --separate-files) in --output-folder, as the reference writes them; or with
+// FASTA output, partition{N}.fasta (--separate-files only, main.rs:6366-6376) from --sequence-files / --sequence-list.
 int partition_main(int argc, char **argv) {
   std::vector<std::string> pafs;
   std::string index_file, ofmt = "bed", mode = "longest", starting, folder;
   long long window = -1, merge_d = 0, v = 0;
   bool have_d = false, no_merge = false, dfs = false, unidirectional = false, separate = false, rehome = true, host_state = false;
+  std::vector<std::string> seq_files;
+  std::string seq_list;
+  int sequence_store = 0;
   long max_depth = 2, min_tl = -1, mdbr = 10, min_missing = 3000, min_boundary = 3000;
   double min_ident = NAN;
   int device = 0, order = IMPG_ORDER_COITREES;
@@ -190,6 +195,15 @@ int partition_main(int argc, char **argv) {
     else if (a == "--output-folder") folder = need(a.c_str());
     else if (a == "-o" || a == "--output-format") ofmt = need("-o");
     else if (a == "--host-state") host_state = true;
+    else if (a == "--sequence-files") {
+      seq_files.push_back(need(a.c_str()));
+      while (i + 1 < argc && argv[i + 1][0] != '-') seq_files.push_back(argv[++i]);
+    } else if (a == "--sequence-list") seq_list = need(a.c_str());
+    else if (a == "--sequence-store") {  // the form the sequences take in HBM (option "sequence_store_packed"); --host-state prints from the host copy
+      const std::string sv = need(a.c_str());
+      if (sv != "bytes" && sv != "packed" && sv != "auto") die("invalid value '" + sv + "' for '--sequence-store'", 2);
+      sequence_store = sv == "bytes" ? 0 : sv == "packed" ? 1 : 2;
+    } else if (a == "--reverse-complement") {}  // accepted as the reference accepts it: a partition's intervals are all forward
     else if (a == "--transitive-dfs") dfs = true;
     else if (a == "-m" || a == "--max-depth") max_depth = num(a, need("-m"), 0, 65535);
     else if (a == "--min-transitive-len") min_tl = num(a, need(a.c_str()), 0, 2147483647);
@@ -214,7 +228,20 @@ int partition_main(int argc, char **argv) {
   if (window == 0) die("--window-size must be greater than 0");
   if (!have_d && !no_merge) die("-d/--merge-distance is required. For `impg partition`, pass `-d <bp>`.");
   if (no_merge) die("--no-merge is not built in impg-gpu partition", 2);
-  if (ofmt != "bed") die("output format '" + ofmt + "' is not built in impg-gpu partition (bed): it needs sequence files", 2);
+  if (ofmt != "bed" && ofmt != "fasta") die("output format '" + ofmt + "' is not built in impg-gpu partition (bed, fasta)", 2);
+  const bool fasta = ofmt == "fasta";
+  if (fasta && !separate) die("Single-file output is only supported for BED format. Use --separate-files for FASTA format.");  // main.rs:6366-6376
+  if (!seq_files.empty() && !seq_list.empty()) die("Cannot specify both --sequence-files and --sequence-list");
+  if (!seq_list.empty()) {  // one path per line (main.rs:4130-4145)
+    std::ifstream in(seq_list);
+    if (!in) die("No such file or directory: " + seq_list);
+    std::string line;
+    while (std::getline(in, line)) {
+      while (!line.empty() && (line.back() == '\r' || line.back() == ' ' || line.back() == '\t')) line.pop_back();
+      if (!line.empty()) seq_files.push_back(line);
+    }
+  }
+  if (fasta && seq_files.empty()) die("FASTA index required for FASTA output");  // partition.rs:1640
   int selection = IMPG_SELECT_LONGEST;
   std::string kind = mode.substr(0, mode.find(',')), sep = mode.find(',') == std::string::npos ? "#" : mode.substr(mode.find(',') + 1);
   if (kind == "longest" && mode == kind) selection = IMPG_SELECT_LONGEST;
@@ -256,10 +283,21 @@ int partition_main(int argc, char **argv) {
   o.separator = sep.c_str();
   o.rehome_singletons = rehome;
   o.state_on_host = host_state;
+  if (fasta) {
+    std::vector<const char *> sp;
+    for (auto &f : seq_files) sp.push_back(f.c_str());
+    impg_gpu_sequences_t *seqs = nullptr;
+    if (impg_gpu_sequences_from_fasta(sp.data(), sp.size(), &seqs) != IMPG_OK) die(impg_gpu_last_error());
+    if (impg_gpu_set_option(ix, "sequence_store_packed", sequence_store) != IMPG_OK) die(impg_gpu_last_error());
+    if (impg_gpu_index_set_sequences(ix, seqs) != IMPG_OK) die(impg_gpu_last_error());
+    impg_gpu_sequences_free(seqs);  // (the handle shares the store)
+  }
   impg_gpu_partition_t *ps = nullptr;
   if (impg_gpu_partition_create(ix, &p, &o, start_ids.data(), start_ids.size(), &ps) != IMPG_OK) die(impg_gpu_last_error());
   uint64_t n_parts = 0;
-  if (impg_gpu_partition_run(ps, folder.empty() ? nullptr : folder.c_str(), separate, nullptr, nullptr, &n_parts) != IMPG_OK) die(impg_gpu_last_error());
+  if (fasta) {
+    if (impg_gpu_partition_run_fasta(ps, folder.empty() ? nullptr : folder.c_str(), &n_parts) != IMPG_OK) die(impg_gpu_last_error());
+  } else if (impg_gpu_partition_run(ps, folder.empty() ? nullptr : folder.c_str(), separate, nullptr, nullptr, &n_parts) != IMPG_OK) die(impg_gpu_last_error());
   fprintf(stderr, "[impg-gpu] partitioned into %llu regions\n", (unsigned long long)n_parts);
   impg_gpu_partition_destroy(ps);
   impg_gpu_index_destroy(ix);

@@ -429,6 +429,14 @@ uint32_t device_fasta_selftest_rows(Engine &E, const impg_gpu_index &ix, const i
 // its sequence) are raised before any text is delivered.  Counts into the handle's fasta_* counters.
 void device_fasta_text(Engine &E, const impg_gpu_index &ix, const DevBuf &rows, uint32_t n_rows, bool reverse_complement,
                        const std::function<void(const char *, size_t)> &sink);
+// `impg partition -o fasta`: n final intervals of one window (PIv, partition.hpp) where they lie in HBM as FASTA records
+// under the partition body rule (no bases: the header alone), in byte-window pieces through a stream its caller keeps
+// (TextStream, text_device.hpp; hint: the size to give its buffers, at most a piece).  Refusals as above; counts into
+// the handle's fasta_records / fasta_text_pieces / fasta_text_bytes without resetting them.
+struct PIv;
+struct TextStream;
+void device_partition_fasta(Engine &E, const impg_gpu_index &ix, TextStream &S, const PIv *d_rows, uint32_t n, unsigned long long hint,
+                            const std::function<void(const char *, size_t)> &sink);
 // the store's bases in HBM for the handle's ids (impg_gpu_index_set_sequences); the handle's seq_store is set
 void upload_sequences(impg_gpu_index &ix);
 // the names BED rows print for ranges [b, e): the caller's, else "{chrom}:{start}-{end}" (partition.rs:1741, :1762)

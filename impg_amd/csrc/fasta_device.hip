@@ -11,9 +11,9 @@
 //             (fasta_pack_kernel, upload_packed).  The kernels below are the same ones: the write kernel is a template on
 //             the store's form and differs in where a lane's 16 source bases come from -- 32 bits of the stream turned into
 //             letters in registers, the runs' bytes laid over them -- and nowhere else; the text is the same byte for byte.
-//   lengths   one thread per record: header + body, body = L + ceil(L / 80) bytes (a single '\n' for L = 0); the same thread
-//             marks the first record whose sequence the store lacks, or whose row leaves its sequence -- refused before any
-//             text is written.
+//   lengths   one thread per record: header + body, body = L + ceil(L / 80) bytes (a single '\n' for L = 0 -- nothing at all
+//             under the partition body rule, below); the same thread marks the first record whose sequence the store lacks,
+//             or whose row leaves its sequence -- refused before any text is written.
 //   text      a record is megabytes of bases, not forty bytes of fields: the write kernel's grid covers the piece's BYTES,
 //             each lane 16 consecutive ones, aligned in the piece buffer.  A lane finds its record in the piece's offsets
 //             (one search for the wave's first byte and one for its last; a search of its own only when those differ).  A
@@ -21,6 +21,12 @@
 //             before and behind it are one contiguous run of the source, read with two aligned 16-byte loads and shifted
 //             into place (read backwards and complemented for "/rc"), the '\n' spliced in, one 16-byte store.  Every other
 //             lane -- headers, a record's last bytes, records a few bytes long -- computes its bytes one at a time.
+//   partition `impg partition -o fasta` (write_partition_fasta, partition.rs:1630-1680; device_partition_fasta below) prints
+//             a window's final intervals from where DeviceRegions::apply leaves them: one kernel makes them the writer's
+//             records, the length kernel takes the partition body rule -- a record of no bases is its header alone -- and
+//             the write kernel its byte-window form: the piece is bytes [base, base + n_bytes) of the text wherever that
+//             falls, its first record may begin before it and its last may end behind it, and every record's length is
+//             its own (off[r + 1] - off[r], the last record's included), never the piece's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -30,6 +36,7 @@
 
 #include "device_prims.hpp"
 #include "engine.hpp"
+#include "partition.hpp"
 #include "text_device.hpp"
 
 namespace impg {
@@ -72,9 +79,11 @@ constexpr uint32_t FASTA_OK = 0xFFFFFFFFu;  // no record to refuse
 __device__ __forceinline__ uint32_t fasta_header_len(const TextTables &t, const BedRow &x, bool flip) {
   return 1u + seq_text_len(t, x.query_id) + 1u + dec_digits((uint32_t)x.start) + 1u + dec_digits((uint32_t)x.end) + (flip ? 3u : 0u) + 1u;
 }
-__device__ __forceinline__ uint32_t fasta_body_len(uint32_t L) { return L ? L + (L + 79u) / 80u : 1u; }
+// PART: the partition body rule (chunks(80) of nothing prints nothing); else output_results_fasta's empty line
+template <bool PART> __device__ __forceinline__ uint32_t fasta_body_len(uint32_t L) { return L ? L + (L + 79u) / 80u : PART ? 0u : 1u; }
 
 // bad[0] / bad[1]: the first record on a sequence the store lacks / that leaves its sequence
+template <bool PART>
 __global__ __launch_bounds__(256) void fasta_len_kernel(const BedRow *__restrict__ rows, uint32_t n, TextTables t, FastaStore st, int reverse_complement,
                                                         uint32_t *__restrict__ len, uint32_t *__restrict__ bad) {
   const uint32_t r = blockIdx.x * 256u + threadIdx.x;
@@ -85,7 +94,14 @@ __global__ __launch_bounds__(256) void fasta_len_kernel(const BedRow *__restrict
   else if (x.start < 0 || x.end < x.start || (uint32_t)x.end > st.len[x.query_id]) atomicMin(&bad[1], r);
   const bool flip = reverse_complement && (x.q_strand >> 31);
   const uint32_t L = x.end >= x.start ? (uint32_t)(x.end - x.start) : 0u;
-  len[r] = fasta_header_len(t, x, flip) + fasta_body_len(L);
+  len[r] = fasta_header_len(t, x, flip) + fasta_body_len<PART>(L);
+}
+// a window's final intervals (DeviceRegions::out_rows) as the writer's records: forward, no range
+__global__ __launch_bounds__(256) void fasta_piv_rows_kernel(const PIv *__restrict__ in, uint32_t n, BedRow *__restrict__ rows) {
+  const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+  if (r >= n) return;
+  const PIv x = in[r];
+  rows[r] = BedRow{0u, x.seq, x.lo, x.hi};
 }
 
 // digit `pos` (0 = the leading one) of v, which prints with `digits` digits
@@ -157,7 +173,8 @@ __device__ __forceinline__ unsigned char store_base(const PackedStore &st, uint3
   return (unsigned char)(ACGT >> (8u * ((st.words[P >> 4] >> ((unsigned)(P & 15ull) * 2u)) & 3u)));
 }
 
-// byte x of a record: its header, then its body
+// byte x of a record rec_len bytes long: its header, then its body (a record without a body -- no bases under the partition
+// body rule -- has rec_len == hl and is never asked for one)
 template <class Store>
 __device__ unsigned char fasta_byte(const TextTables &t, const Store &st, const BedRow &row, bool flip, uint32_t hl, u64 rec_len, u64 x) {
   if (x >= hl) {
@@ -213,7 +230,10 @@ __device__ __forceinline__ u128 load16_any(const unsigned char *base, u64 at) {
 
 // records [0, n_rec) of a piece: record r at out + (off[r] - base), the piece n_bytes long.  One lane per 16 bytes.
 // Store: FastaStore or PackedStore -- the two differ in where a lane's 16 source bases come from, and in fasta_byte's.
-template <class Store>
+// WINDOW: the byte-window form.  The piece is bytes [base, base + n_bytes) of a longer text: off[0] <= base (record 0 may
+// begin before the piece, off[r] - base wraps round and every use of it below is modular), off[n_rec] >= base + n_bytes is
+// there to be read, and a record's length is off[r + 1] - off[r] even where it runs on behind the piece.
+template <class Store, bool WINDOW>
 __global__ __launch_bounds__(256) void fasta_write_kernel(const BedRow *__restrict__ rows, uint32_t n_rec, TextTables t, Store st,
                                                           int reverse_complement, const u64 *__restrict__ off, u64 base, u64 n_bytes,
                                                           char *__restrict__ out) {
@@ -231,9 +251,10 @@ __global__ __launch_bounds__(256) void fasta_write_kernel(const BedRow *__restri
   bool flip = reverse_complement && (row.q_strand >> 31);
   uint32_t hl = fasta_header_len(t, row, flip);
   u64 rec_at = off[r] - base;                                              // the record's first byte in the piece
-  u64 rec_len = (r + 1u < n_rec ? off[r + 1u] - base : n_bytes) - rec_at;
+  u64 rec_len = (WINDOW || r + 1u < n_rec ? off[r + 1u] - base : n_bytes) - rec_at;
   const u64 x0 = p - rec_at;
-  if (x0 >= hl && x0 + 16u < rec_len) {
+  // (WINDOW: the record may go on behind the piece, the buffer does not)
+  if (x0 >= hl && x0 + 16u < rec_len && (!WINDOW || p + 16u <= n_bytes)) {
     // 16 bytes of one body, its last byte not among them: at most one line break, at k (16: none)
     const u64 j0 = x0 - hl;
     const u64 line0 = j0 / 81u;
@@ -293,7 +314,7 @@ __global__ __launch_bounds__(256) void fasta_write_kernel(const BedRow *__restri
         flip = reverse_complement && (row.q_strand >> 31);
         hl = fasta_header_len(t, row, flip);
         rec_at += rec_len;
-        rec_len = (r + 1u < n_rec ? off[r + 1u] - base : n_bytes) - rec_at;
+        rec_len = (WINDOW || r + 1u < n_rec ? off[r + 1u] - base : n_bytes) - rec_at;
       }
       w[i >> 2] |= (uint32_t)fasta_byte(t, st, row, flip, hl, rec_len, g - rec_at) << (8u * (i & 3u));
     }
@@ -522,6 +543,45 @@ void upload_sequences(impg_gpu_index &ix) {
   ix.fasta_stats[FASTA_STORE_BYTES] = bytes;
 }
 
+namespace {
+
+// the store as the kernels take it, in both forms (the length kernel asks for presence and bounds only: one for both)
+struct StoreViews {
+  FastaStore st;
+  PackedStore pst;
+  StoreViews(const impg_gpu_index &ix, const TextTables &t)
+      : st{ix.d_seq_bases.as<unsigned char>(), ix.d_seq_off.as<u64>(), t.seq_len, std::min<uint32_t>((uint32_t)ix.store_of_id.size(), t.n_lens)},
+        pst{ix.d_seq_bases.as<uint32_t>(), st.off, st.len, st.n_ids, ix.d_seq_run_off.as<u64>(), ix.d_seq_runs.as<uint2>(),
+            ix.d_seq_run_byte.as<unsigned char>(), ix.d_seq_blk_off.as<u64>(), ix.d_seq_blk.as<uint32_t>()} {}
+};
+// what fasta_len_kernel marked: the first record on a sequence the store lacks, else the first that leaves its sequence
+void refuse_marked(const impg_gpu_index &ix, const BedRow *rows, const uint32_t *h_bad) {
+  if (h_bad[0] == FASTA_OK && h_bad[1] == FASTA_OK) return;
+  const bool lacks = h_bad[0] != FASTA_OK;
+  BedRow x;
+  IMPG_HIP(hipMemcpy(&x, rows + h_bad[lacks ? 0 : 1], sizeof x, hipMemcpyDeviceToHost));
+  const std::string name = x.query_id < ix.seq.names.size() ? ix.seq.names[x.query_id] : std::to_string(x.query_id);
+  if (lacks) throw Error{IMPG_E_INVALID, "Sequence '" + name + "' not found in the sequence store"};
+  throw Error{IMPG_E_INVALID, "row " + name + ":" + std::to_string(x.start) + "-" + std::to_string(x.end) + " leaves its sequence of " +
+                                  std::to_string(x.query_id < ix.seq.lens.size() ? ix.seq.lens[x.query_id] : 0) + " bases"};
+}
+// one piece's write kernel, of the form the attached store has; under the probe's switch between two events, with the
+// second copy behind it
+template <bool WINDOW>
+void write_piece(const impg_gpu_index &ix, const StoreViews &v, const TextTables &t, PieceTiming &timing, const BedRow *rows, uint32_t n_rec, int rc,
+                 const u64 *off, u64 base, u64 n_bytes, char *out, hipStream_t s) {
+  if (timing.on()) timing.mark(s);
+  if (ix.seq_packed) fasta_write_kernel<PackedStore, WINDOW><<<cdiv(n_bytes, 16u * 256u), 256, 0, s>>>(rows, n_rec, t, v.pst, rc, off, base, n_bytes, out);
+  else fasta_write_kernel<FastaStore, WINDOW><<<cdiv(n_bytes, 16u * 256u), 256, 0, s>>>(rows, n_rec, t, v.st, rc, off, base, n_bytes, out);
+  IMPG_HIP(hipGetLastError());
+  if (timing.on()) {
+    timing.mark(s);
+    timing.copy(out, n_bytes, s);
+  }
+}
+
+}  // namespace
+
 void device_fasta_text(Engine &E, const impg_gpu_index &ix, const DevBuf &rows, uint32_t n_rows, bool reverse_complement,
                        const std::function<void(const char *, size_t)> &sink) {
   if (!ix.seq_store) throw Error{IMPG_E_INVALID, "FASTA output needs a sequence store (impg_gpu_index_set_sequences)"};
@@ -530,53 +590,72 @@ void device_fasta_text(Engine &E, const impg_gpu_index &ix, const DevBuf &rows, 
   // (no range names, and the names as the index has them: --original-sequence-coordinates does not touch FASTA)
   TextTableBufs tb(E, ix, 0, std::vector<std::string>(), false, /*with_lengths=*/true);
   const TextTables t = tb.t;
-  const FastaStore st{ix.d_seq_bases.as<unsigned char>(), ix.d_seq_off.as<u64>(), t.seq_len, std::min<uint32_t>((uint32_t)ix.store_of_id.size(), t.n_lens)};
-  // (the length kernel asks the store for presence and bounds only: one kernel for both forms)
-  const PackedStore pst{ix.d_seq_bases.as<uint32_t>(), st.off, st.len, st.n_ids, ix.d_seq_run_off.as<u64>(), ix.d_seq_runs.as<uint2>(),
-                        ix.d_seq_run_byte.as<unsigned char>(), ix.d_seq_blk_off.as<u64>(), ix.d_seq_blk.as<uint32_t>()};
+  const StoreViews v(ix, t);
   const int rc = reverse_complement ? 1 : 0;
   DevBuf len, bad;
   len.reserve((size_t)n_rows * 4);
   bad.reserve(256);
   IMPG_HIP(hipMemsetAsync(bad.p, 0xFF, 8, s));
-  fasta_len_kernel<<<cdiv(n_rows, 256), 256, 0, s>>>(rows.as<BedRow>(), n_rows, t, st, rc, len.as<uint32_t>(), bad.as<uint32_t>());
+  fasta_len_kernel<false><<<cdiv(n_rows, 256), 256, 0, s>>>(rows.as<BedRow>(), n_rows, t, v.st, rc, len.as<uint32_t>(), bad.as<uint32_t>());
   uint32_t h_bad[2];
   std::vector<uint32_t> h_len(n_rows);
   IMPG_HIP(hipMemcpyAsync(h_bad, bad.p, 8, hipMemcpyDeviceToHost, s));
   IMPG_HIP(hipMemcpyAsync(h_len.data(), len.p, (size_t)n_rows * 4, hipMemcpyDeviceToHost, s));
   IMPG_HIP(hipStreamSynchronize(s));
-  if (h_bad[0] != FASTA_OK || h_bad[1] != FASTA_OK) {
-    const bool lacks = h_bad[0] != FASTA_OK;
-    BedRow x;
-    IMPG_HIP(hipMemcpy(&x, rows.as<BedRow>() + h_bad[lacks ? 0 : 1], sizeof x, hipMemcpyDeviceToHost));
-    const std::string name = x.query_id < ix.seq.names.size() ? ix.seq.names[x.query_id] : std::to_string(x.query_id);
-    if (lacks) throw Error{IMPG_E_INVALID, "Sequence '" + name + "' not found in the sequence store"};
-    throw Error{IMPG_E_INVALID, "row " + name + ":" + std::to_string(x.start) + "-" + std::to_string(x.end) + " leaves its sequence of " +
-                                    std::to_string(x.query_id < ix.seq.lens.size() ? ix.seq.lens[x.query_id] : 0) + " bases"};
-  }
+  refuse_marked(ix, rows.as<BedRow>(), h_bad);
   // the pieces' sizes, which the byte-centric grid needs: the records' offsets on the host
   std::vector<u64> h_off((size_t)n_rows + 1, 0);
   for (uint32_t r = 0; r < n_rows; r++) h_off[r + 1] = h_off[r] + h_len[r];
   PieceTiming timing;
   device_text_pieces(E, len.as<uint32_t>(), n_rows, "FASTA",
                      [&](uint32_t r0, uint32_t r1, const unsigned long long *off, unsigned long long base, char *out) {
-                       const u64 n_bytes = h_off[r1] - h_off[r0];
-                       auto write = [&]() {  // the kernel of the form the attached store has
-                         if (ix.seq_packed)
-                           fasta_write_kernel<PackedStore><<<cdiv(n_bytes, 16u * 256u), 256, 0, s>>>(rows.as<BedRow>() + r0, r1 - r0, t, pst, rc, off, base, n_bytes, out);
-                         else
-                           fasta_write_kernel<FastaStore><<<cdiv(n_bytes, 16u * 256u), 256, 0, s>>>(rows.as<BedRow>() + r0, r1 - r0, t, st, rc, off, base, n_bytes, out);
-                       };
-                       if (timing.on()) {
-                         timing.mark(s);
-                         write();
-                         timing.mark(s);
-                         timing.copy(out, n_bytes, s);
-                         return;
-                       }
-                       write();
+                       write_piece<false>(ix, v, t, timing, rows.as<BedRow>() + r0, r1 - r0, rc, off, base, h_off[r1] - h_off[r0], out, s);
                      },
                      sink, ix.fasta_stats[FASTA_TEXT_PIECES], ix.fasta_stats[FASTA_TEXT_BYTES]);
+  if (timing.on()) timing.report();
+}
+
+// `impg partition -o fasta`: the records of one window's final intervals, n of them at d_rows in HBM (forward, printed in
+// the order they lie in), under the partition body rule, cut into byte-window pieces.  S outlives the call: its tables
+// are uploaded and its buffers made at the first text, `hint` bytes large (and at most a piece) so that a later, longer
+// text finds them large enough.  Refusals as device_fasta_text's, raised before the sink sees a byte.
+void device_partition_fasta(Engine &E, const impg_gpu_index &ix, TextStream &S, const PIv *d_rows, uint32_t n, unsigned long long hint,
+                            const std::function<void(const char *, size_t)> &sink) {
+  if (!ix.seq_store) throw Error{IMPG_E_INVALID, "FASTA output needs a sequence store (impg_gpu_index_set_sequences)"};
+  if (!n) return;
+  hipStream_t s = E.stream;
+  if (!S.tables) {
+    S.tables = std::make_unique<TextTableBufs>(E, ix, 0, std::vector<std::string>(), false, /*with_lengths=*/true);
+    S.uploads++;
+  }
+  const TextTables t = S.tables->t;
+  const StoreViews v(ix, t);
+  prims::grow(S.rows, (size_t)n * sizeof(BedRow));
+  prims::grow(S.len, ((size_t)n + 1) * 4);
+  prims::grow(S.off, ((size_t)n + 1) * 8);
+  prims::grow(S.bad, 256);
+  BedRow *rows = S.rows.as<BedRow>();
+  IMPG_HIP(hipMemsetAsync(S.bad.p, 0xFF, 8, s));
+  IMPG_HIP(hipMemsetAsync(S.len.as<uint32_t>() + n, 0, 4, s));  // (the scan of n + 1 lengths leaves the total in off[n])
+  fasta_piv_rows_kernel<<<cdiv(n, 256), 256, 0, s>>>(d_rows, n, rows);
+  fasta_len_kernel<true><<<cdiv(n, 256), 256, 0, s>>>(rows, n, t, v.st, 0, S.len.as<uint32_t>(), S.bad.as<uint32_t>());
+  IMPG_HIP(hipGetLastError());
+  prims::exclusive_sum(S.stmp, S.len.as<uint32_t>(), S.off.as<u64>(), (size_t)n + 1, s);
+  uint32_t h_bad[2];
+  std::vector<u64> h_off((size_t)n + 1);
+  IMPG_HIP(hipMemcpyAsync(h_bad, S.bad.p, 8, hipMemcpyDeviceToHost, s));
+  IMPG_HIP(hipMemcpyAsync(h_off.data(), S.off.p, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, s));
+  IMPG_HIP(hipStreamSynchronize(s));
+  refuse_marked(ix, rows, h_bad);
+  const u64 PIECE = std::max<u64>((u64)E.opt.bed_text_piece_bytes, 1);
+  S.reserve((size_t)std::min<u64>(PIECE, std::max<u64>(h_off[n], hint)), s);
+  PieceTiming timing;
+  device_text_windows(E, S, h_off.data(), n,
+                      [&](uint32_t r0, uint32_t r1, unsigned long long base, unsigned long long n_bytes, char *out) {
+                        write_piece<true>(ix, v, t, timing, rows + r0, r1 - r0, 0, S.off.as<u64>() + r0, base, n_bytes, out, s);
+                      },
+                      sink, ix.fasta_stats[FASTA_TEXT_PIECES], ix.fasta_stats[FASTA_TEXT_BYTES]);
+  ix.fasta_stats[FASTA_RECORDS] += n;
   if (timing.on()) timing.report();
 }
 

@@ -416,6 +416,11 @@ void seq_exception_runs(const char *bases, size_t n, std::vector<SeqRun> &runs);
 struct SeqRef { const char *bases; uint64_t len; };
 void fasta_range_text(std::vector<impg_gpu_interval_t> &rows, int32_t merge_distance, bool reverse_complement,
                       const std::function<bool(uint32_t, std::string &, SeqRef &)> &fetch, std::string &text);
+// A partition's intervals -> FASTA records appended to `text` (write_partition_fasta, partition.rs:1630-1680): no sweep, every
+// row forward and printed where it stands, and a record of no bases is its header alone.  Every row is checked before
+// the first byte is appended; fetch and the refusals as above.
+void partition_fasta_text(const impg_gpu_partition_row_t *rows, size_t n, const std::function<bool(uint32_t, std::string &, SeqRef &)> &fetch,
+                          std::string &text);
 
 struct Engine;    // engine.hpp
 struct ShardCtx;  // sharded.cpp: this rank's part of an index sharded over GPUs

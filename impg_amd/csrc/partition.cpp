@@ -14,6 +14,7 @@
 #include <unordered_set>
 
 #include "partition.hpp"
+#include "text_device.hpp"
 
 namespace impg {
 void set_error(const std::string &msg);
@@ -313,8 +314,18 @@ static char *dup_text(const std::string &t, size_t *len) {
   if (len) *len = t.size();
   return p;
 }
-static void write_file(const char *folder, const std::string &name, const std::string &text) {
-  std::string path = name;
+static void write_all(int fd, const char *p, size_t n, const std::string &what) {
+  size_t at = 0;
+  while (at < n) {
+    const ssize_t k = write(fd, p + at, n - at);
+    if (k < 0 && errno == EINTR) continue;
+    if (k <= 0) throw Error{IMPG_E_IO, "write failed: " + what};
+    at += (size_t)k;
+  }
+}
+// folder/name created (the folder too) and opened for writing; `path` is what errors call it
+static int create_file(const char *folder, const std::string &name, std::string &path) {
+  path = name;
   if (folder && *folder) {
     if (mkdir(folder, 0777) != 0 && errno != EEXIST) {  // create_output_path (:16-28), one level at a time
       std::string f = folder;
@@ -326,6 +337,11 @@ static void write_file(const char *folder, const std::string &name, const std::s
   }
   const int fd = open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
   if (fd < 0) throw Error{IMPG_E_IO, "cannot create " + path};
+  return fd;
+}
+static void write_file(const char *folder, const std::string &name, const std::string &text) {
+  std::string path;
+  const int fd = create_file(folder, name, path);
   size_t at = 0;
   while (at < text.size()) {
     const ssize_t k = write(fd, text.data() + at, text.size() - at);
@@ -362,9 +378,14 @@ struct impg_gpu_partition {
   bool have_pending = false;
   DevBuf rows;
   int64_t c_windows = 0, c_partitions = 0, c_mask_uploads = 0, c_rows_to_host = 0, c_walk_windows = 0;
+  // FASTA output: the text stream lives as long as the session (made at its first FASTA window)
+  TextStream text;
+  unsigned long long text_hint = 0;  // the size its buffers get: no window prints more bases than the store holds
+  int64_t c_fasta_windows = 0, c_fasta_host_windows = 0;
   ~impg_gpu_partition() {
     if (engine) {
       (void)hipSetDevice(ix->device);
+      text.drop();
       rows.release();
       regions.d.reset();
       engine->masked = false;
@@ -730,6 +751,121 @@ int impg_gpu_partition_run(impg_gpu_partition_t *p, const char *folder, int sepa
   IMPG_CATCH
 }
 
+namespace {
+static_assert(sizeof(PIv) == sizeof(impg_gpu_partition_row_t), "PIv and impg_gpu_partition_row_t are one layout");
+// the host twin over the handle's own names and bases
+void host_rows_fasta(const impg_gpu_index &ix, const impg_gpu_partition_row_t *rows, size_t n, std::string &text) {
+  if (!ix.seq_store) throw Error{IMPG_E_INVALID, "FASTA output needs a sequence store (impg_gpu_index_set_sequences)"};
+  const size_t at = text.size();
+  partition_fasta_text(rows, n, [&ix](uint32_t id, std::string &name, SeqRef &ref) {
+    name = id < ix.seq.names.size() ? ix.seq.names[id] : std::to_string(id);
+    const uint32_t s = id < ix.store_of_id.size() ? ix.store_of_id[id] : SEQ_ABSENT;
+    if (s == SEQ_ABSENT) return false;
+    const SeqStore &st = *ix.seq_store;
+    ref = SeqRef{st.bases.data() + st.off[s], st.off[s + 1] - st.off[s]};
+    return true;
+  }, text);
+  ix.fasta_stats[FASTA_RECORDS] += n;
+  ix.fasta_stats[FASTA_TEXT_BYTES] += text.size() - at;
+}
+// One window: query, update, and the text of what the update left, to `sink`.  The window's rows are in regions.last.
+void window_fasta(impg_gpu_partition &p, const impg_gpu_range_t &w, const std::function<void(const char *, size_t)> &sink) {
+  impg_gpu_index &ix = *p.ix;
+  if (!ix.seq_store) throw Error{IMPG_E_INVALID, "FASTA output needs a sequence store (impg_gpu_index_set_sequences)"};
+  window(p, w, p.regions.last);
+  const std::vector<PIv> &rows = p.regions.last;
+  if (rows.empty()) return;
+  p.c_partitions++;
+  if (p.engine) {
+    if (!p.text_hint) {
+      const unsigned long long bases = ix.seq_store->bases.size();
+      p.text_hint = bases + bases / 80 + 4096;
+    }
+    // (the rows the update left in HBM: DeviceRegions::apply has copied them to `last` and waited for the stream)
+    device_partition_fasta(*p.engine, ix, p.text, p.regions.d->out_rows.as<PIv>(), (uint32_t)rows.size(), p.text_hint, sink);
+    p.c_fasta_windows++;
+    // IMPG_PARTITION_TEXT_STREAM_PER_WINDOW (a probe's switch, read on every window): the stream is dropped behind every
+    // window, as a per-call writer would allocate it -- what the session-lived stream is measured against
+    const char *per_window = getenv("IMPG_PARTITION_TEXT_STREAM_PER_WINDOW");
+    if (per_window && *per_window && *per_window != '0') p.text.drop();
+    return;
+  }
+  std::string t;
+  host_rows_fasta(ix, reinterpret_cast<const impg_gpu_partition_row_t *>(rows.data()), rows.size(), t);
+  p.c_fasta_host_windows++;
+  sink(t.data(), t.size());
+}
+}  // namespace
+
+int impg_gpu_partition_window_fasta(impg_gpu_partition_t *p, const impg_gpu_range_t *w, int fd, char **text, size_t *len, size_t *n_rows) {
+  IMPG_TRY
+  if (!p || !w || !n_rows || (text && !len)) throw Error{IMPG_E_INVALID, "null argument"};
+  if (text) *text = nullptr;
+  *n_rows = 0;
+  p->regions.last.clear();
+  std::string out;
+  window_fasta(*p, *w, [&](const char *b, size_t k) {
+    if (text) out.append(b, k);
+    else write_all(fd, b, k, "the window's FASTA text");
+  });
+  *n_rows = p->regions.last.size();
+  if (text && *n_rows) *text = dup_text(out, len);
+  else if (len) *len = 0;
+  return IMPG_OK;
+  IMPG_CATCH
+}
+
+int impg_gpu_partition_run_fasta(impg_gpu_partition_t *p, const char *folder, uint64_t *n_partitions) {
+  IMPG_TRY
+  if (!p) throw Error{IMPG_E_INVALID, "null argument"};
+  const impg_gpu_index &ix = *p->ix;
+  if (!ix.seq_store) throw Error{IMPG_E_INVALID, "FASTA output needs a sequence store (impg_gpu_index_set_sequences)"};
+  for (size_t id = 0; id < ix.seq.lens.size(); id++)  // every sequence is partitioned eventually: refuse now, not hours in
+    if (ix.seq.lens[id] > 0 && (id >= ix.store_of_id.size() || ix.store_of_id[id] == SEQ_ABSENT))
+      throw Error{IMPG_E_INVALID, "Sequence '" + (id < ix.seq.names.size() ? ix.seq.names[id] : std::to_string(id)) + "' not found in the sequence store"};
+  uint64_t num = 0;
+  std::vector<impg_gpu_range_t> w;
+  for (;;) {
+    next_windows(*p, w);
+    p->have_pending = false;
+    p->pending.clear();
+    if (w.empty()) break;
+    for (const impg_gpu_range_t &r : w) {
+      struct Out { int fd = -1; std::string path; ~Out() { if (fd >= 0) close(fd); } } out;
+      window_fasta(*p, r, [&](const char *b, size_t k) {
+        if (out.fd < 0) out.fd = create_file(folder, "partition" + std::to_string(num) + ".fasta", out.path);  // (at the first byte: a refused window leaves no file)
+        write_all(out.fd, b, k, out.path);
+      });
+      if (!p->regions.last.empty()) num++;
+    }
+  }
+  if (n_partitions) *n_partitions = num;
+  return IMPG_OK;
+  IMPG_CATCH
+}
+
+int impg_gpu_partition_rows_fasta(impg_gpu_index_t *ix, const impg_gpu_partition_row_t *rows, size_t n, int on_host, char **text, size_t *len) {
+  IMPG_TRY
+  if (!ix || !text || !len || (n && !rows)) throw Error{IMPG_E_INVALID, "null argument"};
+  if (ix->shard || ix->cluster) throw Error{IMPG_E_UNSUPPORTED, "device-side FASTA on a sharded index"};
+  if (!ix->seq_store) throw Error{IMPG_E_INVALID, "FASTA output needs a sequence store (impg_gpu_index_set_sequences)"};
+  if (n >= (1ull << 30)) throw Error{IMPG_E_UNSUPPORTED, "more than 2^30 rows in one call"};
+  std::string out;
+  if (on_host) host_rows_fasta(*ix, rows, n, out);
+  else if (n) {
+    IMPG_HIP(hipSetDevice(ix->device));
+    EngineLease lease(*ix);
+    TextStream S;  // (this call's own: made and freed here)
+    DevBuf d_rows;
+    d_rows.reserve(n * sizeof(PIv));
+    IMPG_HIP(hipMemcpyAsync(d_rows.p, rows, n * sizeof(PIv), hipMemcpyHostToDevice, lease->stream));
+    device_partition_fasta(*lease, *ix, S, d_rows.as<PIv>(), (uint32_t)n, 0, [&](const char *b, size_t k) { out.append(b, k); });
+  }
+  *text = dup_text(out, len);
+  return IMPG_OK;
+  IMPG_CATCH
+}
+
 impg_gpu_regions_t *impg_gpu_partition_regions(impg_gpu_partition_t *p) { return p ? &p->regions : nullptr; }
 
 int impg_gpu_partition_counter(const impg_gpu_partition_t *p, const char *key, int64_t *value) {
@@ -741,6 +877,10 @@ int impg_gpu_partition_counter(const impg_gpu_partition_t *p, const char *key, i
   else if (k == "mask_uploads") *value = p->c_mask_uploads;
   else if (k == "rows_to_host") *value = p->c_rows_to_host;
   else if (k == "walk_windows") *value = p->c_walk_windows;
+  else if (k == "fasta_windows") *value = p->c_fasta_windows;
+  else if (k == "fasta_host_windows") *value = p->c_fasta_host_windows;
+  else if (k == "text_buffer_allocs") *value = (int64_t)p->text.allocs;
+  else if (k == "text_table_uploads") *value = (int64_t)p->text.uploads;
   else if (k == "step_launches") *value = p->regions.d ? (int64_t)p->regions.d->launches : 0;
   else throw Error{IMPG_E_INVALID, "unknown counter: " + k};
   return IMPG_OK;

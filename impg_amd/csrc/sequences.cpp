@@ -130,6 +130,45 @@ void fasta_range_text(std::vector<impg_gpu_interval_t> &rows, int32_t merge_dist
   }
 }
 
+void partition_fasta_text(const impg_gpu_partition_row_t *rows, size_t n, const std::function<bool(uint32_t, std::string &, SeqRef &)> &fetch,
+                          std::string &text) {
+  std::string name;
+  std::vector<SeqRef> refs(n, SeqRef{nullptr, 0});
+  size_t bytes = 0;
+  for (int pass = 0; pass < 2; pass++)  // as the device route marks them: a sequence the store lacks first, then a row that leaves its own
+    for (size_t i = 0; i < n; i++) {
+      const impg_gpu_partition_row_t &x = rows[i];
+      name.clear();
+      const bool have = fetch(x.seq_id, name, refs[i]);
+      if (pass == 0) {
+        if (!have) throw Error{IMPG_E_INVALID, "Sequence '" + name + "' not found in the sequence store"};
+        continue;
+      }
+      if (x.start < 0 || x.end < x.start || (uint64_t)x.end > refs[i].len)
+        throw Error{IMPG_E_INVALID, "row " + name + ":" + std::to_string(x.start) + "-" + std::to_string(x.end) + " leaves its sequence of " +
+                                        std::to_string(refs[i].len) + " bases"};
+      const size_t L = (size_t)(x.end - x.start);
+      bytes += name.size() + 32 + L + (L + 79) / 80;
+    }
+  text.reserve(text.size() + bytes);
+  char buf[64];
+  for (size_t i = 0; i < n; i++) {
+    const impg_gpu_partition_row_t &x = rows[i];
+    name.clear();
+    fetch(x.seq_id, name, refs[i]);
+    text += '>';
+    text += name;
+    const int k = snprintf(buf, sizeof buf, ":%u-%u\n", (uint32_t)x.start, (uint32_t)x.end);
+    text.append(buf, (size_t)k);
+    const size_t L = (size_t)(x.end - x.start);
+    const char *b = refs[i].bases + x.start;
+    for (size_t at = 0; at < L; at += 80) {  // (chunks(80) of nothing: a record of no bases is its header alone, partition.rs:1672-1676)
+      text.append(b + at, std::min<size_t>(80, L - at));
+      text += '\n';
+    }
+  }
+}
+
 }  // namespace impg
 
 using namespace impg;
@@ -249,6 +288,30 @@ int impg_gpu_fasta_text(const impg_gpu_sequences_t *seqs, const char *const *nam
   std::vector<impg_gpu_interval_t> v(rows, rows + n);
   std::string out;
   fasta_range_text(v, merge_distance, reverse_complement != 0, [&](uint32_t id, std::string &name, SeqRef &ref) {
+    if (id >= n_ids || !names_of_ids[id]) { name = std::to_string(id); return false; }
+    name = names_of_ids[id];
+    const auto it = st.by_name.find(name);
+    if (it == st.by_name.end()) return false;
+    ref = SeqRef{st.bases.data() + st.off[it->second], st.off[it->second + 1] - st.off[it->second]};
+    return true;
+  }, out);
+  char *t = (char *)malloc(out.size() + 1);
+  if (!t) throw Error{IMPG_E_OOM, "host out of memory"};
+  memcpy(t, out.data(), out.size());
+  t[out.size()] = 0;
+  *text = t;
+  *len = out.size();
+  return IMPG_OK;
+  IMPG_CATCH
+}
+
+int impg_gpu_partition_fasta_text(const impg_gpu_sequences_t *seqs, const char *const *names_of_ids, size_t n_ids,
+                                  const impg_gpu_partition_row_t *rows, size_t n, char **text, size_t *len) {
+  IMPG_TRY
+  if (!seqs || !text || !len || (n && !rows) || (n_ids && !names_of_ids)) throw Error{IMPG_E_INVALID, "null argument"};
+  const SeqStore &st = *seqs->s;
+  std::string out;
+  partition_fasta_text(rows, n, [&](uint32_t id, std::string &name, SeqRef &ref) {
     if (id >= n_ids || !names_of_ids[id]) { name = std::to_string(id); return false; }
     name = names_of_ids[id];
     const auto it = st.by_name.find(name);

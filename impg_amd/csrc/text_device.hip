@@ -93,4 +93,76 @@ void device_text_pieces(Engine &E, const uint32_t *d_len, uint32_t n_rows, const
   }
 }
 
+void TextStream::reserve(size_t bytes, hipStream_t s) {
+  for (int k = 0; k < 2; k++)
+    if (!done[k]) IMPG_HIP(hipEventCreateWithFlags(&done[k], hipEventDisableTiming));
+  bytes = std::max<size_t>(bytes, 256);
+  if (bytes <= cap) return;
+  IMPG_HIP(hipStreamSynchronize(s));  // (nothing of an earlier text is in flight; said once more where buffers go away)
+  for (int k = 0; k < 2; k++) {
+    if (pin[k]) { (void)hipHostFree(pin[k]); pin[k] = nullptr; }
+    cap = 0;
+    piece[k].reserve(bytes);
+    IMPG_HIP(hipHostMalloc((void **)&pin[k], bytes, hipHostMallocDefault));
+  }
+  cap = bytes;
+  allocs++;
+}
+
+void TextStream::drop() {
+  for (int k = 0; k < 2; k++) {
+    if (pin[k]) (void)hipHostFree(pin[k]);
+    if (done[k]) (void)hipEventDestroy(done[k]);
+    pin[k] = nullptr;
+    done[k] = nullptr;
+    piece[k].release();
+  }
+  for (DevBuf *d : {&rows, &len, &off, &bad, &stmp}) d->release();
+  tables.reset();
+  cap = 0;
+}
+
+void device_text_windows(Engine &E, TextStream &S, const unsigned long long *h_off, uint32_t n_rec,
+                         const std::function<void(uint32_t, uint32_t, unsigned long long, unsigned long long, char *)> &write,
+                         const std::function<void(const char *, size_t)> &sink, std::atomic<uint64_t> &pieces, std::atomic<uint64_t> &bytes) {
+  if (!n_rec) return;
+  hipStream_t s = E.stream;
+  const unsigned long long total = h_off[n_rec];
+  const unsigned long long PIECE = std::max<unsigned long long>((unsigned long long)E.opt.bed_text_piece_bytes, 1);
+  if (std::min(total, PIECE) > S.cap) throw Error{IMPG_E_INVALID, "internal: a text piece larger than the stream's buffers"};
+  struct Pending { size_t bytes; bool live; } pend[2] = {{0, false}, {0, false}};
+  // (a sink that throws leaves a copy in flight into a buffer the owner keeps: wait for it before anything else uses it)
+  struct Settle { hipStream_t s; ~Settle() { (void)hipStreamSynchronize(s); } } settle{s};
+  unsigned long long base = 0;
+  uint32_t r0 = 0;  // the record that holds byte `base`
+  int slot = 0;
+  while (base < total || pend[0].live || pend[1].live) {
+    if (base < total) {
+      const unsigned long long n_bytes = std::min(PIECE, total - base), end = base + n_bytes;
+      // records [r0, r1): r1 = the first record that starts at or behind the piece's end
+      const uint32_t r1 = (uint32_t)(std::lower_bound(h_off + r0 + 1, h_off + n_rec, end) - h_off);
+      write(r0, r1, base, n_bytes, S.piece[slot].as<char>());
+      IMPG_HIP(hipMemcpyAsync(S.pin[slot], S.piece[slot].p, (size_t)n_bytes, hipMemcpyDeviceToHost, s));
+      IMPG_HIP(hipEventRecord(S.done[slot], s));
+      pend[slot] = {(size_t)n_bytes, true};
+      pieces++;
+      bytes += n_bytes;
+      base = end;
+      r0 = h_off[r1] == end ? r1 : r1 - 1;  // (r1 = n_rec at the text's end: nothing follows)
+    }
+    // consume the OTHER slot's piece while this one is in flight (or drain at the end)
+    const int other = slot ^ 1;
+    if (pend[other].live) {
+      IMPG_HIP(hipEventSynchronize(S.done[other]));
+      pend[other].live = false;
+      sink(S.pin[other], pend[other].bytes);
+    } else if (base >= total && pend[slot].live) {
+      IMPG_HIP(hipEventSynchronize(S.done[slot]));
+      pend[slot].live = false;
+      sink(S.pin[slot], pend[slot].bytes);
+    }
+    slot ^= 1;
+  }
+}
+
 }  // namespace impg

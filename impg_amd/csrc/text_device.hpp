@@ -7,6 +7,7 @@
 
 #include <atomic>
 #include <functional>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -80,6 +81,36 @@ struct TextTableBufs {
 void device_text_pieces(Engine &E, const uint32_t *d_len, uint32_t n_rows, const char *what,
                         const std::function<void(uint32_t, uint32_t, const unsigned long long *, unsigned long long, char *)> &write,
                         const std::function<void(const char *, size_t)> &sink, std::atomic<uint64_t> &pieces, std::atomic<uint64_t> &bytes);
+
+// What device_text_pieces allocates per call, kept by an owner that makes many calls (a partition session: one text per
+// window): the tables of the index's names, the two piece buffers with their pinned twins and events, and the per-text
+// scratch.  Everything is made at the first text and freed with the owner; `allocs` counts how often the piece buffers
+// were allocated or grown, `uploads` how often the tables were uploaded.  The device is current when it dies.
+struct TextStream {
+  std::unique_ptr<TextTableBufs> tables;
+  DevBuf piece[2];
+  char *pin[2] = {nullptr, nullptr};
+  size_t cap = 0;  // of each of the four buffers
+  hipEvent_t done[2] = {nullptr, nullptr};
+  DevBuf rows, len, off, bad, stmp;  // a text's records, their lengths and offsets ([n + 1] each), the refusal marks
+  uint64_t allocs = 0, uploads = 0;
+  TextStream() = default;
+  TextStream(const TextStream &) = delete;
+  TextStream &operator=(const TextStream &) = delete;
+  ~TextStream() { drop(); }
+  void reserve(size_t bytes, hipStream_t s);  // room for pieces of `bytes` bytes; grows, never shrinks
+  void drop();
+};
+
+// A text of `total` bytes whose record r starts at byte h_off[r] (h_off[n_rec] = total; the same offsets lie on the
+// device), streamed to `sink` in pieces of exactly PIECE bytes (option bed_text_piece_bytes; the last one shorter),
+// cut wherever that falls -- inside a header, on a line break, inside a record that spans many pieces -- through
+// the stream's two pinned buffers.  write(r0, r1, base, n_bytes, out) enqueues the kernel that writes bytes
+// [base, base + n_bytes) of the text to `out`; records [r0, r1) are the ones that hold them.  No record is refused for
+// its length.  S.reserve() has been called with min(PIECE, total) or more.
+void device_text_windows(Engine &E, TextStream &S, const unsigned long long *h_off, uint32_t n_rec,
+                         const std::function<void(uint32_t, uint32_t, unsigned long long, unsigned long long, char *)> &write,
+                         const std::function<void(const char *, size_t)> &sink, std::atomic<uint64_t> &pieces, std::atomic<uint64_t> &bytes);
 
 // n_rows records of type Row (in `rows`, on the device) as text: the chunk's tables, len_kernel for every line's length,
 // then write_kernel piece by piece.  pieces / bytes: the format's two text counters.

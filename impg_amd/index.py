@@ -341,6 +341,20 @@ def fasta_text(sequences, names, rows, merge_distance=0, reverse_complement=Fals
         _lib.free(text)
 
 
+def partition_fasta_text(sequences, names, rows):
+    """impg_gpu_partition_fasta_text (host-only): a partition's intervals [(seq_id, start, end)] -> the records of its
+    partition{N}.fasta as bytes: no sweep, every row forward and printed where it stands, a record of no bases is its header
+    alone.  names[id] = the name of sequence id."""
+    a = np.array([tuple(r) for r in rows], dtype=_lib.PARTITION_ROW_DTYPE)
+    arr = (C.c_char_p * max(len(names), 1))(*[q.encode() if isinstance(q, str) else q for q in names])
+    text, ln = C.c_void_p(None), C.c_size_t(0)
+    check(lib().impg_gpu_partition_fasta_text(sequences._h, arr, len(names), a.ctypes.data, a.size, C.byref(text), C.byref(ln)))
+    try:
+        return _text_bytes(text, ln.value)
+    finally:
+        _lib.free(text)
+
+
 class GpuImpg:
     """`impl ImpgIndex` backed by the HIP engine."""
 
@@ -492,6 +506,26 @@ class GpuImpg:
             return s.run_text()[0]
         finally:
             s.close()
+
+    def partitions_fasta(self, folder, window_size, merge_distance, params=None, **kw):
+        """`impg partition -o fasta --separate-files`: folder/partition{N}.fasta per partition, from the attached sequence
+        store (set_sequences); returns the number of partitions."""
+        s = self.partition_session(window_size, merge_distance, params, **kw)
+        try:
+            return s.run_fasta(folder)
+        finally:
+            s.close()
+
+    def partition_rows_fasta(self, rows, on_host=False):
+        """impg_gpu_partition_rows_fasta: the partition FASTA writer over the caller's rows [(seq_id, start, end)], on the
+        device (uploaded, printed from the store in HBM in byte-window pieces) or by the host twin.  Returns bytes."""
+        a = np.array([tuple(r) for r in rows], dtype=_lib.PARTITION_ROW_DTYPE)
+        text, ln = C.c_void_p(None), C.c_size_t(0)
+        check(lib().impg_gpu_partition_rows_fasta(self._h, a.ctypes.data, a.size, int(bool(on_host)), C.byref(text), C.byref(ln)))
+        try:
+            return _text_bytes(text, ln.value)
+        finally:
+            _lib.free(text)
 
     def refine(self, loci, params=None, span_bp=1000, max_extension=0.5, extension_step=1000, merge_distance=0, level="sequence",
                separator="#", subset_keep=None, blacklist=None, on_host=False, names=None):
@@ -1255,6 +1289,27 @@ class PartitionSession:
         _lib.check(_lib.lib().impg_gpu_partition_run(self._h, None if folder is None else folder.encode(), int(separate_files), None, None,
                                                      C.byref(k)))
         return int(k.value)
+
+    def run_fasta(self, folder):
+        """The whole loop with FASTA output (impg_gpu_partition_run_fasta): folder/partition{N}.fasta per partition (None: the
+        working directory); returns the number of partitions."""
+        k = C.c_uint64(0)
+        _lib.check(_lib.lib().impg_gpu_partition_run_fasta(self._h, None if folder is None else os.fsencode(folder), C.byref(k)))
+        return int(k.value)
+
+    def window_fasta(self, seq_id, start, end, fd=None):
+        """Query, update and FASTA text for one window (impg_gpu_partition_window_fasta) -> (rows, text as bytes); with fd the
+        text is written there and None returned in its place.  No rows: no partition, no text (b"" / nothing written)."""
+        w = np.array([(seq_id, start, end)], dtype=_lib.RANGE_DTYPE)
+        n, ln, text = C.c_size_t(0), C.c_size_t(0), C.c_void_p(None)
+        _lib.check(_lib.lib().impg_gpu_partition_window_fasta(self._h, w.ctypes.data, -1 if fd is None else fd,
+                                                              C.byref(text) if fd is None else None, C.byref(ln), C.byref(n)))
+        try:
+            rows = self.regions()._rows(np.zeros(0, dtype=_lib.PARTITION_ROW_DTYPE), n.value)
+            return rows, (None if fd is not None else _text_bytes(text, ln.value) if n.value else b"")
+        finally:
+            if text:
+                _lib.free(text)
 
     def regions(self):
         return Regions(_borrowed=C.c_void_p(_lib.lib().impg_gpu_partition_regions(self._h)), _owner=self)

@@ -851,11 +851,47 @@ int impg_gpu_partition_window(impg_gpu_partition_t *, const impg_gpu_range_t *wi
  * reference); folder NULL = the working directory. */
 int impg_gpu_partition_run(impg_gpu_partition_t *, const char *folder, int separate_files, char **text, size_t *len,
                            uint64_t *n_partitions);
+/* ---- partition FASTA: `impg partition -o fasta --separate-files` (partition.rs:498-508, :1630-1680) ----------------
+ * One file per partition, folder/partition{N}.fasta, N as impg_gpu_partition_run numbers the same window under
+ * separate_files (a window that leaves no interval writes no file and takes no number; no rehoming).  A file holds one
+ * record per interval of its window, in the order impg_gpu_partition_window returns them: ">{name}:{start}-{end}\n" and
+ * bases [start, end) of the sequence as the attached store holds them, in lines of 80, each followed by '\n'.  A record
+ * of NO bases is its header line alone -- impg_gpu_query_batch_fasta prints an empty line there, the partition writer
+ * (chunks(80) of nothing) prints nothing.  Every interval is forward: there is no reverse_complement argument.  Names as
+ * the index has them, ids where it has none.  An interval on a sequence the store lacks, or one that leaves its sequence:
+ * IMPG_E_INVALID with impg_gpu_query_batch_fasta's messages, before any byte of that window's text is written.
+ * state_on_host = 0: the records are written ON THE DEVICE from the window's intervals where the update leaves them in
+ * HBM (no interval goes to the host for the text's sake) and the store in HBM, in either of its forms, and come to the
+ * host in pieces of exactly "bed_text_piece_bytes" bytes cut wherever that falls -- no record is refused for its length,
+ * unlike impg_gpu_query_batch_fasta's.  The session owns ONE text stream -- the name tables, two piece buffers in HBM,
+ * two pinned ones and two events -- made at its first FASTA window and freed with it.  state_on_host = 1: the host
+ * twin prints the same bytes from the store's host copy.  Sharded handles and tracepoint indexes take no store and are
+ * refused where they already are (impg_gpu_partition_create, impg_gpu_index_set_sequences).
+ *
+ * impg_gpu_partition_run_fasta: the whole loop.  Before the first window: IMPG_E_INVALID if the index has no store, or
+ * if a sequence of non-zero length is absent from it (the message names the first one: every sequence is partitioned
+ * eventually) -- the session has then run no window and its tables are untouched.  folder NULL = the working directory.
+ * impg_gpu_partition_window_fasta: query, update and text for one window; the text goes to fd, or is returned malloc'ed
+ * when text != NULL (fd is then ignored).  *n_rows = 0: no partition and no text.  After a refusal of a record there is
+ * no text, but the state HAS moved on, as the reference's would have: the window's rows stay with the session
+ * (impg_gpu_regions_last_rows). */
+int impg_gpu_partition_run_fasta(impg_gpu_partition_t *, const char *folder, uint64_t *n_partitions);
+int impg_gpu_partition_window_fasta(impg_gpu_partition_t *, const impg_gpu_range_t *window, int fd, char **text, size_t *len, size_t *n_rows);
+/* The partition writer over the caller's rows (start <= end), printed in the order given: on_host = 0 uploads them and
+ * runs the device route on an engine leased for the call, on_host = 1 the host twin.  *text is malloc'ed. */
+int impg_gpu_partition_rows_fasta(impg_gpu_index_t *, const impg_gpu_partition_row_t *rows, size_t n, int on_host, char **text, size_t *len);
+/* Host-only (no device needed), the sibling of impg_gpu_fasta_text: names_of_ids[id] = the name of sequence id. */
+int impg_gpu_partition_fasta_text(const impg_gpu_sequences_t *seqs, const char *const *names_of_ids, size_t n_ids,
+                                  const impg_gpu_partition_row_t *rows, size_t n, char **text, size_t *len);
 impg_gpu_regions_t *impg_gpu_partition_regions(impg_gpu_partition_t *); /* borrowed */
 /* "windows", "partitions", "mask_uploads" (host-to-device copies of mask tables) and "rows_to_host" (query rows copied
  * back): both read off the index's own counters, which are bumped where those copies are issued, as deltas around
  * the session's windows (queries other threads run on the handle meanwhile are counted in), "walk_windows" (windows the per-query walk answered), "step_launches" (kernel launches + rocPRIM calls of the
- * updates; a library sort or scan is several kernels and counts once) */
+ * updates; a library sort or scan is several kernels and counts once); of the FASTA calls: "fasta_windows" (windows
+ * printed on the device), "fasta_host_windows" (by the host twin), "text_buffer_allocs" (times the text stream's
+ * buffers were allocated or grown) and "text_table_uploads" (times its name tables were uploaded).  The index's
+ * "fasta_records" / "fasta_text_pieces" / "fasta_text_bytes" count the partition route's records, pieces and bytes on
+ * top of what they hold (the host twin has no pieces); the partition calls never reset them. */
 int impg_gpu_partition_counter(const impg_gpu_partition_t *, const char *key, int64_t *value);
 void impg_gpu_partition_destroy(impg_gpu_partition_t *);
 
