@@ -272,6 +272,11 @@ SYMBOLS = [
     ("impg_gpu_sequences_exceptions", C.c_int, [_P, C.c_size_t, _P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("impg_gpu_sequences_free", None, [_P]),
     ("impg_gpu_index_set_sequences", C.c_int, [_P, _P]),
+    ("impg_gpu_index_load_sequences", C.c_int, [_P, _P, C.c_size_t]),
+    ("impg_gpu_selftest_sequence_reader", C.c_int, [C.c_char_p, C.c_uint64, C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64),
+                                                    C.POINTER(C.c_uint64)]),
+    ("impg_gpu_selftest_sequence_ingest_host", C.c_int, [_P, C.c_size_t, _P, _P, C.c_size_t, C.c_uint64, C.c_int, _P, C.POINTER(_P),
+                                                         C.POINTER(C.c_size_t), _P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), _P]),
     ("impg_gpu_query_batch_fasta", C.c_int, [_P, _P, C.c_size_t, C.POINTER(Params), _P, C.c_int32, _P, C.c_int, C.POINTER(_P),
                                              C.POINTER(C.c_size_t), _P]),
     ("impg_gpu_query_batch_fasta_fd", C.c_int, [_P, _P, C.c_size_t, C.POINTER(Params), _P, C.c_int32, _P, C.c_int, C.c_int,

@@ -653,6 +653,7 @@ int impg_gpu_set_option(impg_gpu_index_t *ix, const char *key, int64_t value) {
   if (!ix || !key) throw Error{IMPG_E_INVALID, "null argument"};
   const OptionRow *row = option_row(key);
   if (!row) throw Error{IMPG_E_INVALID, std::string("unknown option ") + key};
+  if (!strcmp(key, "sequence_ingest_piece_bytes") && value % 16) throw Error{IMPG_E_INVALID, row->refusal};
   if (!option_store(ix->opt, *row, value)) throw Error{IMPG_E_INVALID, row->refusal};
   if (row->member || !value) return IMPG_OK;
   // the two keys that act instead of storing (options.hpp)
@@ -708,6 +709,8 @@ static const CounterRow COUNTER_TABLE[] = {
     CTR("fasta_text_pieces", fasta_stats[FASTA_TEXT_PIECES]), CTR("fasta_text_bytes", fasta_stats[FASTA_TEXT_BYTES]),
     CTR("fasta_store_bytes", fasta_stats[FASTA_STORE_BYTES]), CTR("fasta_store_packed", fasta_stats[FASTA_STORE_PACKED]),
     CTR("fasta_store_exception_runs", fasta_stats[FASTA_STORE_EXCEPTION_RUNS]),
+    CTR("sequence_ingest_pieces", ingest_stats[0]), CTR("sequence_ingest_text_bytes", ingest_stats[1]), CTR("sequence_ingest_bases", ingest_stats[2]),
+    CTR("sequence_ingest_inflated_blocks", ingest_stats[3]), CTR("sequence_ingest_dropped_sequences", ingest_stats[4]),
     CTR_RANKS("build_device", build_stats[BUILD_DEVICE]), CTR_RANKS("tokenized_device", build_stats[BUILD_TOKENIZED_DEVICE]),
     CTR_RANKS("build_batches", build_stats[BUILD_BATCHES]),
 };

@@ -98,12 +98,13 @@ void usage() {
           "               [--transitive-dfs] [--multi-impg] [--min-transitive-len N] [--min-distance-between-ranges N]\n"
           "               [-l N] [--min-result-identity F] [--subset-sequence-list FILE] [--original-sequence-coordinates]\n"
           "               [--consider-strandness] [-o auto|bed|bedpe|paf|fasta] [--sequence-files F... | --sequence-list FILE]\n"
-          "               [--reverse-complement] [--sequence-store bytes|packed|auto] [--host-merge] [--unidirectional]\n"
+          "               [--reverse-complement] [--sequence-store bytes|packed|auto] [--sequence-ingest host|device] [--host-merge] [--unidirectional]\n"
           "               [--order coitrees|sorted] [--device N]\n"
           "impg-gpu partition (-a <paf>... | -i <file>) -w <bp> -d <bp> [--min-missing-size N] [--min-boundary-distance N]\n"
           "               [--selection-mode longest|total|sample[,sep]|haplotype[,sep]] [--starting-sequences-file FILE]\n"
           "               [--separate-files] [--no-rehome-singletons] [--output-folder DIR] [-o bed|fasta] [--host-state] [-m N]\n"
           "               [--sequence-files F... | --sequence-list FILE] [--sequence-store bytes|packed|auto] [--reverse-complement]\n"
+          "               [--sequence-ingest host|device]\n"
           "               [--transitive-dfs] [--min-transitive-len N] [--min-distance-between-ranges N] [--min-identity F]\n"
           "               [--unidirectional] [--order coitrees|sorted] [--device N]\n"
           "impg-gpu refine (-a <paf>... | -i <file>) (-r seq:start-end | -b <bed>) (-d <bp> | --no-merge) [--span-bp N]\n"
@@ -160,6 +161,7 @@ int partition_main(int argc, char **argv) {
   std::vector<std::string> seq_files;
   std::string seq_list;
   int sequence_store = 0;
+  bool ingest_device = false;  // --sequence-ingest device: impg_gpu_index_load_sequences instead of _from_fasta + _set_sequences
   long max_depth = 2, min_tl = -1, mdbr = 10, min_missing = 3000, min_boundary = 3000;
   double min_ident = NAN;
   int device = 0, order = IMPG_ORDER_COITREES;
@@ -203,6 +205,10 @@ int partition_main(int argc, char **argv) {
       const std::string sv = need(a.c_str());
       if (sv != "bytes" && sv != "packed" && sv != "auto") die("invalid value '" + sv + "' for '--sequence-store'", 2);
       sequence_store = sv == "bytes" ? 0 : sv == "packed" ? 1 : 2;
+    } else if (a == "--sequence-ingest") {  // host: parsed on the host and attached; device: streamed into HBM and parsed there (gzip / BGZF too)
+      const std::string sv = need(a.c_str());
+      if (sv != "host" && sv != "device") die("invalid value '" + sv + "' for '--sequence-ingest'", 2);
+      ingest_device = sv == "device";
     } else if (a == "--reverse-complement") {}  // accepted as the reference accepts it: a partition's intervals are all forward
     else if (a == "--transitive-dfs") dfs = true;
     else if (a == "-m" || a == "--max-depth") max_depth = num(a, need("-m"), 0, 65535);
@@ -242,6 +248,8 @@ int partition_main(int argc, char **argv) {
     }
   }
   if (fasta && seq_files.empty()) die("FASTA index required for FASTA output");  // partition.rs:1640
+  if (ingest_device && host_state && fasta) die("--sequence-ingest device keeps no host copy of the sequences: --host-state cannot print FASTA from it", 2);
+  if (ingest_device && sequence_store == 2) die("--sequence-store auto needs the host's copy of the sequences: with --sequence-ingest device choose bytes or packed", 2);
   int selection = IMPG_SELECT_LONGEST;
   std::string kind = mode.substr(0, mode.find(',')), sep = mode.find(',') == std::string::npos ? "#" : mode.substr(mode.find(',') + 1);
   if (kind == "longest" && mode == kind) selection = IMPG_SELECT_LONGEST;
@@ -286,11 +294,15 @@ int partition_main(int argc, char **argv) {
   if (fasta) {
     std::vector<const char *> sp;
     for (auto &f : seq_files) sp.push_back(f.c_str());
-    impg_gpu_sequences_t *seqs = nullptr;
-    if (impg_gpu_sequences_from_fasta(sp.data(), sp.size(), &seqs) != IMPG_OK) die(impg_gpu_last_error());
     if (impg_gpu_set_option(ix, "sequence_store_packed", sequence_store) != IMPG_OK) die(impg_gpu_last_error());
-    if (impg_gpu_index_set_sequences(ix, seqs) != IMPG_OK) die(impg_gpu_last_error());
-    impg_gpu_sequences_free(seqs);  // (the handle shares the store)
+    if (ingest_device) {
+      if (impg_gpu_index_load_sequences(ix, sp.data(), sp.size()) != IMPG_OK) die(impg_gpu_last_error());
+    } else {
+      impg_gpu_sequences_t *seqs = nullptr;
+      if (impg_gpu_sequences_from_fasta(sp.data(), sp.size(), &seqs) != IMPG_OK) die(impg_gpu_last_error());
+      if (impg_gpu_index_set_sequences(ix, seqs) != IMPG_OK) die(impg_gpu_last_error());
+      impg_gpu_sequences_free(seqs);  // (the handle shares the store)
+    }
   }
   impg_gpu_partition_t *ps = nullptr;
   if (impg_gpu_partition_create(ix, &p, &o, start_ids.data(), start_ids.size(), &ps) != IMPG_OK) die(impg_gpu_last_error());
@@ -526,6 +538,7 @@ int main(int argc, char **argv) {
   std::string seq_list;
   bool reverse_complement = false;
   int sequence_store = 0;
+  bool ingest_device = false;  // --sequence-ingest device: impg_gpu_index_load_sequences instead of _from_fasta + _set_sequences
   for (int i = 2; i < argc; i++) {
     std::string a = argv[i];
     auto need = [&](const char *f) -> const char * {
@@ -560,6 +573,11 @@ int main(int argc, char **argv) {
       const std::string v = need(a.c_str());
       if (v != "bytes" && v != "packed" && v != "auto") die("invalid value '" + v + "' for '--sequence-store'", 2);
       sequence_store = v == "bytes" ? 0 : v == "packed" ? 1 : 2;
+    }
+    else if (a == "--sequence-ingest") {  // host: parsed on the host and attached; device: streamed into HBM and parsed there (gzip / BGZF too)
+      const std::string v = need(a.c_str());
+      if (v != "host" && v != "device") die("invalid value '" + v + "' for '--sequence-ingest'", 2);
+      ingest_device = v == "device";
     }
     else if (a == "--subset-sequence-list") subset_list = need(a.c_str());
     else if (a == "--original-sequence-coordinates") original_coords = true;
@@ -609,6 +627,8 @@ int main(int argc, char **argv) {
       if (!line.empty()) seq_files.push_back(line);
     }
   }
+  if (ingest_device && host_merge) die("--sequence-ingest device keeps no host copy of the sequences: --host-merge cannot print from it", 2);
+  if (ingest_device && sequence_store == 2) die("--sequence-store auto needs the host's copy of the sequences: with --sequence-ingest device choose bytes or packed", 2);
   if (fmt == "fasta" && seq_files.empty())  // main.rs:4243
     die("Sequence files (FASTA/AGC) are required for 'fasta' output format. Use --sequence-files or --sequence-list");
 
@@ -640,11 +660,15 @@ int main(int argc, char **argv) {
   if (fmt == "fasta") {
     std::vector<const char *> sp;
     for (auto &f : seq_files) sp.push_back(f.c_str());
-    impg_gpu_sequences_t *seqs = nullptr;
-    if (impg_gpu_sequences_from_fasta(sp.data(), sp.size(), &seqs) != IMPG_OK) die(impg_gpu_last_error());
     if (impg_gpu_set_option(ix, "sequence_store_packed", sequence_store) != IMPG_OK) die(impg_gpu_last_error());
-    if (impg_gpu_index_set_sequences(ix, seqs) != IMPG_OK) die(impg_gpu_last_error());
-    impg_gpu_sequences_free(seqs);  // (the handle shares the store)
+    if (ingest_device) {
+      if (impg_gpu_index_load_sequences(ix, sp.data(), sp.size()) != IMPG_OK) die(impg_gpu_last_error());
+    } else {
+      impg_gpu_sequences_t *seqs = nullptr;
+      if (impg_gpu_sequences_from_fasta(sp.data(), sp.size(), &seqs) != IMPG_OK) die(impg_gpu_last_error());
+      if (impg_gpu_index_set_sequences(ix, seqs) != IMPG_OK) die(impg_gpu_last_error());
+      impg_gpu_sequences_free(seqs);  // (the handle shares the store)
+    }
   }
 
   std::vector<Target> targets;

@@ -37,6 +37,7 @@
 #include "device_prims.hpp"
 #include "engine.hpp"
 #include "partition.hpp"
+#include "sequence_ingest.hpp"
 #include "text_device.hpp"
 
 namespace impg {
@@ -392,47 +393,22 @@ struct PieceTiming {
 namespace {
 
 constexpr u64 PACK_CHUNK_BASES = 64ull << 20;  // IMPG_SEQ_PACK_CHUNK=<bases> sets another (tests: a chunk's end inside a sequence)
-constexpr size_t RUN_BYTES = sizeof(uint2) + 1;  // a run in HBM
-
-// What the packed form of the attached store would hold: the places, the runs and the block tables, all on the host
-struct PackedPlan {
-  std::vector<u64> off, run_off, blk_off;  // [n_ids], [n_ids + 1], [n_ids]
-  std::vector<uint2> runs;
-  std::vector<unsigned char> run_byte;
-  std::vector<uint32_t> blk;
-  u64 end = 64;  // the stream's bases, the alignment of every sequence included
-  size_t stream_bytes() const { return (size_t)(end / 4u) + 64; }
-  size_t bytes() const { return stream_bytes() + runs.size() * RUN_BYTES + blk.size() * 4; }
-};
+// What the packed form of the attached store would hold (PackedPlan, sequence_ingest.hpp: the places, the runs and the block
+// tables, all on the host; impg_gpu_index_load_sequences builds the same tables from the runs its kernels extract)
 PackedPlan plan_packed(const impg_gpu_index &ix) {
   const SeqStore &st = *ix.seq_store;
   const size_t n_ids = ix.store_of_id.size();
-  PackedPlan p;
-  p.off.assign(std::max<size_t>(n_ids, 1), SEQ_NOT_IN_HBM);
-  p.run_off.assign(n_ids + 1, 0);
-  p.blk_off.assign(std::max<size_t>(n_ids, 1), 0);
+  PackedPlan p(n_ids);
   std::vector<SeqRun> runs;
   for (size_t id = 0; id < n_ids; id++) {
-    p.run_off[id + 1] = p.run_off[id];
+    runs.clear();
     const uint32_t s = ix.store_of_id[id];
-    if (s == SEQ_ABSENT) continue;
+    if (s == SEQ_ABSENT) { p.add_runs(id, 0, runs); continue; }
     const u64 len = st.off[s + 1] - st.off[s];  // (the index's length: below 2^31)
     p.off[id] = p.end;
     p.end += (len + 63u) & ~63ull;
-    runs.clear();
     seq_exception_runs(st.bases.data() + st.off[s], (size_t)len, runs);
-    if (runs.empty()) continue;
-    p.run_off[id + 1] += runs.size();
-    p.blk_off[id] = p.blk.size();
-    size_t k = 0;  // first[b] = the runs that end at or before base 1024 * b
-    for (u64 b = 0; b <= (len + 1023u) >> 10; b++) {
-      while (k < runs.size() && (u64)runs[k].end <= b << 10) k++;
-      p.blk.push_back((uint32_t)k);
-    }
-    for (const SeqRun &r : runs) {
-      p.runs.push_back(make_uint2(r.start, r.end));
-      p.run_byte.push_back(r.byte);
-    }
+    p.add_runs(id, len, runs);
   }
   return p;
 }

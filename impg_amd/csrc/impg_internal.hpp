@@ -402,8 +402,18 @@ struct SeqStore {  // one byte per base, upper-cased at load, back to back
   std::vector<uint64_t> off;  // [n + 1]
   std::string bases;
   std::unordered_map<std::string, uint32_t> by_name;
+  // impg_gpu_index_load_sequences made it: names, lengths (off) and by_name as ever, but no `bases` -- the sequences exist in
+  // HBM alone, and what reads the host copy refuses (host_copy, below) instead of reading an empty string
+  bool device_only = false;
   void add(const std::string &name, const char *b, size_t n);  // IMPG_E_INVALID for a name it already holds
 };
+// the store's host copy for a host route; a store that has none names the call that keeps one
+inline const SeqStore &host_copy(const SeqStore &st) {
+  if (st.device_only)
+    throw Error{IMPG_E_UNSUPPORTED, "the sequences were loaded straight into HBM (impg_gpu_index_load_sequences) and have no host copy: "
+                                    "attach them with impg_gpu_index_set_sequences for FASTA text written on the host"};
+  return st;
+}
 constexpr uint32_t SEQ_ABSENT = 0xFFFFFFFFu;      // impg_gpu_index::store_of_id: the store lacks the sequence
 constexpr uint64_t SEQ_NOT_IN_HBM = ~0ull;        // the device offsets' mark of the same
 constexpr size_t SEQ_PAD = 16;                    // bytes in front of the first base in HBM (and at least as many behind the last)
@@ -500,6 +510,8 @@ struct impg_gpu_index {
   void paf_stats_reset() const { for (auto &b : paf_stats) b = 0; }
   // ... and the last device FASTA call (by impg::FastaStat; fasta_device.hip), kept the same way
   mutable std::atomic<uint64_t> fasta_stats[7] = {};
+  // ... and the last impg_gpu_index_load_sequences (by impg::ingest::Stat; sequence_ingest.hpp)
+  mutable std::atomic<uint64_t> ingest_stats[5] = {};
   void fasta_stats_reset() const { for (int k = 0; k < impg::FASTA_STORE_BYTES; k++) fasta_stats[k] = 0; }  // (the store's size stays: set when it is attached)
   // The sequence store attached by impg_gpu_index_set_sequences (null: none): the host copy the host route reads, which
   // of its sequences every index id is (impg::SEQ_ABSENT: none), and the same bases in HBM for the device route -- SEQ_PAD

@@ -39,6 +39,7 @@ struct Options {
   int64_t bedpe_group_log2 = 2;       // device BEDPE: log2 of the lanes that sum one row's CIGAR (bedpe_device.hip; 2 .. 6; results identical)
   int64_t paf_group_log2 = 2;         // device PAF: log2 of the lanes that fuse and print one row's CIGAR (paf_device.inc; 2 .. 6; results identical)
   int64_t sequence_store_packed = 0;  // the form impg_gpu_index_set_sequences uploads: 0 a byte per base, 1 two bits per base + runs of the other bytes, 2 the smaller (fasta_device.hip; read at attach; text identical)
+  int64_t sequence_ingest_piece_bytes = 64ll << 20;  // impg_gpu_index_load_sequences: bytes of a file's text per piece crossing PCIe (sequence_ingest.cpp; a multiple of 16; results identical)
   int64_t lane_schedule = 0;        // tests: forced lane start / hand-over order of a sharded batch (run_lanes, sharded.cpp; 0 = off, then IMPG_LANE_SCHEDULE)
 };
 
@@ -76,6 +77,7 @@ constexpr OptionRow OPTION_TABLE[] = {
     {"bedpe_group_log2", 2, 6, &Options::bedpe_group_log2, false, false, "bedpe_group_log2 is 2 .. 6"},
     {"paf_group_log2", 2, 6, &Options::paf_group_log2, false, false, "paf_group_log2 is 2 .. 6"},
     {"sequence_store_packed", 0, 2, &Options::sequence_store_packed, false, false, "sequence_store_packed is 0, 1 or 2"},
+    {"sequence_ingest_piece_bytes", 16, 1ll << 32, &Options::sequence_ingest_piece_bytes, false, false, "sequence_ingest_piece_bytes is 16 .. 2^32, a multiple of 16"},
     // Actions, so that a process's FIRST call costs what its later ones do.
     // A pinned host block of this size goes into the library's pool now (host_mem.cpp): the first result-returning call
     // copies into a recycled block like every later one (pinning 5 GB costs ~0.3-1 s, inside the call otherwise).  Blocks

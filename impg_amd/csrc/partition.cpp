@@ -756,6 +756,7 @@ static_assert(sizeof(PIv) == sizeof(impg_gpu_partition_row_t), "PIv and impg_gpu
 // the host twin over the handle's own names and bases
 void host_rows_fasta(const impg_gpu_index &ix, const impg_gpu_partition_row_t *rows, size_t n, std::string &text) {
   if (!ix.seq_store) throw Error{IMPG_E_INVALID, "FASTA output needs a sequence store (impg_gpu_index_set_sequences)"};
+  host_copy(*ix.seq_store);
   const size_t at = text.size();
   partition_fasta_text(rows, n, [&ix](uint32_t id, std::string &name, SeqRef &ref) {
     name = id < ix.seq.names.size() ? ix.seq.names[id] : std::to_string(id);
@@ -778,7 +779,7 @@ void window_fasta(impg_gpu_partition &p, const impg_gpu_range_t &w, const std::f
   p.c_partitions++;
   if (p.engine) {
     if (!p.text_hint) {
-      const unsigned long long bases = ix.seq_store->bases.size();
+      const unsigned long long bases = ix.seq_store->off.empty() ? 0ull : ix.seq_store->off.back();
       p.text_hint = bases + bases / 80 + 4096;
     }
     // (the rows the update left in HBM: DeviceRegions::apply has copied them to `last` and waited for the stream)

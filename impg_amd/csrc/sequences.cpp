@@ -246,6 +246,7 @@ int impg_gpu_index_set_sequences(impg_gpu_index_t *ix, const impg_gpu_sequences_
   if (!ix) throw Error{IMPG_E_INVALID, "null argument"};
   if (ix->shard || ix->cluster) throw Error{IMPG_E_UNSUPPORTED, "a sequence store on a sharded index"};
   IMPG_HIP(hipSetDevice(ix->device));
+  for (auto &c : ix->ingest_stats) c = 0;  // (the attached store is no longer one impg_gpu_index_load_sequences made)
   if (!seqs) {
     ix->seq_store.reset();
     ix->store_of_id.clear();
@@ -337,7 +338,7 @@ namespace impg {
 void render_fasta(const impg_gpu_results &res, const impg_gpu_index &ix, const impg_gpu_params_t &p, int32_t merge_distance, bool reverse_complement,
                   std::vector<std::string> &parts) {
   if (!ix.seq_store) throw Error{IMPG_E_INVALID, "FASTA output needs a sequence store (impg_gpu_index_set_sequences)"};
-  const SeqStore &st = *ix.seq_store;
+  const SeqStore &st = host_copy(*ix.seq_store);
   const size_t nr = res.offsets.size() - 1;
   parts.assign(nr, std::string());
   std::atomic<size_t> next{0};

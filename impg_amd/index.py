@@ -724,6 +724,20 @@ class GpuImpg:
             self.set_option("sequence_store_packed", 2 if packed == "auto" else int(packed))
         check(lib().impg_gpu_index_set_sequences(self._h, None if sequences is None else sequences._h))
 
+    def load_sequences(self, paths, packed=None):
+        """impg_gpu_index_load_sequences: FASTA files (a path or a list; plain, gzip or BGZF) streamed straight into HBM and
+        parsed there; it replaces any attached store and leaves no host copy of the bases.  packed: option
+        "sequence_store_packed" set first -- False one byte per base, True packed; None leaves the option as it is ("auto" is
+        set_sequences' alone)."""
+        if packed is not None:
+            if not any(packed is v for v in (False, True)):
+                raise ValueError("packed is None, False or True")
+            self.set_option("sequence_store_packed", int(packed))
+        if isinstance(paths, (str, bytes, os.PathLike)):
+            paths = [paths]
+        arr = (C.c_char_p * len(paths))(*[os.fsencode(q) for q in paths])
+        check(lib().impg_gpu_index_load_sequences(self._h, arr, len(paths)))
+
     def query_batch_fasta(self, ranges, params=None, merge_distance=0, range_names=None, subset_keep=None, timing=False, raw=False,
                           reverse_complement=False, fd=None, **kw):
         """impg_gpu_query_batch_fasta: query + the query-axis sweep + the records written on the device from the store in
@@ -1573,3 +1587,39 @@ def selftest_key_sort(n_keys, perm, passes, first_in_order, device=0):
     check(lib().impg_gpu_selftest_key_sort(device, n_keys, p.ctypes.data, p.size, int(first_in_order), C.cast(sp, C.c_void_p), len(passes),
                                            order.ctypes.data, sorted_keys.ctypes.data))
     return order, sorted_keys
+
+
+def selftest_sequence_reader(path, piece_bytes):
+    """impg_gpu_selftest_sequence_reader (host-only): the reader of load_sequences alone -> (the concatenation of the file's
+    pieces, their number, the BGZF blocks inflated)."""
+    text, ln, pieces, blocks = C.c_void_p(None), C.c_size_t(0), C.c_uint64(0), C.c_uint64(0)
+    check(lib().impg_gpu_selftest_sequence_reader(os.fsencode(path), piece_bytes, C.byref(text), C.byref(ln), C.byref(pieces), C.byref(blocks)))
+    try:
+        return _text_bytes(text, ln.value), pieces.value, blocks.value
+    finally:
+        _lib.free(text)
+
+
+def selftest_sequence_ingest_host(paths, names, lens, piece_bytes, packed):
+    """impg_gpu_selftest_sequence_ingest_host (host-only): load_sequences with the kernels' host twin in their place, for an
+    index whose ids are names / lens -> dict(off=[n_ids] uint64 (all ones: absent), store=uint8 bytes or packed stream,
+    run_off=[n_ids + 1], run_start, run_end, run_byte, stats=[5])."""
+    if isinstance(paths, (str, bytes, os.PathLike)):
+        paths = [paths]
+    n = len(names)
+    parr = (C.c_char_p * len(paths))(*[os.fsencode(q) for q in paths])
+    narr = (C.c_char_p * n)(*[q.encode() for q in names])
+    ln = np.ascontiguousarray(lens, dtype=np.int64)
+    off, run_off, stats = np.zeros(max(n, 1), dtype=np.uint64), np.zeros(n + 1, dtype=np.uint64), np.zeros(5, dtype=np.uint64)
+    store, rs, re_, rb, sb = C.c_void_p(None), C.c_void_p(None), C.c_void_p(None), C.c_void_p(None), C.c_size_t(0)
+    check(lib().impg_gpu_selftest_sequence_ingest_host(parr, len(paths), narr, ln.ctypes.data, n, piece_bytes, int(bool(packed)), off.ctypes.data,
+                                                       C.byref(store), C.byref(sb), run_off.ctypes.data, C.byref(rs), C.byref(re_), C.byref(rb),
+                                                       stats.ctypes.data))
+    try:
+        k = int(run_off[n])
+        return dict(off=off[:n], store=np.frombuffer(C.string_at(store, sb.value), dtype=np.uint8), run_off=run_off,
+                    run_start=np.frombuffer(C.string_at(rs, 4 * k), dtype=np.uint32), run_end=np.frombuffer(C.string_at(re_, 4 * k), dtype=np.uint32),
+                    run_byte=np.frombuffer(C.string_at(rb, k), dtype=np.uint8), stats=stats)
+    finally:
+        for q in (store, rs, re_, rb):
+            _lib.free(q)

@@ -253,7 +253,9 @@ int impg_gpu_index_approximate(const impg_gpu_index_t *);
  * sequence store in: 0, the default, one byte per base; 1 two bits per base and a table of runs for every byte that is not
  * A/C/G/T; 2 whichever of the two takes fewer bytes in HBM for the store at hand -- see impg_gpu_index_set_sequences.  Read
  * at attach: changing it does not repack an attached store, detach and attach again for that.  The text is identical for
- * every value).  For tests of the multi-rank paths: "lane_schedule" (forced lane start / hand-over order of a sharded
+ * every value), "sequence_ingest_piece_bytes" (16 .. 2^32, a multiple of 16; 64 MiB by default: impg_gpu_index_load_sequences
+ * sends a file's text to the device in pieces of this many bytes; the store is identical for every value).  For tests of
+ * the multi-rank paths: "lane_schedule" (forced lane start / hand-over order of a sharded
  * batch; 0 = off), "debug_fail_owner" / "debug_fail_home" (failure injection: (rank + 1) << 16 | hop of the batch at which
  * that rank throws on the owner / on the home side of the hop; 0 = off).
  * A multi-GPU handle hands "chunk_ranges", "pair_budget", "locality_min", "debug_fail_owner", "debug_fail_home",
@@ -313,7 +315,11 @@ const char *impg_gpu_counter_key(size_t i);
  * "fasta_store_bytes" = bytes of HBM the attached sequence store takes, in whichever form it has -- the bases, and the
  * packed form's runs and block tables (0: none attached), "fasta_store_packed" = 1 if the attached store is the packed
  * form (0: one byte per base, or none attached), "fasta_store_exception_runs" = the runs of bytes other than A/C/G/T the
- * packed form keeps (0 for the byte form, and with none attached).  Of the build of the index itself (a multi-GPU handle answers with the sum over its
+ * packed form keeps (0 for the byte form, and with none attached).  Of the last impg_gpu_index_load_sequences on the handle
+ * (zero after impg_gpu_index_set_sequences): "sequence_ingest_pieces" = text pieces sent to the device,
+ * "sequence_ingest_text_bytes" = bytes of (inflated) text, "sequence_ingest_bases" = bases met, those of dropped sequences
+ * included, "sequence_ingest_inflated_blocks" = BGZF blocks inflated, "sequence_ingest_dropped_sequences" = file sequences
+ * the index does not know.  Of the build of the index itself (a multi-GPU handle answers with the sum over its
  * ranks): "build_device" = 1 if the device builder produced it, 0 if the host builder did (IMPG_BUILD_HOST, tracepoints, a
  * loaded .impg file's entry order, a card short of memory for the build, an index loaded from a saved file);
  * "tokenized_device" = 1 if the device tokenised its CIGAR text (impg_gpu_index_create_from_paf on one GPU);
@@ -606,7 +612,8 @@ int impg_gpu_query_batch_paf_fd(impg_gpu_index_t *, const impg_gpu_range_t *rang
  * dropped; bytes upper-cased at load; an empty sequence and a last line without a newline are accepted), or arrays of the
  * caller's (names[n], off[n + 1] into bases; upper-cased too).  One byte per base on the host, so IUPAC codes and N stay
  * exact; in HBM one byte per base too, or two bits per base with those bytes kept aside (option "sequence_store_packed").
- * IMPG_E_UNSUPPORTED for a file that starts with the gzip magic 1f 8b (no codec here: decompress first); IMPG_E_INVALID,
+ * IMPG_E_UNSUPPORTED for a file that starts with the gzip magic 1f 8b (this route has no codec: decompress first, or use
+ * impg_gpu_index_load_sequences); IMPG_E_INVALID,
  * naming it, for a name that occurs twice, in one file or across files (the reference lets the last file win);
  * IMPG_E_IO for a file that cannot be read.  Host-only.  _name / _bases: sequence i as the store holds it (NULL past the
  * last; the bases are not NUL-terminated, *len = their number). */
@@ -636,6 +643,35 @@ void impg_gpu_sequences_free(impg_gpu_sequences_t *);
  * bases are packed on the device chunk by chunk through one staging buffer (64 MiB), so the attach never holds the store
  * at a byte per base in HBM.  The text every FASTA call prints is the same, byte for byte; the host copy stays as it is. */
 int impg_gpu_index_set_sequences(impg_gpu_index_t *, const impg_gpu_sequences_t *seqs);
+/* The second way to give an index its sequences: FASTA files streamed straight into HBM.  A file's text -- plain, or inflated
+ * on a few host threads if it starts with the gzip magic: BGZF (recognised by its BC subfield) block by block, any other
+ * gzip as one stream -- crosses PCIe in pieces of option "sequence_ingest_piece_bytes" through two pinned blocks, and
+ * everything that touches a base happens on the device: finding the header lines, dropping the line ends, upper-casing,
+ * placing, packing to 2 bits and extracting the runs (sequence_ingest_device.hip).  The store that results is the one
+ * impg_gpu_sequences_from_fasta + impg_gpu_index_set_sequences make from the same text, rule for rule (names, bases, empty
+ * lines, CRLF, a last line without a newline; a name twice, an empty name and text before the first '>' are IMPG_E_INVALID
+ * with the same words; a sequence whose base count differs from impg_gpu_seq_len likewise), in the form option
+ * "sequence_store_packed" names at the call: 0 bytes, 1 packed; 2 is IMPG_E_INVALID here (the smaller form is known only
+ * once every run is counted: impg_gpu_index_set_sequences keeps that choice).  Sequences are placed in file order, in a
+ * reservation made once for ALL of the index's sequences ("fasta_store_bytes" reports what is used); file sequences the
+ * index lacks are parsed and dropped, index sequences the files lack are absent as after impg_gpu_index_set_sequences.
+ * IMPG_E_IO, naming the file: an unreadable file, a truncated gzip stream, a BSIZE or ISIZE that leads outside the file, a
+ * CRC or length mismatch, an inflate error.  IMPG_E_UNSUPPORTED: a tracepoint index, a sharded or multi-GPU handle.  The
+ * call replaces any attached store; after a failure the handle has none.  No host copy of the bases exists afterwards:
+ * impg_gpu_results_fasta, a partition session with its state on the host, and impg_gpu_partition_rows_fasta(on_host)
+ * answer IMPG_E_UNSUPPORTED naming impg_gpu_index_set_sequences.  Sets the "sequence_ingest_*" and "fasta_store_*" counters. */
+int impg_gpu_index_load_sequences(impg_gpu_index_t *, const char *const *paths, size_t n_paths);
+/* Diagnostics, host-only (no GPU call): the reader alone -- the concatenation of `path`'s pieces of piece_bytes, their
+ * number and the BGZF blocks inflated; *text is malloc'ed -- and the whole route with the kernels' host twin
+ * (ingest_piece_host, sequence_ingest.cpp) in their place, for an index of n_ids sequences names_of_ids / lens.  packed: 0 or
+ * 1.  off[n_ids]: every id's place (bytes, or bases of the packed stream; all ones: absent); *store: the bytes, or the packed
+ * stream; run_off[n_ids + 1] and *run_start / *run_end / *run_byte: the packed form's runs by id (ends exclusive);
+ * stats[5] (may be NULL): the five "sequence_ingest_*" counters in the order above.  The arrays are malloc'ed; free() them.
+ * Errors as impg_gpu_index_load_sequences. */
+int impg_gpu_selftest_sequence_reader(const char *path, uint64_t piece_bytes, char **text, size_t *len, uint64_t *n_pieces, uint64_t *inflated_blocks);
+int impg_gpu_selftest_sequence_ingest_host(const char *const *paths, size_t n_paths, const char *const *names_of_ids, const int64_t *lens, size_t n_ids,
+                                           uint64_t piece_bytes, int packed, uint64_t *off, uint8_t **store, size_t *store_bytes, uint64_t *run_off,
+                                           uint32_t **run_start, uint32_t **run_end, uint8_t **run_byte, uint64_t *stats);
 /* perform_query + output_results_fasta for a whole batch, the sweep (merge_query_adjusted_intervals alone, strands kept
  * apart: main.rs:12362, :4395-4409) and the records written ON THE DEVICE (fasta_device.hip) from the store in HBM: per merged
  * row ">{name}:{start}-{end}" ("/rc" appended and the bases reverse-complemented -- A/T/C/G/N, other bytes as they are -- on
