@@ -41,6 +41,7 @@ static void engine_options(impg_gpu_index &ix, Engine *e) {
   e->walk_allowed = o.walk_kernel != 0 && !getenv("IMPG_NO_WALK");
   e->walk_bfs = o.walk_kernel == 2;  // (the environment switch runs a whole test suite on the batch engine)
   e->wide_emit = WideEmit{(uint32_t)o.wide_emit_cap, (uint32_t)o.wide_emit_bins, o.lookup_stats != 0};
+  e->coop_count = CoopCount{(uint32_t)o.lookup_coop_span, o.lookup_coop != 0};
   e->seg_stats = ix.seg_stats;
   e->proj_stats = ix.proj_stats;
   e->upd_stats = ix.upd_stats;
@@ -645,7 +646,7 @@ int impg_gpu_index_approximate(const impg_gpu_index_t *ix) {
 uint64_t impg_gpu_host_pool_trim(uint64_t keep_bytes) { return (uint64_t)impg::pinned_trim((size_t)keep_bytes); }
 
 // (options.hpp is host-only and spells these limits out: they are the kernels')
-static_assert(option_row("walk_members")->hi == WALK_MAX_MEMBERS && option_row("wide_emit_cap")->hi == WIDE_CAP && option_row("wide_emit_bins")->hi == WIDE_BINS,
+static_assert(option_row("walk_members")->hi == WALK_MAX_MEMBERS && option_row("wide_emit_cap")->hi == WIDE_CAP && option_row("wide_emit_bins")->hi == WIDE_BINS && option_row("lookup_coop_span")->hi == LOOKUP_COOP_CAP,
               "the option table's limits are the kernels' capacities");
 
 int impg_gpu_set_option(impg_gpu_index_t *ix, const char *key, int64_t value) {
@@ -691,6 +692,7 @@ static const CounterRow COUNTER_TABLE[] = {
     CTR("update_lane_spill_groups", upd_stats[UPD_LANE_SPILL]),
     CTR("lookup_wide_windows", lk_stats[LK_WIDE]), CTR("lookup_wide_single", lk_stats[LK_SINGLE]), CTR("lookup_wide_grouped", lk_stats[LK_GROUPED]),
     CTR("lookup_wide_group_passes", lk_stats[LK_GROUP_PASSES]), CTR("lookup_wide_overflow", lk_stats[LK_OVERFLOW]),
+    CTR("lookup_coop_waves", lk_stats[LK_COOP]), CTR("lookup_lane_waves_mixed", lk_stats[LK_MIXED]), CTR("lookup_lane_waves_span", lk_stats[LK_SPAN]),
     CTR("refine_passes", refine_stats[REFINE_PASSES]), CTR("refine_candidates", refine_stats[REFINE_CANDIDATES]),
     CTR("refine_parts", refine_stats[REFINE_PARTS]), CTR("refine_rows_to_host", refine_stats[REFINE_ROWS_TO_HOST]),
     CTR("refine_longest_group", refine_stats[REFINE_LONGEST_GROUP]),

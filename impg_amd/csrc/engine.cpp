@@ -419,6 +419,9 @@ void Engine::count_wide_paths(const DeviceIndexView &v, uint32_t n) {
   lk_stats[LK_SINGLE] += reach[LK_REACH_SINGLE];
   lk_stats[LK_GROUPED] += reach[LK_REACH_GROUPED];
   lk_stats[LK_GROUP_PASSES] += reach[LK_REACH_PASSES];
+  lk_stats[LK_COOP] += reach[LK_REACH_COOP];
+  lk_stats[LK_MIXED] += reach[LK_REACH_MIXED];
+  lk_stats[LK_SPAN] += reach[LK_REACH_SPAN];
 }
 
 // lookup + projection of one frontier; fills L (pair_range, hit arrays), returns #pairs
@@ -452,7 +455,7 @@ uint64_t Engine::expand(const DeviceIndexView &v, const FrontierRec *fr, uint32_
   if (ordered) { L.slot_ref.reserve(std::max<size_t>((size_t)n_fr * 4, 256)); ord_cnt.reserve(std::max<size_t>((size_t)n_fr * 4, 256)); }
   launch_lookup_count(v, fr, n_fr, transitive, d_perm, cnt.as<uint32_t>(), win.as<uint4>(), wide_n.as<uint32_t>(),
                       wide_list.as<uint32_t>(), stream, by_place, by_place ? win_se.as<FrontierRec>() : nullptr,
-                      ordered && by_place ? ord_cnt.as<uint32_t>() : nullptr, lk);
+                      ordered && by_place ? ord_cnt.as<uint32_t>() : nullptr, lk, coop_count);
   uint64_t P = scan(cnt.as<uint32_t>(), pair_off.as<uint32_t>(), n_fr);
   if (P > (uint64_t)opt.pair_budget || P >= 0xFFFFFFF0ull) {
     if (split_ok) throw SplitBatch{};

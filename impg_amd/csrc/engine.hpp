@@ -152,6 +152,7 @@ struct Engine {
   // projection order (locality): ranges sorted by window position, their slots listed in that order
   DevBuf wide_n, wide_list;  // ranges whose window is wider than the lane-per-range emit pass takes
   WideEmit wide_emit;        // from options "wide_emit_cap" / "wide_emit_bins" / "lookup_stats" (count_reach: a level's lookup copies its list lengths and reach counters home)
+  CoopCount coop_count;      // from options "lookup_coop" / "lookup_coop_span"
   std::atomic<uint64_t> *lk_stats = nullptr;  // the handle's lookup_wide_* counters (by LookupStat), or null
   void count_wide_paths(const DeviceIndexView &v, uint32_t n);  // after a level's launch_lookup_emit; nothing without the option
   DevBuf lo_key, lo_key2, lo_idx, lo_perm, lo_cnt, lo_off, lo_offp, slot_of;

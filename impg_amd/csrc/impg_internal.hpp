@@ -495,7 +495,7 @@ struct impg_gpu_index {
   // ... and, under option update_stats, the groups each tier of the visited update took and the rare paths they reached (by impg::UpdStat)
   mutable std::atomic<uint64_t> upd_stats[8] = {};
   // ... and, under option lookup_stats, the lookup's wide windows by the path that emitted them (by impg::LookupStat)
-  mutable std::atomic<uint64_t> lk_stats[5] = {};
+  mutable std::atomic<uint64_t> lk_stats[8] = {};
   // ... and what the refine runs on the handle did (by impg::RefineStat; refine.cpp)
   mutable std::atomic<uint64_t> refine_stats[5] = {};
   // ... and the last device BED call on the handle (by impg::BedStat; bed_device.hip): set to zero when a call starts, added

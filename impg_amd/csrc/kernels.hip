@@ -112,29 +112,83 @@ __device__ __forceinline__ void dual_search4(const int32_t *__restrict__ S, uint
   }
 }
 
+// -DIMPG_LOOKUP_CLOCKS (experiments): s_memtime at the count kernels' dependency boundaries, summed over the waves of every
+// 16th block (full waves only: a mark is the whole wave's; the last, partial wave runs unclocked, so the build's answers are
+// the product's); read (and cleared) by impg_gpu_debug_lookup_clocks -- scripts/lookup_clocks.py.  Each mark waits for everything
+// outstanding first, so a phase is what a wave WAITS for.  Words 0..5: the lane kernel's record loads, sample search, block
+// search, window walk, stores, waves; 6..12: the cooperative kernel's record loads, wave searches, staging, searches in LDS,
+// walk in LDS, stores, cooperative waves; 13, 14: the cycles of its waves that took the lane body behind their loads, those waves.
+#ifdef IMPG_LOOKUP_CLOCKS
+__device__ unsigned long long g_lookup_clk[16];
+#define LK_CLOCKS(full) unsigned long long lk_t[8] = {}; const bool lk_on = (blockIdx.x & 15u) == 0u && (full)
+#define LK_MARK(i) do { if (lk_on) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); lk_t[i] = __builtin_readcyclecounter(); } } while (0)
+#define LK_SUM(base, k) do { if (lk_on && lane_id() == 0u) { for (int q = 0; q < (k); q++) atomicAdd(&g_lookup_clk[(base) + q], lk_t[q + 1] - lk_t[q]); atomicAdd(&g_lookup_clk[(base) + (k)], 1ull); } } while (0)
+#define LK_ARG , unsigned long long *lk_t, bool lk_on
+#define LK_PASS , lk_t, lk_on
+extern "C" void impg_gpu_debug_lookup_clocks(unsigned long long *out) {
+  unsigned long long z[16] = {};
+  (void)hipDeviceSynchronize();
+  (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_lookup_clk), sizeof(z));
+  (void)hipMemcpyToSymbol(HIP_SYMBOL(g_lookup_clk), z, sizeof(z));
+}
+#else
+#define LK_CLOCKS(full) do { } while (0)
+#define LK_MARK(i) do { } while (0)
+#define LK_SUM(base, k) do { } while (0)
+#define LK_ARG
+#define LK_PASS
+#endif
+
+// the window [lo, ub) of the end column, eight entries (two aligned 16-byte vectors) per round: hits counted, the first 64 into
+// the mask.  col[b - sub] holds entry b: the column itself (sub = 0) or a wave's LDS copy of it from entry `sub` on.
 template <bool TRANSITIVE>
-__global__ __launch_bounds__(256) void lookup_count_lane_kernel(DeviceIndexView v, const FrontierRec *__restrict__ fr,
-                                                                uint32_t n, const uint32_t *__restrict__ perm,
-                                                                uint32_t *__restrict__ cnt,
-                                                                uint4 *__restrict__ win, uint32_t *__restrict__ wide_n,
-                                                                uint32_t *__restrict__ wide_list, int by_place, FrontierRec *__restrict__ se,
-                                                                uint32_t *__restrict__ cnt_ref) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i >= n) return;
-  // perm (optional): neighbouring lanes take ranges that are neighbours in the entry array, so
-  // their searches and windows share cache lines; results still land at the range's own index --
-  // or, by_place, at the lane's place in that order (coalesced; the emit pass then reads them there)
-  const uint32_t r = perm ? perm[i] : i;
-  const uint32_t o = by_place ? i : r;
-  const FrontierRec f = fr[r];
-  uint32_t a = 0, sn = 0, off0 = 0, cnt0 = 0;
-  if (f.target_id < v.n_seq) {
-    const uint4 *dp = reinterpret_cast<const uint4 *>(v.seg + f.target_id);
+__device__ __forceinline__ void window_walk(const int32_t *col, uint32_t sub, uint32_t lo, uint32_t ub, int32_t qs, bool skip, uint32_t &c,
+                                            unsigned long long &mask) {
+  for (uint32_t b = lo & ~3u; b < ub && !skip; b += 8u) {
+    const int4 e0 = *reinterpret_cast<const int4 *>(col + (b - sub));
+    int4 e1 = make_int4(0, 0, 0, 0);
+    if (b + 4u < ub) e1 = *reinterpret_cast<const int4 *>(col + (b - sub) + 4u);
+    const int32_t ev[8] = {e0.x, e0.y, e0.z, e0.w, e1.x, e1.y, e1.z, e1.w};
+#pragma unroll
+    for (uint32_t k = 0; k < 8; k++) {
+      const uint32_t i = b + k;
+      const bool hit = i >= lo && i < ub && window_hit<TRANSITIVE>(ev[k], qs);
+      c += hit ? 1u : 0u;
+      const uint32_t bit = i - lo;  // (only meaningful for a hit)
+      if (hit && bit < 64u) mask |= 1ull << bit;
+    }
+  }
+}
+// what a lane stores for its range: the count, the window with the mask, the record at its place; a deferred window's listing
+__device__ __forceinline__ void lookup_count_store(const FrontierRec &f, uint32_t r, uint32_t o, uint32_t lo, uint32_t ub, uint32_t c,
+                                                   unsigned long long mask, bool deferred, uint32_t *__restrict__ cnt, uint4 *__restrict__ win,
+                                                   uint32_t *__restrict__ wide_n, uint32_t *__restrict__ wide_list, FrontierRec *__restrict__ se,
+                                                   uint32_t *__restrict__ cnt_ref) {
+  cnt[o] = c;
+  if (cnt_ref) cnt_ref[r] = c;
+  win[o] = make_uint4(lo, ub, (uint32_t)mask, (uint32_t)(mask >> 32));
+  if (se) se[o] = f;  // (the whole record at the range's place: the projection reads its ends there, a kept level its range and target)
+  // windows too wide for the lane-per-range emit pass (dense targets) are listed for lookup_count_wide_kernel and the block-per-range emit
+  if (deferred) wide_list[atomicAdd(wide_n, 1u)] = o;
+}
+// a range's segment: {a, n} and its first sampled level {off0, cnt0} (zeros: no such target, no level)
+__device__ __forceinline__ void lookup_segment(const DeviceIndexView &v, uint32_t target_id, uint32_t &a, uint32_t &sn, uint32_t &off0, uint32_t &cnt0) {
+  a = 0; sn = 0; off0 = 0; cnt0 = 0;
+  if (target_id < v.n_seq) {
+    const uint4 *dp = reinterpret_cast<const uint4 *>(v.seg + target_id);
     const uint4 d0 = dp[0], d1 = dp[1];  // {a, n, nlev, off[0]}, {off[1..3], cnt[0]}
     a = d0.x;
     sn = d0.y;
     if (d0.z) { off0 = d0.w; cnt0 = d1.w; }
   }
+}
+// One lane, one range, every search and the window through the vector-memory path: the whole of lookup_count_lane_kernel, and
+// what a wave of lookup_count_coop_kernel falls back to.
+template <bool TRANSITIVE>
+__device__ __forceinline__ void lookup_count_lane_body(const DeviceIndexView &v, const FrontierRec &f, uint32_t r, uint32_t o, uint32_t a, uint32_t sn,
+                                                       uint32_t off0, uint32_t cnt0, uint32_t *__restrict__ cnt, uint4 *__restrict__ win,
+                                                       uint32_t *__restrict__ wide_n, uint32_t *__restrict__ wide_list, FrontierRec *__restrict__ se,
+                                                       uint32_t *__restrict__ cnt_ref LK_ARG) {
   const int32_t qs = f.start, qe = f.end;
   // first over the segment's samples (the last element of every 64-entry block: a
   // small array that stays in L2), then inside the one block that holds the answer
@@ -146,36 +200,224 @@ __global__ __launch_bounds__(256) void lookup_count_lane_kernel(DeviceIndexView 
     l1 = b1 < cnt0 ? 64u * b1 : sn; h1 = b1 < cnt0 ? min(l1 + 63u, sn) : sn;  // (that last element itself passes)
     l2 = b2 < cnt0 ? 64u * b2 : sn; h2 = b2 < cnt0 ? min(l2 + 63u, sn) : sn;
   }
+  LK_MARK(2);
   dual_search4<TRANSITIVE>(v.starts + a, l1, h1, v.pmax + a, l2, h2, qs, qe);
+  LK_MARK(3);
   const uint32_t ub = a + l1, lo = a + min(l2, l1);
-  // the window, eight entries (two aligned 16-byte vectors) per round
-  const int32_t *ecol = end_col<TRANSITIVE>(v);
   uint32_t c = 0;
   unsigned long long mask = 0;
   // (a window wider than the mask is counted by a wave of lookup_count_wide_kernel, which takes it off the wide list: a lane
   // walking thousands of entries of a dense target kept its 63 neighbours waiting -- 3.6 of a skewed step's 22 ms)
   const bool wide = lo < ub && ub - (lo & ~3u) > 64u;
   const bool deferred = wide && wide_list != nullptr;
-  for (uint32_t b = lo & ~3u; b < ub && !deferred; b += 8u) {
-    const int4 e0 = *reinterpret_cast<const int4 *>(ecol + b);
-    int4 e1 = make_int4(0, 0, 0, 0);
-    if (b + 4u < ub) e1 = *reinterpret_cast<const int4 *>(ecol + b + 4u);
-    const int32_t ev[8] = {e0.x, e0.y, e0.z, e0.w, e1.x, e1.y, e1.z, e1.w};
-#pragma unroll
-    for (uint32_t k = 0; k < 8; k++) {
-      const uint32_t i = b + k;
-      const bool hit = i >= lo && i < ub && window_hit<TRANSITIVE>(ev[k], qs);
-      c += hit ? 1u : 0u;
-      const uint32_t bit = i - lo;  // (only meaningful for a hit)
-      if (hit && bit < 64u) mask |= 1ull << bit;
-    }
+  window_walk<TRANSITIVE>(end_col<TRANSITIVE>(v), 0u, lo, ub, qs, deferred, c, mask);
+  LK_MARK(4);
+  lookup_count_store(f, r, o, lo, ub, c, mask, deferred, cnt, win, wide_n, wide_list, se, cnt_ref);
+}
+template <bool TRANSITIVE>
+__global__ __launch_bounds__(256) void lookup_count_lane_kernel(DeviceIndexView v, const FrontierRec *__restrict__ fr,
+                                                                uint32_t n, const uint32_t *__restrict__ perm,
+                                                                uint32_t *__restrict__ cnt,
+                                                                uint4 *__restrict__ win, uint32_t *__restrict__ wide_n,
+                                                                uint32_t *__restrict__ wide_list, int by_place, FrontierRec *__restrict__ se,
+                                                                uint32_t *__restrict__ cnt_ref) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  LK_CLOCKS(i - lane_id() + 63u < n);
+  LK_MARK(0);
+  // perm (optional): neighbouring lanes take ranges that are neighbours in the entry array, so
+  // their searches and windows share cache lines; results still land at the range's own index --
+  // or, by_place, at the lane's place in that order (coalesced; the emit pass then reads them there)
+  const uint32_t r = perm ? perm[i] : i;
+  const uint32_t o = by_place ? i : r;
+  const FrontierRec f = fr[r];
+  uint32_t a, sn, off0, cnt0;
+  lookup_segment(v, f.target_id, a, sn, off0, cnt0);
+  LK_MARK(1);
+  lookup_count_lane_body<TRANSITIVE>(v, f, r, o, a, sn, off0, cnt0, cnt, win, wide_n, wide_list, se, cnt_ref LK_PASS);
+  LK_MARK(5);
+  LK_SUM(0, 5);
+}
+
+// ---------------------------------------------------------------------------
+// K1a': the same counts, a WAVE working together where its 64 ranges are neighbours -- which the lookup order makes
+// them: sorted by order_key, a wave's ranges lie within a few kilobases of one target and their windows overlap almost
+// entirely.  The lane kernel still sends every lane through ~17 dependent global round trips (two 4-ary searches over the
+// samples and inside a block, then the window eight entries a round), each lane pulling its own copy of the same few
+// lines.  Here the wave
+//   1. reduces its ranges to qs_min, qe_min, qe_max (true reductions: equal keys are unordered, ends are not sorted);
+//   2. runs three boundary searches with all 64 lanes probing -- L2 = l2(qs_min) on pmax, L1a = l1(qe_min) and L1b =
+//      l1(qe_max) on starts: the samples (up to 256 of them in one round: every lane counts the probes that fail), then the
+//      one 64-entry block, the three searches' loads in flight together.  The predicates are monotone in their threshold, so
+//      every lane's l2 >= L2 and every lane's l1 lies in [L1a, L1b];
+//   3. copies starts, pmax and the end column of [S0, S1) = [min(L2, L1a) & ~3, L1b) into its LDS slice, one 16-byte vector a
+//      lane and column, when that span is at most LOOKUP_COOP_CAP entries;
+//   4. lets every lane finish as in the lane kernel -- its own two searches (now inside the staged span) and its window walk --
+//      on LDS reads.  Same windows, masks, counts, wide rule and stores.
+// A wave whose live lanes do not all name one valid target with a non-empty segment, or whose span is wider, takes the
+// lane body as a whole (the choice is wave-uniform).  reach (option lookup_stats): the level's LK_REACH_* words, bumped
+// by a wave's first lane.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ int32_t wave_min_i32(int32_t x) {
+  x = min(x, (int32_t)dpp_or_self<0x111, 0xF>((uint32_t)x));
+  x = min(x, (int32_t)dpp_or_self<0x112, 0xF>((uint32_t)x));
+  x = min(x, (int32_t)dpp_or_self<0x114, 0xF>((uint32_t)x));
+  x = min(x, (int32_t)dpp_or_self<0x118, 0xF>((uint32_t)x));
+  x = min(x, (int32_t)dpp_or_self<0x142, 0xA>((uint32_t)x));
+  x = min(x, (int32_t)dpp_or_self<0x143, 0xC>((uint32_t)x));
+  return __builtin_amdgcn_readlane(x, 63);
+}
+__device__ __forceinline__ int32_t wave_max_i32(int32_t x) {
+  x = max(x, (int32_t)dpp_or_self<0x111, 0xF>((uint32_t)x));
+  x = max(x, (int32_t)dpp_or_self<0x112, 0xF>((uint32_t)x));
+  x = max(x, (int32_t)dpp_or_self<0x114, 0xF>((uint32_t)x));
+  x = max(x, (int32_t)dpp_or_self<0x118, 0xF>((uint32_t)x));
+  x = max(x, (int32_t)dpp_or_self<0x142, 0xA>((uint32_t)x));
+  x = max(x, (int32_t)dpp_or_self<0x143, 0xC>((uint32_t)x));
+  return __builtin_amdgcn_readlane(x, 63);
+}
+// the searches' predicates as the lane kernel has them: on starts x >= key (transitive) / x > key, on pmax x > key / x >= key
+template <bool TRANSITIVE, bool PMAX>
+__device__ __forceinline__ bool coop_pass(int32_t x, int32_t key) { return (TRANSITIVE != PMAX) ? x >= key : x > key; }
+// [l, h) narrowed 64 probes a round until at most 256 elements remain (first passing element of [l, h), else h: unchanged)
+template <bool TRANSITIVE, bool PMAX>
+__device__ __forceinline__ void coop_narrow(const int32_t *__restrict__ col, uint32_t &l, uint32_t &h, int32_t key, uint32_t lane) {
+  while (h - l > 256u) {
+    const uint32_t step = (h - l + 63u) / 64u;
+    const uint32_t idx = min(l + (lane + 1u) * step - 1u, h - 1u);
+    const unsigned long long m = __ballot(coop_pass<TRANSITIVE, PMAX>(col[idx], key));
+    if (!m) { l = h; return; }  // (the last probe is h - 1)
+    const uint32_t k = (uint32_t)__ffsll((long long)m) - 1u;
+    h = min(l + (k + 1u) * step - 1u, h - 1u);  // passes: the first one is at or before it
+    l = l + k * step;                           // (the probe before it, if any, did not pass)
   }
-  cnt[o] = c;
-  if (cnt_ref) cnt_ref[r] = c;
-  win[o] = make_uint4(lo, ub, (uint32_t)mask, (uint32_t)(mask >> 32));
-  if (se) se[o] = f;  // (the whole record at the range's place: the projection reads its ends there, a kept level its range and target)
-  // windows too wide for the lane-per-range emit pass (dense targets) are listed for lookup_count_wide_kernel and the block-per-range emit
-  if (deferred) wide_list[atomicAdd(wide_n, 1u)] = o;
+}
+// The three boundary searches over one pair of columns: S (starts or their samples) for qe_min and qe_max, P (pmax) for
+// qs_min.  In: the searches' ranges, each of at most 64 * ROUNDS elements; out: the first passing element of each (else
+// its h).  A monotone predicate fails on exactly the elements before the first that passes, so the answer is l + the
+// number of failing probes: ROUNDS coalesced loads a lane and search, all in flight together, one ballot each.
+template <bool TRANSITIVE, uint32_t ROUNDS>
+__device__ __forceinline__ void coop_first3(const int32_t *__restrict__ S, const int32_t *__restrict__ P, uint32_t &la, uint32_t ha, uint32_t &lb,
+                                            uint32_t hb, uint32_t &l2, uint32_t h2, int32_t qe_min, int32_t qe_max, int32_t qs_min, uint32_t lane) {
+  int32_t xa[ROUNDS], xb[ROUNDS], x2[ROUNDS];
+#pragma unroll
+  for (uint32_t u = 0; u < ROUNDS; u++) {
+    const uint32_t ia = la + 64u * u + lane, ib = lb + 64u * u + lane, i2 = l2 + 64u * u + lane;
+    xa[u] = ia < ha ? S[ia] : 0;
+    xb[u] = ib < hb ? S[ib] : 0;
+    x2[u] = i2 < h2 ? P[i2] : 0;
+  }
+  uint32_t fa = 0, fb = 0, f2 = 0;
+#pragma unroll
+  for (uint32_t u = 0; u < ROUNDS; u++) {
+    const uint32_t ia = la + 64u * u + lane, ib = lb + 64u * u + lane, i2 = l2 + 64u * u + lane;
+    fa += (uint32_t)__popcll(__ballot(ia < ha && !coop_pass<TRANSITIVE, false>(xa[u], qe_min)));
+    fb += (uint32_t)__popcll(__ballot(ib < hb && !coop_pass<TRANSITIVE, false>(xb[u], qe_max)));
+    f2 += (uint32_t)__popcll(__ballot(i2 < h2 && !coop_pass<TRANSITIVE, true>(x2[u], qs_min)));
+  }
+  la += fa; lb += fb; l2 += f2;
+}
+template <bool TRANSITIVE>
+__global__ __launch_bounds__(256) void lookup_count_coop_kernel(DeviceIndexView v, const FrontierRec *__restrict__ fr, uint32_t n,
+                                                                const uint32_t *__restrict__ perm, uint32_t *__restrict__ cnt,
+                                                                uint4 *__restrict__ win, uint32_t *__restrict__ wide_n,
+                                                                uint32_t *__restrict__ wide_list, int by_place, FrontierRec *__restrict__ se,
+                                                                uint32_t *__restrict__ cnt_ref, uint32_t span_cap, uint32_t *__restrict__ reach) {
+  // a wave's slice: starts, pmax, the end column of [S0, S0 + LOOKUP_COOP_CAP)
+  __shared__ __attribute__((aligned(16))) int32_t stage[4][3][LOOKUP_COOP_CAP];
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x, lane = lane_id();
+  if (i - lane >= n) return;  // (a whole wave behind the end; in the last wave with ranges the lanes behind it stay: they probe and stage)
+  LK_CLOCKS(i - lane + 63u < n);
+  LK_MARK(0);
+  const bool live = i < n;
+  uint32_t r = 0;
+  FrontierRec f{0xFFFFFFFFu, 0, 0, 0u};
+  if (live) { r = perm[i]; f = fr[r]; }
+  const uint32_t o = by_place ? i : r;
+  uint32_t a_l, sn_l, off0_l, cnt0_l;
+  lookup_segment(v, f.target_id, a_l, sn_l, off0_l, cnt0_l);  // (a lane behind the end names no target: zeros)
+  LK_MARK(1);
+  // one valid target with a non-empty segment in every live lane?  (lane 0 is live; its descriptor is then the wave's: scalars)
+  const uint32_t t0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)f.target_id);
+  const bool one_target = __ballot(live && f.target_id != t0) == 0ull && t0 < v.n_seq;
+  const uint32_t a = (uint32_t)__builtin_amdgcn_readfirstlane((int)a_l), sn = (uint32_t)__builtin_amdgcn_readfirstlane((int)sn_l);
+  const uint32_t off0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)off0_l), cnt0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)cnt0_l);
+  const int32_t qs = f.start, qe = f.end;
+  // (a segment without a sampled level holds at most 64 entries -- the index builders make a level from 65 on -- and the wave's
+  // one round of 64 probes over [0, sn) relies on it: an index that says otherwise goes range by range, which searches any [0, sn))
+  uint32_t path = one_target && sn != 0u && (cnt0 != 0u || sn <= 64u) ? LK_REACH_COOP : LK_REACH_MIXED;
+  uint32_t L1a = 0, L1b = 0, L2 = 0, S0 = 0, S1 = 0;
+  if (path == LK_REACH_COOP) {
+    const int32_t qs_min = wave_min_i32(live ? qs : INT32_MAX), qe_min = wave_min_i32(live ? qe : INT32_MAX);
+    const int32_t qe_max = wave_max_i32(live ? qe : INT32_MIN);
+    // the wave's three searches: first block whose last element passes, then inside that block (as the lane kernel's two)
+    uint32_t H1a = sn, H1b = sn, H2 = sn;
+    if (cnt0) {
+      const int32_t *Sl = v.starts_lvl + off0, *Pl = v.pmax_lvl + off0;
+      uint32_t ba = 0, ea = cnt0, bb = 0, eb = cnt0, b2 = 0, e2 = cnt0;
+      if (cnt0 > 256u) {  // (a segment of more than 16 384 entries)
+        coop_narrow<TRANSITIVE, false>(Sl, ba, ea, qe_min, lane);
+        coop_narrow<TRANSITIVE, false>(Sl, bb, eb, qe_max, lane);
+        coop_narrow<TRANSITIVE, true>(Pl, b2, e2, qs_min, lane);
+      }
+      coop_first3<TRANSITIVE, 4u>(Sl, Pl, ba, ea, bb, eb, b2, e2, qe_min, qe_max, qs_min, lane);
+      L1a = ba < cnt0 ? 64u * ba : sn; H1a = ba < cnt0 ? min(L1a + 63u, sn) : sn;  // (that last element itself passes)
+      L1b = bb < cnt0 ? 64u * bb : sn; H1b = bb < cnt0 ? min(L1b + 63u, sn) : sn;
+      L2 = b2 < cnt0 ? 64u * b2 : sn; H2 = b2 < cnt0 ? min(L2 + 63u, sn) : sn;
+    }
+    coop_first3<TRANSITIVE, 1u>(v.starts + a, v.pmax + a, L1a, H1a, L1b, H1b, L2, H2, qe_min, qe_max, qs_min, lane);
+    LK_MARK(2);
+    // no lane's lo lies below S0, no lane's ub above S1 (places in the entry array; S0 on a vector boundary, as the walk starts)
+    S0 = (a + min(L2, L1a)) & ~3u; S1 = a + L1b;
+    if (S1 - S0 > span_cap) path = LK_REACH_SPAN;
+  }
+  if (reach && lane == 0u) atomicAdd(reach + path, 1u);
+  if (path != LK_REACH_COOP) {  // the whole wave, range by range
+    if (live) lookup_count_lane_body<TRANSITIVE>(v, f, r, o, a_l, sn_l, off0_l, cnt0_l, cnt, win, wide_n, wide_list, se, cnt_ref LK_PASS);
+#ifdef IMPG_LOOKUP_CLOCKS
+    LK_MARK(5);
+    if (lk_on && lane == 0u) { atomicAdd(&g_lookup_clk[13], lk_t[5] - lk_t[1]); atomicAdd(&g_lookup_clk[14], 1ull); }
+#endif
+    return;
+  }
+  const uint32_t wv = threadIdx.x >> 6;
+  int32_t *const sS = stage[wv][0], *const sP = stage[wv][1], *const sE = stage[wv][2];
+  // span <= LOOKUP_COOP_CAP = 4 * 64: a vector a lane and column.  (The index arrays end in slack for whole vectors; the searches
+  // below stay inside [S0, S1) and the walk tests i < ub, so what a vector holds beyond S1 is never used -- the end column's
+  // slots there are still set to INT_MIN, which no test passes.)
+  if (4u * lane < S1 - S0) {
+    const uint32_t g = S0 + 4u * lane;
+    const int4 xs = *reinterpret_cast<const int4 *>(v.starts + g), xp = *reinterpret_cast<const int4 *>(v.pmax + g);
+    int4 xe = *reinterpret_cast<const int4 *>(end_col<TRANSITIVE>(v) + g);
+    if (g + 1u >= S1) xe.y = INT32_MIN;
+    if (g + 2u >= S1) xe.z = INT32_MIN;
+    if (g + 3u >= S1) xe.w = INT32_MIN;
+    *reinterpret_cast<int4 *>(sS + 4u * lane) = xs;
+    *reinterpret_cast<int4 *>(sP + 4u * lane) = xp;
+    *reinterpret_cast<int4 *>(sE + 4u * lane) = xe;
+  }
+  // (one wave's ds_ instructions run in program order: only the compiler has to be kept from moving them)
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  LK_MARK(3);
+  if (live) {
+    // the lane's own two searches, in slots of the slice: l1 in [L1a, L1b], l2 from L2 on -- beyond S1 it could only
+    // exceed l1, and lo = min(l2, l1) either way
+    uint32_t l1 = a + L1a - S0, h1 = S1 - S0, l2 = a + min(L2, L1b) - S0, h2 = S1 - S0;
+    dual_search4<TRANSITIVE>(sS, l1, h1, sP, l2, h2, qs, qe);
+    LK_MARK(4);
+    const uint32_t ub = S0 + l1, lo = S0 + min(l2, l1);
+    uint32_t c = 0;
+    unsigned long long mask = 0;
+    const bool wide = lo < ub && ub - (lo & ~3u) > 64u;
+    const bool deferred = wide && wide_list != nullptr;
+    window_walk<TRANSITIVE>(sE, S0, lo, ub, qs, deferred, c, mask);
+    LK_MARK(5);
+    lookup_count_store(f, r, o, lo, ub, c, mask, deferred, cnt, win, wide_n, wide_list, se, cnt_ref);
+  }
+  LK_MARK(6);
+  LK_SUM(6, 6);
 }
 // ... and the wide windows' counts: a wave per listed window, 64 entries a round
 template <bool TRANSITIVE>
@@ -5097,13 +5339,18 @@ static inline uint32_t wave_grid(uint32_t n_items) {  // one wave per item, 4 wa
 
 void launch_lookup_count(const DeviceIndexView &v, const FrontierRec *fr, uint32_t n, bool transitive, const uint32_t *perm,
                          uint32_t *cnt, uint4 *win, uint32_t *wide_n, uint32_t *wide_list, hipStream_t s, bool by_place, FrontierRec *se,
-                         uint32_t *cnt_ref, bool count_reach) {
+                         uint32_t *cnt_ref, bool count_reach, CoopCount coop) {
   if (!n) return;
   const bool lanes = emit_by_lanes(v);
   const int bp = by_place && perm ? 1 : 0;
   if (!bp) se = nullptr;
   if (lanes) IMPG_HIP(hipMemsetAsync(wide_n, 0, count_reach ? LK_WORDS * 4 : 8, s));  // (the wide list's length, and its overflow list's: launch_lookup_emit; option lookup_stats: the reach words too)
-  if (transitive) lookup_count_lane_kernel<true><<<cdiv(n, 256), 256, 0, s>>>(v, fr, n, perm, cnt, win, wide_n, lanes ? wide_list : nullptr, bp, se, cnt_ref);
+  if (perm && coop.on) {  // a level with a lookup order: a wave's ranges are neighbours
+    uint32_t *reach = lanes && count_reach ? wide_n + LK_REACH_BASE : nullptr;
+    const uint32_t span = std::min(coop.span, LOOKUP_COOP_CAP);
+    if (transitive) lookup_count_coop_kernel<true><<<cdiv(n, 256), 256, 0, s>>>(v, fr, n, perm, cnt, win, wide_n, lanes ? wide_list : nullptr, bp, se, cnt_ref, span, reach);
+    else lookup_count_coop_kernel<false><<<cdiv(n, 256), 256, 0, s>>>(v, fr, n, perm, cnt, win, wide_n, lanes ? wide_list : nullptr, bp, se, cnt_ref, span, reach);
+  } else if (transitive) lookup_count_lane_kernel<true><<<cdiv(n, 256), 256, 0, s>>>(v, fr, n, perm, cnt, win, wide_n, lanes ? wide_list : nullptr, bp, se, cnt_ref);
   else lookup_count_lane_kernel<false><<<cdiv(n, 256), 256, 0, s>>>(v, fr, n, perm, cnt, win, wide_n, lanes ? wide_list : nullptr, bp, se, cnt_ref);
   if (lanes) {  // the listed (wide) windows' counts; the list's length stays on the device: a grid of at most 8 192 waves strides over it
     const uint32_t g = std::min(cdiv(n, 4u), 2048u);

@@ -54,20 +54,31 @@ struct VisitedTables {
 // wide_n: LK_WORDS words.  [0] the length of the wide list (windows wider than the count pass's 64-bit hit mask), [1] that of its
 // overflow list (windows lookup_emit_wide_kernel hands to lookup_emit_kernel), both cleared by the count pass; from LK_REACH_BASE
 // on, the reach counters lookup_emit_wide_kernel bumps, once per window and only under count_reach (option lookup_stats):
-// windows sorted in one LDS pass, windows split into rank-bin groups, the collect-sort-write passes of those
+// windows sorted in one LDS pass, windows split into rank-bin groups, the collect-sort-write passes of those -- and the waves of
+// lookup_count_coop_kernel by the path they took: cooperative, the lane body because their ranges name more than one target
+// (or an invalid one, or one without entries), the lane body because their span is wider than the slice
 constexpr uint32_t LK_WORDS = 8, LK_REACH_BASE = 2, LK_REACH_SINGLE = 0, LK_REACH_GROUPED = 1, LK_REACH_PASSES = 2;
+constexpr uint32_t LK_REACH_COOP = 3, LK_REACH_MIXED = 4, LK_REACH_SPAN = 5;
+static_assert(LK_REACH_BASE + LK_REACH_SPAN < LK_WORDS, "the reach words fit");
+// entries of starts / pmax / the end column a wave of lookup_count_coop_kernel stages in LDS (a 16-byte vector a lane and
+// column; 3 KB a wave) ...
+constexpr uint32_t LOOKUP_COOP_CAP = 256;
+// ... and what a launch uses of it (options lookup_coop / lookup_coop_span: A/B runs and testing; results identical)
+struct CoopCount { uint32_t span = LOOKUP_COOP_CAP; bool on = true; };
 // lookup_emit_wide_kernel's key buffer and rank bins (the size of its LDS arrays) ...
 constexpr uint32_t WIDE_CAP = 4096, WIDE_BINS = 1024;
 // ... and what a launch uses of them (options wide_emit_cap / wide_emit_bins: testing; results identical)
 struct WideEmit { uint32_t cap = WIDE_CAP, bins = WIDE_BINS; bool count_reach = false; };
-// the lookup's wide windows by the path that emitted them (impg_gpu_get_counter "lookup_wide_*"; option lookup_stats)
-enum LookupStat { LK_WIDE = 0, LK_SINGLE, LK_GROUPED, LK_GROUP_PASSES, LK_OVERFLOW, LK_STATS };
+// the lookup's wide windows by the path that emitted them (impg_gpu_get_counter "lookup_wide_*"; option lookup_stats), and the
+// count pass's waves by theirs ("lookup_coop_waves", "lookup_lane_waves_*")
+enum LookupStat { LK_WIDE = 0, LK_SINGLE, LK_GROUPED, LK_GROUP_PASSES, LK_OVERFLOW, LK_COOP, LK_MIXED, LK_SPAN, LK_STATS };
 static_assert(LK_STATS == sizeof(impg_gpu_index::lk_stats) / sizeof(impg_gpu_index::lk_stats[0]), "one counter per path");
 void launch_lookup_count(const DeviceIndexView &v, const FrontierRec *fr, uint32_t n, bool transitive, const uint32_t *perm,
                          uint32_t *cnt, uint4 *win, uint32_t *wide_n, uint32_t *wide_list, hipStream_t s, bool by_place = false,
                          FrontierRec *se = nullptr /* by_place: the ranges' records at their places (the projection reads the ends there) */,
                          uint32_t *cnt_ref = nullptr /* by_place: the counts in FRONTIER order too (ordered rows) */,
-                         bool count_reach = false /* wide_n's reach words cleared too */);
+                         bool count_reach = false /* wide_n's reach words cleared too */,
+                         CoopCount coop = CoopCount{} /* with perm: lookup_count_coop_kernel, staging spans of at most coop.span entries */);
 // visit position of every hit of the windows of <= 64 entries, by place: vpos[pair_off[i] + k] for range i's k-th hit in index order
 // (dest: the ranges' first rows, computed by the same kernel: dest[place] = offsets[query] + lvbase[query] + slot_ref[range])
 struct OrdDestArgs { const FrontierRec *frp; const uint32_t *perm, *slot_ref, *offsets, *lvbase; uint32_t *dest; };

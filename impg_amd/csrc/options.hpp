@@ -27,6 +27,8 @@ struct Options {
   int64_t lookup_stats = 0;           // lookup: every level's wide windows counted by the path that emitted them into the lookup_wide_* counters (1: one small copy per level)
   int64_t wide_emit_cap = 4096;       // hits lookup_emit_wide_kernel sorts in one LDS pass (testing; results identical)
   int64_t wide_emit_bins = 1024;      // rank bins it groups a window's hits by beyond that (testing; results identical)
+  int64_t lookup_coop = 1;            // lookup: a level with a lookup order is counted by lookup_count_coop_kernel (1) or by the lane kernel (0); results identical
+  int64_t lookup_coop_span = 256;     // entries a wave of that kernel stages at most; a wider span takes the lane body (testing; results identical)
   // store_cigar on a tracepoint index: 0 refused; 1 every row carries the approximate mode's CIGAR, [matches '='] [mismatches 'X']
   // with a zero count left out (impg.rs:1479-1486) -- statistics, not an alignment: the lengths do not add up to the row's
   // coordinates.  No effect on a CIGAR index; not saved with the index.
@@ -68,6 +70,8 @@ constexpr OptionRow OPTION_TABLE[] = {
     {"lookup_stats", INT64_MIN, INT64_MAX, &Options::lookup_stats, true, false, ""},
     {"wide_emit_cap", 64, 4096, &Options::wide_emit_cap, false, false, "wide_emit_cap is 64 .. 4096"},
     {"wide_emit_bins", 2, 1024, &Options::wide_emit_bins, false, false, "wide_emit_bins is 2 .. 1024"},
+    {"lookup_coop", INT64_MIN, INT64_MAX, &Options::lookup_coop, true, false, ""},
+    {"lookup_coop_span", 4, 256, &Options::lookup_coop_span, false, false, "lookup_coop_span is 4 .. 256"},
     {"approximate_cigar", 0, 1, &Options::approximate_cigar, false, true, "approximate_cigar is 0 or 1"},
     {"free_slot_order", INT64_MIN, INT64_MAX, &Options::free_slot_order, true, false, ""},
     {"debug_fail_owner", 0, 0xFFFFFFFFll, &Options::debug_fail_owner, false, true, "debug_fail_* out of range"},

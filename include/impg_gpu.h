@@ -233,6 +233,10 @@ int impg_gpu_index_approximate(const impg_gpu_index_t *);
  * "wide_emit_cap" (64 .. 4096, the default) and "wide_emit_bins" (2 .. 1024, the default): the hits the lookup sorts in one
  * pass for a window of more than 64 entries, and the rank bins it groups a window's hits by beyond that -- for tests;
  * results are identical,
+ * "lookup_coop" (1, the default: a level whose ranges are taken in the lookup order is counted wave by wave, a wave
+ * searching once for its 64 ranges and reading their windows from its copy of the index columns; 0: range by range;
+ * results identical) and "lookup_coop_span" (4 .. 256, the default: the entries such a wave copies at most; a wave whose
+ * ranges span more counts range by range -- for tests; results identical),
  * "fuse_final_level" (1, the default: the final level of such a run -- no update follows, no row is kept --
  * takes its (range, entry) pairs straight from the lookup's per-range windows inside the projection kernel; the emit
  * pass and its pair lists are skipped; counts and checksums are identical either way),
@@ -294,7 +298,10 @@ const char *impg_gpu_counter_key(size_t i);
  * "lookup_stats" = 1 (0, the default: nothing is copied or counted) every level's lookup counts its windows of more than 64
  * entries: "lookup_wide_windows" (all of them), "lookup_wide_single" (hits sorted in one pass), "lookup_wide_grouped" (hits
  * split into groups of rank bins), "lookup_wide_group_passes" (the passes those took), "lookup_wide_overflow" (one rank bin
- * alone beyond the buffer: handed to the wave-per-range kernel).  Of the last device BED call on the handle
+ * alone beyond the buffer: handed to the wave-per-range kernel); and the waves of a level counted under option
+ * "lookup_coop": "lookup_coop_waves" (counted together), "lookup_lane_waves_mixed" (range by range: more than one target,
+ * an unknown one or one without entries), "lookup_lane_waves_span" (range by range: a span beyond "lookup_coop_span").
+ * Of the last device BED call on the handle
  * (impg_gpu_query_batch_bed, impg_gpu_query_batch_bed_fd, impg_gpu_selftest_bed_rows; zero when it starts, every chunk adds;
  * on a multi-GPU handle its ranks count, not the handle): "bed_rows" = rows entering the merges, "bed_gap_roots" = rows
  * after merge_adjusted_intervals_gap_2d, "bed_runs" = merged rows out, "bed_text_pieces" = text pieces sent to the host,
