@@ -44,6 +44,7 @@ static void engine_options(impg_gpu_index &ix, Engine *e) {
   e->coop_count = CoopCount{(uint32_t)o.lookup_coop_span, o.lookup_coop != 0};
   e->seg_stats = ix.seg_stats;
   e->proj_stats = ix.proj_stats;
+  e->place_block_levels = &ix.place_block_levels;
   e->upd_stats = ix.upd_stats;
   e->dfs_stats = ix.dfs_stats;
   e->lk_stats = ix.lk_stats;
@@ -686,6 +687,7 @@ static const CounterRow COUNTER_TABLE[] = {
     CTR("project_staged_rows_levels", proj_stats[PROJ_ARM_STAGED_ROWS]), CTR("project_entries_slots_levels", proj_stats[PROJ_ARM_ENTRIES_SLOTS]),
     CTR("project_entries_qs_levels", proj_stats[PROJ_ARM_ENTRIES_QS]), CTR("project_entries_rows_levels", proj_stats[PROJ_ARM_ENTRIES_ROWS]),
     CTR("project_entries_ident_levels", proj_stats[PROJ_ARM_ENTRIES_IDENT]), CTR("project_tp_levels", proj_stats[PROJ_ARM_TP]),
+    CTR("place_offsets_block_levels", place_block_levels),
     CTR("update_lane_groups", upd_stats[UPD_LANE]), CTR("update_mid_groups", upd_stats[UPD_MID]), CTR("update_wave_tiny_groups", upd_stats[UPD_WAVE_TINY]),
     CTR("update_wave_small_groups", upd_stats[UPD_WAVE_SMALL]), CTR("update_wave_large_groups", upd_stats[UPD_WAVE_LARGE]),
     CTR("update_inplace_groups", upd_stats[UPD_INPLACE]), CTR("update_tiled_sort_groups", upd_stats[UPD_TILED_SORT]),

@@ -317,14 +317,16 @@ uint64_t Engine::read_slots(DevBuf &b) {
   return t;
 }
 
-uint64_t Engine::scan(const uint32_t *in, uint32_t *out, uint32_t n) {
-  if (n == 0) return 0;
+uint64_t Engine::scan(const uint32_t *in, uint32_t *out, uint32_t n, const uint32_t *d_extra, uint32_t *h_extra, uint32_t n_extra) {
+  if (n == 0) { if (n_extra) memset(h_extra, 0, (size_t)n_extra * 4); return 0; }
   scan_tmp.reserve(scan_scratch_bytes(n));
   launch_exclusive_scan(in, out, n, scan_tmp.as<unsigned long long>(), counters.as<unsigned long long>() + 3, stream);
   // (the bad-range flag of device-resident ranges comes back with the total: the first level's scan raises it before any
   // pair is projected)
   IMPG_HIP(hipMemcpyAsync(h_counters, counters.as<uint64_t>() + 3, 24, hipMemcpyDeviceToHost, stream));
+  if (n_extra) IMPG_HIP(hipMemcpyAsync(h_counters + 3, d_extra, (size_t)n_extra * 4, hipMemcpyDeviceToHost, stream));
   IMPG_HIP(hipStreamSynchronize(stream));
+  if (n_extra) memcpy(h_extra, h_counters + 3, (size_t)n_extra * 4);
   if (h_counters[2]) throw Error{IMPG_E_INVALID, "query range must satisfy start < end"};
   return h_counters[0];
 }
@@ -351,6 +353,10 @@ static HitArrays hit_arrays(LevelBufs &L, uint32_t n_pairs) {
   return HitArrays{L.qid.as<uint32_t>(), L.coords.as<int4>()};
 }
 
+static bool lib_sort_selected() {  // (A/B: IMPG_LIB_SORT=1 orders the keys with the library's radix sort, whose values are the idx array)
+  static const bool b = getenv("IMPG_LIB_SORT") && atoi(getenv("IMPG_LIB_SORT")) != 0;
+  return b;
+}
 // Lookup / projection order: the slots stay in the reference's order, but the count,
 // emit and projection kernels take the ranges in the order of their (estimated)
 // windows in the entry array, so that lanes and workgroups in flight together
@@ -372,14 +378,13 @@ const uint32_t *Engine::lookup_order(const DeviceIndexView &v, const FrontierRec
   if (!blocks && keys_for && keys_for == (const void *)fr && keys_n == n_fr) {
     // (frontier_emit wrote them beside this frontier's records)
   } else
-    launch_order_keys(v, fr, n_fr, lo_key.as<uint32_t>(), lo_idx.as<uint32_t>(), stream, blocks ? blocks->d_bounds : nullptr,
+    launch_order_keys(v, fr, n_fr, lo_key.as<uint32_t>(), lib_sort_selected() ? lo_idx.as<uint32_t>() : nullptr, stream, blocks ? blocks->d_bounds : nullptr,
                       blocks ? blocks->n_blocks : 0u, block_shift);
   keys_for = nullptr;
   // (every bit of the key is sorted.  Round 5, measured: leaving the low 5 bits unsorted -- two radix passes instead of
   // three -- takes 0.35 ms off the lookup and puts 4.4 ms ON the projection (22.1 -> 26.5 ms: the entries kernel's waves
   // find their entry's places in shorter runs); 9 bits: 87 ms.)
-  static const bool lib_sort = getenv("IMPG_LIB_SORT") && atoi(getenv("IMPG_LIB_SORT")) != 0;  // (A/B: the library's radix sort)
-  if (lib_sort) {
+  if (lib_sort_selected()) {
     const size_t tb = sort_u32_scratch_bytes(n_fr);
     sort_tmp.reserve(tb);
     launch_sort_u32(sort_tmp.p, tb, lo_key.as<uint32_t>(), lo_key2.as<uint32_t>(), lo_idx.as<uint32_t>(), lo_perm.as<uint32_t>(), n_fr,
@@ -453,10 +458,36 @@ uint64_t Engine::expand(const DeviceIndexView &v, const FrontierRec *fr, uint32_
   if (by_place) win_se.reserve(std::max<size_t>((size_t)n_fr * sizeof(FrontierRec), 256));
   const bool ordered = run_modes.ordered_rows && !raw;
   if (ordered) { L.slot_ref.reserve(std::max<size_t>((size_t)n_fr * 4, 256)); ord_cnt.reserve(std::max<size_t>((size_t)n_fr * 4, 256)); }
-  launch_lookup_count(v, fr, n_fr, transitive, d_perm, cnt.as<uint32_t>(), win.as<uint4>(), wide_n.as<uint32_t>(),
-                      wide_list.as<uint32_t>(), stream, by_place, by_place ? win_se.as<FrontierRec>() : nullptr,
-                      ordered && by_place ? ord_cnt.as<uint32_t>() : nullptr, lk, coop_count);
-  uint64_t P = scan(cnt.as<uint32_t>(), pair_off.as<uint32_t>(), n_fr);
+  // A fused level that project_entries_kernel will run reads a range's first place only as block_base + local_off (WindowLists):
+  // the count pass leaves every place's offset inside its block of PLACE_BLOCK places (a wave's) and the blocks' sums, and the scan
+  // runs over those sums -- n / 64 words instead of n.  Whether that kernel runs the level is known once P is (project_entry_major),
+  // and a deferred wide window is missing from the sums (wide_n[0], home with P): either way the per-range scan below runs
+  // as it always did, over the cnt[] the count pass still writes, and every other consumer finds pair_off[] as before.
+  const uint32_t n_pb = (n_fr + PLACE_BLOCK - 1u) / PLACE_BLOCK;
+  bool place_blocks = fused && opt.place_offsets_blocks && !raw && !ordered;
+  if (place_blocks) {
+    place_local.reserve(std::max<size_t>((size_t)n_fr * 4, 256));
+    place_sum.reserve(std::max<size_t>((size_t)n_pb * 4, 256)); place_base.reserve(std::max<size_t>((size_t)n_pb * 4, 256));
+  }
+  place_blocks = launch_lookup_count(v, fr, n_fr, transitive, d_perm, cnt.as<uint32_t>(), win.as<uint4>(), wide_n.as<uint32_t>(),
+                                     wide_list.as<uint32_t>(), stream, by_place, by_place ? win_se.as<FrontierRec>() : nullptr,
+                                     ordered && by_place ? ord_cnt.as<uint32_t>() : nullptr, lk, coop_count,
+                                     place_blocks ? place_local.as<uint32_t>() : nullptr, place_blocks ? place_sum.as<uint32_t>() : nullptr);
+  // (a fused level's wide list lengths come home with P: its wide-window emit kernels are launched only when something is listed)
+  uint32_t n_wide[2] = {0u, 0u};
+  bool wide_known = false;
+  uint64_t P = 0;
+  if (place_blocks) {
+    P = scan(place_sum.as<uint32_t>(), place_base.as<uint32_t>(), n_pb, wide_n.as<uint32_t>(), n_wide, 2);
+    wide_known = true;
+    if (n_wide[0] || !project_entry_major(v, P, min_identity)) place_blocks = false;
+    else if (place_block_levels) (*place_block_levels)++;
+  }
+  if (!place_blocks) {
+    const bool ask = fused && !wide_known;
+    P = scan(cnt.as<uint32_t>(), pair_off.as<uint32_t>(), n_fr, ask ? wide_n.as<uint32_t>() : nullptr, n_wide, ask ? 2u : 0u);
+    wide_known = wide_known || ask;
+  }
   if (P > (uint64_t)opt.pair_budget || P >= 0xFFFFFFF0ull) {
     if (split_ok) throw SplitBatch{};
     if (P >= 0xFFFFFFF0ull) throw Error{IMPG_E_UNSUPPORTED, "more than 2^32 candidate pairs for a single range"};
@@ -480,11 +511,14 @@ uint64_t Engine::expand(const DeviceIndexView &v, const FrontierRec *fr, uint32_
     // (tile_first[]: only project_kernel needs it -- the kernels of a dense level search their own block's offsets)
     const bool staged = project_is_staged(v, P, !store_cigar && !(min_identity == min_identity));
     tile_first.reserve(((size_t)(P + 255) / 256 + 1) * 4);
-    if (!staged) launch_tile_first(cnt.as<uint32_t>(), pair_off.as<uint32_t>(), n_fr, tile_first.as<uint32_t>(), stream);
-    launch_lookup_emit(v, fr, n_fr, transitive, pair_off.as<uint32_t>(), win.as<uint4>(), L.pair_range.as<uint32_t>(),
-                       pair_entry.as<uint32_t>(), d_perm, nullptr, pl, wide_n.as<uint32_t>(), wide_list.as<uint32_t>(), stream, true, true, we);
+    if (!staged && !place_blocks) launch_tile_first(cnt.as<uint32_t>(), pair_off.as<uint32_t>(), n_fr, tile_first.as<uint32_t>(), stream);
+    // (the wide windows' two emit kernels: not launched when the count pass listed none -- then neither can hand one on)
+    if (!(wide_known && !n_wide[0] && !n_wide[1]))
+      launch_lookup_emit(v, fr, n_fr, transitive, pair_off.as<uint32_t>(), win.as<uint4>(), L.pair_range.as<uint32_t>(),
+                         pair_entry.as<uint32_t>(), d_perm, nullptr, pl, wide_n.as<uint32_t>(), wide_list.as<uint32_t>(), stream, true, true, we);
     wlists = WindowLists{tile_first.as<uint32_t>(), pair_off.as<uint32_t>(), win.as<uint4>(), win_se.as<FrontierRec>(), d_perm, n_fr,
                          fuse_need_ranges && !direct ? L.pair_range.as<uint32_t>() : nullptr, 1u, fuse_range_places ? 1u : 0u};
+    if (place_blocks) { wlists.block_base = place_base.as<uint32_t>(); wlists.local_off = place_local.as<uint32_t>(); }
     last_range_places = fuse_need_ranges && fuse_range_places && !direct;
     if (project_entry_major(v, P, min_identity) && !store_cigar) {  // the slice list and the range blocks' place counters of its heavy blocks
       const uint32_t cap = project_entry_slice_cap(P), nb = project_entry_blocks(n_fr);
@@ -805,7 +839,14 @@ uint32_t Engine::update(const DeviceIndexView &v, const FrontierRec *fr, LevelBu
       vt->off.reserve((size_t)n_groups * 4);
       poff.reserve((size_t)n_groups * 4);
       uint64_t cap_total = 0, pcap_total = 0;
-      scan2(cap.as<uint32_t>(), vt->off.as<uint32_t>(), pcap.as<uint32_t>(), poff.as<uint32_t>(), n_groups, cap_total, pcap_total);
+      // (the groups listed by tier ahead of the two scans: the lists' lengths come home behind the scans' synchronisation, and
+      // launch_visited_update launches the listed kernels by them)
+      big_list.reserve((size_t)n_groups * 12);  // three lists: [small from the front | large from the back], [tiny], [mid] (big_groups_kernel)
+      uint32_t *d_nbig = (uint32_t *)(counters.as<uint64_t>() + 8);
+      uint32_t h_lists[VU_LIST_WORDS] = {0};
+      launch_big_groups(cap.as<uint32_t>(), pcap.as<uint32_t>(), n_groups, big_list.as<uint32_t>(), d_nbig, stream);
+      scan2(cap.as<uint32_t>(), vt->off.as<uint32_t>(), pcap.as<uint32_t>(), poff.as<uint32_t>(), n_groups, cap_total, pcap_total, d_nbig, h_lists,
+            VU_LIST_WORDS);
       if (cap_total >= 0xFFFFFFF0ull || pcap_total >= 0xFFFFFFF0ull)
         { if (split_ok) throw SplitBatch{}; throw Error{IMPG_E_UNSUPPORTED, "visited sets exceed 2^32 ranges"}; }
       vt->ranges.reserve(std::max<size_t>(cap_total * 8, 256));
@@ -813,13 +854,12 @@ uint32_t Engine::update(const DeviceIndexView &v, const FrontierRec *fr, LevelBu
       pieces.reserve(std::max<size_t>(pcap_total * 8, 256));
       n_pieces.reserve((size_t)n_groups * 4);
       foff.reserve((size_t)n_groups * 4);
-      big_list.reserve((size_t)n_groups * 12);  // three lists: [small from the front | large from the back], [tiny], [mid] (big_groups_kernel)
       launch_visited_update(replay_vals, masked ? mask_touch_len.as<int32_t>() : v.seq_len, vt->keys.as<unsigned long long>(),
                             gstart.as<uint32_t>(), glen.as<uint32_t>(), old_src.as<const int2 *>(),
                             vt->off.as<uint32_t>(), poff.as<uint32_t>(), n_groups, p.min_transitive_len,
                             p.min_distance_between_ranges, vt->ranges.as<int2>(), vt->len.as<uint32_t>(),
                             pieces.as<int2>(), n_pieces.as<uint32_t>(), cap.as<uint32_t>(), pcap.as<uint32_t>(), big_list.as<uint32_t>(),
-                            (uint32_t *)(counters.as<uint64_t>() + 8), opt.update_stats && upd_stats, stream);
+                            d_nbig, opt.update_stats && upd_stats, stream, h_lists);
       uint64_t nn = scan(n_pieces.as<uint32_t>(), foff.as<uint32_t>(), n_groups);
       if (opt.update_stats && upd_stats && n_groups) {  // (the scan has waited for the update: its words are final)
         IMPG_HIP(hipMemcpyAsync(h_counters, counters.as<uint64_t>() + 8, VU_NBIG_WORDS * 4, hipMemcpyDeviceToHost, stream));
@@ -842,7 +882,7 @@ uint32_t Engine::update(const DeviceIndexView &v, const FrontierRec *fr, LevelBu
       if (keys_too) { lo_key.reserve((size_t)n_next * 4); lo_idx.reserve((size_t)n_next * 4); }
       launch_frontier_emit(vt->keys.as<unsigned long long>(), poff.as<uint32_t>(), n_pieces.as<uint32_t>(),
                            foff.as<uint32_t>(), n_groups, pieces.as<int2>(), next_frontier.as<FrontierRec>(), stream,
-                           keys_too ? &v : nullptr, lo_key.as<uint32_t>(), lo_idx.as<uint32_t>());
+                           keys_too ? &v : nullptr, lo_key.as<uint32_t>(), lib_sort_selected() ? lo_idx.as<uint32_t>() : nullptr);
       keys_for = keys_too ? next_frontier.p : nullptr;
       keys_n = n_next;
       vt->n_groups = n_groups;

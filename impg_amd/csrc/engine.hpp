@@ -147,6 +147,7 @@ struct Engine {
   float ms_place = 0;
   DevBuf ent_work, ent_alloc;      // project_entries_kernel: the slice list of its heavy blocks, a place counter per range block
   DevBuf win_se, tile_first;       // the ranges' (start, end) by place; first range of every projection tile
+  DevBuf place_local, place_sum, place_base;  // a fused level's place offsets in two levels (WindowLists::local_off; option "place_offsets_blocks")
   uint64_t covered_dropped = 0;    // hits option "filter_covered" dropped, over the engine's life (tuning aid)
   DevBuf m_dest, m_qid, m_coords, m_pe, m_sa, m_sn, m_so, m_sr;  // 5-key sort: destination + double buffers
   // projection order (locality): ranges sorted by window position, their slots listed in that order
@@ -163,8 +164,9 @@ struct Engine {
   ~Engine();
   hipEvent_t event();
   uint64_t read_counter(int k);
-  uint64_t scan(const uint32_t *in, uint32_t *out, uint32_t n);
-  // two scans over n items each and up to four extra device words (a kernel's flags) behind ONE synchronisation
+  // (up to eight extra device words, a kernel's flags or list lengths, come home behind the same synchronisation)
+  uint64_t scan(const uint32_t *in, uint32_t *out, uint32_t n, const uint32_t *d_extra = nullptr, uint32_t *h_extra = nullptr, uint32_t n_extra = 0);
+  // two scans over n items each and up to ten extra device words (a kernel's flags or list lengths) behind ONE synchronisation
   void scan2(const uint32_t *in_a, uint32_t *out_a, const uint32_t *in_b, uint32_t *out_b, uint32_t n, uint64_t &total_a, uint64_t &total_b,
              const uint32_t *d_extra = nullptr, uint32_t *h_extra = nullptr, uint32_t n_extra = 0);
   // lookup / projection order (locality): lookup_order() before the count pass gives the permutation (null
@@ -253,6 +255,7 @@ struct Engine {
   std::atomic<uint64_t> *proj_stats = nullptr;  // ... and its levels per projection kernel (impg_gpu_index::proj_stats, by ProjArm)
   std::atomic<uint64_t> *upd_stats = nullptr;  // ... and its groups per tier / rare path of the visited update (by UpdStat; option update_stats)
   std::atomic<uint64_t> *dfs_stats = nullptr;  // ... and its DFS rounds and visited-table folds (impg_gpu_index::dfs_stats)
+  std::atomic<uint64_t> *place_block_levels = nullptr;  // ... and its fused levels whose place offsets came in two levels (Engine::expand)
   void count_arm(int arm) { if (proj_stats && arm >= 0 && arm < PROJ_ARMS) proj_stats[arm]++; }
   uint32_t walk_group_size(const impg_gpu_index &ix, uint32_t n, const impg_gpu_params_t &p) const;
   char *small_in = nullptr;    // pinned: the ranges on their way in

@@ -492,6 +492,7 @@ struct impg_gpu_index {
   mutable std::atomic<uint64_t> seg_stats[3] = {};
   // ... and which kernel projected each level (by impg::ProjArm: launch_project's return value, counted by the engine)
   mutable std::atomic<uint64_t> proj_stats[8] = {};
+  mutable std::atomic<uint64_t> place_block_levels{0};  // ... and the fused levels that took their place offsets in two levels (option place_offsets_blocks)
   // ... and, under option update_stats, the groups each tier of the visited update took and the rare paths they reached (by impg::UpdStat)
   mutable std::atomic<uint64_t> upd_stats[8] = {};
   // ... and, under option lookup_stats, the lookup's wide windows by the path that emitted them (by impg::LookupStat)

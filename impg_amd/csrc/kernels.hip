@@ -185,7 +185,7 @@ __device__ __forceinline__ void lookup_segment(const DeviceIndexView &v, uint32_
 // One lane, one range, every search and the window through the vector-memory path: the whole of lookup_count_lane_kernel, and
 // what a wave of lookup_count_coop_kernel falls back to.
 template <bool TRANSITIVE>
-__device__ __forceinline__ void lookup_count_lane_body(const DeviceIndexView &v, const FrontierRec &f, uint32_t r, uint32_t o, uint32_t a, uint32_t sn,
+__device__ __forceinline__ uint32_t lookup_count_lane_body(const DeviceIndexView &v, const FrontierRec &f, uint32_t r, uint32_t o, uint32_t a, uint32_t sn,
                                                        uint32_t off0, uint32_t cnt0, uint32_t *__restrict__ cnt, uint4 *__restrict__ win,
                                                        uint32_t *__restrict__ wide_n, uint32_t *__restrict__ wide_list, FrontierRec *__restrict__ se,
                                                        uint32_t *__restrict__ cnt_ref LK_ARG) {
@@ -213,6 +213,7 @@ __device__ __forceinline__ void lookup_count_lane_body(const DeviceIndexView &v,
   window_walk<TRANSITIVE>(end_col<TRANSITIVE>(v), 0u, lo, ub, qs, deferred, c, mask);
   LK_MARK(4);
   lookup_count_store(f, r, o, lo, ub, c, mask, deferred, cnt, win, wide_n, wide_list, se, cnt_ref);
+  return c;
 }
 template <bool TRANSITIVE>
 __global__ __launch_bounds__(256) void lookup_count_lane_kernel(DeviceIndexView v, const FrontierRec *__restrict__ fr,
@@ -317,16 +318,17 @@ __device__ __forceinline__ void coop_first3(const int32_t *__restrict__ S, const
   }
   la += fa; lb += fb; l2 += f2;
 }
+// (the kernel's work; returns the lane's count -- 0 for a lane behind the end and for a deferred window)
 template <bool TRANSITIVE>
-__global__ __launch_bounds__(256) void lookup_count_coop_kernel(DeviceIndexView v, const FrontierRec *__restrict__ fr, uint32_t n,
-                                                                const uint32_t *__restrict__ perm, uint32_t *__restrict__ cnt,
-                                                                uint4 *__restrict__ win, uint32_t *__restrict__ wide_n,
-                                                                uint32_t *__restrict__ wide_list, int by_place, FrontierRec *__restrict__ se,
-                                                                uint32_t *__restrict__ cnt_ref, uint32_t span_cap, uint32_t *__restrict__ reach) {
+__device__ __forceinline__ uint32_t lookup_count_coop_body(const DeviceIndexView &v, const FrontierRec *__restrict__ fr, uint32_t n,
+                                                           const uint32_t *__restrict__ perm, uint32_t *__restrict__ cnt,
+                                                           uint4 *__restrict__ win, uint32_t *__restrict__ wide_n,
+                                                           uint32_t *__restrict__ wide_list, int by_place, FrontierRec *__restrict__ se,
+                                                           uint32_t *__restrict__ cnt_ref, uint32_t span_cap, uint32_t *__restrict__ reach) {
   // a wave's slice: starts, pmax, the end column of [S0, S0 + LOOKUP_COOP_CAP)
   __shared__ __attribute__((aligned(16))) int32_t stage[4][3][LOOKUP_COOP_CAP];
   const uint32_t i = blockIdx.x * 256u + threadIdx.x, lane = lane_id();
-  if (i - lane >= n) return;  // (a whole wave behind the end; in the last wave with ranges the lanes behind it stay: they probe and stage)
+  if (i - lane >= n) return 0u;  // (a whole wave behind the end; in the last wave with ranges the lanes behind it stay: they probe and stage)
   LK_CLOCKS(i - lane + 63u < n);
   LK_MARK(0);
   const bool live = i < n;
@@ -373,12 +375,13 @@ __global__ __launch_bounds__(256) void lookup_count_coop_kernel(DeviceIndexView 
   }
   if (reach && lane == 0u) atomicAdd(reach + path, 1u);
   if (path != LK_REACH_COOP) {  // the whole wave, range by range
-    if (live) lookup_count_lane_body<TRANSITIVE>(v, f, r, o, a_l, sn_l, off0_l, cnt0_l, cnt, win, wide_n, wide_list, se, cnt_ref LK_PASS);
+    uint32_t c = 0;
+    if (live) c = lookup_count_lane_body<TRANSITIVE>(v, f, r, o, a_l, sn_l, off0_l, cnt0_l, cnt, win, wide_n, wide_list, se, cnt_ref LK_PASS);
 #ifdef IMPG_LOOKUP_CLOCKS
     LK_MARK(5);
     if (lk_on && lane == 0u) { atomicAdd(&g_lookup_clk[13], lk_t[5] - lk_t[1]); atomicAdd(&g_lookup_clk[14], 1ull); }
 #endif
-    return;
+    return c;
   }
   const uint32_t wv = threadIdx.x >> 6;
   int32_t *const sS = stage[wv][0], *const sP = stage[wv][1], *const sE = stage[wv][2];
@@ -401,6 +404,7 @@ __global__ __launch_bounds__(256) void lookup_count_coop_kernel(DeviceIndexView 
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   LK_MARK(3);
+  uint32_t c = 0;
   if (live) {
     // the lane's own two searches, in slots of the slice: l1 in [L1a, L1b], l2 from L2 on -- beyond S1 it could only
     // exceed l1, and lo = min(l2, l1) either way
@@ -408,7 +412,6 @@ __global__ __launch_bounds__(256) void lookup_count_coop_kernel(DeviceIndexView 
     dual_search4<TRANSITIVE>(sS, l1, h1, sP, l2, h2, qs, qe);
     LK_MARK(4);
     const uint32_t ub = S0 + l1, lo = S0 + min(l2, l1);
-    uint32_t c = 0;
     unsigned long long mask = 0;
     const bool wide = lo < ub && ub - (lo & ~3u) > 64u;
     const bool deferred = wide && wide_list != nullptr;
@@ -418,6 +421,28 @@ __global__ __launch_bounds__(256) void lookup_count_coop_kernel(DeviceIndexView 
   }
   LK_MARK(6);
   LK_SUM(6, 6);
+  return c;
+}
+// local_off / block_sum (optional, by place): two-level place offsets for a level project_entries_kernel takes its places from
+// (WindowLists::local_off) -- a place's exclusive offset among the PLACE_BLOCK places of its wave and the wave's sum, so that a
+// scan over the n / PLACE_BLOCK sums stands in for the scan over the n counts.  A wave's own scan on the DPP network: no LDS, no
+// barrier.  (Measured with blocks of 256 places, the four waves' sums met behind one barrier: the final level's call 1.96 ->
+// 2.19 ms -- a wave that is done kept its slot until the block's slowest gather came back -- which is what the scan saves.)
+// A deferred window counts as 0 here (lookup_count_wide_kernel fills in cnt[] only): wide_n[0] != 0 tells the engine that the
+// sums are short, and it scans cnt[] instead.
+template <bool TRANSITIVE>
+__global__ __launch_bounds__(256) void lookup_count_coop_kernel(DeviceIndexView v, const FrontierRec *__restrict__ fr, uint32_t n,
+                                                                const uint32_t *__restrict__ perm, uint32_t *__restrict__ cnt,
+                                                                uint4 *__restrict__ win, uint32_t *__restrict__ wide_n,
+                                                                uint32_t *__restrict__ wide_list, int by_place, FrontierRec *__restrict__ se,
+                                                                uint32_t *__restrict__ cnt_ref, uint32_t span_cap, uint32_t *__restrict__ reach,
+                                                                uint32_t *__restrict__ local_off, uint32_t *__restrict__ block_sum) {
+  static_assert(PLACE_BLOCK == 64u, "a wave of the count kernel is a block of places");
+  const uint32_t c = lookup_count_coop_body<TRANSITIVE>(v, fr, n, perm, cnt, win, wide_n, wide_list, by_place, se, cnt_ref, span_cap, reach);
+  if (!local_off) return;  // (uniform)
+  const uint32_t inc = wave_incl_scan(c), i = blockIdx.x * 256u + threadIdx.x;  // (every lane of the wave is here: the body returns, it does not retire)
+  if (i < n) local_off[i] = inc - c;
+  if (lane_id() == 63u && i - 63u < n) block_sum[i / PLACE_BLOCK] = inc;  // (a wave wholly behind the end has no block)
 }
 // ... and the wide windows' counts: a wave per listed window, 64 entries a round
 template <bool TRANSITIVE>
@@ -854,7 +879,7 @@ __global__ __launch_bounds__(256) void order_keys_kernel(DeviceIndexView v, cons
     k |= lo << block_shift;
   }
   key[r] = k;
-  idx[r] = r;
+  if (idx) idx[r] = r;  // (the library sort's values; launch_order_sort takes a key's index for its value)
 }
 __global__ __launch_bounds__(256) void scatter_u32_kernel(const uint32_t *__restrict__ in, const uint32_t *__restrict__ perm,
                                                           uint32_t n, uint32_t *__restrict__ out) {
@@ -2572,6 +2597,10 @@ constexpr uint32_t ENT_SLICE_PAIRS = IMPG_ENT_SLICE_PAIRS, ENT_MAX_SLICES = 64u;
 #define IMPG_ENT_SPARSE 4
 #endif
 constexpr uint32_t ENT_SPARSE = IMPG_ENT_SPARSE;  // a block with fewer pairs than this per entry of its span runs a lane per place instead
+// first place of the range at place i of the lookup order: from the two-level offsets where the count pass left those (WindowLists)
+__device__ __forceinline__ uint32_t window_place(const WindowLists &wl, uint32_t i) {
+  return wl.local_off ? wl.block_base[i / PLACE_BLOCK] + wl.local_off[i] : wl.pair_off[i];
+}
 struct EntSlices {
   uint32_t *work;   // [0] items listed, [1 ..] sblock << 12 | slice << 6 | (slices - 1)
   uint32_t *alloc;  // [range blocks] places handed out so far (zeroed before phase 0)
@@ -2625,9 +2654,9 @@ void project_entries_kernel(DeviceIndexView v, const uint32_t *__restrict__ pair
 #pragma unroll
   for (uint32_t t = threadIdx.x; t < ENT_RANGES; t += ENT_THREADS) {
     // (st_off[nr] = where the block's places end, all ones beyond: the searches never step past the block's ranges)
-    if (t < nr) st_off[t] = wl.pair_off[r0 + t];
+    if (t < nr) st_off[t] = window_place(wl, r0 + t);
     else st_off[t + 1u] = 0xFFFFFFFFu;
-    if (t == 0) st_off[nr] = r0 + nr < wl.n_fr ? wl.pair_off[r0 + nr] : n_pairs;
+    if (t == 0) st_off[nr] = r0 + nr < wl.n_fr ? window_place(wl, r0 + nr) : n_pairs;
     uint32_t glo = 0xFFFFFFFFu, ghi = 0u;
     if (t < nr) {
       const uint4 w = wl.win[r0 + t];
@@ -4753,7 +4782,7 @@ __global__ __launch_bounds__(256) void frontier_emit_kernel(const unsigned long 
       f.end = piece.y;
       f.qidx = khi;
       out[o] = f;
-      if (key) { key[o] = order_key(seg, seq_len, n_seq, klo, piece.x); idx[o] = o; }
+      if (key) { key[o] = order_key(seg, seq_len, n_seq, klo, piece.x); if (idx) idx[o] = o; }  // (idx: only the library sort reads it)
     }
   }
 }
@@ -5337,19 +5366,22 @@ static inline uint32_t wave_grid(uint32_t n_items) {  // one wave per item, 4 wa
   return blocks < 1 ? 1 : (blocks > cap ? cap : blocks);
 }
 
-void launch_lookup_count(const DeviceIndexView &v, const FrontierRec *fr, uint32_t n, bool transitive, const uint32_t *perm,
+bool launch_lookup_count(const DeviceIndexView &v, const FrontierRec *fr, uint32_t n, bool transitive, const uint32_t *perm,
                          uint32_t *cnt, uint4 *win, uint32_t *wide_n, uint32_t *wide_list, hipStream_t s, bool by_place, FrontierRec *se,
-                         uint32_t *cnt_ref, bool count_reach, CoopCount coop) {
-  if (!n) return;
+                         uint32_t *cnt_ref, bool count_reach, CoopCount coop, uint32_t *local_off, uint32_t *block_sum) {
+  if (!n) return false;
   const bool lanes = emit_by_lanes(v);
   const int bp = by_place && perm ? 1 : 0;
   if (!bp) se = nullptr;
+  // (the two-level place offsets: by place, from the cooperative kernel, where wide windows are deferred -- so wide_n[0] tells of them)
+  const bool blocks = bp && perm && coop.on && lanes && local_off && block_sum;
+  if (!blocks) local_off = block_sum = nullptr;
   if (lanes) IMPG_HIP(hipMemsetAsync(wide_n, 0, count_reach ? LK_WORDS * 4 : 8, s));  // (the wide list's length, and its overflow list's: launch_lookup_emit; option lookup_stats: the reach words too)
   if (perm && coop.on) {  // a level with a lookup order: a wave's ranges are neighbours
     uint32_t *reach = lanes && count_reach ? wide_n + LK_REACH_BASE : nullptr;
     const uint32_t span = std::min(coop.span, LOOKUP_COOP_CAP);
-    if (transitive) lookup_count_coop_kernel<true><<<cdiv(n, 256), 256, 0, s>>>(v, fr, n, perm, cnt, win, wide_n, lanes ? wide_list : nullptr, bp, se, cnt_ref, span, reach);
-    else lookup_count_coop_kernel<false><<<cdiv(n, 256), 256, 0, s>>>(v, fr, n, perm, cnt, win, wide_n, lanes ? wide_list : nullptr, bp, se, cnt_ref, span, reach);
+    if (transitive) lookup_count_coop_kernel<true><<<cdiv(n, 256), 256, 0, s>>>(v, fr, n, perm, cnt, win, wide_n, lanes ? wide_list : nullptr, bp, se, cnt_ref, span, reach, local_off, block_sum);
+    else lookup_count_coop_kernel<false><<<cdiv(n, 256), 256, 0, s>>>(v, fr, n, perm, cnt, win, wide_n, lanes ? wide_list : nullptr, bp, se, cnt_ref, span, reach, local_off, block_sum);
   } else if (transitive) lookup_count_lane_kernel<true><<<cdiv(n, 256), 256, 0, s>>>(v, fr, n, perm, cnt, win, wide_n, lanes ? wide_list : nullptr, bp, se, cnt_ref);
   else lookup_count_lane_kernel<false><<<cdiv(n, 256), 256, 0, s>>>(v, fr, n, perm, cnt, win, wide_n, lanes ? wide_list : nullptr, bp, se, cnt_ref);
   if (lanes) {  // the listed (wide) windows' counts; the list's length stays on the device: a grid of at most 8 192 waves strides over it
@@ -5357,6 +5389,7 @@ void launch_lookup_count(const DeviceIndexView &v, const FrontierRec *fr, uint32
     if (transitive) lookup_count_wide_kernel<true><<<g, 256, 0, s>>>(v, fr, perm, wide_n, wide_list, win, bp, cnt, cnt_ref);
     else lookup_count_wide_kernel<false><<<g, 256, 0, s>>>(v, fr, perm, wide_n, wide_list, win, bp, cnt, cnt_ref);
   }
+  return blocks;
 }
 // tile_first[t] = the range whose places include place t * PROJ_BLOCK (see WindowLists): one thread per range, which
 // names itself at every tile border inside its run of places (a run of <= 64 places crosses at most one)
@@ -5645,6 +5678,7 @@ int launch_project(const DeviceIndexView &v, const FrontierRec *fr, const uint32
     if (mode != 0) return PROJ_ARM_ENTRIES_IDENT;
     return out == OUT_ROWS ? PROJ_ARM_ENTRIES_ROWS : out == OUT_QS ? PROJ_ARM_ENTRIES_QS : PROJ_ARM_ENTRIES_SLOTS;
   }
+  if (wl.local_off) throw Error{IMPG_E_INVALID, "internal: two-level place offsets on a level that is not projected entry by entry"};
   // (a level named by masks has no tile_first[] once the engine has seen it dense: it stays on the staged kernels)
   if (mode == 0 && dense && (wl.masks != 0 || (double)n_pairs >= stage_density_listed() * (double)v.n_entries)) {
     const uint32_t gs = (cdiv(wl.n_fr, STG_RANGES) + 7u) & ~7u;
@@ -5779,32 +5813,44 @@ void launch_visited_update(const unsigned long long *svals, const int32_t *seq_l
                            const int2 *const *old_src, const uint32_t *noff, const uint32_t *poff,
                            uint32_t n_groups, int32_t min_transitive_len, int32_t mdbr, int2 *new_ranges,
                            uint32_t *new_len, int2 *pieces, uint32_t *n_pieces, const uint32_t *cap, const uint32_t *pcap,
-                           uint32_t *big_list, uint32_t *n_big, bool count_reach, hipStream_t s) {
+                           uint32_t *big_list, uint32_t *n_big, bool count_reach, hipStream_t s, const uint32_t *h_lists) {
   if (!n_groups) return;
-  // three list lengths, three work counters, the mid list's length, a spare word, the reach counters (VU_REACH_*)
-  (void)hipMemsetAsync(n_big, 0, VU_NBIG_WORDS * 4, s);
   uint32_t *reach = count_reach ? n_big + VU_REACH_BASE : nullptr;
-  big_groups_kernel<<<cdiv(n_groups, BG_THREADS * BG_PER_THREAD), BG_THREADS, 0, s>>>(cap, pcap, n_groups, big_list, n_big);
+  // (h_lists: the lists' lengths as launch_big_groups left them in n_big[0 .. 6], on the host -- a kernel whose list is empty is
+  // not launched, and no grid is larger than its list)
+  const uint32_t n_small = h_lists[0], n_large = h_lists[1], n_tiny = h_lists[2], n_mid = h_lists[6];
   const unsigned long long *srcs = reinterpret_cast<const unsigned long long *>(old_src);
   visited_update_kernel<VU_LDS_CAP, false><<<cdiv(n_groups, 64), 64, 0, s>>>(svals, seq_len, gkey, gstart, glen, srcs, cap, noff, poff, n_groups,
                                                                              min_transitive_len, mdbr, new_ranges, new_len, pieces, n_pieces,
                                                                              nullptr, nullptr, reach);
   // the listed groups: as many blocks as stay resident (their number is on the device), each striding over the list
-  const uint32_t mid_blocks = std::min<uint32_t>(cdiv(n_groups, 64), 256u * std::min(32u, (160u * 1024u) / (VU_MID_CAP * 64u * 8u)));
-  visited_update_kernel<VU_MID_CAP, true><<<mid_blocks, 64, 0, s>>>(svals, seq_len, gkey, gstart, glen, srcs, cap, noff, poff, n_groups,
-                                                                    min_transitive_len, mdbr, new_ranges, new_len, pieces, n_pieces,
-                                                                    big_list + 2u * (size_t)n_groups, n_big + 6, reach);
-  // one wave per big group, grid-strided over however many there are (the count stays on the device)
-  const uint32_t blocks = std::min<uint32_t>(n_groups, 256u * std::min(32u, (160u * 1024u) / (VW_CAP_SMALL * 8u)));
-  visited_update_wave_kernel<VW_CAP_SMALL><<<blocks, 64, 0, s>>>(
-      svals, seq_len, gkey, gstart, glen, old_src, cap, noff, poff, big_list, n_big, n_big + 3, 0u, min_transitive_len, mdbr, new_ranges,
-      new_len, pieces, n_pieces, reach);
-  visited_update_wave_kernel<VW_CAP_TINY, true><<<std::min<uint32_t>(n_groups, 256u * 32u), 64, 0, s>>>(
-      svals, seq_len, gkey, gstart, glen, old_src, cap, noff, poff, big_list + n_groups, n_big + 2, n_big + 5, 0u, min_transitive_len, mdbr, new_ranges,
-      new_len, pieces, n_pieces, reach);
-  visited_update_wave_kernel<VW_CAP_LARGE><<<std::min<uint32_t>(n_groups, 256u * 5u), 64, 0, s>>>(
-      svals, seq_len, gkey, gstart, glen, old_src, cap, noff, poff, big_list, n_big + 1, n_big + 4, n_groups, min_transitive_len, mdbr,
-      new_ranges, new_len, pieces, n_pieces, reach);
+  const uint32_t mid_blocks = std::min<uint32_t>(cdiv(n_mid, 64), 256u * std::min(32u, (160u * 1024u) / (VU_MID_CAP * 64u * 8u)));
+  if (n_mid)
+    visited_update_kernel<VU_MID_CAP, true><<<mid_blocks, 64, 0, s>>>(svals, seq_len, gkey, gstart, glen, srcs, cap, noff, poff, n_groups,
+                                                                      min_transitive_len, mdbr, new_ranges, new_len, pieces, n_pieces,
+                                                                      big_list + 2u * (size_t)n_groups, n_big + 6, reach);
+  // one wave per big group, at most as many blocks as stay resident, each taking groups until the list is done
+  const uint32_t blocks = std::min<uint32_t>(n_small, 256u * std::min(32u, (160u * 1024u) / (VW_CAP_SMALL * 8u)));
+  if (n_small)
+    visited_update_wave_kernel<VW_CAP_SMALL><<<blocks, 64, 0, s>>>(
+        svals, seq_len, gkey, gstart, glen, old_src, cap, noff, poff, big_list, n_big, n_big + 3, 0u, min_transitive_len, mdbr, new_ranges,
+        new_len, pieces, n_pieces, reach);
+  if (n_tiny)
+    visited_update_wave_kernel<VW_CAP_TINY, true><<<std::min<uint32_t>(n_tiny, 256u * 32u), 64, 0, s>>>(
+        svals, seq_len, gkey, gstart, glen, old_src, cap, noff, poff, big_list + n_groups, n_big + 2, n_big + 5, 0u, min_transitive_len, mdbr, new_ranges,
+        new_len, pieces, n_pieces, reach);
+  if (n_large)
+    visited_update_wave_kernel<VW_CAP_LARGE><<<std::min<uint32_t>(n_large, 256u * 5u), 64, 0, s>>>(
+        svals, seq_len, gkey, gstart, glen, old_src, cap, noff, poff, big_list, n_big + 1, n_big + 4, n_groups, min_transitive_len, mdbr,
+        new_ranges, new_len, pieces, n_pieces, reach);
+}
+// the groups beyond the dense lane kernel's reach, listed by tier (big_groups_kernel): n_big's words cleared, then [0] [1] [2] [6]
+// the lists' lengths -- ahead of the scans that size the update, so that the lengths come home behind the scans' synchronisation
+void launch_big_groups(const uint32_t *cap, const uint32_t *pcap, uint32_t n_groups, uint32_t *big_list, uint32_t *n_big, hipStream_t s) {
+  if (!n_groups) return;
+  // three list lengths, three work counters, the mid list's length, a spare word, the reach counters (VU_REACH_*)
+  (void)hipMemsetAsync(n_big, 0, VU_NBIG_WORDS * 4, s);
+  big_groups_kernel<<<cdiv(n_groups, BG_THREADS * BG_PER_THREAD), BG_THREADS, 0, s>>>(cap, pcap, n_groups, big_list, n_big);
 }
 void launch_covered_flags(const unsigned long long *svals, const uint32_t *head, const uint32_t *gid,
                           const unsigned long long *gkey, const int2 *const *old_src, const uint32_t *cap, const uint32_t *glen,

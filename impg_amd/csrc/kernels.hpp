@@ -73,12 +73,15 @@ struct WideEmit { uint32_t cap = WIDE_CAP, bins = WIDE_BINS; bool count_reach = 
 // count pass's waves by theirs ("lookup_coop_waves", "lookup_lane_waves_*")
 enum LookupStat { LK_WIDE = 0, LK_SINGLE, LK_GROUPED, LK_GROUP_PASSES, LK_OVERFLOW, LK_COOP, LK_MIXED, LK_SPAN, LK_STATS };
 static_assert(LK_STATS == sizeof(impg_gpu_index::lk_stats) / sizeof(impg_gpu_index::lk_stats[0]), "one counter per path");
-void launch_lookup_count(const DeviceIndexView &v, const FrontierRec *fr, uint32_t n, bool transitive, const uint32_t *perm,
+// (returns whether local_off / block_sum were written)
+bool launch_lookup_count(const DeviceIndexView &v, const FrontierRec *fr, uint32_t n, bool transitive, const uint32_t *perm,
                          uint32_t *cnt, uint4 *win, uint32_t *wide_n, uint32_t *wide_list, hipStream_t s, bool by_place = false,
                          FrontierRec *se = nullptr /* by_place: the ranges' records at their places (the projection reads the ends there) */,
                          uint32_t *cnt_ref = nullptr /* by_place: the counts in FRONTIER order too (ordered rows) */,
                          bool count_reach = false /* wide_n's reach words cleared too */,
-                         CoopCount coop = CoopCount{} /* with perm: lookup_count_coop_kernel, staging spans of at most coop.span entries */);
+                         CoopCount coop = CoopCount{} /* with perm: lookup_count_coop_kernel, staging spans of at most coop.span entries */,
+                         uint32_t *local_off = nullptr, uint32_t *block_sum = nullptr /* by place, cooperative: the two-level place
+                         offsets (WindowLists::local_off; [n] and [n / PLACE_BLOCK rounded up]); short of the wide windows when wide_n[0] != 0 */);
 // visit position of every hit of the windows of <= 64 entries, by place: vpos[pair_off[i] + k] for range i's k-th hit in index order
 // (dest: the ranges' first rows, computed by the same kernel: dest[place] = offsets[query] + lvbase[query] + slot_ref[range])
 struct OrdDestArgs { const FrontierRec *frp; const uint32_t *perm, *slot_ref, *offsets, *lvbase; uint32_t *dest; };
@@ -126,7 +129,11 @@ struct WindowLists {
   uint32_t *slice_work, *slice_alloc;  // project_entries_kernel's heavy blocks (EntSlices): the slice list [1 + slice_cap] (word 0 zeroed), a
   uint32_t slice_cap;                  // counter per range block (zeroed); slice_cap >= n_pairs / 32768 + 1.  Null / 0: blocks are taken whole
   OrderedOut ord;              // rows != null: the kernel writes finished rows (see OrderedOut); range_out and the hit arrays are not used
+  // the ranges' first places in two levels instead of pair_off[] (project_entries_kernel only; null: pair_off[] holds them):
+  // first place of range i = block_base[i / PLACE_BLOCK] + local_off[i] -- what the count pass and a scan over its block sums leave
+  const uint32_t *block_base = nullptr, *local_off = nullptr;
 };
+constexpr uint32_t PLACE_BLOCK = 64;  // places of one wave of lookup_count_coop_kernel: a block of the two-level offsets
 // whether launch_project will run a plain projection of n_pairs by-place pairs on the staged kernels (no tile_first[] needed)
 bool project_is_staged(const DeviceIndexView &v, uint64_t n_pairs, bool plain);
 bool project_entry_major(const DeviceIndexView &v, uint64_t n_pairs, double min_identity);
@@ -239,7 +246,9 @@ void launch_table_qoff(const unsigned long long *keys, uint32_t n_groups, uint32
 void launch_group_prepare(const VisitedTables &vt, const unsigned long long *gkey, const uint32_t *gstart,
                           uint32_t n_groups, uint32_t n_active, uint32_t *glen, const int2 **old_src,
                           uint32_t *cap, uint32_t *pcap, hipStream_t s);
-// n_big: VU_NBIG_WORDS words, cleared by the launch.  [0] [1] [2] [6]: the groups listed for the wave kernel's small, large
+// n_big: VU_NBIG_WORDS words, cleared by launch_big_groups, which lists the groups of every tier ahead of the update itself;
+// launch_visited_update takes the lists' lengths from the host (h_lists: n_big's first seven words as that kernel left them),
+// launches only the kernels whose list holds a group and no more blocks than it holds.  [0] [1] [2] [6]: the groups listed for the wave kernel's small, large
 // and tiny working set and for the listed lane kernel (big_groups_kernel); [3..5] the wave kernels' work counters; from
 // VU_REACH_BASE on, the reach counters only the rare paths bump, and only under count_reach (option update_stats): groups whose replay ran in
 // place on the global slice, groups whose pieces took wave_sort_pieces_tiled, lane groups whose pieces left the LDS column
@@ -249,7 +258,9 @@ void launch_visited_update(const unsigned long long *svals, const int32_t *seq_l
                            const int2 *const *old_src, const uint32_t *noff, const uint32_t *poff,
                            uint32_t n_groups, int32_t min_transitive_len, int32_t mdbr, int2 *new_ranges,
                            uint32_t *new_len, int2 *pieces, uint32_t *n_pieces, const uint32_t *cap, const uint32_t *pcap,
-                           uint32_t *big_list, uint32_t *n_big, bool count_reach, hipStream_t s);
+                           uint32_t *big_list, uint32_t *n_big, bool count_reach, hipStream_t s, const uint32_t *h_lists);
+constexpr uint32_t VU_LIST_WORDS = 7;  // n_big's words that hold a list's length, with the work counters between them
+void launch_big_groups(const uint32_t *cap, const uint32_t *pcap, uint32_t n_groups, uint32_t *big_list, uint32_t *n_big, hipStream_t s);
 // hits covered by their group's old list dropped before the replay (kernels.hip "covered_flags")
 void launch_covered_flags(const unsigned long long *svals, const uint32_t *head, const uint32_t *gid,
                           const unsigned long long *gkey, const int2 *const *old_src, const uint32_t *cap, const uint32_t *glen,

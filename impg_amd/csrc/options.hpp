@@ -29,6 +29,7 @@ struct Options {
   int64_t wide_emit_bins = 1024;      // rank bins it groups a window's hits by beyond that (testing; results identical)
   int64_t lookup_coop = 1;            // lookup: a level with a lookup order is counted by lookup_count_coop_kernel (1) or by the lane kernel (0); results identical
   int64_t lookup_coop_span = 256;     // entries a wave of that kernel stages at most; a wider span takes the lane body (testing; results identical)
+  int64_t place_offsets_blocks = 1;   // a fused final level takes its place offsets in two levels, a scan over the sums of the count pass's waves (1), or from the scan over every range's count (0); results identical
   // store_cigar on a tracepoint index: 0 refused; 1 every row carries the approximate mode's CIGAR, [matches '='] [mismatches 'X']
   // with a zero count left out (impg.rs:1479-1486) -- statistics, not an alignment: the lengths do not add up to the row's
   // coordinates.  No effect on a CIGAR index; not saved with the index.
@@ -72,6 +73,7 @@ constexpr OptionRow OPTION_TABLE[] = {
     {"wide_emit_bins", 2, 1024, &Options::wide_emit_bins, false, false, "wide_emit_bins is 2 .. 1024"},
     {"lookup_coop", INT64_MIN, INT64_MAX, &Options::lookup_coop, true, false, ""},
     {"lookup_coop_span", 4, 256, &Options::lookup_coop_span, false, false, "lookup_coop_span is 4 .. 256"},
+    {"place_offsets_blocks", INT64_MIN, INT64_MAX, &Options::place_offsets_blocks, true, false, ""},
     {"approximate_cigar", 0, 1, &Options::approximate_cigar, false, true, "approximate_cigar is 0 or 1"},
     {"free_slot_order", INT64_MIN, INT64_MAX, &Options::free_slot_order, true, false, ""},
     {"debug_fail_owner", 0, 0xFFFFFFFFll, &Options::debug_fail_owner, false, true, "debug_fail_* out of range"},

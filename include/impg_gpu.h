@@ -237,6 +237,7 @@ int impg_gpu_index_approximate(const impg_gpu_index_t *);
  * searching once for its 64 ranges and reading their windows from its copy of the index columns; 0: range by range;
  * results identical) and "lookup_coop_span" (4 .. 256, the default: the entries such a wave copies at most; a wave whose
  * ranges span more counts range by range -- for tests; results identical),
+ * "place_offsets_blocks" (1, the default: a fused final level's place offsets in two levels, per block of 64 places (a wave of the count pass); 0: one scan over every range -- A/B runs and tests; results identical),
  * "fuse_final_level" (1, the default: the final level of such a run -- no update follows, no row is kept --
  * takes its (range, entry) pairs straight from the lookup's per-range windows inside the projection kernel; the emit
  * pass and its pair lists are skipped; counts and checksums are identical either way),
@@ -290,7 +291,8 @@ const char *impg_gpu_counter_key(size_t i);
  * because one query held more hits than a wave should take, "segment_library_levels" = levels that went through the
  * library's radix sort instead; which kernel projected each level: "project_lane_levels", "project_staged_levels",
  * "project_staged_rows_levels", "project_entries_slots_levels", "project_entries_qs_levels", "project_entries_rows_levels",
- * "project_entries_ident_levels", "project_tp_levels".  With option "update_stats" = 1 (0, the default: nothing is copied or counted) every
+ * "project_entries_ident_levels", "project_tp_levels"; "place_offsets_block_levels" = fused final levels whose ranges found
+ * their places through per-block offsets (option "place_offsets_blocks") instead of a scan over every range.  With option "update_stats" = 1 (0, the default: nothing is copied or counted) every
  * level's visited update also counts its (query, sequence) groups by the kernel that took them -- "update_lane_groups",
  * "update_mid_groups", "update_wave_tiny_groups", "update_wave_small_groups", "update_wave_large_groups" -- and by the
  * rare path they reached: "update_inplace_groups" (the replay ran on the group's global slice), "update_tiled_sort_groups"
