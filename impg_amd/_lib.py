@@ -135,6 +135,10 @@ SYMBOLS = [
     ("impg_gpu_index_create_tracepoints_multi", C.c_int, [_P, C.c_size_t, _P, _P, _P, C.c_size_t, _P, _P, C.c_uint32, C.c_int, C.c_int, _P, C.c_int, C.c_int,
                                                     C.POINTER(_P)]),
     ("impg_gpu_index_create_from_paf", C.c_int, [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
+    ("impg_gpu_index_create_from_paf_streamed", C.c_int, [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.POINTER(_P)]),
+    ("impg_gpu_selftest_paf_ingest", C.c_int, [C.POINTER(C.c_char_p), C.c_size_t, C.c_uint64, C.c_int, C.c_int, C.c_uint, C.c_uint64, C.POINTER(_P),
+                                               C.POINTER(C.c_size_t), C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(_P), C.POINTER(C.c_size_t),
+                                               C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(_P), _P]),
     ("impg_gpu_index_save", C.c_int, [_P, C.c_char_p]),
     ("impg_gpu_index_load", C.c_int, [C.c_char_p, C.c_int, C.POINTER(_P)]),
     ("impg_gpu_query_batch_stream", C.c_int, [_P, _P, C.c_size_t, _P, _P, _P, C.c_size_t, C.c_size_t, _P, _P, C.POINTER(C.c_uint64)]),

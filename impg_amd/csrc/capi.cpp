@@ -14,6 +14,7 @@
 #include <new>
 
 #include "engine.hpp"
+#include "paf_ingest.hpp"
 #include "partition.hpp"
 #include "refine.hpp"
 
@@ -569,6 +570,73 @@ int impg_gpu_index_create_from_paf(const char *const *paths, int n_paths, int bi
   IMPG_CATCH
 }
 
+// The second way from PAF files to an index: the files streamed into HBM in pieces and parsed there (paf_ingest.hpp).  From
+// the hand-off on -- records on the host, the op pool in HBM -- the code is impg_gpu_index_create_from_paf's.  One difference
+// in what a bad input is told: that route tokenises last, so a bad head anywhere is reported before any bad CIGAR; this one
+// reports whichever line comes first in file order.
+int impg_gpu_index_create_from_paf_streamed(const char *const *paths, int n_paths, int bidirectional, int order_policy, int device,
+                                            uint64_t piece_bytes, impg_gpu_index_t **out) {
+  IMPG_TRY
+  if (!out || !paths || n_paths <= 0) throw Error{IMPG_E_INVALID, "bad arguments"};
+  require_device(device);
+  if (order_policy != IMPG_ORDER_COITREES && order_policy != IMPG_ORDER_SORTED) throw Error{IMPG_E_INVALID, "bad order policy"};
+  std::vector<std::string> ps;
+  for (int i = 0; i < n_paths; i++) {
+    if (!paths[i]) throw Error{IMPG_E_INVALID, "null argument"};
+    ps.push_back(paths[i]);
+  }
+  const bool timing = build_switches().timing;
+  const auto t0 = std::chrono::steady_clock::now();
+  paf_ingest::Loaded L;
+  ParsedPaf pp;
+  DevBuf d_ops;
+  paf_ingest_device(ps, (size_t)piece_bytes, device, L, pp.records, d_ops);  // (a failure leaves nothing behind: the backend owns every block)
+  if (timing)
+    fprintf(stderr, "[build] %-28s %.3f s (reader %.3f s, names %.3f s)\n", "PAF streamed into HBM",
+            std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), L.read_seconds, L.resolve_seconds);
+  if (const char *hp = getenv("IMPG_PAF_INGEST_TIMING")) {
+    if (FILE *f = *hp ? fopen(hp, "a") : nullptr) {  // (behind the backend's line)
+      fprintf(f, "handoff_s %.6f reader_s %.6f names_s %.6f\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(),
+              L.read_seconds, L.resolve_seconds);
+      fclose(f);
+    }
+  }
+  pp.seq = L.seq;
+  pp.file_first = L.file_first;
+  const uint64_t n_ops = L.n_ops;
+  std::vector<int64_t> lens = pp.seq.lens;
+  auto stamp = [&](impg_gpu_index &ix) {
+    ix.build_stats[BUILD_TOKENIZED_DEVICE] = 1;
+    for (int k = 0; k < paf_ingest::N_STATS; k++) ix.paf_ingest_stats[k] = L.stats[k];
+    ix.paf_ingest_stats[paf_ingest::DEVICE] = 1;
+  };
+  {
+    auto ix = std::make_unique<impg_gpu_index>();
+    ix->device = device;
+    ix->seq = pp.seq;
+    if (pp.file_first.size() < 2 || pp.file_first.front() != 0 || pp.file_first.back() != pp.records.size())
+      throw Error{IMPG_E_INVALID, "internal: bad file boundaries"};
+    ix->file_first = pp.file_first;
+    if (build_index_device(*ix, pp.records.data(), pp.records.size(), nullptr, n_ops, lens.data(), (uint32_t)lens.size(), bidirectional != 0,
+                           order_policy, 0, 1, nullptr, d_ops.as<uint32_t>())) {
+      { EngineLease warm(*ix); }
+      stamp(*ix);
+      *out = ix.release();
+      return IMPG_OK;
+    }
+  }
+  // (the device was short of memory for the build: the ops come home and the host builder takes over)
+  pp.ops.resize(n_ops);
+  if (n_ops) IMPG_HIP(hipMemcpy(pp.ops.data(), d_ops.p, n_ops * 4, hipMemcpyDeviceToHost));
+  d_ops.release();
+  auto ix = make_index(pp.records.data(), pp.records.size(), pp.ops.data(), pp.ops.size(), lens.data(), (uint32_t)lens.size(), bidirectional,
+                       order_policy, device, 0, 1, &pp.seq, &pp.file_first, nullptr);
+  stamp(*ix);
+  *out = ix.release();
+  return IMPG_OK;
+  IMPG_CATCH
+}
+
 int impg_gpu_parse_subsequence(const char *seq_name, char *base_out, size_t base_cap, int32_t *start_offset) {
   IMPG_TRY
   if (!seq_name || !base_out || !start_offset) throw Error{IMPG_E_INVALID, "null argument"};
@@ -715,6 +783,10 @@ static const CounterRow COUNTER_TABLE[] = {
     CTR("fasta_store_exception_runs", fasta_stats[FASTA_STORE_EXCEPTION_RUNS]),
     CTR("sequence_ingest_pieces", ingest_stats[0]), CTR("sequence_ingest_text_bytes", ingest_stats[1]), CTR("sequence_ingest_bases", ingest_stats[2]),
     CTR("sequence_ingest_inflated_blocks", ingest_stats[3]), CTR("sequence_ingest_dropped_sequences", ingest_stats[4]),
+    CTR("paf_ingest_device", paf_ingest_stats[0]), CTR("paf_ingest_pieces", paf_ingest_stats[1]), CTR("paf_ingest_text_bytes", paf_ingest_stats[2]),
+    CTR("paf_ingest_lines", paf_ingest_stats[3]), CTR("paf_ingest_carried_bytes", paf_ingest_stats[4]),
+    CTR("paf_ingest_buffer_grows", paf_ingest_stats[5]), CTR("paf_ingest_pool_regrows", paf_ingest_stats[6]),
+    CTR("paf_ingest_unknown_names", paf_ingest_stats[7]), CTR("paf_ingest_inflated_blocks", paf_ingest_stats[8]),
     CTR_RANKS("build_device", build_stats[BUILD_DEVICE]), CTR_RANKS("tokenized_device", build_stats[BUILD_TOKENIZED_DEVICE]),
     CTR_RANKS("build_batches", build_stats[BUILD_BATCHES]),
 };

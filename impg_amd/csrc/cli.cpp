@@ -99,19 +99,36 @@ void usage() {
           "               [-l N] [--min-result-identity F] [--subset-sequence-list FILE] [--original-sequence-coordinates]\n"
           "               [--consider-strandness] [-o auto|bed|bedpe|paf|fasta] [--sequence-files F... | --sequence-list FILE]\n"
           "               [--reverse-complement] [--sequence-store bytes|packed|auto] [--sequence-ingest host|device] [--host-merge] [--unidirectional]\n"
+          "               [--alignment-ingest host|device]\n"
           "               [--order coitrees|sorted] [--device N]\n"
           "impg-gpu partition (-a <paf>... | -i <file>) -w <bp> -d <bp> [--min-missing-size N] [--min-boundary-distance N]\n"
           "               [--selection-mode longest|total|sample[,sep]|haplotype[,sep]] [--starting-sequences-file FILE]\n"
           "               [--separate-files] [--no-rehome-singletons] [--output-folder DIR] [-o bed|fasta] [--host-state] [-m N]\n"
           "               [--sequence-files F... | --sequence-list FILE] [--sequence-store bytes|packed|auto] [--reverse-complement]\n"
-          "               [--sequence-ingest host|device]\n"
+          "               [--sequence-ingest host|device] [--alignment-ingest host|device]\n"
           "               [--transitive-dfs] [--min-transitive-len N] [--min-distance-between-ranges N] [--min-identity F]\n"
           "               [--unidirectional] [--order coitrees|sorted] [--device N]\n"
           "impg-gpu refine (-a <paf>... | -i <file>) (-r seq:start-end | -b <bed>) (-d <bp> | --no-merge) [--span-bp N]\n"
           "               [--max-extension F] [--extension-step N] [--pansn-mode sample|haplotype] [--support-output FILE]\n"
           "               [--blacklist-bed FILE] [-x] [-m N] [--transitive-dfs] [--multi-impg] [--min-transitive-len N]\n"
           "               [--min-distance-between-ranges N] [--min-result-identity F] [--subset-sequence-list FILE]\n"
-          "               [--unidirectional] [--order coitrees|sorted] [--device N]\n");
+          "               [--alignment-ingest host|device] [--unidirectional] [--order coitrees|sorted] [--device N]\n");
+}
+
+// --alignment-ingest host|device (query, partition, refine): who parses the alignment files' lines -- the host
+// (impg_gpu_index_create_from_paf) or the device, the files streamed into HBM (impg_gpu_index_create_from_paf_streamed)
+bool g_alignment_ingest_device = false;
+bool alignment_ingest_arg(const std::string &a, int &i, int argc, char **argv) {
+  if (a != "--alignment-ingest") return false;
+  if (i + 1 >= argc) die("a value is required for '--alignment-ingest'", 2);
+  const std::string sv = argv[++i];
+  if (sv != "host" && sv != "device") die("invalid value '" + sv + "' for '--alignment-ingest'", 2);
+  g_alignment_ingest_device = sv == "device";
+  return true;
+}
+int create_from_paf(const std::vector<const char *> &pp, bool unidirectional, int order, int device, impg_gpu_index_t **ix) {
+  if (g_alignment_ingest_device) return impg_gpu_index_create_from_paf_streamed(pp.data(), (int)pp.size(), unidirectional ? 0 : 1, order, device, 0, ix);
+  return impg_gpu_index_create_from_paf(pp.data(), (int)pp.size(), unidirectional ? 0 : 1, order, device, ix);
 }
 
 // the index of a command: the saved file if it exists, else built from the alignment files (and saved where -i names a file)
@@ -125,7 +142,7 @@ impg_gpu_index_t *open_index(const std::vector<std::string> &pafs, const std::st
     if (impg_gpu_index_load(index_file.c_str(), device, &ix) != IMPG_OK) die(impg_gpu_last_error());
   } else {
     if (pafs.empty()) die("No such file or directory: " + index_file);
-    if (impg_gpu_index_create_from_paf(pp.data(), (int)pp.size(), unidirectional ? 0 : 1, order, device, &ix) != IMPG_OK) die(impg_gpu_last_error());
+    if (create_from_paf(pp, unidirectional, order, device, &ix) != IMPG_OK) die(impg_gpu_last_error());
     if (!index_file.empty() && impg_gpu_index_save(ix, index_file.c_str()) != IMPG_OK) die(impg_gpu_last_error());
   }
   return ix;
@@ -226,6 +243,7 @@ int partition_main(int argc, char **argv) {
       if (o != "sorted" && o != "coitrees") die("invalid value '" + o + "' for '--order'", 2);
       order = o == "sorted" ? IMPG_ORDER_SORTED : IMPG_ORDER_COITREES;
     } else if (a == "-t" || a == "--threads" || a == "-v" || a == "--verbose") need(a.c_str());  // accepted, unused
+    else if (alignment_ingest_arg(a, i, argc, argv)) {}
     else if (a == "-h" || a == "--help") { usage(); return 0; }
     else die("unexpected argument '" + a + "'", 2);
   }
@@ -408,6 +426,7 @@ int refine_main(int argc, char **argv) {
       if (o != "sorted" && o != "coitrees") die("invalid value '" + o + "' for '--order'", 2);
       order = o == "sorted" ? IMPG_ORDER_SORTED : IMPG_ORDER_COITREES;
     } else if (a == "-t" || a == "--threads" || a == "-v" || a == "--verbose") need(a.c_str());  // accepted, unused
+    else if (alignment_ingest_arg(a, i, argc, argv)) {}
     else if (a == "-h" || a == "--help") { usage(); return 0; }
     else die("unexpected argument '" + a + "'", 2);
   }
@@ -592,6 +611,7 @@ int main(int argc, char **argv) {
     else if (a == "-i" || a == "--index") index_file = need("-i");
     else if (a == "-v" || a == "--verbose") verbose = (int)num(a, need(a.c_str()), 0, 9);  // >= 1: phase timings on stderr
     else if (a == "-t" || a == "--threads") need(a.c_str());  // accepted, unused
+    else if (alignment_ingest_arg(a, i, argc, argv)) {}
     else if (a == "-h" || a == "--help") { usage(); return 0; }
     else die("unexpected argument '" + a + "'", 2);
   }
@@ -601,7 +621,7 @@ int main(int argc, char **argv) {
     std::vector<const char *> pp;
     for (auto &p : pafs) pp.push_back(p.c_str());
     impg_gpu_index_t *ix = nullptr;
-    if (impg_gpu_index_create_from_paf(pp.data(), (int)pp.size(), unidirectional ? 0 : 1, order, device, &ix) != IMPG_OK)
+    if (create_from_paf(pp, unidirectional, order, device, &ix) != IMPG_OK)
       die(impg_gpu_last_error());
     if (impg_gpu_index_save(ix, index_file.c_str()) != IMPG_OK) die(impg_gpu_last_error());
     impg_gpu_index_destroy(ix);
@@ -652,7 +672,7 @@ int main(int argc, char **argv) {
     else fprintf(stderr, "[impg-gpu] %s: %s -- rebuilding it from the alignment files\n", index_file.c_str(), impg_gpu_last_error());
   }
   if (!loaded) {
-    if (impg_gpu_index_create_from_paf(pp.data(), (int)pp.size(), unidirectional ? 0 : 1, order, device, &ix) != IMPG_OK)
+    if (create_from_paf(pp, unidirectional, order, device, &ix) != IMPG_OK)
       die(impg_gpu_last_error());
     if (!index_file.empty() && impg_gpu_index_save(ix, index_file.c_str()) != IMPG_OK) die(impg_gpu_last_error());
   }

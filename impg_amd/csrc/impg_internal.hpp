@@ -513,6 +513,8 @@ struct impg_gpu_index {
   mutable std::atomic<uint64_t> fasta_stats[7] = {};
   // ... and the last impg_gpu_index_load_sequences (by impg::ingest::Stat; sequence_ingest.hpp)
   mutable std::atomic<uint64_t> ingest_stats[5] = {};
+  // ... and the ingest of impg_gpu_index_create_from_paf_streamed (by impg::paf_ingest::Stat; paf_ingest.hpp): all zero on any other index
+  mutable std::atomic<uint64_t> paf_ingest_stats[9] = {};
   void fasta_stats_reset() const { for (int k = 0; k < impg::FASTA_STORE_BYTES; k++) fasta_stats[k] = 0; }  // (the store's size stays: set when it is attached)
   // The sequence store attached by impg_gpu_index_set_sequences (null: none): the host copy the host route reads, which
   // of its sequences every index id is (impg::SEQ_ABSENT: none), and the same bases in HBM for the device route -- SEQ_PAD

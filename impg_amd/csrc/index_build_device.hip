@@ -308,6 +308,19 @@ __global__ __launch_bounds__(256) void cigar_tokens_kernel(const char *__restric
 
 }  // namespace
 
+// the tokenizer's two kernels for the streamed PAF ingest (paf_ingest_device.hip), which has its spans in a piece of text
+void cigar_count_launch(const char *text, const unsigned long long *boff, const uint32_t *blen, uint32_t n, uint32_t *cnt, uint32_t *bad, hipStream_t s) {
+  if (!n) return;
+  cigar_count_kernel<<<cdiv(n, 4), 256, 0, s>>>(text, boff, blen, n, cnt, bad);
+  IMPG_HIP(hipGetLastError());
+}
+void cigar_tokens_launch(const char *text, const unsigned long long *boff, const uint32_t *blen, uint32_t n, const unsigned long long *op_off, uint32_t *ops,
+                         hipStream_t s) {
+  if (!n) return;
+  cigar_tokens_kernel<<<cdiv(n, 4), 256, 0, s>>>(text, boff, blen, n, op_off, ops);
+  IMPG_HIP(hipGetLastError());
+}
+
 // false: not taken (the caller runs the host builder).  Same inputs and the same resulting arrays as build_index.
 bool build_index_device(impg_gpu_index &ix, const impg_gpu_record_t *records, size_t n_records, const uint32_t *cigar_ops, size_t n_ops,
                         const int64_t *seq_len, uint32_t n_seq, bool bidirectional, int order_policy, uint32_t shard, uint32_t n_shards,

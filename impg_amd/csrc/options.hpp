@@ -121,13 +121,15 @@ struct BuildSwitches {
   bool host_build;      // IMPG_BUILD_HOST: host threads build (and tokenise) instead of the device
   bool timing;          // IMPG_BUILD_TIMING: the builders' phases on stderr
   uint64_t batch_ops;   // IMPG_BUILD_BATCH_OPS: ops per upload of the device builder's batches (tests; the host builder has no batches)
+  uint64_t paf_pool_ops;  // IMPG_PAF_INGEST_POOL_OPS: the first size of the streamed PAF ingest's op pool (tests; 0: from the files' sizes)
 };
 constexpr uint64_t BUILD_BATCH_OPS = 64ull << 20;  // 256 MB of ops per upload
 inline BuildSwitches build_switches() {
-  const char *pfx = getenv("IMPG_PREFIX_LINES"), *idl = getenv("IMPG_IDENTITY_LINES"), *bat = getenv("IMPG_BUILD_BATCH_OPS");
+  const char *pfx = getenv("IMPG_PREFIX_LINES"), *idl = getenv("IMPG_IDENTITY_LINES"), *bat = getenv("IMPG_BUILD_BATCH_OPS"),
+             *ppo = getenv("IMPG_PAF_INGEST_POOL_OPS");
   const unsigned long long b = bat ? strtoull(bat, nullptr, 10) : 0ull;
   return BuildSwitches{!(pfx && atoi(pfx) == 0), idl && atoi(idl) == 1, getenv("IMPG_BUILD_HOST") != nullptr, getenv("IMPG_BUILD_TIMING") != nullptr,
-                       b ? (uint64_t)b : BUILD_BATCH_OPS};
+                       b ? (uint64_t)b : BUILD_BATCH_OPS, ppo ? (uint64_t)strtoull(ppo, nullptr, 10) : 0ull};
 }
 
 }  // namespace impg

@@ -451,13 +451,24 @@ class GpuImpg:
         return ix
 
     @classmethod
-    def from_paf(cls, paths, bidirectional=True, order=_lib.ORDER_COITREES, device=0, devices=None, lanes=2, comm=None):
-        """devices / comm: as in from_records (impg_gpu_index_create_from_paf_multi / _rank)."""
+    def from_paf(cls, paths, bidirectional=True, order=_lib.ORDER_COITREES, device=0, devices=None, lanes=2, comm=None, ingest="host",
+                 piece_bytes=None):
+        """devices / comm: as in from_records (impg_gpu_index_create_from_paf_multi / _rank).  ingest="device": the files are
+        streamed into HBM in pieces of piece_bytes (None: 64 MiB) and parsed there (impg_gpu_index_create_from_paf_streamed;
+        one GPU: not with devices= or comm=); "host" is the host's line and field parser."""
         if isinstance(paths, str):
             paths = [paths]
+        if ingest not in ("host", "device"):
+            raise ValueError("ingest is 'host' or 'device'")
+        if ingest == "device" and (devices is not None or comm is not None):
+            raise ValueError("ingest='device' builds on one GPU: not with devices= or comm=")
+        if ingest == "host" and piece_bytes is not None:
+            raise ValueError("piece_bytes belongs to ingest='device'")
         arr = (C.c_char_p * len(paths))(*[p.encode() for p in paths])
         h = C.c_void_p(None)
-        if devices is not None:
+        if ingest == "device":
+            check(lib().impg_gpu_index_create_from_paf_streamed(arr, len(paths), int(bidirectional), order, device, int(piece_bytes or 0), C.byref(h)))
+        elif devices is not None:
             dv = np.ascontiguousarray(devices, dtype=np.int32)
             check(lib().impg_gpu_index_create_from_paf_multi(arr, len(paths), int(bidirectional), order, dv.ctypes.data, dv.size,
                                                              lanes, C.byref(h)))

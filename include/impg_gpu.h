@@ -165,6 +165,28 @@ int impg_gpu_index_create_tracepoints_multi(const impg_gpu_tp_record_t *records,
 int impg_gpu_index_create_from_paf(const char *const *paths, int n_paths,
                                    int bidirectional, int order_policy,
                                    int device, impg_gpu_index_t **out);
+/* The second way from PAF files to the same index: the files (plain, gzip, BGZF -- recognised by their magic, as
+ * impg_gpu_index_load_sequences does) are streamed into HBM in pieces of whole lines and parsed there -- lines, fields,
+ * the cg:Z: tag and the CIGARs; the host keeps lines whole across pieces and gives the names the device did not know
+ * their ids, and reads no other byte of a line.  piece_bytes: 0 = 64 MiB; else 16 .. 2^32, a multiple of 16 (a line longer
+ * than the buffer makes the buffer double; offsets in a piece are 32 bits, so a line of 4 GiB is IMPG_E_UNSUPPORTED).  One
+ * GPU.  The index is the one impg_gpu_index_create_from_paf builds from the same files.  Errors are that call's, with one
+ * difference: that call tokenises last and so reports a bad head anywhere before any "Invalid CIGAR operation"; this
+ * one reports the first bad line in file order (a line's head checks before its CIGAR).  Reader trouble is IMPG_E_IO
+ * naming the file.  The op pool is reserved from the files' sizes (IMPG_PAF_INGEST_POOL_OPS sets the first size) and
+ * grows by half when a piece does not fit; where it cannot, the call fails with IMPG_E_OOM and names
+ * impg_gpu_index_create_from_paf.  After a failure no handle exists and no HBM is kept.  Counters "paf_ingest_*". */
+int impg_gpu_index_create_from_paf_streamed(const char *const *paths, int n_paths, int bidirectional, int order_policy,
+                                            int device, uint64_t piece_bytes, impg_gpu_index_t **out);
+/* The hand-off alone, for the tests: what the ingest leaves for the builder, malloc'ed.  on_host = 1 runs the host twin
+ * of the kernels (no device needed); hash_bits < 64 truncates the name hash (collisions on purpose); initial_pool_ops
+ * sizes the first op pool (0 = the default rule).  stats: the nine "paf_ingest_*" counters in the order of their keys below
+ * (may be null). */
+int impg_gpu_selftest_paf_ingest(const char *const *paths, size_t n_paths, uint64_t piece_bytes, int on_host, int device,
+                                 unsigned hash_bits, uint64_t initial_pool_ops, /* out: */ impg_gpu_record_t **records,
+                                 size_t *n_records, uint32_t **ops, size_t *n_ops, char **names /* '\n'-joined, id order */,
+                                 size_t *names_len, int64_t **lens, size_t *n_seq, uint64_t **file_first /* n_paths + 1 */,
+                                 uint64_t *stats);
 /* A built index as one file: the role of the reference's `.impg` file (writer impg.rs:1655-1721, reader
  * :1787-1850; `impg index` / the implicit index cache of `impg query`, main.rs:11321-11386): pay for
  * parsing and tokenising once.  The file holds the device arrays as they sit in HBM plus the sequence
@@ -328,10 +350,17 @@ const char *impg_gpu_counter_key(size_t i);
  * (zero after impg_gpu_index_set_sequences): "sequence_ingest_pieces" = text pieces sent to the device,
  * "sequence_ingest_text_bytes" = bytes of (inflated) text, "sequence_ingest_bases" = bases met, those of dropped sequences
  * included, "sequence_ingest_inflated_blocks" = BGZF blocks inflated, "sequence_ingest_dropped_sequences" = file sequences
- * the index does not know.  Of the build of the index itself (a multi-GPU handle answers with the sum over its
+ * the index does not know.  Of the ingest of impg_gpu_index_create_from_paf_streamed (all zero on any other index):
+ * "paf_ingest_device" = 1 on that route, "paf_ingest_pieces" = text pieces sent to the device, "paf_ingest_text_bytes" =
+ * bytes of (inflated) text, "paf_ingest_lines" = lines parsed, "paf_ingest_carried_bytes" = bytes behind a piece's last
+ * newline moved to the front of the next piece, "paf_ingest_buffer_grows" = doublings of the piece buffer for a line longer
+ * than it, "paf_ingest_pool_regrows" = device-to-device copies of the op pool into a larger one,
+ * "paf_ingest_unknown_names" = name occurrences sent home because the device's table did not hold them,
+ * "paf_ingest_inflated_blocks" = BGZF blocks inflated.  Of the build of the index itself (a multi-GPU handle answers with the sum over its
  * ranks): "build_device" = 1 if the device builder produced it, 0 if the host builder did (IMPG_BUILD_HOST, tracepoints, a
  * loaded .impg file's entry order, a card short of memory for the build, an index loaded from a saved file);
- * "tokenized_device" = 1 if the device tokenised its CIGAR text (impg_gpu_index_create_from_paf on one GPU);
+ * "tokenized_device" = 1 if the device tokenised its CIGAR text (impg_gpu_index_create_from_paf and
+ * impg_gpu_index_create_from_paf_streamed on one GPU);
  * "build_batches" = the op-pool uploads of the device build, one tiles launch each (1 unless the pool exceeds the batch
  * size, 64 M ops or IMPG_BUILD_BATCH_OPS). */
 int impg_gpu_get_counter(const impg_gpu_index_t *, const char *key, int64_t *value_out);
