@@ -122,8 +122,12 @@ bool Engine::run_small(const impg_gpu_index &ix, const impg_gpu_range_t *h_range
 }
 
 bool Engine::walk_applicable(const impg_gpu_index &ix, uint32_t n, const impg_gpu_params_t &p) const {
-  if (!walk_allowed || !n || !p.transitive || p.multi_impg || p.store_cigar || remote || ix.tp_mode) return false;
+  if (!walk_allowed || !n || !p.transitive || p.store_cigar || remote || ix.tp_mode) return false;
   if (ix.view.n_seq > 65536u) return false;  // (hit keys are sequence << 15 | slot in 32 bits)
+  // MultiImpg worklists (popped at either end): the one-wave form's MULTI arm, batches of any size like DFS ones -- but not
+  // under a mask, whose absent sequences open by a rule of their own (multi_impg.rs:827-830).  No upper bound: a 1 000-range
+  // `-m 3` batch on the headline index takes the walk 0.14 s and the batch engine 2.19 s (a lone call 60 ms against 387 ms)
+  if (p.multi_impg) return !masked;
   // (a mask with empty ranges gives self pieces that touch: the reference's stack merges them after the first pop, the
   // walk's per-sequence stack lists only where new pieces land -- the batch engine runs those)
   if (masked && mask_has_empty && p.dfs) return false;
@@ -143,7 +147,7 @@ bool Engine::walk_applicable(const impg_gpu_index &ix, uint32_t n, const impg_gp
   return p.max_depth >= 2 && walk_group_size(ix, n, p) >= 2;
 }
 uint32_t Engine::walk_group_size(const impg_gpu_index &ix, uint32_t n, const impg_gpu_params_t &p) const {
-  if (p.dfs || p.max_depth < 2 || n > SMALL_RANGES || opt.walk_members == 1) return 1;
+  if (p.dfs || p.multi_impg || p.max_depth < 2 || n > SMALL_RANGES || opt.walk_members == 1) return 1;
   int cus = 256;
   (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ix.device);
   // every workgroup of the launch must be resident (the members wait for each other): one 1024-thread workgroup per CU --
@@ -199,7 +203,7 @@ bool Engine::run_walk(const impg_gpu_index &ix, const impg_gpu_range_t *d_ranges
   if (p.min_identity == p.min_identity && ix.lacks_identity_lines()) const_cast<impg_gpu_index &>(ix).ensure_identity_lines();
   IMPG_HIP(hipSetDevice(ix.device));
   // a BFS processes whole levels: 16 waves per query; a DFS step is one popped range: one wave, cheap barriers
-  const bool wide = !p.dfs;
+  const bool wide = !(p.dfs || p.multi_impg);  // (a MultiImpg worklist is single pops whichever end it pops)
   WalkArgs a;
   memset(&a, 0, sizeof a);
   walk_caps(wide, a);
@@ -261,7 +265,7 @@ bool Engine::run_walk(const impg_gpu_index &ix, const impg_gpu_range_t *d_ranges
     a.dbg = d_dbg.as<unsigned long long>();
   }
   if (st) memset(st, 0, sizeof *st);
-  launch_walk(a, n_wg, wide, ident, stream);
+  launch_walk(a, n_wg, wide, ident, stream, p.multi_impg != 0);
   uint32_t flags[2] = {0, 0};
   IMPG_HIP(hipMemcpyAsync(flags, walk_ctr.p, 8, hipMemcpyDeviceToHost, stream));
   if (rows && h_n_rows) IMPG_HIP(hipMemcpyAsync(h_n_rows, rows->n_rows.p, (size_t)n * 4, hipMemcpyDeviceToHost, stream));  // (under the same synchronisation)
@@ -274,8 +278,8 @@ bool Engine::run_walk(const impg_gpu_index &ix, const impg_gpu_range_t *d_ranges
             h[24], h[25], h[26], h[27], h[28], h[29], h[30]);
   }
   if (dbg)
-    fprintf(stderr, "[walk] n=%u %s wg=%u members=%u slab=%.2f MB dfs=%d depth=%u overflow=0x%x (1 unknown target, 2 pairs per step, 4 visited pool, 8 piece scratch, 16 pieces, 32 stack / frontier, 128 hand-off timed out) %.3f ms\n",
-            n, wide ? "wide" : "wave", n_wg, members, slab / 1048576.0, a.dfs, a.max_depth, flags[1], st ? st->ms_total : -1.0f);
+    fprintf(stderr, "[walk] n=%u %s wg=%u members=%u slab=%.2f MB dfs=%d multi=%d depth=%u overflow=0x%x (1 unknown target, 2 pairs per step, 4 visited pool, 8 piece scratch, 16 pieces, 32 stack / frontier, 128 hand-off timed out, 256 pop budget) %.3f ms\n",
+            n, wide ? "wide" : "wave", n_wg, members, slab / 1048576.0, a.dfs, p.multi_impg ? 1 : 0, a.max_depth, flags[1], st ? st->ms_total : -1.0f);
   ix.walk_last_members = members;
   ix.walk_last_overflow = flags[1];  // the cause word of this launch (0: taken), bits as in impg_gpu.h
   if (flags[1]) { ix.walk_fallbacks++; return false; }  // a query outgrew its slab: the batch engine runs the batch

@@ -6245,9 +6245,14 @@ uint32_t walk_grid_blocks_per_cu() {
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&c, walk_grid_kernel<16, 4096, MODE_IDENT | MODE_WALK>, 1024, 0) != hipSuccess) return 0;
   return (uint32_t)std::max(0, std::min({a, b, c}));
 }
-void launch_walk(const WalkArgs &a, uint32_t n_workgroups, bool wide, bool ident_mode, hipStream_t s) {
+void launch_walk(const WalkArgs &a, uint32_t n_workgroups, bool wide, bool ident_mode, hipStream_t s, bool multi) {
   if (!n_workgroups) return;
-  if (wide && a.members > 1) {
+  if (multi) {  // a MultiImpg worklist: the one-wave form only
+    if (wide || a.members > 1) throw Error{IMPG_E_INVALID, "internal: the walk's MultiImpg arm is the one-wave form's"};
+    if (ident_mode && !a.v.pfx) walk_wave_kernel<256, MODE_IDENT | MODE_WALK, true><<<n_workgroups, 64, 0, s>>>(a);
+    else if (ident_mode) walk_wave_kernel<256, MODE_IDENT, true><<<n_workgroups, 64, 0, s>>>(a);
+    else walk_wave_kernel<256, 0, true><<<n_workgroups, 64, 0, s>>>(a);
+  } else if (wide && a.members > 1) {
     if (ident_mode && !a.v.pfx) walk_grid_kernel<16, 4096, MODE_IDENT | MODE_WALK><<<n_workgroups, 1024, 0, s>>>(a);
     else if (ident_mode) walk_grid_kernel<16, 4096, MODE_IDENT><<<n_workgroups, 1024, 0, s>>>(a);
     else walk_grid_kernel<16, 4096, 0><<<n_workgroups, 1024, 0, s>>>(a);

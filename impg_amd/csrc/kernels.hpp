@@ -401,6 +401,7 @@ size_t walk_slab_bytes(uint32_t n_seq, bool wide, uint32_t wcap, uint32_t hcap, 
 #endif
 constexpr uint32_t WALK_WAVES_PER_SIMD = IMPG_WALK_WAVES;  // resident waves per SIMD the one-wave-per-query walk is compiled for
 uint32_t walk_grid_blocks_per_cu();  // the occupancy query behind the grid form's launch size (Engine::walk_group_size)
-void launch_walk(const WalkArgs &a, uint32_t n_workgroups, bool wide, bool ident_mode, hipStream_t s);  // (members > 1: n_workgroups = queries x members)
+// multi: the MultiImpg worklist arm of the one-wave form (a.dfs says which end is popped; never wide, never members > 1)
+void launch_walk(const WalkArgs &a, uint32_t n_workgroups, bool wide, bool ident_mode, hipStream_t s, bool multi = false);  // (members > 1: n_workgroups = queries x members)
 
 }  // namespace impg

@@ -31,8 +31,11 @@
 //             first takes the query up to its last level -- the big one, whose update is dead (impg.rs:2376) -- and
 //             publishes that frontier; all members share its ranges out (walk_final_level), two grid-wide hand-offs
 //
-// Not taken here (the caller falls back to the batch engine): MultiImpg worklists, store_cigar, tracepoint
-// indexes, more than 2^17 sequences, and any query that outgrows its slab (`overflow`).
+//   multi     a MultiImpg worklist (multi_impg.rs:796-991): the DFS arm popped at either end, its steps Impg::query calls, a
+//             pop's hits in five-key order (walk_body's MULTI); one wave per query, a budget of explored pops
+//
+// Not taken here (the caller falls back to the batch engine): store_cigar, MultiImpg under a mask, tracepoint
+// indexes, more than 2^16 sequences, and any query that outgrows its slab or its pop budget (`overflow`).
 struct WRec {
   uint32_t seq;
   int32_t start, end;
@@ -92,6 +95,15 @@ template <uint32_t NW> struct WalkLds {
   WRec top;
   unsigned long long acc_count, acc_cksum;
 };
+
+// What the MultiImpg arm keeps beside WalkLds (a struct of its own: the other instantiations' LDS stays as it was)
+struct WalkMultiLds {
+  int bot_seq;  // lowest sequence with a non-empty stack list, for the pop at the front (0x7FFFFFFF: the stack is empty)
+};
+// The arm's pop budget.  The reference's worklist always ends (visited lists only grow); a wrong kernel's may not, and a wave
+// must not spin on a device that others use.  The headline index's lone `-m 3` call explores 834 pops (of 20 147): the cap is
+// three orders above that.  Past it the query gives up with cause bit 256 and the batch engine answers, as for a slab limit.
+constexpr uint32_t WALK_POP_BUDGET = 1u << 20;
 
 template <uint32_t NW> __device__ __forceinline__ uint32_t wk_scan(uint32_t x, uint32_t *wsum, uint32_t &total) {
   const uint32_t inc = wave_incl_scan(x);
@@ -160,14 +172,16 @@ __device__ __forceinline__ uint32_t wk_wave_first(const int32_t *__restrict__ co
 }
 
 // hits of range r (window [lo, ub) of the entry columns) in visit order at pair_*[off ..): one wave (lookup_emit_kernel)
+// TR: the transitive lookup's open test on ends_t, else Impg::query's closed one on ends (a MultiImpg step)
+template <bool TR = true>
 __device__ __forceinline__ void wk_emit_range(const DeviceIndexView &v, uint32_t lo, uint32_t ub, int32_t qs, uint32_t off, uint32_t r,
                                               uint32_t *__restrict__ pair_range, uint32_t *__restrict__ pair_entry) {
-  const int32_t *ecol = v.ends_t;
+  const int32_t *ecol = end_col<TR>(v);
   const unsigned lane = lane_id();
   if (lo >= ub) return;
   if (ub - lo <= 64u) {
     const uint32_t i = lo + lane;
-    const bool hit = i < ub && window_hit<true>(ecol[i], qs);
+    const bool hit = i < ub && window_hit<TR>(ecol[i], qs);
     const unsigned long long m0 = __ballot(hit);
     uint32_t rk = hit ? (v.sorted_order ? lane : v.rank[i]) : 0xFFFFFFFFu;
     uint32_t who = lane;
@@ -192,12 +206,12 @@ __device__ __forceinline__ void wk_emit_range(const DeviceIndexView &v, uint32_t
   // windows wider than one wave (dense targets): every hit counts the hits with a smaller rank
   for (uint32_t base = lo; base < ub; base += 64u) {
     const uint32_t i = base + lane;
-    const bool hit = i < ub && window_hit<true>(ecol[i], qs);
+    const bool hit = i < ub && window_hit<TR>(ecol[i], qs);
     const uint32_t rk = hit ? (v.sorted_order ? i - lo : v.rank[i]) : 0xFFFFFFFFu;
     uint32_t pos = 0;
     for (uint32_t b2 = lo; b2 < ub; b2 += 64u) {
       const uint32_t i2 = b2 + lane;
-      const bool hit2 = i2 < ub && window_hit<true>(ecol[i2], qs);
+      const bool hit2 = i2 < ub && window_hit<TR>(ecol[i2], qs);
       const uint32_t rk2 = hit2 ? (v.sorted_order ? i2 - lo : v.rank[i2]) : 0xFFFFFFFFu;
       unsigned long long m = __ballot(hit2);
       while (m) {
@@ -410,10 +424,22 @@ __device__ __forceinline__ bool walk_final_level(const WalkArgs &A, const uint32
   return fine;
 }
 
-template <uint32_t NW, uint32_t LCAP, int MODE, bool GRID>
+// MULTI: a MultiImpg worklist (MultiImpg::transitive_query_impl, multi_impg.rs:796-991) -- the DFS arm's one pop at a time with
+//   pop      A.dfs: at the back, as the DFS arm; else at the front -- the first record of the lowest non-empty list
+//   step     an Impg::query: the closed overlap test, the unclipped range (what Engine::expand selects for MultiImpg)
+//   hits     in (query_id, q_first, q_last, t_first, t_last) order, ties by the entry's mrank, then the slot (key5_less): the
+//            row order and the replay order; a hit on the popped sequence itself is no hit at all (multi_impg.rs:883-885)
+//   budget   WALK_POP_BUDGET explored pops a query
+// (written out at every use, not held in a variable: the other instantiations then read A.dfs where they always did)
+#define WK_STACK (MULTI || A.dfs)   /* a stack / worklist of single pops (else: BFS levels) */
+#define WK_BACK (!MULTI || A.dfs)   /* which end is popped */
+template <uint32_t NW, uint32_t LCAP, int MODE, bool GRID, bool MULTI = false>
 __device__ __forceinline__ void walk_body(const WalkArgs &A) {
+  static_assert(!MULTI || (NW == 1 && !GRID), "the MultiImpg arm is the one-wave form's");
   constexpr uint32_t T = NW * 64u;
+  constexpr bool TR = !MULTI;  // the lookups' and projections' TRANSITIVE
   __shared__ WalkLds<NW> S;
+  __shared__ WalkMultiLds SM;
   __shared__ __attribute__((aligned(8))) uint32_t lkeys[LCAP];
   const uint32_t tid = threadIdx.x;
   const DeviceIndexView &v = A.v;
@@ -459,7 +485,7 @@ __device__ __forceinline__ void walk_body(const WalkArgs &A) {
       else {
         const uint32_t ma = A.mask_off[rq.target_id], mlen = A.mask_off[rq.target_id + 1] - ma;
         const uint32_t cap0 = max(8u, 2u * (mlen + 1u));
-        if (cap0 > A.vcap || mlen + 1u > A.gcap || mlen + 1u > A.wcap || (A.dfs && mlen + 1u > A.scap)) { if (tid == 0) S.flag = 4; }
+        if (cap0 > A.vcap || mlen + 1u > A.gcap || mlen + 1u > A.wcap || (WK_STACK && mlen + 1u > A.scap)) { if (tid == 0) S.flag = 4; }
         else {
           int2 *Rl = B.vpool;
           for (uint32_t i = tid; i < mlen; i += T) Rl[i] = A.mask_ranges[ma + i];
@@ -513,13 +539,13 @@ __device__ __forceinline__ void walk_body(const WalkArgs &A) {
               }
               if (abs(pc.x - pc.y) >= A.min_transitive_len) {
                 B.wa[nf] = WRec{rq.target_id, pc.x, pc.y, 0u};
-                if (A.dfs) B.spool[nf] = make_int4(pc.x, pc.y, 0, 0);
+                if (WK_STACK) B.spool[nf] = make_int4(pc.x, pc.y, 0, 0);
                 nf += 1;
               }
             }
             S.rows_run = np;
             S.nw = nf;
-            if (A.dfs && nf) {
+            if (WK_STACK && nf) {
               B.st_off[rq.target_id] = 0; B.st_len[rq.target_id] = nf; B.st_cap[rq.target_id] = max(8u, nf);
               S.spused = max(8u, nf);
               S.top_seq = (int)rq.target_id;
@@ -546,7 +572,7 @@ __device__ __forceinline__ void walk_body(const WalkArgs &A) {
           if (abs(start - end) >= A.min_transitive_len) {
             B.wa[0] = WRec{rq.target_id, start, end, 0u};
             S.nw = 1;
-            if (A.dfs) {  // the stack's first record
+            if (WK_STACK) {  // the stack's first record
               B.st_off[rq.target_id] = 0; B.st_len[rq.target_id] = 1; B.st_cap[rq.target_id] = 8;
               B.spool[0] = make_int4(start, end, 0, 0);
               S.spused = 8;
@@ -556,22 +582,24 @@ __device__ __forceinline__ void walk_body(const WalkArgs &A) {
         }
       }
     }
+    if (MULTI && tid == 0) { SM.bot_seq = S.top_seq >= 0 ? S.top_seq : 0x7FFFFFFF; }  // (thread 0 set top_seq itself)
     __syncthreads();
     uint32_t level = 0;
+    uint32_t pops = 0;  // MULTI: explored pops of this query
     bool failed = S.flag != 0;
     bool named = false;  // the failure's cause bit is in A.overflow already
     if (A.dbg && tid == 0) tmark = clock64();
     // ---- the walk -----------------------------------------------------------------------------------------------------
     while (!failed) {
       uint32_t nw = S.nw;
-      if (!A.dfs && nw == 0) break;
+      if (!WK_STACK && nw == 0) break;
       uint32_t first, count, cur_depth;
       bool do_update;
-      if (A.dfs) {
+      if (WK_STACK) {
         // Pop (impg.rs:2120-2127): the stack's top is the last record of the highest non-empty sequence list.  Records
         // too deep to be explored are popped and dropped: the list's tail of such records goes in one step (wave 0).
         if (S.top_seq < 0) break;
-        if (tid < 64) {
+        if (WK_BACK && tid < 64) {
           int sq_i = S.top_seq;
           bool got_one = false;
           while (sq_i >= 0 && !got_one) {  // (wave 0 alone, no barrier: lists of records too deep to explore go one after the other)
@@ -610,6 +638,55 @@ __device__ __forceinline__ void walk_body(const WalkArgs &A) {
             }
           }
           if (lane_id() == 0) { S.top_seq = sq_i; S.tmp = got_one ? 1u : 0u; }
+        } else if (MULTI && tid < 64) {
+          // The front (multi_impg.rs:849-854): the first record of the lowest non-empty list.  The mirror image of the above:
+          // a list's head of records too deep to explore goes in one step, the list then starts behind them (its offset
+          // moves up, its capacity shrinks by as much); an emptied list sends the cursor up, 64 sequences per look.
+          // (top_seq is only ever raised while the front is popped: it bounds the looks from above)
+          int sq_i = SM.bot_seq;
+          const int hi_seq = S.top_seq;
+          bool got_one = false;
+          while (sq_i <= hi_seq && !got_one) {
+            const uint32_t sq = (uint32_t)sq_i;
+            const uint32_t len = B.st_len[sq], off = B.st_off[sq];
+            const int4 *L = B.spool + off;
+            uint32_t found = 0xFFFFFFFFu;  // index of the first explorable record
+            for (uint32_t lo = 0; lo < len && found == 0xFFFFFFFFu; lo += 64u) {
+              const uint32_t idx = lo + lane_id();
+              const bool in = idx < len;
+              const bool ok = in && !(A.max_depth > 0 && (uint32_t)L[in ? idx : 0].z >= A.max_depth);
+              const unsigned long long m = __ballot(ok);
+              if (m) found = lo + (uint32_t)(__ffsll((long long)m) - 1);
+            }
+            const uint32_t gone = found != 0xFFFFFFFFu ? found + 1u : len;  // records that leave the list's head
+            if (found != 0xFFFFFFFFu) {
+              if (lane_id() == 0) {
+                const int4 t = L[found];
+                S.top = WRec{sq, t.x, t.y, (uint32_t)t.z};
+                B.st_off[sq] = off + gone; B.st_len[sq] = len - gone; B.st_cap[sq] = B.st_cap[sq] - gone;  // (cap >= len >= gone)
+                if (A.dbg) atomicAdd(&A.dbg[17], (unsigned long long)found);
+              }
+              got_one = true;
+            } else if (lane_id() == 0) {
+              B.st_len[sq] = 0;
+              if (A.dbg) atomicAdd(&A.dbg[17], (unsigned long long)len);
+            }
+            if (gone == len) {  // the list is empty now: the next non-empty sequence above
+              int nt = 0x7FFFFFFF;
+              for (int base = sq_i + 1; base <= hi_seq && nt == 0x7FFFFFFF; base += 64) {
+                const int i = base + (int)lane_id();
+                const unsigned long long m = __ballot(i <= hi_seq && B.st_len[i <= hi_seq ? i : hi_seq] != 0u);
+                if (m) nt = base + (__ffsll((long long)m) - 1);
+              }
+              sq_i = nt;
+            }
+          }
+          if (lane_id() == 0) {
+            const bool empty = sq_i > hi_seq;
+            SM.bot_seq = empty ? 0x7FFFFFFF : sq_i;
+            if (empty) S.top_seq = -1;
+            S.tmp = got_one ? 1u : 0u;
+          }
         }
         __syncthreads();
         const bool got = S.tmp != 0;
@@ -617,6 +694,7 @@ __device__ __forceinline__ void walk_body(const WalkArgs &A) {
         __syncthreads();
         if (!got) { lap(0); continue; }
         bump(16, 1);
+        if (MULTI && ++pops > WALK_POP_BUDGET) { failed = true; if (tid == 0) S.flag |= 256u; break; }  // the pop budget
         if (tid == 0) B.wc[0] = top;  // the step's range
         __syncthreads();
         first = 0; count = 1; cur_depth = top.depth; do_update = true;
@@ -639,7 +717,7 @@ __device__ __forceinline__ void walk_body(const WalkArgs &A) {
           break;
         }
       }
-      const WRec *R = A.dfs ? B.wc : B.wa;
+      const WRec *R = WK_STACK ? B.wc : B.wa;
       if (tid == 0) S.npc = 0;
       __syncthreads();
       // ---- the level's / pop's ranges in sub-steps ------------------------------------------------------------------
@@ -661,13 +739,13 @@ __device__ __forceinline__ void walk_body(const WalkArgs &A) {
             }
             uint32_t l1 = 0, h1 = sn, l2 = 0, h2 = sn;
             if (cnt0) {
-              const uint32_t b1 = wk_wave_first<true>(v.starts_lvl + off0, 0u, cnt0, f.end);
-              const uint32_t b2 = wk_wave_first<false>(v.pmax_lvl + off0, 0u, cnt0, f.start);
+              const uint32_t b1 = wk_wave_first<TR>(v.starts_lvl + off0, 0u, cnt0, f.end);
+              const uint32_t b2 = wk_wave_first<!TR>(v.pmax_lvl + off0, 0u, cnt0, f.start);
               l1 = b1 < cnt0 ? 64u * b1 : sn; h1 = b1 < cnt0 ? min(l1 + 63u, sn) : sn;
               l2 = b2 < cnt0 ? 64u * b2 : sn; h2 = b2 < cnt0 ? min(l2 + 63u, sn) : sn;
             }
-            l1 = wk_wave_first<true>(v.starts + a, l1, h1, f.end);
-            l2 = wk_wave_first<false>(v.pmax + a, l2, h2, f.start);
+            l1 = wk_wave_first<TR>(v.starts + a, l1, h1, f.end);
+            l2 = wk_wave_first<!TR>(v.pmax + a, l2, h2, f.start);
             if (tid == 0) B.win[0] = make_uint2(a + min(l2, l1), a + l1);
           }
         } else if (tid < s_n) {
@@ -682,11 +760,11 @@ __device__ __forceinline__ void walk_body(const WalkArgs &A) {
           uint32_t l1 = 0, h1 = sn, l2 = 0, h2 = sn;
           if (cnt0) {
             uint32_t b1 = 0, e1 = cnt0, b2 = 0, e2 = cnt0;
-            dual_search4<true>(v.starts_lvl + off0, b1, e1, v.pmax_lvl + off0, b2, e2, f.start, f.end);
+            dual_search4<TR>(v.starts_lvl + off0, b1, e1, v.pmax_lvl + off0, b2, e2, f.start, f.end);
             l1 = b1 < cnt0 ? 64u * b1 : sn; h1 = b1 < cnt0 ? min(l1 + 63u, sn) : sn;
             l2 = b2 < cnt0 ? 64u * b2 : sn; h2 = b2 < cnt0 ? min(l2 + 63u, sn) : sn;
           }
-          dual_search4<true>(v.starts + a, l1, h1, v.pmax + a, l2, h2, f.start, f.end);
+          dual_search4<TR>(v.starts + a, l1, h1, v.pmax + a, l2, h2, f.start, f.end);
           const uint32_t ub = a + l1, lo = a + min(l2, l1);
           B.win[tid] = make_uint2(lo, ub);
         }
@@ -699,7 +777,7 @@ __device__ __forceinline__ void walk_body(const WalkArgs &A) {
           uint32_t k = 0;
           for (uint32_t b = w.x; b < w.y; b += 64u) {
             const uint32_t i = b + lane_id();
-            k += (uint32_t)__popcll(__ballot(i < w.y && window_hit<true>(v.ends_t[i], qs)));
+            k += (uint32_t)__popcll(__ballot(i < w.y && window_hit<TR>(end_col<TR>(v)[i], qs)));
           }
           if (lane_id() == 0) B.cnt[r] = k;
         }
@@ -713,13 +791,16 @@ __device__ __forceinline__ void walk_body(const WalkArgs &A) {
           sub = max(1u, s_n >> 1);  // fewer ranges per sub-step
           continue;
         }
+        // (MULTI: the sorted copy of a pop of more than 64 hits goes through gp[], 16 bytes a hit -- with the present caps,
+        // hcap <= gcap / 2, this cannot fire)
+        if (MULTI && P > 64u && 2ull * P > A.gcap) { failed = true; if (tid == 0) S.flag |= 8u; break; }
         if (tid < s_n) B.cnt[tid] = off;
         __syncthreads();
         lap(2);
         // b. the pairs in visit order (a wave per range)
         for (uint32_t r = tid >> 6; r < s_n; r += NW) {
           const uint2 w = B.win[r];
-          wk_emit_range(v, w.x, w.y, R[done + r].start, B.cnt[r], r, B.pair_range, B.pair_entry);
+          wk_emit_range<TR>(v, w.x, w.y, R[done + r].start, B.cnt[r], r, B.pair_range, B.pair_entry);
         }
         __syncthreads();
         lap(3);
@@ -740,14 +821,20 @@ __device__ __forceinline__ void walk_body(const WalkArgs &A) {
 #ifdef IMPG_PHASE_CLOCKS
             unsigned long long phase_t[10];
 #endif
-            project_pair<true, MODE>(v, B.pair_entry[p], f.start, f.end, p, ident ? A.min_identity : 0.0, A.err_flag, no_sl, A.accepted, ok, qid, res PHASE_PASS);
+            project_pair<TR, MODE>(v, B.pair_entry[p], f.start, f.end, p, ident ? A.min_identity : 0.0, A.err_flag, no_sl, A.accepted, ok, qid, res PHASE_PASS);
             if (ok) {
               hc = make_int4(res.pqs, res.pqe, res.pts, res.pte);
               // subset filter: a hit whose sequence is neither the query's own target nor kept is no hit (impg.rs:2430-2439)
               if (A.subset_keep && qid != rq.target_id && !A.subset_keep[qid]) qid = HIT_NONE;
+              if (MULTI && qid == tgt) qid = HIT_NONE;  // a hit on the popped sequence itself: not reported, not replayed (multi_impg.rs:883-885)
             }
             B.hqid[p] = qid;
             B.hc[p] = hc;
+          }
+          if (MULTI) {  // (rows, counts and checksums once the pop's hits are in order, below)
+            const unsigned long long okm = __ballot(ok);
+            if (lane_id() == 0) n_ok += (uint32_t)__popcll(okm);
+            continue;
           }
           const bool emit = qid != HIT_NONE && !(A.min_output_length >= 0 && abs(hc.y - hc.x) < A.min_output_length);  // impg.rs:2482-2504
           unsigned long long ck = 0;
@@ -773,6 +860,79 @@ __device__ __forceinline__ void walk_body(const WalkArgs &A) {
           __syncthreads();
           if (tid == 0) { S.rows_run = run + n_emit; S.acc_count += n_emit; }
           __syncthreads();
+        }
+        if (MULTI) {
+          // The pop's hits in the order of MultiImpg::query_all_indices (multi_impg.rs:582-592): a rank sort, every hit counting
+          // the hits that sort before it (sort5_kernel's way).  A pop of at most 64 hits stays in the wave's registers and is
+          // stored back in place; a longer one is read chunk by chunk from the slab and goes through skey[] / gp[].
+          __syncthreads();
+          int4 *hc2 = reinterpret_cast<int4 *>(B.gp);
+          const bool big = P > 64u;
+          for (uint32_t base = 0; base < P && P > 1u; base += 64u) {
+            const uint32_t i = base + tid;
+            uint32_t q5 = HIT_NONE, km = 0;
+            int4 k5 = make_int4(0, 0, 0, 0);
+            if (i < P) {
+              q5 = B.hqid[i];
+              if (q5 != HIT_NONE) { k5 = B.hc[i]; km = v.mrank ? v.mrank[B.pair_entry[i]] : 0u; }
+            }
+            uint32_t pos = 0;
+            for (uint32_t b2 = 0; b2 < P; b2 += 64u) {
+              uint32_t q2 = q5, jm = km;
+              int4 j5 = k5;
+              if (b2 != base) {
+                const uint32_t i2 = b2 + tid;
+                q2 = HIT_NONE; jm = 0; j5 = make_int4(0, 0, 0, 0);
+                if (i2 < P) {
+                  q2 = B.hqid[i2];
+                  if (q2 != HIT_NONE) { j5 = B.hc[i2]; jm = v.mrank ? v.mrank[B.pair_entry[i2]] : 0u; }
+                }
+              }
+              const uint32_t cntl = min(64u, P - b2);
+              for (uint32_t t = 0; t < cntl; t++) {
+                const uint32_t oq = (uint32_t)__shfl((int)q2, (int)t), om = (uint32_t)__shfl((int)jm, (int)t);
+                const int32_t o1 = __shfl(j5.x, (int)t), o2 = __shfl(j5.y, (int)t), o3 = __shfl(j5.z, (int)t), o4 = __shfl(j5.w, (int)t);
+                pos += key5_less(oq, o1, o2, o3, o4, om, b2 + t, q5, k5.x, k5.y, k5.z, k5.w, km, i) ? 1u : 0u;
+              }
+            }
+            if (i < P) {  // (every hit of the wave was read before the first is stored; empty slots sort last)
+              if (big) { B.skey[pos] = q5; hc2[pos] = k5; }
+              else { B.hqid[pos] = q5; B.hc[pos] = k5; }
+            }
+          }
+          __syncthreads();
+          if (big) {
+            for (uint32_t i = tid; i < P; i += T) { B.hqid[i] = B.skey[i]; B.hc[i] = hc2[i]; }
+            __syncthreads();
+          }
+          // rows, counts and checksums in that order
+          const uint32_t tgt = R[done].seq;
+          for (uint32_t pb = 0; pb < P; pb += T) {
+            const uint32_t p = pb + tid;
+            const uint32_t qid = p < P ? B.hqid[p] : HIT_NONE;
+            int4 hc = make_int4(0, 0, 0, 0);
+            if (qid != HIT_NONE) hc = B.hc[p];
+            const bool emit = qid != HIT_NONE && !(A.min_output_length >= 0 && abs(hc.y - hc.x) < A.min_output_length);  // multi_impg.rs:905-914
+            unsigned long long ck = 0;
+            if (emit) {
+              ck = mix64(((unsigned long long)qid << 32) | (uint32_t)hc.x);
+              ck = mix64(ck ^ (((unsigned long long)(uint32_t)hc.y << 32) | tgt));
+              ck = mix64(ck ^ (((unsigned long long)(uint32_t)hc.z << 32) | (uint32_t)hc.w));
+            }
+            uint32_t n_emit;
+            const uint32_t epos = wk_scan<NW>(emit ? 1u : 0u, S.wsum, n_emit);
+            const uint32_t run = S.rows_run;
+            if (emit && A.rows && run + epos < row_cap) {
+              impg_gpu_interval_t iv{qid, hc.x, hc.y, tgt, hc.z, hc.w};
+              A.rows[row_base + run + epos] = iv;
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) ck += (unsigned long long)__shfl_xor((long long)ck, o);
+            if (lane_id() == 0 && ck) atomicAdd(&S.acc_cksum, ck);
+            __syncthreads();
+            if (tid == 0) { S.rows_run = run + n_emit; S.acc_count += n_emit; }
+            __syncthreads();
+          }
         }
         {  // accepted projections of the sub-step (counted before the subset filter, like project_kernel)
           uint32_t tot;
@@ -939,7 +1099,7 @@ __device__ __forceinline__ void walk_body(const WalkArgs &A) {
         __syncthreads();
       }
       lap(8); peak(19, npc);
-      if (!A.dfs) {
+      if (!WK_STACK) {
         // BFS: the pieces are the next frontier
         if (n_new > A.wcap) { failed = true; if (tid == 0) S.flag |= 32u; break; }
         for (uint32_t i = tid; i < n_new; i += T) B.wa[i] = B.wb[i];
@@ -1009,6 +1169,7 @@ __device__ __forceinline__ void walk_body(const WalkArgs &A) {
           L[wi] = cur;
           B.st_len[seq] = wi + 1u;
           atomicMax(&S.top_seq, (int)seq);
+          if (MULTI) atomicMin(&SM.bot_seq, (int)seq);
         }
         __syncthreads();
         if (S.flag) { failed = true; break; }
@@ -1028,6 +1189,9 @@ __device__ __forceinline__ void walk_body(const WalkArgs &A) {
     __syncthreads();
   }
 }
+
+#undef WK_STACK
+#undef WK_BACK
 
 // 16 waves per query (a handful of queries: a BFS level spread over a workgroup) ...
 template <uint32_t NW, uint32_t LCAP, int MODE>
@@ -1056,7 +1220,8 @@ __global__ __launch_bounds__(NW * 64) void walk_grid_kernel(WalkArgs A) {
 }
 // ... or one wave per query (batches): the register budget is set by how many waves a SIMD should hold -- the walk is a
 // chain of dependent loads, so resident waves are its throughput (WALK_WAVES_PER_SIMD, kernels.hpp)
-template <uint32_t LCAP, int MODE>
+// (MULTI: the MultiImpg worklist arm, see walk_body)
+template <uint32_t LCAP, int MODE, bool MULTI = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WALK_WAVES_PER_SIMD, WALK_WAVES_PER_SIMD))) void walk_wave_kernel(WalkArgs A) {
-  walk_body<1, LCAP, MODE, false>(A);
+  walk_body<1, LCAP, MODE, false, MULTI>(A);
 }

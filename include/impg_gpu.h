@@ -298,13 +298,14 @@ int impg_gpu_set_option(impg_gpu_index_t *, const char *key, int64_t value);
 const char *impg_gpu_option_key(size_t i);
 const char *impg_gpu_counter_key(size_t i);
 /* Read-only counters of an index handle (no reference counterpart; they tell a test, or an operator, which engine
- * answered): "walk_launches" = per-query walk launches that answered their batch (walk_device.inc: DFS batches, small
- * depth-limited BFS batches incl. masked ones -- the shape of partition.rs:359-391), "walk_fallbacks" = launches whose
- * batch the batch engine had to run again (a query outgrew its slab), "walk_members" = workgroups per query of the
+ * answered): "walk_launches" = per-query walk launches that answered their batch (walk_device.inc: DFS batches, MultiImpg
+ * worklists of either end -- not under a mask --, small depth-limited BFS batches incl. masked ones -- the shape of
+ * partition.rs:359-391), "walk_fallbacks" = launches whose
+ * batch the batch engine had to run again (a query outgrew its slab or its pop budget), "walk_members" = workgroups per query of the
  * last grid-form launch (1: not the grid form), "walk_overflow" = the cause word of the most recent walk launch (0: the
  * launch answered its batch; otherwise the limits its queries outgrew, ORed: 1 unknown target, 2 pairs of one step / of one
  * member's share of the last level, 4 visited pool or a mask list, 8 piece scratch, 16 pieces of one level / pop, 32 DFS
- * stack (a BFS frontier is bounded by 16 first), 64 unnamed, 128 a grid hand-off timed out),
+ * stack (a BFS frontier is bounded by 16 first), 64 unnamed, 128 a grid hand-off timed out, 256 pop budget: a MultiImpg worklist explored more than 2^20 pops),
  * "small_batches" = plain batches of <= 64 ranges answered by the one-chain
  * small-batch path; "dfs_rounds" = rounds of the batch engine's DFS / MultiImpg worklist (Engine::run_dfs) in which some
  * query still had a stack -- a round that only drops too-deep records counts, a batch the walk answered adds none --,
