@@ -94,7 +94,18 @@ class SortPass(C.Structure):  # impg_gpu_sort_pass_t
     _fields_ = [("keys", C.c_void_p), ("wide", C.c_int), ("bits", C.c_uint)]
 
 
-REFINE_RECORD_DTYPE = np.dtype([("target_id", "<u4"), ("refined_start", "<i4"), ("refined_end", "<i4"), ("original_start", "<i4"),
+RESOLVE_FIELDS = ("records", "resolved", "absent", "inconsistent", "ops_in", "ops_out", "m_ops", "m_bases", "m_eq_bases", "m_x_bases",
+                  "bad_eq_bases", "bad_x_bases")
+
+
+class ResolveReport(C.Structure):  # impg_gpu_resolve_report_t
+    _fields_ = [(k, C.c_uint64) for k in RESOLVE_FIELDS]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k in RESOLVE_FIELDS}
+
+
+REFINE_RECORD_DTYPE =np.dtype([("target_id", "<u4"), ("refined_start", "<i4"), ("refined_end", "<i4"), ("original_start", "<i4"),
                                 ("original_end", "<i4"), ("left_extension", "<i4"), ("right_extension", "<i4"), ("support_count", "<u4"),
                                 ("original_support_count", "<u4")])  # impg_gpu_refine_record_t
 ROWS_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p))
@@ -139,6 +150,12 @@ SYMBOLS = [
     ("impg_gpu_selftest_paf_ingest", C.c_int, [C.POINTER(C.c_char_p), C.c_size_t, C.c_uint64, C.c_int, C.c_int, C.c_uint, C.c_uint64, C.POINTER(_P),
                                                C.POINTER(C.c_size_t), C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(_P), C.POINTER(C.c_size_t),
                                                C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(_P), _P]),
+    ("impg_gpu_cigar_resolve", C.c_int, [_P, C.c_size_t, _P, C.c_size_t, _P, _P, C.c_uint32, _P, C.c_int, C.c_int, C.POINTER(_P), C.POINTER(_P),
+                                         C.POINTER(C.c_size_t), C.POINTER(_P), C.POINTER(ResolveReport)]),
+    ("impg_gpu_selftest_cigar_resolve", C.c_int, [_P, C.c_size_t, _P, C.c_size_t, _P, _P, C.c_uint32, _P, C.c_int, C.c_int, C.c_uint32, C.POINTER(_P),
+                                                  C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(_P), C.POINTER(ResolveReport)]),
+    ("impg_gpu_index_create_from_paf_resolved", C.c_int, [C.POINTER(C.c_char_p), C.c_int, _P, C.c_int, C.c_int, C.c_int, C.POINTER(ResolveReport),
+                                                          C.POINTER(_P), C.POINTER(_P)]),
     ("impg_gpu_index_save", C.c_int, [_P, C.c_char_p]),
     ("impg_gpu_index_load", C.c_int, [C.c_char_p, C.c_int, C.POINTER(_P)]),
     ("impg_gpu_query_batch_stream", C.c_int, [_P, _P, C.c_size_t, _P, _P, _P, C.c_size_t, C.c_size_t, _P, _P, C.POINTER(C.c_uint64)]),

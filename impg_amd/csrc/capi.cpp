@@ -13,6 +13,7 @@
 #include <memory>
 #include <new>
 
+#include "cigar_resolve.hpp"
 #include "engine.hpp"
 #include "paf_ingest.hpp"
 #include "partition.hpp"
@@ -570,6 +571,78 @@ int impg_gpu_index_create_from_paf(const char *const *paths, int n_paths, int bi
   IMPG_CATCH
 }
 
+// impg_gpu_index_create_from_paf with the M ops resolved between the tokeniser and the builder (cigar_resolve.hpp): the pool
+// is rewritten where it lies in HBM and the builder reads the new one; the records' new offsets and lengths come home for
+// its host loops.
+int impg_gpu_index_create_from_paf_resolved(const char *const *paths, int n_paths, const impg_gpu_sequences_t *seqs, int bidirectional,
+                                            int order_policy, int device, impg_gpu_resolve_report_t *report, uint8_t **flags,
+                                            impg_gpu_index_t **out) {
+  IMPG_TRY
+  if (!out || !paths || n_paths <= 0 || !seqs) throw Error{IMPG_E_INVALID, "bad arguments"};
+  if (order_policy != IMPG_ORDER_COITREES && order_policy != IMPG_ORDER_SORTED) throw Error{IMPG_E_INVALID, "bad order policy"};
+  require_device(device);
+  const SeqStore &st = host_copy(store_of(seqs));
+  ParsedPaf pp;
+  std::vector<std::string> ps;
+  for (int i = 0; i < n_paths; i++) {
+    if (!paths[i]) throw Error{IMPG_E_INVALID, "null argument"};
+    ps.push_back(paths[i]);
+  }
+  const bool raw = !build_switches().host_build;
+  parse_paf_files(ps, pp, raw);
+  IMPG_HIP(hipSetDevice(device));
+  DevBuf d_ops, d_new;
+  uint64_t n_ops = pp.ops.size();
+  if (raw) n_ops = tokenize_on_device(pp, device, d_ops);
+  else {
+    d_ops.reserve(std::max<size_t>(n_ops * 4, 256));
+    if (n_ops) IMPG_HIP(hipMemcpy(d_ops.p, pp.ops.data(), n_ops * 4, hipMemcpyHostToDevice));
+  }
+  std::vector<const char *> names;
+  for (const std::string &n : pp.seq.names) names.push_back(n.c_str());
+  std::vector<int64_t> lens = pp.seq.lens;
+  const cigar_resolve::Plan plan = cigar_resolve::make_plan(pp.records.data(), pp.records.size(), n_ops, names.data(), lens.data(), (uint32_t)lens.size(), st);
+  cigar_resolve::Result res;
+  cigar_resolve::resolve_device(pp.records.data(), pp.records.size(), d_ops.as<uint32_t>(), n_ops, plan, st, 0, device, res, d_new);
+  d_ops.release();
+  for (size_t i = 0; i < pp.records.size(); i++) {
+    pp.records[i].cigar_off = res.off[i];
+    pp.records[i].cigar_len = res.len[i];
+  }
+  if (pp.file_first.size() < 2 || pp.file_first.front() != 0 || pp.file_first.back() != pp.records.size())
+    throw Error{IMPG_E_INVALID, "internal: bad file boundaries"};
+  auto stamp = [&](impg_gpu_index &ix) {
+    if (raw) ix.build_stats[BUILD_TOKENIZED_DEVICE] = 1;
+    const uint64_t *f = &res.report.records;
+    for (int k = 0; k < 12; k++) ix.resolve_stats[k] = f[k];
+  };
+  auto ix = std::make_unique<impg_gpu_index>();
+  ix->device = device;
+  ix->seq = pp.seq;
+  ix->file_first = pp.file_first;
+  if (build_index_device(*ix, pp.records.data(), pp.records.size(), nullptr, res.n_out, lens.data(), (uint32_t)lens.size(), bidirectional != 0,
+                         order_policy, 0, 1, nullptr, d_new.as<uint32_t>())) {
+    { EngineLease warm(*ix); }
+  } else {  // (the device was short of memory for the build: the new ops come home and the host builder takes over)
+    pp.ops.resize(res.n_out);
+    if (res.n_out) IMPG_HIP(hipMemcpy(pp.ops.data(), d_new.p, res.n_out * 4, hipMemcpyDeviceToHost));
+    d_new.release();
+    ix = make_index(pp.records.data(), pp.records.size(), pp.ops.data(), pp.ops.size(), lens.data(), (uint32_t)lens.size(), bidirectional,
+                    order_policy, device, 0, 1, &pp.seq, &pp.file_first, nullptr);
+  }
+  stamp(*ix);
+  if (flags) {
+    uint8_t *f = (uint8_t *)malloc(std::max<size_t>(res.flags.size(), 1));
+    if (!f) throw std::bad_alloc();
+    if (!res.flags.empty()) memcpy(f, res.flags.data(), res.flags.size());
+    *flags = f;
+  }
+  if (report) *report = res.report;
+  *out = ix.release();
+  return IMPG_OK;
+  IMPG_CATCH
+}
+
 // The second way from PAF files to an index: the files streamed into HBM in pieces and parsed there (paf_ingest.hpp).  From
 // the hand-off on -- records on the host, the op pool in HBM -- the code is impg_gpu_index_create_from_paf's.  One difference
 // in what a bad input is told: that route tokenises last, so a bad head anywhere is reported before any bad CIGAR; this one
@@ -787,6 +860,10 @@ static const CounterRow COUNTER_TABLE[] = {
     CTR("paf_ingest_lines", paf_ingest_stats[3]), CTR("paf_ingest_carried_bytes", paf_ingest_stats[4]),
     CTR("paf_ingest_buffer_grows", paf_ingest_stats[5]), CTR("paf_ingest_pool_regrows", paf_ingest_stats[6]),
     CTR("paf_ingest_unknown_names", paf_ingest_stats[7]), CTR("paf_ingest_inflated_blocks", paf_ingest_stats[8]),
+    CTR("resolve_records", resolve_stats[0]), CTR("resolve_resolved", resolve_stats[1]), CTR("resolve_absent", resolve_stats[2]),
+    CTR("resolve_inconsistent", resolve_stats[3]), CTR("resolve_ops_in", resolve_stats[4]), CTR("resolve_ops_out", resolve_stats[5]),
+    CTR("resolve_m_ops", resolve_stats[6]), CTR("resolve_m_bases", resolve_stats[7]), CTR("resolve_m_eq_bases", resolve_stats[8]),
+    CTR("resolve_m_x_bases", resolve_stats[9]), CTR("resolve_bad_eq_bases", resolve_stats[10]), CTR("resolve_bad_x_bases", resolve_stats[11]),
     CTR_RANKS("build_device", build_stats[BUILD_DEVICE]), CTR_RANKS("tokenized_device", build_stats[BUILD_TOKENIZED_DEVICE]),
     CTR_RANKS("build_batches", build_stats[BUILD_BATCHES]),
 };

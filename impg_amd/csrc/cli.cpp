@@ -99,20 +99,21 @@ void usage() {
           "               [-l N] [--min-result-identity F] [--subset-sequence-list FILE] [--original-sequence-coordinates]\n"
           "               [--consider-strandness] [-o auto|bed|bedpe|paf|fasta] [--sequence-files F... | --sequence-list FILE]\n"
           "               [--reverse-complement] [--sequence-store bytes|packed|auto] [--sequence-ingest host|device] [--host-merge] [--unidirectional]\n"
-          "               [--alignment-ingest host|device]\n"
+          "               [--alignment-ingest host|device] [--resolve-matches]\n"
           "               [--order coitrees|sorted] [--device N]\n"
           "impg-gpu partition (-a <paf>... | -i <file>) -w <bp> -d <bp> [--min-missing-size N] [--min-boundary-distance N]\n"
           "               [--selection-mode longest|total|sample[,sep]|haplotype[,sep]] [--starting-sequences-file FILE]\n"
           "               [--separate-files] [--no-rehome-singletons] [--output-folder DIR] [-o bed|fasta] [--host-state] [-m N]\n"
           "               [--sequence-files F... | --sequence-list FILE] [--sequence-store bytes|packed|auto] [--reverse-complement]\n"
-          "               [--sequence-ingest host|device] [--alignment-ingest host|device]\n"
+          "               [--sequence-ingest host|device] [--alignment-ingest host|device] [--resolve-matches]\n"
           "               [--transitive-dfs] [--min-transitive-len N] [--min-distance-between-ranges N] [--min-identity F]\n"
           "               [--unidirectional] [--order coitrees|sorted] [--device N]\n"
           "impg-gpu refine (-a <paf>... | -i <file>) (-r seq:start-end | -b <bed>) (-d <bp> | --no-merge) [--span-bp N]\n"
           "               [--max-extension F] [--extension-step N] [--pansn-mode sample|haplotype] [--support-output FILE]\n"
           "               [--blacklist-bed FILE] [-x] [-m N] [--transitive-dfs] [--multi-impg] [--min-transitive-len N]\n"
           "               [--min-distance-between-ranges N] [--min-result-identity F] [--subset-sequence-list FILE]\n"
-          "               [--alignment-ingest host|device] [--unidirectional] [--order coitrees|sorted] [--device N]\n");
+          "               [--alignment-ingest host|device] [--resolve-matches --sequence-files F... | --sequence-list FILE]\n"
+          "               [--unidirectional] [--order coitrees|sorted] [--device N]\n");
 }
 
 // --alignment-ingest host|device (query, partition, refine): who parses the alignment files' lines -- the host
@@ -126,7 +127,50 @@ bool alignment_ingest_arg(const std::string &a, int &i, int argc, char **argv) {
   g_alignment_ingest_device = sv == "device";
   return true;
 }
+// --resolve-matches (query, partition, refine, wherever they build an index from -a): every 'M' op is rewritten as the
+// '=' / 'X' runs the sequences of --sequence-files / --sequence-list spell before the index is built
+// (impg_gpu_index_create_from_paf_resolved); under -v the report is one line on stderr
+struct ResolveArgs {
+  bool on = false;
+  int verbose = 0;
+  std::vector<std::string> files;
+} g_resolve;
+void read_sequence_list(const std::string &seq_list, std::vector<std::string> &seq_files) {  // one path per line (main.rs:4130-4145)
+  std::ifstream in(seq_list);
+  if (!in) die("No such file or directory: " + seq_list);
+  std::string line;
+  while (std::getline(in, line)) {
+    while (!line.empty() && (line.back() == '\r' || line.back() == ' ' || line.back() == '\t')) line.pop_back();
+    if (!line.empty()) seq_files.push_back(line);
+  }
+}
+// after the arguments are read: what --resolve-matches cannot go with, each with its reason
+void resolve_check(const std::string &index_file, bool sequence_ingest_device, const std::vector<std::string> &seq_files, int verbose) {
+  if (!g_resolve.on) return;
+  if (!index_file.empty()) die("--resolve-matches rewrites the CIGARs while the index is built from -a: a saved index (-i) holds the ops as they were", 2);
+  if (g_alignment_ingest_device) die("--resolve-matches sits behind the host's line parser: not with --alignment-ingest device", 2);
+  if (sequence_ingest_device) die("--resolve-matches compares against the host's copy of the sequences: not with --sequence-ingest device", 2);
+  if (seq_files.empty()) die("--resolve-matches needs the sequences: use --sequence-files or --sequence-list", 2);
+  g_resolve.files = seq_files;
+  g_resolve.verbose = verbose;
+}
 int create_from_paf(const std::vector<const char *> &pp, bool unidirectional, int order, int device, impg_gpu_index_t **ix) {
+  if (g_resolve.on) {
+    std::vector<const char *> sp;
+    for (auto &f : g_resolve.files) sp.push_back(f.c_str());
+    impg_gpu_sequences_t *seqs = nullptr;
+    if (impg_gpu_sequences_from_fasta(sp.data(), sp.size(), &seqs) != IMPG_OK) return IMPG_E_INVALID;
+    impg_gpu_resolve_report_t r;
+    const int rc = impg_gpu_index_create_from_paf_resolved(pp.data(), (int)pp.size(), seqs, unidirectional ? 0 : 1, order, device, &r, nullptr, ix);
+    impg_gpu_sequences_free(seqs);
+    if (rc == IMPG_OK && g_resolve.verbose >= 1)
+      fprintf(stderr, "[impg-gpu] resolve-matches: records %llu resolved %llu absent %llu inconsistent %llu ops %llu -> %llu; M ops %llu bases %llu = %llu X %llu; "
+                      "bad = bases %llu bad X bases %llu\n",
+              (unsigned long long)r.records, (unsigned long long)r.resolved, (unsigned long long)r.absent, (unsigned long long)r.inconsistent,
+              (unsigned long long)r.ops_in, (unsigned long long)r.ops_out, (unsigned long long)r.m_ops, (unsigned long long)r.m_bases,
+              (unsigned long long)r.m_eq_bases, (unsigned long long)r.m_x_bases, (unsigned long long)r.bad_eq_bases, (unsigned long long)r.bad_x_bases);
+    return rc;
+  }
   if (g_alignment_ingest_device) return impg_gpu_index_create_from_paf_streamed(pp.data(), (int)pp.size(), unidirectional ? 0 : 1, order, device, 0, ix);
   return impg_gpu_index_create_from_paf(pp.data(), (int)pp.size(), unidirectional ? 0 : 1, order, device, ix);
 }
@@ -179,6 +223,7 @@ int partition_main(int argc, char **argv) {
   std::string seq_list;
   int sequence_store = 0;
   bool ingest_device = false;  // --sequence-ingest device: impg_gpu_index_load_sequences instead of _from_fasta + _set_sequences
+  int verbose = 0;
   long max_depth = 2, min_tl = -1, mdbr = 10, min_missing = 3000, min_boundary = 3000;
   double min_ident = NAN;
   int device = 0, order = IMPG_ORDER_COITREES;
@@ -242,7 +287,9 @@ int partition_main(int argc, char **argv) {
       std::string o = need("--order");
       if (o != "sorted" && o != "coitrees") die("invalid value '" + o + "' for '--order'", 2);
       order = o == "sorted" ? IMPG_ORDER_SORTED : IMPG_ORDER_COITREES;
-    } else if (a == "-t" || a == "--threads" || a == "-v" || a == "--verbose") need(a.c_str());  // accepted, unused
+    } else if (a == "-t" || a == "--threads") need(a.c_str());  // accepted, unused
+    else if (a == "-v" || a == "--verbose") verbose = (int)num(a, need(a.c_str()), 0, 9);  // >= 1: the report of --resolve-matches on stderr
+    else if (a == "--resolve-matches") g_resolve.on = true;
     else if (alignment_ingest_arg(a, i, argc, argv)) {}
     else if (a == "-h" || a == "--help") { usage(); return 0; }
     else die("unexpected argument '" + a + "'", 2);
@@ -275,6 +322,7 @@ int partition_main(int argc, char **argv) {
   else if (kind == "sample") selection = IMPG_SELECT_SAMPLE;
   else if (kind == "haplotype") selection = IMPG_SELECT_HAPLOTYPE;
   else die("Invalid selection mode. Must be 'longest', 'total', 'sample[,sep]', or 'haplotype[,sep]'.");
+  resolve_check(index_file, ingest_device, seq_files, verbose);
   impg_gpu_index_t *ix = open_index(pafs, index_file, unidirectional, order, device);
   std::vector<uint32_t> start_ids;
   if (!starting.empty()) {  // partition.rs:186-212: first tab field, trimmed; empty lines, '#' comments and unknown names skipped
@@ -374,7 +422,9 @@ int refine_main(int argc, char **argv) {
   bool have_d = false, no_merge = false, transitive = false, dfs = false, multi = false, unidirectional = false;
   long max_depth = 2, min_tl = -1, mdbr = 10, span_bp = 1000, step = 1000;
   double min_ident = NAN, max_ext = 0.5;
-  int device = 0, order = IMPG_ORDER_COITREES;
+  int device = 0, order = IMPG_ORDER_COITREES, verbose = 0;
+  std::vector<std::string> seq_files;  // --sequence-files / --sequence-list: what --resolve-matches compares against
+  std::string seq_list;
   auto num = [](const std::string &flag, const char *x, long lo, long hi) -> long {
     char *end = nullptr;
     errno = 0;
@@ -425,7 +475,13 @@ int refine_main(int argc, char **argv) {
       std::string o = need("--order");
       if (o != "sorted" && o != "coitrees") die("invalid value '" + o + "' for '--order'", 2);
       order = o == "sorted" ? IMPG_ORDER_SORTED : IMPG_ORDER_COITREES;
-    } else if (a == "-t" || a == "--threads" || a == "-v" || a == "--verbose") need(a.c_str());  // accepted, unused
+    } else if (a == "-t" || a == "--threads") need(a.c_str());  // accepted, unused
+    else if (a == "-v" || a == "--verbose") verbose = (int)num(a, need(a.c_str()), 0, 9);  // >= 1: the report of --resolve-matches on stderr
+    else if (a == "--resolve-matches") g_resolve.on = true;
+    else if (a == "--sequence-files") {  // (read by --resolve-matches alone: refine prints no bases)
+      seq_files.push_back(need(a.c_str()));
+      while (i + 1 < argc && argv[i + 1][0] != '-') seq_files.push_back(argv[++i]);
+    } else if (a == "--sequence-list") seq_list = need(a.c_str());
     else if (alignment_ingest_arg(a, i, argc, argv)) {}
     else if (a == "-h" || a == "--help") { usage(); return 0; }
     else die("unexpected argument '" + a + "'", 2);
@@ -439,6 +495,9 @@ int refine_main(int argc, char **argv) {
   if (!pansn.empty() && pansn != "sample" && pansn != "haplotype" && pansn != "sequence") die("invalid value '" + pansn + "' for '--pansn-mode'", 2);
   if (pafs.empty() && index_file.empty()) die("the following required arguments were not provided: --alignment-files", 2);
   if (range.empty() && bed.empty()) die("Either --target-range or --target-bed must be provided");
+  if (!seq_files.empty() && !seq_list.empty()) die("Cannot specify both --sequence-files and --sequence-list");
+  if (!seq_list.empty()) read_sequence_list(seq_list, seq_files);
+  resolve_check(index_file, false, seq_files, verbose);
   impg_gpu_index_t *ix = open_index(pafs, index_file, unidirectional, order, device);
   std::vector<uint8_t> keep;
   if (!subset_list.empty()) keep = load_subset_keep(ix, subset_list);
@@ -611,6 +670,7 @@ int main(int argc, char **argv) {
     else if (a == "-i" || a == "--index") index_file = need("-i");
     else if (a == "-v" || a == "--verbose") verbose = (int)num(a, need(a.c_str()), 0, 9);  // >= 1: phase timings on stderr
     else if (a == "-t" || a == "--threads") need(a.c_str());  // accepted, unused
+    else if (a == "--resolve-matches") g_resolve.on = true;
     else if (alignment_ingest_arg(a, i, argc, argv)) {}
     else if (a == "-h" || a == "--help") { usage(); return 0; }
     else die("unexpected argument '" + a + "'", 2);
@@ -618,6 +678,7 @@ int main(int argc, char **argv) {
   auto file_exists = [](const std::string &p) { FILE *f = fopen(p.c_str(), "rb"); if (f) fclose(f); return f != nullptr; };
   if (index_only) {  // `impg index` (main.rs:11321-11386): build once, keep the result
     if (pafs.empty() || index_file.empty()) die("impg-gpu index needs --alignment-files and --index", 2);
+    if (g_resolve.on) die("--resolve-matches belongs to query, partition and refine: a saved index holds the ops as they were", 2);
     std::vector<const char *> pp;
     for (auto &p : pafs) pp.push_back(p.c_str());
     impg_gpu_index_t *ix = nullptr;
@@ -651,6 +712,7 @@ int main(int argc, char **argv) {
   if (ingest_device && sequence_store == 2) die("--sequence-store auto needs the host's copy of the sequences: with --sequence-ingest device choose bytes or packed", 2);
   if (fmt == "fasta" && seq_files.empty())  // main.rs:4243
     die("Sequence files (FASTA/AGC) are required for 'fasta' output format. Use --sequence-files or --sequence-list");
+  resolve_check(index_file, ingest_device, seq_files, verbose);
 
   std::vector<const char *> pp;
   for (auto &p : pafs) pp.push_back(p.c_str());

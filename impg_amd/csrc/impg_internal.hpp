@@ -414,6 +414,7 @@ inline const SeqStore &host_copy(const SeqStore &st) {
                                     "attach them with impg_gpu_index_set_sequences for FASTA text written on the host"};
   return st;
 }
+const SeqStore &store_of(const impg_gpu_sequences_t *seqs);  // (sequences.cpp: the handle's store, for the other files)
 constexpr uint32_t SEQ_ABSENT = 0xFFFFFFFFu;      // impg_gpu_index::store_of_id: the store lacks the sequence
 constexpr uint64_t SEQ_NOT_IN_HBM = ~0ull;        // the device offsets' mark of the same
 constexpr size_t SEQ_PAD = 16;                    // bytes in front of the first base in HBM (and at least as many behind the last)
@@ -515,6 +516,9 @@ struct impg_gpu_index {
   mutable std::atomic<uint64_t> ingest_stats[5] = {};
   // ... and the ingest of impg_gpu_index_create_from_paf_streamed (by impg::paf_ingest::Stat; paf_ingest.hpp): all zero on any other index
   mutable std::atomic<uint64_t> paf_ingest_stats[9] = {};
+  // ... and the report of impg_gpu_index_create_from_paf_resolved, in the order of impg_gpu_resolve_report_t's fields
+  // (cigar_resolve.hpp): all zero on any other index
+  mutable std::atomic<uint64_t> resolve_stats[12] = {};
   void fasta_stats_reset() const { for (int k = 0; k < impg::FASTA_STORE_BYTES; k++) fasta_stats[k] = 0; }  // (the store's size stays: set when it is attached)
   // The sequence store attached by impg_gpu_index_set_sequences (null: none): the host copy the host route reads, which
   // of its sequences every index id is (impg::SEQ_ABSENT: none), and the same bases in HBM for the device route -- SEQ_PAD

@@ -13,6 +13,8 @@ struct impg_gpu_sequences {
 
 namespace impg {
 
+const SeqStore &store_of(const impg_gpu_sequences_t *seqs) { return *seqs->s; }
+
 void SeqStore::add(const std::string &name, const char *b, size_t n) {
   if (name.empty()) throw Error{IMPG_E_INVALID, "a sequence without a name"};
   if (!by_name.emplace(name, (uint32_t)names.size()).second) throw Error{IMPG_E_INVALID, "sequence '" + name + "' occurs twice in the sequence files"};

@@ -452,10 +452,13 @@ class GpuImpg:
 
     @classmethod
     def from_paf(cls, paths, bidirectional=True, order=_lib.ORDER_COITREES, device=0, devices=None, lanes=2, comm=None, ingest="host",
-                 piece_bytes=None):
+                 piece_bytes=None, resolve_matches=None):
         """devices / comm: as in from_records (impg_gpu_index_create_from_paf_multi / _rank).  ingest="device": the files are
         streamed into HBM in pieces of piece_bytes (None: 64 MiB) and parsed there (impg_gpu_index_create_from_paf_streamed;
-        one GPU: not with devices= or comm=); "host" is the host's line and field parser."""
+        one GPU: not with devices= or comm=); "host" is the host's line and field parser.  resolve_matches=Sequences: every
+        'M' op is rewritten on the device as the '=' / 'X' runs the sequences spell before the index is built
+        (impg_gpu_index_create_from_paf_resolved; ingest="host" on one GPU only); resolve_report() and resolve_flags say
+        what the pass found."""
         if isinstance(paths, str):
             paths = [paths]
         if ingest not in ("host", "device"):
@@ -464,8 +467,21 @@ class GpuImpg:
             raise ValueError("ingest='device' builds on one GPU: not with devices= or comm=")
         if ingest == "host" and piece_bytes is not None:
             raise ValueError("piece_bytes belongs to ingest='device'")
+        if resolve_matches is not None and (ingest != "host" or devices is not None or comm is not None):
+            raise ValueError("resolve_matches sits behind the host ingest on one GPU: not with ingest='device', devices= or comm=")
         arr = (C.c_char_p * len(paths))(*[p.encode() for p in paths])
         h = C.c_void_p(None)
+        if resolve_matches is not None:
+            rep, fl = _lib.ResolveReport(), C.c_void_p(None)
+            check(lib().impg_gpu_index_create_from_paf_resolved(arr, len(paths), resolve_matches._h, int(bidirectional), order, device,
+                                                                C.byref(rep), C.byref(fl), C.byref(h)))
+            ix = cls(h)
+            ix._comm = None
+            try:
+                ix.resolve_flags = np.frombuffer(C.string_at(fl, int(rep.records)), dtype=np.uint8).copy()
+            finally:
+                _lib.free(fl)
+            return ix
         if ingest == "device":
             check(lib().impg_gpu_index_create_from_paf_streamed(arr, len(paths), int(bidirectional), order, device, int(piece_bytes or 0), C.byref(h)))
         elif devices is not None:
@@ -610,6 +626,11 @@ class GpuImpg:
         v = C.c_int64(0)
         check(lib().impg_gpu_get_counter(self._h, key.encode(), C.byref(v)))
         return v.value
+
+    def resolve_report(self):
+        """The report of from_paf(..., resolve_matches=) as a dict (impg_gpu_resolve_report_t; the "resolve_*" counters):
+        all zero on a handle made any other way."""
+        return {k: self.counter("resolve_" + k) for k in _lib.RESOLVE_FIELDS}
 
     # ---- queries ---------------------------------------------------------------
     @staticmethod
@@ -1463,6 +1484,35 @@ def _keys(fn):
     while (k := fn(len(out))) is not None:
         out.append(k.decode())
     return out
+
+
+def resolve_cigars(records, ops, names, seq_len, sequences, on_host=False, device=0, tile_bases=None):
+    """impg_gpu_cigar_resolve: every 'M' op of the records rewritten as the '=' / 'X' runs that `sequences` spell ->
+    (records, ops, flags, report): the records with cigar_off / cigar_len rewritten, the new pool in record order, a flag
+    byte per record (0 resolved or without ops, 1 a sequence absent from the store, 2 inconsistent: ops copied) and the
+    report as a dict.  names[id] / seq_len[id]: the sequence table.  on_host: the host twin (no device needed);
+    tile_bases: impg_gpu_selftest_cigar_resolve's bases per wave (tests; the answer does not depend on it)."""
+    rec = np.ascontiguousarray(records, dtype=RECORD_DTYPE)
+    pool = np.ascontiguousarray(ops, dtype=np.uint32)
+    sl = np.ascontiguousarray(seq_len, dtype=np.int64)
+    if len(names) != sl.size:
+        raise _lib.ImpgGpuError(_lib.IMPG_E_INVALID, "one name per sequence length")
+    arr = (C.c_char_p * max(len(names), 1))(*[q.encode() if isinstance(q, str) else q for q in names])
+    ro, oo, fo, no, rep = C.c_void_p(None), C.c_void_p(None), C.c_void_p(None), C.c_size_t(0), _lib.ResolveReport()
+    head = (rec.ctypes.data, rec.size, pool.ctypes.data, pool.size, arr, sl.ctypes.data, sl.size, sequences._h, int(bool(on_host)), device)
+    tail = (C.byref(ro), C.byref(oo), C.byref(no), C.byref(fo), C.byref(rep))
+    if tile_bases is None:
+        check(lib().impg_gpu_cigar_resolve(*head, *tail))
+    else:
+        check(lib().impg_gpu_selftest_cigar_resolve(*head, int(tile_bases), *tail))
+    try:
+        out_rec = np.frombuffer(C.string_at(ro, rec.size * RECORD_DTYPE.itemsize), dtype=RECORD_DTYPE).copy()
+        out_ops = np.frombuffer(C.string_at(oo, no.value * 4), dtype=np.uint32).copy()
+        flags = np.frombuffer(C.string_at(fo, rec.size), dtype=np.uint8).copy()
+    finally:
+        for q in (ro, oo, fo):
+            _lib.free(q)
+    return out_rec, out_ops, flags, rep.as_dict()
 
 
 def option_keys():

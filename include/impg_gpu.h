@@ -187,6 +187,61 @@ int impg_gpu_selftest_paf_ingest(const char *const *paths, size_t n_paths, uint6
                                  size_t *n_records, uint32_t **ops, size_t *n_ops, char **names /* '\n'-joined, id order */,
                                  size_t *names_len, int64_t **lens, size_t *n_seq, uint64_t **file_first /* n_paths + 1 */,
                                  uint64_t *stats);
+/* ---- M ops resolved against the sequences.  The reference counts every 'M' base as a match
+ * ("We overestimate num. of matches by assuming 'M' represents matches for simplicity", main.rs:11944; the identity filter
+ * alike, impg.rs:2952-2973), so on a PAF written without --eqx its identity filter passes everything.  This pass rewrites,
+ * before the index is built, every 'M' op as the '=' / 'X' runs the two sequences spell and checks the '=' and 'X' ops
+ * that are there: the index is then the one the same PAF builds with each 'M' written out as its '=' / 'X' runs.
+ *   A record with cigar_len > 0 is resolvable if both its sequences are in the store, their stored lengths equal seq_len,
+ * 0 <= start <= end <= len on both axes, every op code is <= 4, the lengths of its '=' 'X' 'M' 'D' ops sum to target_end -
+ * target_start and those of its '=' 'X' 'M' 'I' ops to query_end - query_start.  Otherwise its ops are copied unchanged and
+ * its flag byte is 1 (a sequence absent from the store) or 2 (any other condition); no byte of a sequence is read for it.
+ * Records without ops pass through with flag 0.
+ *   Position p of an op that starts at (t, q) of its record compares T[target_start + t + p] with Q[query_start + q + p] on
+ * '+' and with comp(Q[query_end - 1 - q - p]) on '-' (comp: A<->T, C<->G, every other byte itself; the store is upper
+ * case).  Equal bytes match -- N against N too.  An 'M' of length L > 0 becomes its maximal runs of matching / differing
+ * positions, '=' (code 0) and 'X' (code 1) ops in order; an 'M' of length 0 becomes one '=' of length 0; '=' 'X' 'I' 'D' are
+ * kept verbatim and nothing is fused across op borders ("2=3M" over equal bases is "2=3=").
+ *   The report (also the counters "resolve_records", "resolve_resolved", "resolve_absent", "resolve_inconsistent",
+ * "resolve_ops_in", "resolve_ops_out", "resolve_m_ops", "resolve_m_bases", "resolve_m_eq_bases", "resolve_m_x_bases",
+ * "resolve_bad_eq_bases", "resolve_bad_x_bases" of a handle impg_gpu_index_create_from_paf_resolved made; 0 on every
+ * other handle): records = n_records; resolved / absent / inconsistent = records with ops by their flag 0 / 1 / 2; ops_in /
+ * ops_out = the records' ops before and after; over the resolvable records: m_ops 'M' ops of m_bases bases, of which
+ * m_eq_bases matched and m_x_bases did not, bad_eq_bases positions under an '=' whose bytes differ and bad_x_bases
+ * positions under an 'X' whose bytes are equal (such ops are counted, not changed). */
+typedef struct {
+  uint64_t records, resolved, absent, inconsistent, ops_in, ops_out, m_ops, m_bases, m_eq_bases, m_x_bases, bad_eq_bases, bad_x_bases;
+} impg_gpu_resolve_report_t;
+typedef struct impg_gpu_sequences impg_gpu_sequences_t; /* the sequence store: impg_gpu_sequences_from_fasta, below */
+/* The pass alone.  records address the pool `ops` in any order; names_of_ids[id] / seq_len[id] are the sequence table.
+ * Out, malloc'ed: the records with cigar_off (the ops of the records before it: the new pool is in record order) and
+ * cigar_len rewritten and every other field untouched, the new pool, a flag byte per record; report may be NULL.
+ * on_host = 1 runs the host twin of the kernels (single-threaded; no device needed).  On the device the store's
+ * sequences that the table names are uploaded one byte a base beside both pools: IMPG_E_OOM, naming the bytes it
+ * wanted, if they do not fit together.  IMPG_E_INVALID: a sequence id >= n_seq, a CIGAR outside the pool;
+ * IMPG_E_UNSUPPORTED: a record whose new cigar_len passes the build's limit of 2^29 - 1 ops (the build's own error), a
+ * pool of 2^32 op tiles, a store without a host copy (impg_gpu_index_load_sequences). */
+int impg_gpu_cigar_resolve(const impg_gpu_record_t *records, size_t n_records, const uint32_t *ops, size_t n_ops,
+                           const char *const *names_of_ids, const int64_t *seq_len, uint32_t n_seq,
+                           const impg_gpu_sequences_t *seqs, int on_host, int device,
+                           impg_gpu_record_t **records_out, uint32_t **ops_out, size_t *n_ops_out, uint8_t **flags_out,
+                           impg_gpu_resolve_report_t *report);
+/* The same for the tests, with the bases of an op one wave compares: tile_bases = 0 is the default (1 024), else a
+ * multiple of 64 up to 4 096 (IMPG_E_INVALID otherwise).  The answer does not depend on it. */
+int impg_gpu_selftest_cigar_resolve(const impg_gpu_record_t *records, size_t n_records, const uint32_t *ops, size_t n_ops,
+                                    const char *const *names_of_ids, const int64_t *seq_len, uint32_t n_seq,
+                                    const impg_gpu_sequences_t *seqs, int on_host, int device, uint32_t tile_bases,
+                                    impg_gpu_record_t **records_out, uint32_t **ops_out, size_t *n_ops_out, uint8_t **flags_out,
+                                    impg_gpu_resolve_report_t *report);
+/* impg_gpu_index_create_from_paf with the pass between the tokeniser and the builder: the host splits lines and fields,
+ * the device tokenises, resolves the pool where it lies in HBM and builds from the new pool; only the records' new
+ * cigar_off / cigar_len come home, the ops never do.  report and flags (malloc'ed, one byte per record in file order)
+ * may be NULL.  No flag makes the call fail: a caller that wants strictness reads the report.  The store is not
+ * attached (impg_gpu_index_set_sequences does that, as before).  One GPU. */
+int impg_gpu_index_create_from_paf_resolved(const char *const *paths, int n_paths, const impg_gpu_sequences_t *seqs,
+                                            int bidirectional, int order_policy, int device,
+                                            impg_gpu_resolve_report_t *report, uint8_t **flags, impg_gpu_index_t **out);
+
 /* A built index as one file: the role of the reference's `.impg` file (writer impg.rs:1655-1721, reader
  * :1787-1850; `impg index` / the implicit index cache of `impg query`, main.rs:11321-11386): pay for
  * parsing and tokenising once.  The file holds the device arrays as they sit in HBM plus the sequence
@@ -655,8 +710,8 @@ int impg_gpu_query_batch_paf_fd(impg_gpu_index_t *, const impg_gpu_range_t *rang
  * impg_gpu_index_load_sequences); IMPG_E_INVALID,
  * naming it, for a name that occurs twice, in one file or across files (the reference lets the last file win);
  * IMPG_E_IO for a file that cannot be read.  Host-only.  _name / _bases: sequence i as the store holds it (NULL past the
- * last; the bases are not NUL-terminated, *len = their number). */
-typedef struct impg_gpu_sequences impg_gpu_sequences_t;
+ * last; the bases are not NUL-terminated, *len = their number).  (impg_gpu_sequences_t is declared above, with the
+ * resolve pass that reads it.) */
 int impg_gpu_sequences_from_fasta(const char *const *paths, size_t n_paths, impg_gpu_sequences_t **out);
 int impg_gpu_sequences_from_memory(const char *const *names, const uint64_t *off, const char *bases, size_t n, impg_gpu_sequences_t **out);
 size_t impg_gpu_sequences_num(const impg_gpu_sequences_t *);
